@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- sequences/sec of the fused SRFRD train step (reference trainer.py:27-41) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
         N > 1: one rank per GPU over RCCL.  Under torch.distributed.run (WORLD_SIZE set) this process IS a rank; started
         plainly, it launches `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself as a child (before any
         GPU call), relays the child's output and exits with its status.
+        DIR: what the last timed step computed - the loss it returned and every parameter after its Adam update - as
+        DIR/<name>.npy (float32).  Model, batches and dropout seed are fixed: the same arguments give the same inputs.  The
+        default item-table scatter uses float atomics, whose rounding Adam amplifies step by step (after 300 steps two runs
+        of one build differ by up to ~1e-2 in a weight); with --deterministic the outputs are bitwise reproducible, so two
+        builds can be compared output for output.
 
 Workload (BASELINE.json configs[1], "C2"): SASRec (discriminator off), 50 000 items, seq_len 50, batch 512 per GPU,
 hidden 50, 2 blocks, 1 head, dropout 0.5, Adam(1e-3, betas=(0.9, 0.98)), fp32 arithmetic, synthetic ids already in HBM.
@@ -37,6 +42,22 @@ WORKLOADS = {
 }
 PEAK_F32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md: peak FP32 (matrix) dense
 PEAK_HBM_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E spec
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: C2 writes 9.7 MB
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs: what a caller of the timed step holds after its last step - the loss it returned and the parameters
+    its Adam update wrote, in the reference's state_dict layout - as float32 out_dir/<name>.npy.  Returns the bytes written."""
+    import numpy as np
+    arrays = {"loss": loss, **model.state_dict()}
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def algorithmic_flops_per_token(L, D, d_item, nb):
@@ -230,7 +251,13 @@ def main():
     ap.add_argument("--predict", action="store_true", help="time forward + full-catalog top-10 instead of the train step")
     ap.add_argument("--spin-up", type=int, default=200, help="untimed replays of the captured step inside a state snapshot before the "
                     "W warm-up steps (steady-state clocks / caches; state restored bit for bit; reported in config.spin_up_replays)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the loss and the parameters after the last timed step as "
+                    "DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.predict or args.autograd or args.workload != "C2"):
+        ap.error("--dump-outputs writes the outputs of the C2 train step: not with --predict, --autograd or --workload")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args)                      # never returns
@@ -296,6 +323,9 @@ def main():
         elapsed = float(t.item())
     loss = float(tr.loss.cpu())
     log(f"timed region: {elapsed:.4f} s for {args.steps} steps, loss {loss:.5f}")
+    if args.dump_outputs and rank == 0:         # (before time_kernels: it steps the model further)
+        n_bytes = dump_outputs(args.dump_outputs, tr.loss, model)
+        log(f"outputs of the last timed step: {n_bytes} bytes under {args.dump_outputs}")
 
     # ---- dominant-kernel timing: HIP events around each launch of the same K steps, eager, on the launch stream
     kt = {"srfrd_encoder_fwd": 0.0, "srfrd_encoder_bwd": 0.0}

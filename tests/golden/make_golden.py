@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Generate golden fixtures from the REFERENCE's own classes (run in the build container only).
 
-    python -B tests/golden/make_golden.py            # writes tests/golden/*.npz
+    SRFRD_REFERENCE=<reference checkout> python -B tests/golden/make_golden.py      # writes tests/golden/*.npz
 
-Imports ``/root/reference/SRFR_model.py`` (torch + numpy only), applies the trainer's
+Imports ``$SRFRD_REFERENCE/SRFR_model.py`` (torch + numpy only), applies the trainer's
 xavier_normal_ init (reference trainer.py:364-369) under a fixed seed, and records, per class:
 inputs, the full state_dict, eval-mode ``forward`` outputs, ``predict`` logits, and - with
 ``dropout_rate=0`` - the restated train step of reference trainer.py:31-41: loss, every parameter
@@ -11,6 +11,7 @@ gradient, and weights after 1 and 3 ``torch.optim.Adam(lr=1e-3, betas=(0.9, 0.98
 Only inputs/outputs are stored; no reference source text is copied.  The reference does not exist
 on the GPU box, so nothing at test time imports it.
 """
+import math
 import os
 import sys
 
@@ -19,7 +20,10 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.dont_write_bytecode = True
-sys.path.insert(0, "/root/reference")
+REFERENCE = os.environ.get("SRFRD_REFERENCE")     # a checkout of github.com/oss0430/SRFRD
+if not REFERENCE:
+    sys.exit("set SRFRD_REFERENCE to a checkout of the reference (github.com/oss0430/SRFRD)")
+sys.path.insert(0, REFERENCE)
 import SRFR_model as ref  # noqa: E402
 
 I, L, B = 1000, 20, 8            # C1's catalog (BASELINE configs[0]: 1k items, seq_len 20)
@@ -191,8 +195,9 @@ def c2_checksum():
         with torch.no_grad():
             h, pl, nl = model(u, seq, rsq, pos, prs, neg, nrs)
         out[f"{kind}/seed"] = np.array([seed, 11 + k_i], np.int64)
-        out[f"{kind}/w_sum"] = np.array([float(v.double().sum()) for v in model.state_dict().values()], np.float64)
-        out[f"{kind}/w_abs"] = np.array([float(v.double().abs().sum()) for v in model.state_dict().values()], np.float64)
+        # correctly rounded sums (math.fsum): torch's parallel sum() depends on the host's thread count
+        out[f"{kind}/w_sum"] = np.array([math.fsum(v.double().flatten().tolist()) for v in model.state_dict().values()], np.float64)
+        out[f"{kind}/w_abs"] = np.array([math.fsum(v.double().abs().flatten().tolist()) for v in model.state_dict().values()], np.float64)
         out[f"{kind}/pos_logits"] = pl.numpy()
         out[f"{kind}/neg_logits"] = nl.numpy()
         out[f"{kind}/h_last"] = h[:, -1].numpy()

@@ -7,15 +7,19 @@ so - as SURVEY.md 8c records - its text is executed with only that class skipped
 """
 import json
 import os
+import sys
 
 import numpy as np
 import pandas as pd
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+REFERENCE = os.environ.get("SRFRD_REFERENCE")     # a checkout of github.com/oss0430/SRFRD
+if not REFERENCE:
+    sys.exit("set SRFRD_REFERENCE to a checkout of the reference (github.com/oss0430/SRFRD)")
 
 
 def load_reference_utils():
-    lines = open("/root/reference/utils.py").read().split("\n")
+    lines = open(os.path.join(REFERENCE, "utils.py")).read().split("\n")
     src = "\n".join(lines[:141] + lines[194:])
     ns = {}
     exec(compile(src, "reference_utils", "exec"), ns)

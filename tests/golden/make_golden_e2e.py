@@ -42,7 +42,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.dont_write_bytecode = True
 sys.path.insert(0, ROOT)
-sys.path.insert(0, "/root/reference")
+REFERENCE = os.environ.get("SRFRD_REFERENCE")     # a checkout of github.com/oss0430/SRFRD
+if not REFERENCE:
+    sys.exit("set SRFRD_REFERENCE to a checkout of the reference (github.com/oss0430/SRFRD)")
+sys.path.insert(0, REFERENCE)
 import SRFR_model as ref  # noqa: E402
 
 from oracle import srfrd_oracle as O  # noqa: E402
@@ -57,7 +60,7 @@ KINDS = {"SASRec": 0, "SRFRN": 1, "SRFU_B": 2}
 
 
 def load_reference_utils():
-    lines = open("/root/reference/utils.py").read().split("\n")
+    lines = open(os.path.join(REFERENCE, "utils.py")).read().split("\n")
     src = "\n".join(lines[:141] + lines[194:])
     ns = {}
     exec(compile(src, "reference_utils", "exec"), ns)

@@ -5,6 +5,7 @@ The weights (10 MB per kind) are not stored: under the same ``torch.manual_seed`
 parameter containers in the reference's construction order, so the trainer's ``xavier_normal_`` loop (reference
 trainer.py:364-369) yields the reference's weights bit for bit - checked through stored per-tensor checksums on CPU - and
 the -m gpu test compares the HIP forward with the reference's full pos / neg logits and last-position hidden states."""
+import math
 import os
 
 import numpy as np
@@ -19,6 +20,11 @@ KINDS = ("SASRec", "SRFRN", "SRFU_B")
 def _fixture():
     z = np.load(os.path.join(GOLDEN, "c2_reference_outputs.npz"))
     return {k: z[k] for k in z.files}
+
+
+def _exact_sum(t):
+    """the correctly rounded float64 sum, the same on every host (torch's parallel sum() depends on the thread count)"""
+    return math.fsum(t.double().flatten().tolist())
 
 
 def _build(kind, g, device):
@@ -48,7 +54,7 @@ def test_same_seed_reproduces_the_reference_weights(kind):
     sd = m.state_dict()
     assert len(sd) == len(g[f"{kind}/w_sum"])
     for j, v in enumerate(sd.values()):
-        assert float(v.double().sum()) == g[f"{kind}/w_sum"][j] and float(v.double().abs().sum()) == g[f"{kind}/w_abs"][j], j
+        assert _exact_sum(v) == g[f"{kind}/w_sum"][j] and _exact_sum(v.abs()) == g[f"{kind}/w_abs"][j], j
 
 
 @pytest.mark.gpu

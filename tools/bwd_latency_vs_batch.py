@@ -7,7 +7,7 @@ Companion of tools/fwd_latency_vs_batch.py: at the C2 geometry one sequence's ba
 buy and why the register budget eats it.
 """
 import os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import srfrd_amd
 dev = "cuda"
 torch.manual_seed(0)

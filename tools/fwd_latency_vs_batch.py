@@ -8,7 +8,7 @@ batches of 64 .. 512 sequences.  The point it makes: up to 256 sequences (one wo
 set by the length of that chain, not by matrix-pipe or HBM throughput.
 """
 import os, sys, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import srfrd_amd
 dev = "cuda"
 torch.manual_seed(0)
