@@ -1,4 +1,6 @@
 """Shared test helpers: golden-fixture loading and oracle configuration."""
+import hashlib
+import math
 import os
 
 import numpy as np
@@ -29,6 +31,93 @@ def load_golden(kind, heads=1, l2=False):
     sd = {k[2:]: torch.from_numpy(v.copy()) for k, v in g.items() if k.startswith("w/")}
     batch = tuple(torch.from_numpy(g[k]) for k in ("seq", "rsq", "pos", "prs", "neg", "nrs"))
     return g, sd, batch
+
+
+# Train-mode (dropout > 0) fixtures tests/golden/<name>.npz (make_golden.py --dropout): the reference's own classes in
+# .train() with torch.nn.functional.dropout replaced by the project's coordinate-hash keep masks.
+# (name, class, seq_len, batch, items, num_heads, p).  seq_len 20: the inputs and initial weights are those of the
+# dropout-free fixture <class>.npz / <class>_h<heads>.npz (not stored twice).
+DROP_CASES = (
+    ("drop_SASRec_L20", "SASRec", 20, 8, 1000, 1, 0.5),
+    ("drop_SRFRN_L20", "SRFRN", 20, 8, 1000, 1, 0.5),
+    ("drop_SRFU_B_L20", "SRFU_B", 20, 8, 1000, 1, 0.5),
+    ("drop_SASRec_L20_h2", "SASRec", 20, 8, 1000, 2, 0.5),
+    ("drop_SASRec_L50", "SASRec", 50, 512, 400, 1, 0.5),
+    ("drop_SRFR_L50", "SRFR", 50, 64, 400, 1, 0.5),
+    ("drop_SRFRN_L50", "SRFRN", 50, 64, 400, 1, 0.5),
+    ("drop_SRFU_B_L50", "SRFU_B", 50, 64, 400, 1, 0.5),
+    ("drop_SASRec_L50_p03", "SASRec", 50, 64, 400, 1, 0.3),
+    ("drop_SASRec_L100", "SASRec", 100, 300, 400, 1, 0.5),
+    ("drop_SASRec_L200", "SASRec", 200, 64, 400, 1, 0.5),
+    ("drop_SRFRN_L200", "SRFRN", 200, 64, 400, 1, 0.5),
+)
+DROP_NAMES = tuple(c[0] for c in DROP_CASES)
+
+
+def drop_case(name):
+    return next(c for c in DROP_CASES if c[0] == name)
+
+
+def drop_cfg(name):
+    _, kind, L, _, I, heads, p = drop_case(name)
+    if kind == "SASRec":
+        return O.Cfg(kind, I, L, 50, dropout=p, num_heads=heads)
+    if kind in ("SRFR", "SRFRN"):
+        return O.Cfg(kind, I, L, 45, d_fake=5, dropout=p, num_heads=heads)
+    nl = {"SRFU_B": 3, "SRFU_F": L + 1, "SRFU_R": 11}[kind]
+    return O.Cfg(kind, I, L, 50, n_labels=nl, dropout=p, num_heads=heads)
+
+
+def drop_init_weights(seed, shapes):
+    """Initial weights of the seq_len >= 50 DROP_CASES fixtures, regenerated from the fixture's ``init_seed`` rather than
+    stored.  shapes: {state_dict name: shape}; one numpy RandomState draws the tensors in sorted-name order:
+    xavier_normal_'s standard deviation for >= 2-D tensors, 1 + 0.05 N(0, 1) for LayerNorm weights, 0.05 N(0, 1) for the
+    other 1-D tensors."""
+    rs = np.random.RandomState(seed)
+    out = {}
+    for k in sorted(shapes):
+        shp = tuple(int(n) for n in shapes[k])
+        z = rs.standard_normal(shp)
+        if len(shp) >= 2:
+            rf = int(np.prod(shp[2:]))
+            a = z * math.sqrt(2.0 / (shp[1] * rf + shp[0] * rf))
+        elif "layernorm" in k and k.endswith("weight"):
+            a = 1.0 + 0.05 * z
+        else:
+            a = 0.05 * z
+        out[k] = torch.from_numpy(a.astype(np.float32))
+    return out
+
+
+def weights_sha256(sd):
+    """SHA-256 (uint8 (32,)) of a state_dict's float32 bytes in sorted-name order"""
+    h = hashlib.sha256()
+    for k in sorted(sd):
+        h.update(np.ascontiguousarray(sd[k].numpy() if hasattr(sd[k], "numpy") else sd[k], np.float32).tobytes())
+    return np.frombuffer(h.digest(), np.uint8)
+
+
+def load_drop(name):
+    """-> (fixture dict, initial state_dict, batch (6 x int64 (B, L)), oracle Cfg) of one DROP_CASES fixture.
+    The weights after steps 1 and 3 are stored as the XOR of their float32 bit patterns with the previous weights'
+    (``x1/``, ``x3/``); they are returned decoded as ``w1/`` and ``w3/`` entries of the fixture dict."""
+    _, kind, L, B, _, heads, p = drop_case(name)
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    g = {k: z[k] for k in z.files}
+    assert float(g["p"]) == p
+    if L == G_L:
+        _, sd, batch = load_golden(kind, heads)
+    else:
+        sd = drop_init_weights(int(g["init_seed"]), {k[2:]: v.shape for k, v in g.items() if k.startswith("g/")})
+        batch = tuple(torch.from_numpy(g[k].astype(np.int64)) for k in ("seq", "rsq", "pos", "prs", "neg", "nrs"))
+    assert (weights_sha256(sd) == g["w_sha256"]).all(), "initial weights differ from the generator's"
+    assert batch[0].shape == (B, L)
+    prev = {k: v.numpy() for k, v in sd.items()}
+    for s in (1, 3):
+        for k in prev:
+            prev[k] = (prev[k].view(np.int32) ^ g[f"x{s}/" + k]).view(np.float32)
+            g[f"w{s}/" + k] = prev[k]
+    return g, sd, batch, drop_cfg(name)
 
 
 def sub(g, prefix):
