@@ -343,6 +343,36 @@ int srfrd_logits_topk(const srfrd_layout* lay, const void* item_table, const flo
 int srfrd_topk_merge(const int64_t* cand_idx, const float* cand_val, int B, int n_cand, int k,
                      int64_t* topk_idx, float* topk_val, void* stream);
 
+/*
+ * Full-catalog ranking with per-user exclusion sets (items a user already has; the `rated` set of a full-catalog evaluation).
+ * Row b's set is excl_items[excl_ptr[b] .. excl_ptr[b + 1]) (CSR over the batch: excl_ptr int64 (B + 1), excl_items int32):
+ * unsorted, duplicates, ids outside [item_lo, item_hi) and 0 are all accepted; a row may be empty.  max_row [host] bounds
+ * every row's length (the launchers read at most that many ids of a row); max_row > SRFRD_EXCL_CAP -> SRFRD_E_UNSUPPORTED.
+ * A pre-pass sorts and deduplicates each row into the exclusion workspace; the ranking passes mask the excluded
+ * (user, item) scores inside every pass (chunk maxima, threshold, collection, the exhaustive path).
+ * excl_ptr == NULL: no exclusion (srfrd_logits_topk_excl then launches exactly what srfrd_logits_topk does).
+ *
+ * srfrd_logits_topk_excl: srfrd_logits_topk over {i in [item_lo, item_hi) : i not in excl[b], !(exclude_pad && i == 0)};
+ *   fewer than k such items -> trailing slots idx -1 / val -inf.  workspace: srfrd_topk_workspace_bytes(B, k, n_rows),
+ *   excl_workspace: srfrd_excl_workspace_bytes(B, max_row, n_rows) (n_rows = item_hi - item_lo).
+ * srfrd_target_rank: rank[b] = #{i in [item_lo, item_hi) : i != t_b, i not in excl[b], !(exclude_pad && i == 0),
+ *   s(b, i) > s(b, t_b)} with targets t (int64 (B)); s(b, t_b) is the score the ranking pass's own tile arithmetic gives
+ *   t_b's row, so a bit-identical duplicate of the target ties and is not counted; t_b is ranked even when it is in its own
+ *   set.  Ranks over disjoint item ranges add up.  metric_acc (double[3], may be NULL): [0] += [rank < cut_k] /
+ *   log2(rank + 2), [1] += [rank < cut_k], [2] += 1.  workspace: srfrd_excl_workspace_bytes(B, max_row, n_rows) bytes
+ *   (max_row 0 without exclusion).
+ */
+#define SRFRD_EXCL_CAP 4096
+int64_t srfrd_excl_workspace_bytes(int B, int max_row, int64_t n_rows);
+int srfrd_logits_topk_excl(const srfrd_layout* lay, const void* item_table, const float* dense,
+                           const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
+                           const int64_t* user_label, int k, const int64_t* excl_ptr, const int32_t* excl_items, int max_row,
+                           int64_t* topk_idx, float* topk_val, void* workspace, void* excl_workspace, void* stream);
+int srfrd_target_rank(const srfrd_layout* lay, const void* item_table, const float* dense, const float* hidden,
+                      int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad, const int64_t* user_label,
+                      const int64_t* targets, const int64_t* excl_ptr, const int32_t* excl_items, int max_row,
+                      int cut_k, int32_t* rank, double* metric_acc, void* workspace, void* stream);
+
 /* HR@10 / NDCG@10 inputs (reference utils.py:589-597): rank[b] = #{i >= 1 : logits[b][i] > logits[b][0]};
  * metric_acc[0] += [rank<10] / log2(rank+2), metric_acc[1] += [rank<10], metric_acc[2] += 1 (double[3]). */
 int srfrd_eval_rank(const float* logits, int B, int n_cand, int32_t* rank, double* metric_acc, void* stream);

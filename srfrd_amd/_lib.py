@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("SRFRD_LIB_PATH") or os.path.join(_HERE, "lib", "libsr
 
 MAX_BLOCKS = 8
 MAX_D = 64
+EXCL_CAP = 4096                 # SRFRD_EXCL_CAP: most ids one row of an exclusion set may hold
 KINDS = {"SASRec": 0, "SRFR": 1, "SRFRN": 2, "SRFU_B": 3, "SRFU_F": 4, "SRFU_R": 5}
 _ERR = {-1: "SRFRD_E_ARG (bad argument)", -2: "SRFRD_E_UNSUPPORTED (configuration outside the fused kernels: "
         "hidden width > 64, hidden width not divisible by num_heads, a debug tap of a kernel without taps, or a caller-provided "
@@ -72,6 +73,9 @@ SIGNATURES = {
     "srfrd_topk_workspace_bytes": (_i64, [_i, _i, _i64]),
     "srfrd_logits_topk": (_i, [_LP, _P, _P, _P, _i, _i, _i64, _i64, _i, _P, _i, _P, _P, _P, _P]),
     "srfrd_topk_merge": (_i, [_P, _P, _i, _i, _i, _P, _P, _P]),
+    "srfrd_excl_workspace_bytes": (_i64, [_i, _i, _i64]),
+    "srfrd_logits_topk_excl": (_i, [_LP, _P, _P, _P, _i, _i, _i64, _i64, _i, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P]),
+    "srfrd_target_rank": (_i, [_LP, _P, _P, _P, _i, _i, _i64, _i64, _i, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P]),
     "srfrd_eval_rank": (_i, [_P, _i, _i, _P, _P, _P]),
     "srfrd_sample_batch": (_i, [_P, _P, _P, _i, _i, _i, _i, _u32, _u32, _P, _P, _P]),
 }

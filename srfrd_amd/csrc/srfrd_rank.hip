@@ -99,7 +99,92 @@ struct TopkArgs {
   float* tau;           // (B)
   Cand* cand;           // (B, kCandMax)
   int32_t* ccnt;        // (B) + 1 overflow flag at [B]
+  // per-user exclusion sets (srfrd_logits_topk_excl / srfrd_target_rank; unused by the unmasked instantiations):
+  const int32_t* xs;    // (B, xstride): row b's excluded ids inside [item_lo, item_hi), ascending, deduplicated, then INT32_MAX
+  const int2* xoff;     // (B, xchunks): {first position p in xs[b] of an id >= item_lo + 256 c, xs[b][p]}
+  int xstride, xchunks;
 };
+
+// ---- exclusion sets ---------------------------------------------------------------------------------------------------
+// Every (user, 256-row block of [item_lo, item_hi)) owns the contiguous sub-range [xoff[b][c].x, xoff[b][c + 1].x) of the
+// user's sorted list, so a ranking pass finds the excluded ids of a chunk with two loads and no search.  The list ends in an
+// INT32_MAX sentinel and xoff[b][c].y is the id at the sub-range's start: a cursor walking a chunk needs neither the end
+// of its sub-range nor a dependent load to start.
+constexpr int kExclCap = SRFRD_EXCL_CAP;        // most ids one row's list may hold (duplicates and out-of-range ids included)
+
+__device__ __forceinline__ bool excl_has(const TopkArgs& a, int b, int64_t item) {
+  const int c = (int)((item - a.item_lo) >> 8);
+  const int32_t* x = a.xs + (int64_t)b * a.xstride;
+  const int p1 = a.xoff[(int64_t)b * a.xchunks + c + 1].x;
+  for (int p = a.xoff[(int64_t)b * a.xchunks + c].x; p < p1; ++p)
+    if (x[p] == item) return true;
+  return false;
+}
+
+// one workgroup per row: the row's ids (out-of-range ones dropped) sorted in LDS by a bitonic network, duplicates marked and
+// sorted to the end again, then the sorted list and the row's block offsets are written out
+__global__ void __launch_bounds__(1024) excl_prep_kernel(const int64_t* __restrict__ excl_ptr, const int32_t* __restrict__ excl_items,
+                                                        int max_row, int P, int64_t item_lo, int64_t item_hi,
+                                                        int32_t* __restrict__ xs, int xstride, int2* __restrict__ xoff,
+                                                        int xchunks) {
+  __shared__ int32_t sk[kExclCap];
+  __shared__ int s_m;
+  const int tid = threadIdx.x, nthr = blockDim.x, b = blockIdx.x;
+  const int64_t p0 = excl_ptr[b];
+  int64_t n64 = excl_ptr[b + 1] - p0;
+  const int n = (int)(n64 < 0 ? 0 : n64 > max_row ? max_row : n64);
+  if (tid == 0) s_m = 0;
+  for (int i = tid; i < P; i += nthr) {
+    int32_t v = INT32_MAX;
+    if (i < n) {
+      const int32_t x = excl_items[p0 + i];
+      if (x >= item_lo && x < item_hi) v = x;
+    }
+    sk[i] = v;
+  }
+  __syncthreads();
+  auto sort = [&]() {
+    for (int k = 2; k <= P; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < P; i += nthr) {
+          const int ixj = i ^ j;
+          if (ixj > i) {
+            const int32_t x = sk[i], y = sk[ixj];
+            if ((x > y) == ((i & k) == 0)) { sk[i] = y; sk[ixj] = x; }
+          }
+        }
+        __syncthreads();
+      }
+  };
+  sort();
+  constexpr int PT = kExclCap / 1024;            // elements per thread (P <= kExclCap, blockDim.x == 1024)
+  bool dup[PT];
+  int kept = 0;
+#pragma unroll
+  for (int u = 0; u < PT; ++u) {
+    const int i = tid + u * nthr;
+    dup[u] = i < P && i > 0 && sk[i] == sk[i - 1];
+    kept += i < P && sk[i] != INT32_MAX && !dup[u];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < PT; ++u)
+    if (dup[u]) sk[tid + u * nthr] = INT32_MAX;
+  if (kept) atomicAdd(&s_m, kept);
+  __syncthreads();
+  sort();
+  const int m = s_m;
+  for (int i = tid; i <= m; i += nthr) xs[(int64_t)b * xstride + i] = i < m ? sk[i] : INT32_MAX;   // (xstride > max_row)
+  for (int c = tid; c < xchunks; c += nthr) {
+    const int64_t key = item_lo + 256 * (int64_t)c;
+    int lo = 0, hi = m;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if ((int64_t)sk[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    xoff[(int64_t)b * xchunks + c] = make_int2(lo, lo < m ? sk[lo] : INT32_MAX);
+  }
+}
 
 // contiguous global [rows][cols] -> LDS [rows][ld] with ITER loads in flight per thread (clamped indices, no predicate
 // between the loads): a plain `for (i = tid; ...) lds[..] = g[i]` copy pays one L2 / HBM round trip per iteration -
@@ -131,7 +216,7 @@ __device__ __forceinline__ void stage_item_rows(lds_f* dst, int ld, const srfrd_
 }
 
 // stage a chunk of item rows and then, for this workgroup's user tiles, leave the 16 x kChunk logits tile in sS
-template <class F>
+template <bool EXCL = false, class F>
 __device__ __forceinline__ void topk_tiles(const TopkArgs& a, F&& per_tile) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, nw = blockDim.x >> 6;
@@ -194,6 +279,17 @@ __device__ __forceinline__ void topk_tiles(const TopkArgs& a, F&& per_tile) {
       sS[c * SLD + r] = ok ? v : -INFINITY;
     });
     __syncthreads();
+    if constexpr (EXCL) {                                               // the excluded (user, item) scores leave the tile
+      for (int w = tid; w < 16 * 16; w += blockDim.x) {
+        const int r = w >> 4, j = w & 15, u = u0 + r;
+        if (u < a.B) {
+          const int32_t* x = a.xs + (int64_t)u * a.xstride;
+          const int p1 = a.xoff[(int64_t)u * a.xchunks + chunk + 1].x;
+          for (int p = a.xoff[(int64_t)u * a.xchunks + chunk].x + j; p < p1; p += 16) sS[r * SLD + (int)(x[p] - i0)] = -INFINITY;
+        }
+      }
+      __syncthreads();
+    }
     per_tile(u0, chunk, i0, sS, SLD);
   }
 }
@@ -202,7 +298,7 @@ __device__ __forceinline__ void topk_tiles(const TopkArgs& a, F&& per_tile) {
 // into elem(user_in_tile, item, value) - a running maximum (pass A) or a compare against tau (pass B) - so the
 // 16 x kChunk tile never makes the round trip through LDS.  Eight waves, the next user tile's hidden rows are
 // requested before the current tile's GEMM and land in the other half of a two-deep LDS buffer.
-template <class BEG, class ELEM, class END>
+template <bool EXCL = false, class BEG, class ELEM, class END>
 __device__ __forceinline__ void topk_stream(const TopkArgs& a, BEG&& begin, ELEM&& elem, END&& end) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, nw = blockDim.x >> 6, nthr = blockDim.x;
@@ -214,6 +310,7 @@ __device__ __forceinline__ void topk_stream(const TopkArgs& a, BEG&& begin, ELEM
   lds_f* sH = sE + kChunk * DSi;          // [2][16][DSi]
   lds_f* sF = sH + 2 * 16 * DSi;          // [2][16]
   lds_f* sM = sF + 32;                    // scratch of the end() step: [nw][16]
+  uint32_t* sX = (uint32_t*)(smem + (kChunk * DSi + 2 * 16 * DSi + 32 + nw * 16));   // EXCL: [16 users][kChunk / 32] bits
   const int chunk = blockIdx.x / a.user_splits, split = blockIdx.x - chunk * a.user_splits;
   const int64_t i0 = a.item_lo + (int64_t)chunk * kChunk;
   const int n_here = (int)((a.item_hi - i0) < kChunk ? (a.item_hi - i0) : kChunk);
@@ -266,13 +363,30 @@ __device__ __forceinline__ void topk_stream(const TopkArgs& a, BEG&& begin, ELEM
     const bool more = u0 + ustep < a.B;
     if (more) fetch(u0 + ustep);
     begin(u0);
+    if constexpr (EXCL) {                 // bit (user, row) of this user tile's excluded items in the chunk
+      for (int idx = tid; idx < 16 * (kChunk / 32); idx += nthr) sX[idx] = 0;
+      __syncthreads();
+      for (int w = tid; w < 16 * 32; w += nthr) {
+        const int r = w >> 5, j = w & 31, u = u0 + r;
+        if (u < a.B) {
+          const int32_t* x = a.xs + (int64_t)u * a.xstride;
+          const int p1 = a.xoff[(int64_t)u * a.xchunks + chunk + 1].x;
+          for (int p = a.xoff[(int64_t)u * a.xchunks + chunk].x + j; p < p1; p += 32) {
+            const int rel = (int)(x[p] - i0);
+            atomicOr(&sX[r * (kChunk / 32) + (rel >> 5)], 1u << (rel & 31));
+          }
+        }
+      }
+      __syncthreads();
+    }
     const lds_f* hcur = sH + cur * 16 * DSi;
     const lds_f* fcur = sF + cur * 16;
     // items on the M side (a wave walks its row tiles four at a time: one hidden-state fragment, four independent
     // accumulator chains), the 16 users as the single column strip
     gemm_tiles<0>(nw, kChunk / 16, 1, DKi, Mat{sE, DSi}, MatT{hcur, DSi}, [&](int r, int c, float v) {
       if (srfrn) v += fcur[c];
-      const bool ok = r < n_here && !(a.exclude_pad && i0 + r == 0);
+      bool ok = r < n_here && !(a.exclude_pad && i0 + r == 0);
+      if constexpr (EXCL) ok = ok && !((sX[c * (kChunk / 32) + (r >> 5)] >> (r & 31)) & 1u);
       elem(u0, c, i0 + r, ok ? v : -INFINITY);
     });
     if (more) put(u0 + ustep, cur ^ 1);
@@ -303,6 +417,7 @@ constexpr int kChunk16 = 512;                   // most item rows of a chunk
 constexpr int kStageSlots16 = 13;               // staging registers per thread: a chunk's rows x copy elements per row <= 13 x 1024
 constexpr int kHS = 72;                         // bf16 row stride of an item row in LDS (64 + 8: rows 144 B apart)
 constexpr int kStream16Lds = 2 * kChunk16 * kHS * 2;
+constexpr int kStream16LdsX = kStream16Lds + 2 * 2 * kWaves16 * 64 * 4;     // + the EXCL item masks (NU <= 2): 160 KiB
 
 // begin(ut, user0) once per owned user tile; elem(ut, user0, item0, v) with the lane's four consecutive items of user user0 + li;
 // end(ut, user0, chunk) once per (user tile, chunk); need(chunk, user0[]) -> wave-uniform bool: false lets the wave skip the
@@ -313,7 +428,76 @@ constexpr int kStream16Lds = 2 * kChunk16 * kHS * 2;
 //   two barriers), and a logit takes the six products whose weight is above 2^-24 of the largest one - h1e1, h1e2, h2e1,
 //   h1e3, h2e2, h3e1 (smallest first) - twelve bf16 MFMAs per 16 x 16 tile against thirteen fp32 ones at twice the
 //   cycles each, with fp32-grade results (the dropped products are at the level of an fp32 rounding).
-template <int NU, bool SPLIT_E, class BEG, class ELEM, class END, class NEED>
+// user tile n of a wave: the hidden state of user user0 + li split into three exact bf16 fragments, and the SRFRN side term
+template <int NU>
+__device__ __forceinline__ void split_user16(const TopkArgs& a, int n, int user0, int li, int lq, bf16x8 (&bfr)[NU][3][2],
+                                             float (&fs)[NU]) {
+  const srfrd_layout& ly = a.ly;
+  const int di = ly.d_item, dout = ly.d_out, D = ly.D;
+  const int ub = min(user0 + li, a.B - 1);
+  const float* hrow = a.hidden + ((int64_t)ub * a.L + (a.L - 1)) * dout;
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    union { bf16x8 v; uint16_t h[8]; } t1, t2, t3;
+    float xv[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) xv[e] = hrow[min(32 * ks + 8 * lq + e, di - 1)];      // (clamped, unconditional: one round trip)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int k = 32 * ks + 8 * lq + e;
+      const float x = k < di ? xv[e] : 0.f;
+      const uint16_t h1 = f32_to_bf16(x);
+      const float r1 = x - bf16_to_f32(h1);
+      const uint16_t h2 = f32_to_bf16(r1);
+      const float r2 = r1 - bf16_to_f32(h2);
+      t1.h[e] = h1; t2.h[e] = h2; t3.h[e] = f32_to_bf16(r2);
+    }
+    bfr[n][0][ks] = t1.v; bfr[n][1][ks] = t2.v; bfr[n][2][ks] = t3.v;
+  }
+  float sacc = 0.f;
+  if (ly.kind == SRFRD_SRFRN) {
+    const int lab = clamp_id(a.user_label[ub], 2);
+    for (int c = di; c < D; ++c) sacc += hrow[c] * a.dense[ly.off_side + lab * ly.d_fake + (c - di)];
+  }
+  fs[n] = sacc;
+}
+
+// A fragments of one 16-item tile (NE bf16 planes) and the 16 x 16 (items x users) products of the NU user tiles: the
+// accumulation chains interleaved (independent chains back to back), smallest products first
+template <int NE>
+struct AF16 { bf16x8 f[NE][2]; };
+template <int NU, bool SPLIT_E>
+__device__ __forceinline__ void tile_mma16(const AF16<SPLIT_E ? 3 : 1>& af, const bf16x8 (&bfr)[NU][3][2], f32x4 (&acc)[NU]) {
+#pragma unroll
+  for (int n = 0; n < NU; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (SPLIT_E) {
+    constexpr int TH[6] = {2, 1, 0, 1, 0, 0}, TE[6] = {0, 1, 2, 0, 1, 0};
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+#pragma unroll
+      for (int n = 0; n < NU; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.f[TE[q]][0], bfr[n][TH[q]][0], acc[n], 0, 0, 0);
+#pragma unroll
+      for (int n = 0; n < NU; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.f[TE[q]][1], bfr[n][TH[q]][1], acc[n], 0, 0, 0);
+    }
+  } else {
+#pragma unroll
+    for (int tm = 2; tm >= 0; --tm) {
+#pragma unroll
+      for (int n = 0; n < NU; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.f[0][0], bfr[n][tm][0], acc[n], 0, 0, 0);
+#pragma unroll
+      for (int n = 0; n < NU; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.f[0][1], bfr[n][tm][1], acc[n], 0, 0, 0);
+    }
+  }
+}
+
+// EXCL: a lane's cursor into its user's sorted list - the position and the next excluded id relative to the chunk - lives
+// in LDS behind the item buffers (kStream16LdsX: the NU = 2 kernels have no register to spare for it), one slot pair per
+// (user tile, thread), read and written only by its own lane.  A chunk starts at xoff[u][chunk start] (prefetched with the
+// chunk's rows); ids at or past the chunk's end (the next chunk's, or the list's INT32_MAX sentinel) never match, so the
+// cursor needs no end.  A wave whose users have no id in the chunk (wave-uniform test) runs the unmasked epilogue;
+// otherwise each lane advances its cursor alongside its items (ascending in the tile index): one LDS read and one compare
+// per (user tile, item tile), plus one step per excluded id.
+template <int NU, bool SPLIT_E, bool EXCL = false, class BEG, class ELEM, class END, class NEED>
 __device__ __forceinline__ void topk_stream16(const TopkArgs& a, BEG&& begin, ELEM&& elem, END&& end, NEED&& need) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int NE = SPLIT_E ? 3 : 1;                  // bf16 planes of an item chunk
@@ -333,34 +517,46 @@ __device__ __forceinline__ void topk_stream16(const TopkArgs& a, BEG&& begin, EL
 #pragma unroll
   for (int n = 0; n < NU; ++n) {
     user0[n] = (group * kWaves16 * NU + n * kWaves16 + wave) << 4;
-    const int ub = min(user0[n] + li, a.B - 1);
-    const float* hrow = a.hidden + ((int64_t)ub * a.L + (a.L - 1)) * dout;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      union { bf16x8 v; uint16_t h[8]; } t1, t2, t3;
-      float xv[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) xv[e] = hrow[min(32 * ks + 8 * lq + e, di - 1)];      // (clamped, unconditional: one round trip)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int k = 32 * ks + 8 * lq + e;
-        const float x = k < di ? xv[e] : 0.f;
-        const uint16_t h1 = f32_to_bf16(x);
-        const float r1 = x - bf16_to_f32(h1);
-        const uint16_t h2 = f32_to_bf16(r1);
-        const float r2 = r1 - bf16_to_f32(h2);
-        t1.h[e] = h1; t2.h[e] = h2; t3.h[e] = f32_to_bf16(r2);
-      }
-      bfr[n][0][ks] = t1.v; bfr[n][1][ks] = t2.v; bfr[n][2][ks] = t3.v;
-    }
-    float sacc = 0.f;
-    if (srfrn) {
-      const int lab = clamp_id(a.user_label[ub], 2);
-      for (int c = di; c < D; ++c) sacc += hrow[c] * a.dense[ly.off_side + lab * ly.d_fake + (c - di)];
-    }
-    fs[n] = sacc;
+    split_user16<NU>(a, n, user0[n], li, lq, bfr, fs);
     begin(n, user0[n]);
   }
+  lds_u32* sXM = (lds_u32*)((char*)smem + kStream16Lds);     // EXCL: [NU][2][nthr] the lane's excluded-item bits
+  // the chunk's xoff entries, prefetched one chunk ahead: the wave's 16 x NU users need 2 x 16 x NU ints, one per lane
+  // (lane = component + 2 (n + NU user)), so the prefetch holds one register
+  int xpre = 0;
+  auto xload = [&](int chunk) {
+    const int c0 = chunk * a.crows >> 8;
+    const int comp = lane & 1, n = (lane >> 1) & (NU - 1), us = lane >> (NU == 2 ? 2 : 1);
+    const int u = (n == 0 ? user0[0] : user0[NU - 1]) + us;
+    xpre = comp ? INT32_MAX : 0;
+    if (us < 16 && u < a.B) xpre = reinterpret_cast<const int*>(a.xoff)[2 * ((int64_t)u * a.xchunks + c0) + comp];
+  };
+  // a 256-row chunk gives every lane 64 items (tile t, element e: bit 4 t + e); the lane walks its user's ids in the chunk
+  // (from the prefetched first one: usually none or one at C5 sizes) and keeps the ids of its own items.  -> wave-uniform
+  // "some user of this wave has an excluded id here".  Runs before the tile loop, where no accumulator is live.
+  auto xmask = [&](int chunk) {
+    const int i0c = (int)(a.item_lo + (int64_t)chunk * a.crows);
+    bool any = false;
+#pragma unroll
+    for (int n = 0; n < NU; ++n) {
+      const int src = 2 * (n + NU * li);
+      int pos = __shfl(xpre, src, 64);
+      int rel = __shfl(xpre, src + 1, 64) - i0c;        // (ids are >= the chunk start; the host keeps item_hi < 2^31 - 1024)
+      uint32_t w0 = 0, w1 = 0;
+      while (rel < a.crows) {                            // (the next chunk's ids and the INT32_MAX sentinel end the walk)
+        if (((rel >> 2) & 3) == lq) {
+          const int bit = ((rel >> 4) << 2) + (rel & 3);
+          if (bit < 32) w0 |= 1u << bit; else w1 |= 1u << (bit - 32);
+        }
+        ++pos;
+        rel = a.xs[(int64_t)(user0[n] + li) * a.xstride + pos] - i0c;
+      }
+      sXM[(n * 2 + 0) * nthr + tid] = w0;
+      sXM[(n * 2 + 1) * nthr + tid] = w1;
+      any |= (w0 | w1) != 0;
+    }
+    return __any(any) != 0;
+  };
   // ---- item chunks: table -> registers -> LDS; thread t owns copy elements t, t + nthr, ... of the chunk
   const bool dw = !SPLIT_E && (di & 1) == 0;           // bf16 rows that are whole dwords (d_item even): 4-byte copies
   const int rw = SPLIT_E ? di : (dw ? di >> 1 : di);   // copy elements per row
@@ -435,19 +631,27 @@ __device__ __forceinline__ void topk_stream16(const TopkArgs& a, BEG&& begin, EL
   __syncthreads();                       // (the zero fill above)
   if (chunk < a.n_chunks) { fetch(chunk); put(chunk, 0); }
   bool work = chunk < a.n_chunks ? need(chunk, user0) : false;
+  if constexpr (EXCL) {
+    if (chunk < a.n_chunks) xload(chunk);
+  }
   __syncthreads();
   for (; chunk < a.n_chunks; chunk += a.wg_per_group) {
     const int nxt = chunk + a.wg_per_group;
     if (nxt < a.n_chunks) fetch(nxt);
     const bool work_next = nxt < a.n_chunks ? need(nxt, user0) : false;      // (its loads land under this chunk's tiles)
     const int64_t i0 = a.item_lo + (int64_t)chunk * a.crows;
+    bool xdirty = false;
+    if constexpr (EXCL) {
+      xdirty = xmask(chunk);
+      if (nxt < a.n_chunks) xload(nxt);
+    }
     const int ntile = a.crows >> 4;
     // every row of the chunk is a rankable item (all chunks but the last one and, with exclude_pad, the one holding item 0):
     // the epilogue then has no per-element validity arithmetic - at 12 MFMAs per item tile it would cost more issue slots
     // than the MFMAs themselves
     const bool full = a.item_hi - i0 >= a.crows && !(a.exclude_pad && i0 == 0);
     const lds_u16* rowp = sE + ((SPLIT_E ? 0 : cur) * CH + li) * kHS + 8 * lq;
-    struct AF { bf16x8 f[NE][2]; };
+    using AF = AF16<NE>;
     auto tile_load = [&](int t) {
       AF r;
 #pragma unroll
@@ -457,30 +661,8 @@ __device__ __forceinline__ void topk_stream16(const TopkArgs& a, BEG&& begin, EL
       }
       return r;
     };
-    // the accumulation chains of the NU user tiles, interleaved (independent chains back to back), smallest products first
-    auto tile_mma = [&](const AF& af, f32x4 (&acc)[NU]) {
-#pragma unroll
-      for (int n = 0; n < NU; ++n) acc[n] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if constexpr (SPLIT_E) {
-        constexpr int TH[6] = {2, 1, 0, 1, 0, 0}, TE[6] = {0, 1, 2, 0, 1, 0};
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-#pragma unroll
-          for (int n = 0; n < NU; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.f[TE[q]][0], bfr[n][TH[q]][0], acc[n], 0, 0, 0);
-#pragma unroll
-          for (int n = 0; n < NU; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.f[TE[q]][1], bfr[n][TH[q]][1], acc[n], 0, 0, 0);
-        }
-      } else {
-#pragma unroll
-        for (int tm = 2; tm >= 0; --tm) {
-#pragma unroll
-          for (int n = 0; n < NU; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.f[0][0], bfr[n][tm][0], acc[n], 0, 0, 0);
-#pragma unroll
-          for (int n = 0; n < NU; ++n) acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af.f[0][1], bfr[n][tm][1], acc[n], 0, 0, 0);
-        }
-      }
-    };
-    auto tile_out = [&](int t, f32x4 (&acc)[NU], bool masked) {
+    auto tile_mma = [&](const AF& af, f32x4 (&acc)[NU]) { tile_mma16<NU, SPLIT_E>(af, bfr, acc); };
+    auto tile_out = [&](int t, f32x4 (&acc)[NU], bool masked, bool xm) {
       const int64_t item0 = i0 + (t << 4) + (lq << 2);
 #pragma unroll
       for (int n = 0; n < NU; ++n) {
@@ -493,31 +675,42 @@ __device__ __forceinline__ void topk_stream16(const TopkArgs& a, BEG&& begin, EL
             acc[n][e] = ok ? acc[n][e] : -INFINITY;
           }
         }
+        if constexpr (EXCL) {
+          if (xm) {                              // bits 4 (t & 7) .. + 3 of the lane's mask word t >> 3: its four items
+            const uint32_t w = sXM[(n * 2 + (t >> 3)) * nthr + tid] >> ((t & 7) << 2);
+            acc[n][0] = (w & 1u) ? -INFINITY : acc[n][0];
+            acc[n][1] = (w & 2u) ? -INFINITY : acc[n][1];
+            acc[n][2] = (w & 4u) ? -INFINITY : acc[n][2];
+            acc[n][3] = (w & 8u) ? -INFINITY : acc[n][3];
+          }
+        }
         elem(n, user0[n], item0, acc[n]);
       }
     };
     if (!work) {
       // nothing in this chunk can matter to this wave's users
-    } else if (full) {
+    } else if (full && !(EXCL && xdirty)) {
       // software-pipelined over the item tiles: the MFMAs of tile t are in flight while tile t - 1 leaves its accumulators
       // and the fragments of tile t + 1 arrive from LDS (two tiles per trip: the accumulator sets alternate statically)
       f32x4 accA[NU], accB[NU];
       tile_mma(tile_load(0), accA);
       for (int t = 1; t + 1 < ntile; t += 2) {
         tile_mma(tile_load(t), accB);
-        tile_out(t - 1, accA, false);
+        tile_out(t - 1, accA, false, false);
         tile_mma(tile_load(t + 1), accA);
-        tile_out(t, accB, false);
+        tile_out(t, accB, false, false);
       }
       // (ntile is even - 16 or 32: the loop leaves tile ntile - 2 in accA and tile ntile - 1 to do)
       tile_mma(tile_load(ntile - 1), accB);
-      tile_out(ntile - 2, accA, false);
-      tile_out(ntile - 1, accB, false);
+      tile_out(ntile - 2, accA, false, false);
+      tile_out(ntile - 1, accB, false, false);
     } else {
+      // (EXCL: also every chunk where a user of this wave has an excluded id - one accumulator set leaves the registers
+      // the mask needs; the pipelined form has none to spare at NU = 2)
       for (int t = 0; t < ntile; ++t) {
         f32x4 acc[NU];
         tile_mma(tile_load(t), acc);
-        tile_out(t, acc, true);
+        tile_out(t, acc, EXCL ? !full : true, EXCL && xdirty);
       }
     }
     if (work) {
@@ -544,11 +737,11 @@ __device__ __forceinline__ float vmax3(float x, float y, float z) {
   return r;
 }
 
-template <int NU, bool SPLIT_E>
+template <int NU, bool SPLIT_E, bool EXCL = false>
 __global__ void __launch_bounds__(kWaves16 * 64) topk_max16_kernel(const TopkArgs a) {
   const int lane = threadIdx.x & 63;
   float m[NU];
-  topk_stream16<NU, SPLIT_E>(a,
+  topk_stream16<NU, SPLIT_E, EXCL>(a,
       [&](int n, int) { m[n] = -INFINITY; },
       [&](int n, int, int64_t, const f32x4& v) { m[n] = vmax3(vmax3(m[n], v[0], v[1]), v[2], v[3]); },
       [&](int n, int u0, int chunk) {
@@ -596,10 +789,11 @@ __global__ void __launch_bounds__(kWaves16 * 64) topk_collect16_kernel(const Top
       });
 }
 
+template <bool EXCL = false>
 __global__ void __launch_bounds__(512) topk_max_kernel(const TopkArgs a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   float m = -INFINITY;                     // this lane's user column (lane & 15) over the row tiles of its wave
-  topk_stream(a,
+  topk_stream<EXCL>(a,
       [&](int) { m = -INFINITY; },
       [&](int, int, int64_t, float v) { m = fmaxf(m, v); },
       [&](int u0, int chunk, lds_f* sM) {
@@ -683,6 +877,20 @@ __global__ void __launch_bounds__(512) topk_collect_kernel(const TopkArgs a) {
       [&](int, int, lds_f*) {});
 }
 
+// Exclusion sets: the collection passes compare against a tau taken over unexcluded scores only, so at least k unexcluded
+// items are among a user's candidates; the excluded ones that also reach tau (rare: about as many as the user's excluded
+// items that would have made the top k) are dropped here, one wave per user, before the selection.  (Collecting them costs
+// candidate slots: a list they overflow arms the exhaustive path, which masks them itself.)
+__global__ void __launch_bounds__(256) topk_excl_filter_kernel(const TopkArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (b >= a.B) return;
+  Cand* c = a.cand + (int64_t)b * kCandMax;
+  const int n = min(a.ccnt[b], kCandMax);
+  for (int j = lane; j < n; j += 64)
+    if (excl_has(a, b, c[j].i)) c[j].i = -1;
+}
+
 __global__ void __launch_bounds__(256) topk_select_kernel(const TopkArgs a, int64_t* __restrict__ topk_idx,
                                                          float* __restrict__ topk_val) {
   const int lane = threadIdx.x & 63;
@@ -743,17 +951,21 @@ __device__ __forceinline__ void wave_select_topk(lds_f* sc, const int* ids, int 
   }
 }
 
+template <bool EXCL = false>
 __global__ void __launch_bounds__(256) topk_stage1_kernel(srfrd_layout ly, const void* __restrict__ table,
                                                          const float* __restrict__ dense, const float* __restrict__ hidden,
                                                          int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
                                                          const int64_t* __restrict__ user_label, int k, int n_chunks,
-                                                         Cand* __restrict__ ws, const int32_t* __restrict__ overflow) {
+                                                         Cand* __restrict__ ws, const int32_t* __restrict__ overflow,
+                                                         const int32_t* __restrict__ xs, const int2* __restrict__ xoff,
+                                                         int xstride, int xchunks) {
   if (*overflow == 0) return;                      // the threshold scheme succeeded: nothing to do
   TopkArgs a = {};
   a.ly = ly; a.table = table; a.dense = dense; a.hidden = hidden; a.user_label = user_label;
   a.B = B; a.L = L; a.exclude_pad = exclude_pad; a.k = k; a.n_chunks = n_chunks; a.user_splits = 1;
   a.item_lo = item_lo; a.item_hi = item_hi;
-  topk_tiles(a, [&](int u0, int chunk, int64_t i0, lds_f* sS, int SLD) {
+  a.xs = xs; a.xoff = xoff; a.xstride = xstride; a.xchunks = xchunks;
+  topk_tiles<EXCL>(a, [&](int u0, int chunk, int64_t i0, lds_f* sS, int SLD) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     for (int r = wave; r < 16; r += nw)
       if (u0 + r < B) {
@@ -799,6 +1011,170 @@ __global__ void __launch_bounds__(256) topk_stage2_kernel(const Cand* __restrict
     __threadfence_block();
     __builtin_amdgcn_wave_barrier();
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// target rank: rank[b] = #{i in [item_lo, item_hi), unexcluded, s(b, i) > s(b, t_b)}.  s_t comes from a pre-pass that runs
+// the ranking pass's own tile code (the same fragments, the same MFMA chain) over the 16-row block holding t_b, with user b
+// in its own lane, so a bit-identical copy of the target's row scores exactly s_t wherever it sits and is never counted.
+// The count pass is one streamed pass; every lane counts in a register and adds once per (user, workgroup).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t target_block(int64_t t, int64_t item_lo) {
+  const int64_t r = (t - item_lo) % 16;
+  return t - (r < 0 ? r + 16 : r);
+}
+
+// one wave per 16-user tile (bf16 matrix-core form): a.tau <- s_t, a.ccnt <- 0
+template <bool SPLIT_E>
+__global__ void __launch_bounds__(64) target_score16_kernel(const TopkArgs a, const int64_t* __restrict__ targets) {
+  constexpr int NE = SPLIT_E ? 3 : 1;
+  const int lane = threadIdx.x & 63, li = lane & 15, lq = lane >> 4;
+  const int u0 = blockIdx.x << 4;
+  const int di = a.ly.d_item, n_items = a.ly.n_items;
+  bf16x8 bfr[1][3][2];
+  float fs[1];
+  split_user16<1>(a, 0, u0, li, lq, bfr, fs);
+  for (int j = 0; j < 16 && u0 + j < a.B; ++j) {
+    const int u = u0 + j;
+    const int64_t t = clamp_id(targets[u], n_items);
+    const int64_t blk = target_block(t, a.item_lo);
+    const int off = (int)(t - blk);
+    const int64_t row = blk + li;
+    const bool rok = row >= 0 && row <= n_items;
+    AF16<NE> af;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      union { bf16x8 v; uint16_t h[8]; } p[NE];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int k = 32 * ks + 8 * lq + e;
+        const bool ok = rok && k < di;
+        if constexpr (SPLIT_E) {               // the three planes exactly as the staging of a chunk splits them
+          const float x = ok ? ((const float*)a.table)[row * di + k] : 0.f;
+          const uint16_t e1 = f32_to_bf16(x);
+          const float r1 = x - bf16_to_f32(e1);
+          const uint16_t e2 = f32_to_bf16(r1);
+          const float r2 = r1 - bf16_to_f32(e2);
+          p[0].h[e] = e1; p[1].h[e] = e2; p[2].h[e] = f32_to_bf16(r2);
+        } else {
+          p[0].h[e] = ok ? ((const uint16_t*)a.table)[row * di + k] : (uint16_t)0;
+        }
+      }
+#pragma unroll
+      for (int pl = 0; pl < NE; ++pl) af.f[pl][ks] = p[pl].v;
+    }
+    f32x4 acc[1];
+    tile_mma16<1, SPLIT_E>(af, bfr, acc);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[0][e] += fs[0];
+    const int ce = off & 3;
+    const float mine = ce == 0 ? acc[0][0] : ce == 1 ? acc[0][1] : ce == 2 ? acc[0][2] : acc[0][3];
+    const float st = __shfl(mine, j + 16 * (off >> 2), 64);      // element (item row off, user column j)
+    if (lane == 0) { a.tau[u] = st; a.ccnt[u] = 0; }
+  }
+}
+
+// the same for the fp32 matrix-core stream (topk_stream's tile code): one wave per 16-user tile
+__global__ void __launch_bounds__(64) target_score_kernel(const TopkArgs a, const int64_t* __restrict__ targets) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x;
+  const srfrd_layout& ly = a.ly;
+  const int di = ly.d_item, dout = ly.d_out, D = ly.D, n_items = ly.n_items;
+  const bool srfrn = ly.kind == SRFRD_SRFRN;
+  const int DKi = (di + 3) & ~3, DSi = DKi + 2;
+  lds_f* sE = (lds_f*)smem;
+  lds_f* sH = sE + 16 * DSi;
+  lds_f* sF = sH + 16 * DSi;
+  const int u0 = blockIdx.x << 4;
+  for (int idx = tid; idx < 16 * DSi; idx += blockDim.x) {
+    const int r = idx / DSi, c = idx - r * DSi;
+    sH[idx] = (u0 + r < a.B && c < di) ? a.hidden[((int64_t)(u0 + r) * a.L + (a.L - 1)) * dout + c] : 0.f;
+  }
+  if (tid < 16) {
+    float sacc = 0.f;
+    if (srfrn && u0 + tid < a.B) {
+      const int lab = clamp_id(a.user_label[u0 + tid], 2);
+      for (int c = di; c < D; ++c)
+        sacc += a.hidden[((int64_t)(u0 + tid) * a.L + (a.L - 1)) * dout + c] * a.dense[ly.off_side + lab * ly.d_fake + (c - di)];
+    }
+    sF[tid] = sacc;
+  }
+  for (int j = 0; j < 16 && u0 + j < a.B; ++j) {
+    const int u = u0 + j;
+    const int64_t t = clamp_id(targets[u], n_items);
+    const int64_t blk = target_block(t, a.item_lo);
+    const int off = (int)(t - blk);
+    __syncthreads();
+    for (int idx = tid; idx < 16 * DSi; idx += blockDim.x) {
+      const int r = idx / DSi, c = idx - r * DSi;
+      const int64_t row = blk + r;
+      float x = 0.f;
+      if (row >= 0 && row <= n_items && c < di)
+        x = ly.table_bf16 ? bf16_to_f32(((const uint16_t*)a.table)[row * di + c]) : ((const float*)a.table)[row * di + c];
+      sE[idx] = x;
+    }
+    __syncthreads();
+    gemm_tiles<0>(1, 1, 1, DKi, Mat{sE, DSi}, MatT{sH, DSi}, [&](int r, int c, float v) {
+      if (srfrn) v += sF[c];
+      if (r == off && c == j) { a.tau[u] = v; a.ccnt[u] = 0; }
+    });
+  }
+}
+
+template <int NU, bool SPLIT_E, bool EXCL>
+__global__ void __launch_bounds__(kWaves16 * 64) target_count16_kernel(const TopkArgs a) {
+  const int lane = threadIdx.x & 63, li = lane & 15;
+  float st[NU];
+  int cnt[NU];
+  topk_stream16<NU, SPLIT_E, EXCL>(a,
+      [&](int n, int u0) { st[n] = u0 + li < a.B ? a.tau[u0 + li] : INFINITY; cnt[n] = 0; },
+      [&](int n, int, int64_t, const f32x4& v) {
+        cnt[n] += (int)(v[0] > st[n]) + (int)(v[1] > st[n]) + (int)(v[2] > st[n]) + (int)(v[3] > st[n]);
+      },
+      [&](int, int, int) {},
+      [&](int, const int*) { return true; });
+#pragma unroll
+  for (int n = 0; n < NU; ++n) {
+    int c = cnt[n] + __shfl_xor(cnt[n], 16, 64);
+    c += __shfl_xor(c, 32, 64);
+    const int group = blockIdx.x / a.wg_per_group, wave = threadIdx.x >> 6;        // (topk_stream16's user tiles)
+    const int u = ((group * kWaves16 * NU + n * kWaves16 + wave) << 4) + li;
+    if (lane < 16 && u < a.B && c) atomicAdd(&a.ccnt[u], c);
+  }
+}
+
+template <bool EXCL>
+__global__ void __launch_bounds__(512) target_count_kernel(const TopkArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6, li = lane & 15;
+  float st = INFINITY;
+  int cnt = 0;
+  topk_stream<EXCL>(a,
+      [&](int u0) { st = u0 + li < a.B ? a.tau[u0 + li] : INFINITY; cnt = 0; },
+      [&](int, int, int64_t, float v) { cnt += (int)(v > st); },
+      [&](int u0, int, lds_f* sM) {
+        int c = cnt + __shfl_xor(cnt, 16, 64);
+        c += __shfl_xor(c, 32, 64);
+        if (lane < 16) sM[wave * 16 + lane] = __int_as_float(c);
+        __syncthreads();
+        if (threadIdx.x < 16 && u0 + (int)threadIdx.x < a.B) {
+          int tot = 0;
+          for (int w = 0; w < nw; ++w) tot += __float_as_int(sM[w * 16 + threadIdx.x]);
+          if (tot) atomicAdd(&a.ccnt[u0 + threadIdx.x], tot);
+        }
+      });
+}
+
+// HR@K / NDCG@K accumulation of the finished ranks (fp64, as srfrd_eval_rank)
+__global__ void __launch_bounds__(256) target_metric_kernel(const int32_t* __restrict__ rank, int B, int cut_k,
+                                                           double* __restrict__ metric_acc) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int r = rank[b];
+  if (r < cut_k) {
+    atomicAdd(&metric_acc[0], 1.0 / log2((double)r + 2.0));
+    atomicAdd(&metric_acc[1], 1.0);
+  }
+  atomicAdd(&metric_acc[2], 1.0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -942,31 +1318,184 @@ extern "C" int64_t srfrd_topk_workspace_bytes(int B, int k, int64_t n_rows) {
   return topk_off(B, k, n_chunks, 5);
 }
 
-extern "C" int srfrd_logits_topk(const srfrd_layout* lay, const void* item_table, const float* dense,
-                                 const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
-                                 const int64_t* user_label, int k, int64_t* topk_idx, float* topk_val, void* workspace,
-                                 void* stream) {
-  if (!lay || !item_table || !dense || !hidden || !topk_idx || !topk_val || !workspace) return SRFRD_E_ARG;
-  if (B <= 0 || L <= 0 || k <= 0 || k > 64 || item_lo < 0 || item_hi <= item_lo || item_hi > (int64_t)lay->n_items + 1) return SRFRD_E_ARG;
-  if (lay->D > SRFRD_MAX_D) return SRFRD_E_UNSUPPORTED;
+// exclusion sets of one launch: the pre-pass's outputs (null xs: no exclusion)
+struct ExclSet {
+  const int32_t* xs = nullptr;
+  const int2* xoff = nullptr;
+  int xstride = 0, xchunks = 0;
+};
+
+// excl workspace layout: [s_t B f32][xs B*xstride i32][xoff B*xchunks int2]
+static int excl_stride(int max_row) { return (max_row + 1 + 3) & ~3; }      // (+ the sentinel)
+static int64_t excl_off(int B, int max_row, int64_t n_rows, int which) {
+  const int64_t xchunks = (n_rows + 255) / 256 + 1;
+  const int64_t sizes[3] = {(int64_t)B * 4, (int64_t)B * excl_stride(max_row) * 4, (int64_t)B * xchunks * 8};
+  int64_t off = 0;
+  for (int i = 0; i < which; ++i) off += (sizes[i] + 255) & ~255ll;
+  return off;
+}
+
+extern "C" int64_t srfrd_excl_workspace_bytes(int B, int max_row, int64_t n_rows) {
+  if (B <= 0 || max_row < 0 || max_row > kExclCap || n_rows <= 0) return 0;
+  return excl_off(B, max_row, n_rows, 3);
+}
+
+// host-side checks of an exclusion CSR (no device reads) and the pre-pass launch
+static int excl_args(const int64_t* excl_ptr, const int32_t* excl_items, int max_row, const void* excl_ws) {
+  if (!excl_ptr) return 0;
+  if (!excl_items || !excl_ws || max_row < 0) return SRFRD_E_ARG;
+  if (max_row > kExclCap) return SRFRD_E_UNSUPPORTED;
+  return 0;
+}
+// what the masked passes' 32-bit cursor arithmetic covers (list positions, ids relative to a chunk start)
+static int excl_range(int B, int max_row, int64_t item_hi) {
+  if ((int64_t)B * excl_stride(max_row) >= INT32_MAX || item_hi >= (int64_t)INT32_MAX - 1024) return SRFRD_E_UNSUPPORTED;
+  return 0;
+}
+static ExclSet excl_prepare(const int64_t* excl_ptr, const int32_t* excl_items, int max_row, int B, int64_t item_lo,
+                            int64_t item_hi, void* excl_ws, hipStream_t st) {
+  ExclSet x;
+  if (!excl_ptr) return x;
+  const int64_t n_rows = item_hi - item_lo;
+  char* ws = (char*)excl_ws;
+  x.xstride = excl_stride(max_row);
+  x.xchunks = (int)((n_rows + 255) / 256 + 1);
+  int32_t* xs = (int32_t*)(ws + excl_off(B, max_row, n_rows, 1));
+  int2* xoff = (int2*)(ws + excl_off(B, max_row, n_rows, 2));
+  int P = 1;
+  while (P < max_row) P <<= 1;
+  // (the row is sorted in a kExclCap-entry LDS array: P <= kExclCap since max_row <= kExclCap)
+  hipLaunchKernelGGL(excl_prep_kernel, dim3(B), dim3(1024), 0, st, excl_ptr, excl_items, max_row, P, item_lo, item_hi, xs,
+                     x.xstride, xoff, x.xchunks);
+  x.xs = xs;
+  x.xoff = xoff;
+  return x;
+}
+
+// launch geometry of the bf16 matrix-core streams (users in registers, item chunks streamed through LDS)
+struct Plan16 {
+  bool on;
+  int nu;
+  dim3 grid;
+  TopkArgs h;
+};
+static int plan_stream16(const srfrd_layout* lay, const TopkArgs& a, int dev, Plan16& p, bool excl) {
+  const bool bf16_tab = lay->table_bf16 != 0;
+  p.on = getenv("SRFRD_TOPK_FP32") == nullptr &&
+         (bf16_tab ? (lay->d_item <= 64 && ((lay->d_item & 1) == 0 || lay->d_item <= 51)) : lay->d_item <= 52);
+  if (!p.on) return 0;
+  static std::mutex mu16;
+  static bool opted16[64] = {false};
+  {
+    std::lock_guard<std::mutex> lock(mu16);
+    if (!opted16[dev]) {
+      const void* fns[] = {(const void*)topk_max16_kernel<1, false>, (const void*)topk_max16_kernel<2, false>,
+                           (const void*)topk_collect16_kernel<1, false>, (const void*)topk_collect16_kernel<2, false>,
+                           (const void*)topk_max16_kernel<1, true>, (const void*)topk_max16_kernel<2, true>,
+                           (const void*)topk_collect16_kernel<1, true>, (const void*)topk_collect16_kernel<2, true>,
+                           (const void*)target_count16_kernel<1, false, false>, (const void*)target_count16_kernel<2, false, false>,
+                           (const void*)target_count16_kernel<1, true, false>, (const void*)target_count16_kernel<2, true, false>};
+      const void* fns_x[] = {(const void*)topk_max16_kernel<1, false, true>, (const void*)topk_max16_kernel<1, true, true>,
+                             (const void*)target_count16_kernel<1, false, true>, (const void*)target_count16_kernel<1, true, true>};
+      for (const void* fn : fns)
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kStream16Lds) != hipSuccess) return SRFRD_E_DEVICE;
+      for (const void* fn : fns_x)
+        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kStream16LdsX) != hipSuccess) return SRFRD_E_DEVICE;
+      opted16[dev] = true;
+    }
+  }
+  hipDeviceProp_t prop;
+  static int cu_cached[64] = {0};
+  if (cu_cached[dev] == 0) cu_cached[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+  const int cu = cu_cached[dev];
+  const int64_t n_rows = a.item_hi - a.item_lo;
+  const int user_tiles = (a.B + 15) / 16;
+  int nu = user_tiles > kWaves16 ? 2 : 1;
+  int groups = (user_tiles + kWaves16 * nu - 1) / (kWaves16 * nu);
+  int crows = bf16_tab ? kChunk16 : 256;
+  if ((lay->d_item & 1) != 0 || ((n_rows + crows - 1) / crows) * groups < 2 * (int64_t)cu) crows = 256;
+  if (excl) {
+    // the masked forms keep 64 item bits per lane and user tile (256-row chunks) and run one user tile per wave: at two the
+    // kernel needs more than the 128 VGPRs a 1024-thread workgroup allows and spills in the tile loop
+    crows = 256;
+    nu = 1;
+    groups = (user_tiles + kWaves16 - 1) / kWaves16;
+  }
+  // a chunk is staged through kStageSlots16 registers per thread: rows x copy elements per row must fit them (a 512-row
+  // chunk of a bf16 table does up to d_item 52; wider rows take 256-row chunks - rows beyond the slots would never be copied)
+  const int64_t copy_w = bf16_tab ? ((lay->d_item & 1) == 0 ? lay->d_item >> 1 : lay->d_item) : lay->d_item;
+  if ((int64_t)crows * copy_w > (int64_t)kStageSlots16 * kWaves16 * 64) crows = 256;
+  if ((int64_t)crows * copy_w > (int64_t)kStageSlots16 * kWaves16 * 64) return SRFRD_E_UNSUPPORTED;
+  int64_t nch = (n_rows + crows - 1) / crows;
+  if (nch * groups < cu && nu == 2) { nu = 1; groups = (user_tiles + kWaves16 - 1) / kWaves16; }
+  int per_group = cu / groups < 1 ? 1 : cu / groups;
+  if (per_group > nch) per_group = (int)nch;
+  p.h = a;
+  p.h.n_chunks = (int)nch;
+  p.h.crows = crows;
+  p.h.wg_per_group = per_group;
+  p.nu = nu;
+  p.grid = dim3(groups * per_group);
+  return 0;
+}
+
+// one launch of a stream16 kernel template at the plan's (NU, SPLIT_E); LDS = kStream16Lds, or kStream16LdsX for EXCL forms
+// SRFRD_L16X: the masked (EXCL) forms, which the plan always gives one user tile per wave
+#define SRFRD_L16X(P, KERNEL) do { \
+    const dim3 blk16(kWaves16 * 64); \
+    if ((P).h.ly.table_bf16) hipLaunchKernelGGL((KERNEL<1, false, true>), (P).grid, blk16, kStream16LdsX, st, (P).h); \
+    else hipLaunchKernelGGL((KERNEL<1, true, true>), (P).grid, blk16, kStream16LdsX, st, (P).h); } while (0)
+#define SRFRD_L16(P, LDS, KERNEL, ...) do { \
+    const dim3 blk16(kWaves16 * 64); \
+    if ((P).h.ly.table_bf16) { if ((P).nu == 2) hipLaunchKernelGGL((KERNEL<2, false __VA_ARGS__>), (P).grid, blk16, LDS, st, (P).h); \
+                               else hipLaunchKernelGGL((KERNEL<1, false __VA_ARGS__>), (P).grid, blk16, LDS, st, (P).h); } \
+    else { if ((P).nu == 2) hipLaunchKernelGGL((KERNEL<2, true __VA_ARGS__>), (P).grid, blk16, LDS, st, (P).h); \
+           else hipLaunchKernelGGL((KERNEL<1, true __VA_ARGS__>), (P).grid, blk16, LDS, st, (P).h); } } while (0)
+
+static int topk_args_check(const srfrd_layout* lay, const void* item_table, const float* dense, const float* hidden, int B, int L,
+                           int64_t item_lo, int64_t item_hi, const int64_t* user_label) {
+  if (!lay || !item_table || !dense || !hidden) return SRFRD_E_ARG;
+  if (B <= 0 || L <= 0 || item_lo < 0 || item_hi <= item_lo || item_hi > (int64_t)lay->n_items + 1) return SRFRD_E_ARG;
+  if (lay->D > SRFRD_MAX_D) return SRFRD_E_UNSUPPORTED;           // (srfrd_logits_topk's order of checks)
   if (lay->kind == SRFRD_SRFRN && !user_label) return SRFRD_E_ARG;
+  return 0;
+}
+
+// the four-launch threshold scheme (+ the armed exhaustive path); ex.xs != null runs the masked instantiations
+static int logits_topk_impl(const srfrd_layout* lay, const void* item_table, const float* dense,
+                            const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
+                            const int64_t* user_label, int k, int64_t* topk_idx, float* topk_val, void* workspace,
+                            const ExclSet& ex, hipStream_t st) {
+  if (lay->D > SRFRD_MAX_D) return SRFRD_E_UNSUPPORTED;
+  const bool excl = ex.xs != nullptr;
   const int n_chunks = (int)((item_hi - item_lo + kChunk - 1) / kChunk);
   const int DSi = ((lay->d_item + 3) & ~3) + 2;
   const size_t lds = ((size_t)kChunk * DSi + 16 * DSi + 16 * (kChunk + 2) + 16 + kSlack) * sizeof(float);
   if (lds > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
   const size_t lds_stream = ((size_t)kChunk * DSi + 2 * 16 * DSi + 32 + 8 * 16 + kSlack) * sizeof(float);   // topk_stream
+  const size_t lds_stream_x = lds_stream + 16 * (kChunk / 32) * sizeof(uint32_t);                          // + EXCL bits
+  if (excl && lds_stream_x > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
   static std::mutex attr_mu;
-  static size_t attr_dev[64] = {0};
+  static size_t attr_dev[64] = {0}, attr_dev_x[64] = {0};
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SRFRD_E_DEVICE;
-  std::lock_guard<std::mutex> attr_lock(attr_mu);
-  size_t& s_attr = attr_dev[dev];
-  if (lds > s_attr) {
-    if (hipFuncSetAttribute((const void*)topk_stage1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-        hipFuncSetAttribute((const void*)topk_max_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stream) != hipSuccess ||
-        hipFuncSetAttribute((const void*)topk_collect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stream) != hipSuccess)
-      return SRFRD_E_DEVICE;
-    s_attr = lds;
+  {
+    std::lock_guard<std::mutex> attr_lock(attr_mu);
+    size_t& s_attr = attr_dev[dev];
+    if (lds > s_attr) {
+      if (hipFuncSetAttribute((const void*)topk_stage1_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+          hipFuncSetAttribute((const void*)topk_max_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stream) != hipSuccess ||
+          hipFuncSetAttribute((const void*)topk_collect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stream) != hipSuccess)
+        return SRFRD_E_DEVICE;
+      s_attr = lds;
+    }
+    size_t& x_attr = attr_dev_x[dev];
+    if (excl && lds > x_attr) {
+      if (hipFuncSetAttribute((const void*)topk_stage1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+          hipFuncSetAttribute((const void*)topk_max_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stream_x) != hipSuccess)
+        return SRFRD_E_DEVICE;
+      x_attr = lds;
+    }
   }
   char* ws = (char*)workspace;
   TopkArgs a = {};
@@ -977,6 +1506,7 @@ extern "C" int srfrd_logits_topk(const srfrd_layout* lay, const void* item_table
   a.tau = (float*)(ws + topk_off(B, k, n_chunks, 1));
   a.ccnt = (int32_t*)(ws + topk_off(B, k, n_chunks, 2));
   a.cand = (Cand*)(ws + topk_off(B, k, n_chunks, 3));
+  a.xs = ex.xs; a.xoff = ex.xoff; a.xstride = ex.xstride; a.xchunks = ex.xchunks;
   Cand* fb = (Cand*)(ws + topk_off(B, k, n_chunks, 4));
   const int user_tiles = (B + 15) / 16;
   // user tiles are split over `splits` workgroups per chunk.  Each workgroup re-stages its chunk (~7 user tiles' worth of
@@ -992,74 +1522,127 @@ extern "C" int srfrd_logits_topk(const srfrd_layout* lay, const void* item_table
     if (cost < best) { best = cost; splits = sp; }
   }
   a.user_splits = splits;
-  hipStream_t st = (hipStream_t)stream;
-  const bool bf16_tab = lay->table_bf16 != 0;
-  const bool stream16 = getenv("SRFRD_TOPK_FP32") == nullptr &&
-                        (bf16_tab ? (lay->d_item <= 64 && ((lay->d_item & 1) == 0 || lay->d_item <= 51)) : lay->d_item <= 52);
-  if (stream16) {
-    // the two threshold passes on the bf16 matrix cores (users in registers, item chunks streamed through LDS): a bf16
-    // table as it is, an fp32 table split into three exact bf16 planes while it is staged.  The chunk-maxima array is walked
-    // with this path's chunk count, everything else (tau, candidate lists, selection, the armed exhaustive path with its own
-    // 256-item chunks) is shared
-    static std::mutex mu16;
-    static bool opted16[64] = {false};
-    {
-      std::lock_guard<std::mutex> lock(mu16);
-      if (!opted16[dev]) {
-        const void* fns[8] = {(const void*)topk_max16_kernel<1, false>, (const void*)topk_max16_kernel<2, false>,
-                              (const void*)topk_collect16_kernel<1, false>, (const void*)topk_collect16_kernel<2, false>,
-                              (const void*)topk_max16_kernel<1, true>, (const void*)topk_max16_kernel<2, true>,
-                              (const void*)topk_collect16_kernel<1, true>, (const void*)topk_collect16_kernel<2, true>};
-        for (const void* fn : fns)
-          if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kStream16Lds) != hipSuccess) return SRFRD_E_DEVICE;
-        opted16[dev] = true;
-      }
-    }
-    hipDeviceProp_t prop;
-    static int cu_cached[64] = {0};
-    if (cu_cached[dev] == 0) cu_cached[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    const int cu = cu_cached[dev];
-    const int64_t n_rows = item_hi - item_lo;
-    int nu = user_tiles > kWaves16 ? 2 : 1;
-    int groups = (user_tiles + kWaves16 * nu - 1) / (kWaves16 * nu);
-    int crows = bf16_tab ? kChunk16 : 256;
-    if ((lay->d_item & 1) != 0 || ((n_rows + crows - 1) / crows) * groups < 2 * (int64_t)cu) crows = 256;
-    // a chunk is staged through kStageSlots16 registers per thread: rows x copy elements per row must fit them (a 512-row
-    // chunk of a bf16 table does up to d_item 52; wider rows take 256-row chunks - rows beyond the slots would never be copied)
-    const int64_t copy_w = bf16_tab ? ((lay->d_item & 1) == 0 ? lay->d_item >> 1 : lay->d_item) : lay->d_item;
-    if ((int64_t)crows * copy_w > (int64_t)kStageSlots16 * kWaves16 * 64) crows = 256;
-    if ((int64_t)crows * copy_w > (int64_t)kStageSlots16 * kWaves16 * 64) return SRFRD_E_UNSUPPORTED;
-    int64_t nch = (n_rows + crows - 1) / crows;
-    if (nch * groups < cu && nu == 2) { nu = 1; groups = (user_tiles + kWaves16 - 1) / kWaves16; }
-    int per_group = cu / groups < 1 ? 1 : cu / groups;
-    if (per_group > nch) per_group = (int)nch;
-    TopkArgs h = a;
-    h.n_chunks = (int)nch;
-    h.crows = crows;
-    h.wg_per_group = per_group;
-    const dim3 grid16(groups * per_group), blk16(kWaves16 * 64);
-#define SRFRD_L16(KERNEL) do { \
-      if (bf16_tab) { if (nu == 2) hipLaunchKernelGGL((KERNEL<2, false>), grid16, blk16, kStream16Lds, st, h); \
-                      else hipLaunchKernelGGL((KERNEL<1, false>), grid16, blk16, kStream16Lds, st, h); } \
-      else { if (nu == 2) hipLaunchKernelGGL((KERNEL<2, true>), grid16, blk16, kStream16Lds, st, h); \
-             else hipLaunchKernelGGL((KERNEL<1, true>), grid16, blk16, kStream16Lds, st, h); } } while (0)
-    SRFRD_L16(topk_max16_kernel);
-    if (int trc = launch_tau(h, st)) return trc;
-    SRFRD_L16(topk_collect16_kernel);
-#undef SRFRD_L16
+  Plan16 p;
+  if (int rc = plan_stream16(lay, a, dev, p, excl)) return rc;
+  if (p.on) {
+    // the two threshold passes on the bf16 matrix cores: a bf16 table as it is, an fp32 table split into three exact bf16
+    // planes while it is staged.  The chunk-maxima array is walked with this path's chunk count, everything else (tau,
+    // candidate lists, selection, the armed exhaustive path with its own 256-item chunks) is shared
+    if (excl) SRFRD_L16X(p, topk_max16_kernel);
+    else SRFRD_L16(p, kStream16Lds, topk_max16_kernel, );
+    if (int trc = launch_tau(p.h, st)) return trc;
+    SRFRD_L16(p, kStream16Lds, topk_collect16_kernel, );
+  } else if (excl) {
+    hipLaunchKernelGGL(topk_max_kernel<true>, dim3(n_chunks * splits), dim3(512), lds_stream_x, st, a);
+    if (int trc = launch_tau(a, st)) return trc;
+    hipLaunchKernelGGL(topk_collect_kernel, dim3(n_chunks * splits), dim3(512), lds_stream, st, a);
   } else {
-    hipLaunchKernelGGL(topk_max_kernel, dim3(n_chunks * splits), dim3(512), lds_stream, st, a);
+    hipLaunchKernelGGL(topk_max_kernel<false>, dim3(n_chunks * splits), dim3(512), lds_stream, st, a);
     if (int trc = launch_tau(a, st)) return trc;
     hipLaunchKernelGGL(topk_collect_kernel, dim3(n_chunks * splits), dim3(512), lds_stream, st, a);
   }
+  if (excl) hipLaunchKernelGGL(topk_excl_filter_kernel, dim3((B + 3) / 4), dim3(256), 0, st, a);
   hipLaunchKernelGGL(topk_select_kernel, dim3((B + 3) / 4), dim3(256), 0, st, a, topk_idx, topk_val);
   // exhaustive path, armed only if a candidate list overflowed (device-side flag: no host synchronisation)
-  hipLaunchKernelGGL(topk_stage1_kernel, dim3(n_chunks), dim3(256), lds, st, *lay, item_table, dense, hidden, B, L, item_lo,
-                     item_hi, exclude_pad, user_label, k, n_chunks, fb, (const int32_t*)(a.ccnt + B));
+  if (excl)
+    hipLaunchKernelGGL(topk_stage1_kernel<true>, dim3(n_chunks), dim3(256), lds, st, *lay, item_table, dense, hidden, B, L, item_lo,
+                       item_hi, exclude_pad, user_label, k, n_chunks, fb, (const int32_t*)(a.ccnt + B), ex.xs, ex.xoff, ex.xstride,
+                       ex.xchunks);
+  else
+    hipLaunchKernelGGL(topk_stage1_kernel<false>, dim3(n_chunks), dim3(256), lds, st, *lay, item_table, dense, hidden, B, L, item_lo,
+                       item_hi, exclude_pad, user_label, k, n_chunks, fb, (const int32_t*)(a.ccnt + B), nullptr, nullptr, 0, 0);
   hipLaunchKernelGGL(topk_stage2_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const Cand*)fb, B, k, n_chunks, topk_idx,
                      topk_val, (const int32_t*)(a.ccnt + B));
   return (int)hipGetLastError();
 }
+
+extern "C" int srfrd_logits_topk(const srfrd_layout* lay, const void* item_table, const float* dense,
+                                 const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
+                                 const int64_t* user_label, int k, int64_t* topk_idx, float* topk_val, void* workspace,
+                                 void* stream) {
+  if (!topk_idx || !topk_val || !workspace || k <= 0 || k > 64) return SRFRD_E_ARG;
+  if (int rc = topk_args_check(lay, item_table, dense, hidden, B, L, item_lo, item_hi, user_label)) return rc;
+  return logits_topk_impl(lay, item_table, dense, hidden, B, L, item_lo, item_hi, exclude_pad, user_label, k, topk_idx, topk_val,
+                          workspace, ExclSet{}, (hipStream_t)stream);
+}
+
+extern "C" int srfrd_logits_topk_excl(const srfrd_layout* lay, const void* item_table, const float* dense,
+                                      const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
+                                      const int64_t* user_label, int k, const int64_t* excl_ptr, const int32_t* excl_items,
+                                      int max_row, int64_t* topk_idx, float* topk_val, void* workspace, void* excl_workspace,
+                                      void* stream) {
+  if (!topk_idx || !topk_val || !workspace || k <= 0 || k > 64) return SRFRD_E_ARG;
+  if (int rc = topk_args_check(lay, item_table, dense, hidden, B, L, item_lo, item_hi, user_label)) return rc;
+  if (int rc = excl_args(excl_ptr, excl_items, max_row, excl_workspace)) return rc;
+  if (excl_ptr)
+    if (int rc = excl_range(B, max_row, item_hi)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const ExclSet ex = excl_prepare(excl_ptr, excl_items, max_row, B, item_lo, item_hi, excl_workspace, st);
+  return logits_topk_impl(lay, item_table, dense, hidden, B, L, item_lo, item_hi, exclude_pad, user_label, k, topk_idx, topk_val,
+                          workspace, ex, st);
+}
+
+extern "C" int srfrd_target_rank(const srfrd_layout* lay, const void* item_table, const float* dense, const float* hidden,
+                                 int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad, const int64_t* user_label,
+                                 const int64_t* targets, const int64_t* excl_ptr, const int32_t* excl_items, int max_row,
+                                 int cut_k, int32_t* rank, double* metric_acc, void* workspace, void* stream) {
+  if (!targets || !rank || !workspace || cut_k <= 0) return SRFRD_E_ARG;
+  if (int rc = topk_args_check(lay, item_table, dense, hidden, B, L, item_lo, item_hi, user_label)) return rc;
+  if (excl_ptr && (!excl_items || max_row < 0)) return SRFRD_E_ARG;
+  if (excl_ptr && max_row > kExclCap) return SRFRD_E_UNSUPPORTED;
+  if (excl_ptr)
+    if (int rc = excl_range(B, max_row, item_hi)) return rc;
+  const int DSi = ((lay->d_item + 3) & ~3) + 2;
+  const size_t lds_stream = ((size_t)kChunk * DSi + 2 * 16 * DSi + 32 + 8 * 16 + kSlack) * sizeof(float);
+  const size_t lds_stream_x = lds_stream + 16 * (kChunk / 32) * sizeof(uint32_t);
+  if (lds_stream_x > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
+  const size_t lds_score = ((size_t)2 * 16 * DSi + 16 + kSlack) * sizeof(float);
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SRFRD_E_DEVICE;
+  {
+    static std::mutex mu;
+    static bool opted[64] = {false};
+    std::lock_guard<std::mutex> lock(mu);
+    if (!opted[dev]) {
+      if (hipFuncSetAttribute((const void*)target_count_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit) != hipSuccess ||
+          hipFuncSetAttribute((const void*)target_count_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit) != hipSuccess)
+        return SRFRD_E_DEVICE;
+      opted[dev] = true;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const ExclSet ex = excl_prepare(excl_ptr, excl_items, max_row, B, item_lo, item_hi, workspace, st);
+  TopkArgs a = {};
+  a.ly = *lay; a.table = item_table; a.dense = dense; a.hidden = hidden; a.user_label = user_label;
+  a.B = B; a.L = L; a.exclude_pad = exclude_pad; a.k = 1;
+  a.item_lo = item_lo; a.item_hi = item_hi;
+  a.n_chunks = (int)((item_hi - item_lo + kChunk - 1) / kChunk);
+  a.user_splits = 1;
+  a.tau = (float*)workspace;                     // s_t
+  a.ccnt = rank;
+  a.xs = ex.xs; a.xoff = ex.xoff; a.xstride = ex.xstride; a.xchunks = ex.xchunks;
+  const bool excl = ex.xs != nullptr;
+  Plan16 p;
+  if (int rc = plan_stream16(lay, a, dev, p, excl)) return rc;
+  const dim3 tiles((B + 15) / 16);
+  if (p.on) {
+    if (lay->table_bf16) hipLaunchKernelGGL(target_score16_kernel<false>, tiles, dim3(64), 0, st, a, targets);
+    else hipLaunchKernelGGL(target_score16_kernel<true>, tiles, dim3(64), 0, st, a, targets);
+    if (excl) SRFRD_L16X(p, target_count16_kernel);
+    else SRFRD_L16(p, kStream16Lds, target_count16_kernel, , false);
+  } else {
+    hipLaunchKernelGGL(target_score_kernel, tiles, dim3(64), lds_score, st, a, targets);
+    // (one user tile per workgroup and chunk: the count needs no split heuristics - the pass reads every chunk once per tile)
+    a.user_splits = (B + 15) / 16 < 8 ? (B + 15) / 16 : 8;
+    if (excl) hipLaunchKernelGGL(target_count_kernel<true>, dim3(a.n_chunks * a.user_splits), dim3(512), lds_stream_x, st, a);
+    else hipLaunchKernelGGL(target_count_kernel<false>, dim3(a.n_chunks * a.user_splits), dim3(512), lds_stream, st, a);
+  }
+  if (metric_acc)
+    hipLaunchKernelGGL(target_metric_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const int32_t*)rank, B, cut_k, metric_acc);
+  return (int)hipGetLastError();
+}
+#undef SRFRD_L16
+#undef SRFRD_L16X
 
 extern "C" int srfrd_topk_merge(const int64_t* cand_idx, const float* cand_val, int B, int n_cand, int k, int64_t* topk_idx,
                                 float* topk_val, void* stream) {

@@ -128,20 +128,37 @@ def window_labels(rsq: torch.Tensor):
 
 @torch.no_grad()
 def evaluation(model, data: InteractionData, maxlen: int, batch: int = 2048, n_neg: int = 100, seed: int = 0,
-               max_users: int = 10000, with_labels: bool = False, candidates=None):
+               max_users: int = 10000, with_labels: bool = False, candidates=None, full_catalog: bool = False, k: int = 10):
     """``evaluation`` (NDCG@10, HR@10) - and with ``with_labels`` the per-label breakdowns of ``evaluation_with_label``
-    (utils.py:628-752) as {label: [HR, NDCG, count]} dicts - batched on the GPU.  ``candidates``: see eval_inputs."""
+    (utils.py:628-752) as {label: [HR, NDCG, count]} dicts - batched on the GPU.  ``candidates``: see eval_inputs.
+    ``full_catalog``: "full-sort" (NDCG@k, HR@k) instead - the held-out item ranked against every item outside
+    ``set(train[u]) | {0}`` (srfrd::target_rank with the user's training items as its exclusion set); the sampled form
+    (the default) always reports @10.  A user with more than ``_lib.EXCL_CAP`` (4096) distinct training items makes the
+    full-catalog form raise (SRFRD_E_UNSUPPORTED)."""
     from .evaluate import ranks_from_logits
     users = np.arange(1, data.usernum + 1)
     if data.usernum > max_users:                             # utils.py:551-552
         users = np.random.RandomState(seed).choice(users, max_users, replace=False)
-    uid, seq, rsq, cand = eval_inputs(data, maxlen, n_neg, seed, users, candidates)
+    uid, seq, rsq, cand = eval_inputs(data, maxlen, 0 if full_catalog else n_neg, seed, users, None if full_catalog else candidates)
     dev = next(model.parameters()).device
     was = model.training
     model.eval()
     ranks = []
     for s in range(0, uid.numel(), batch):
         sl = slice(s, s + batch)
+        if full_catalog:
+            u = uid[sl].numpy()
+            lo, hi = data.train_ptr[u], data.train_ptr[u + 1]
+            # each row deduplicated (a training history may repeat items); a user with more than EXCL_CAP distinct
+            # training items cannot be masked by the kernels and raises (SRFRD_E_UNSUPPORTED) instead of ranking wrongly
+            xrows = [np.unique(data.train_items[a:b]) for a, b in zip(lo, hi)]
+            xptr = np.zeros(u.size + 1, np.int64)
+            np.cumsum([r.size for r in xrows], out=xptr[1:])
+            xitems = np.concatenate(xrows) if xrows else np.zeros(0, np.int32)
+            r = model.target_rank(uid[sl].to(dev), seq[sl].to(dev), rsq[sl].to(dev), cand[sl, 0].to(dev),
+                                  exclude=(torch.from_numpy(xptr), torch.from_numpy(xitems.astype(np.int32))))
+            ranks.append(r.cpu().long())
+            continue
         logits = model.predict(uid[sl].to(dev), seq[sl].to(dev), rsq[sl].to(dev), cand[sl].to(dev))
         if logits.dim() == 1:
             logits = logits.unsqueeze(0)
@@ -150,7 +167,7 @@ def evaluation(model, data: InteractionData, maxlen: int, batch: int = 2048, n_n
     if hasattr(model, "check_ids"):
         model.check_ids()                                    # an out-of-table id anywhere above raises here
     rank = torch.cat(ranks)
-    hit = rank < 10
+    hit = rank < (k if full_catalog else 10)
     ndcg_u = torch.where(hit, 1.0 / torch.log2(rank.double() + 2.0), torch.zeros((), dtype=torch.float64))
     ndcg, hr = float(ndcg_u.mean()), float(hit.double().mean())
     if not with_labels:

@@ -493,16 +493,40 @@ class _SRFRDBase(nn.Module):
                 self.check_ids()
         return torch.ops.srfrd.predict_logits(hidden.contiguous(), cand.contiguous(), ulab, ops.register_model(self))
 
-    def topk(self, user_ids, input_ids, fake_ids, k=10, exclude_pad=True, item_range=None):
-        """Full-catalog ranking: (indices int64 (B,k), scores (B,k)); the (B, I) logits never reach HBM."""
+    def topk(self, user_ids, input_ids, fake_ids, k=10, exclude_pad=True, item_range=None, exclude=None):
+        """Full-catalog ranking: (indices int64 (B,k), scores (B,k)); the (B, I) logits never reach HBM.
+        ``exclude``: items never to return, per user - None, "input" (the ids of the user's input window), a (ptr, items)
+        CSR tuple over the batch, or a list of B 1-D tensors.  Fewer than k rankable items leave trailing -1 / -inf slots."""
         with torch.no_grad():
             ids = self._prep(input_ids, fake_ids, None, None, None, None)
             hidden = self._launch_fwd_last(ids[0], ids[1])
         lay = self.layout
         lo, hi = item_range if item_range is not None else (0, lay.n_items + 1)
         ulab = self.user_labels(ids[1]) if self._kind == "SRFRN" else None
-        idx, val = torch.ops.srfrd.logits_topk(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad))
+        if exclude is None:
+            idx, val = torch.ops.srfrd.logits_topk(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad))
+        else:
+            xp, xi, mr = ops.excl_csr(exclude, ids[0], hidden.shape[0], hidden.device)
+            idx, val = torch.ops.srfrd.logits_topk_excl(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad),
+                                                        xp, xi, mr)
         return idx, val
+
+    def target_rank(self, user_ids, input_ids, fake_ids, targets, exclude=None, item_range=None, exclude_pad=True):
+        """Full-catalog rank of ``targets`` (B,): int32 (B,) counts of the items in ``item_range`` (default: the whole
+        catalog) that score strictly higher than the user's target, skipping the ``exclude`` set (as in ``topk``) and,
+        with ``exclude_pad``, item 0.  The target itself is ranked even when it is excluded; ranks over disjoint item
+        ranges add up.  ``rank < K`` is a hit at K; NDCG@K = 1 / log2(rank + 2)."""
+        with torch.no_grad():
+            ids = self._prep(input_ids, fake_ids, None, None, None, None)
+            hidden = self._launch_fwd_last(ids[0], ids[1])
+        lay = self.layout
+        lo, hi = item_range if item_range is not None else (0, lay.n_items + 1)
+        ulab = self.user_labels(ids[1]) if self._kind == "SRFRN" else None
+        tg = _ids(targets, hidden.device).reshape(-1)
+        if tg.numel() != hidden.shape[0]:
+            raise ValueError("targets must hold one item id per user")
+        xp, xi, mr = ops.excl_csr(exclude, ids[0], hidden.shape[0], hidden.device)
+        return torch.ops.srfrd.target_rank(hidden, ulab, tg, ops.register_model(self), lo, hi, bool(exclude_pad), xp, xi, mr)
 
 
 class SRFR(_SRFRDBase):

@@ -9,6 +9,8 @@ backward - instead of being an opaque ctypes call from Python:
     srfrd::encoder_bwd     the fused backward (reference trainer.py:40)
     srfrd::predict_logits  candidate logits of predict() (SRFR_model.py:144-152 and twins)
     srfrd::logits_topk     full-catalog top-k over an item range, logits never in HBM
+    srfrd::logits_topk_excl  the same with a per-user exclusion set (CSR over the batch) masked inside the ranking passes
+    srfrd::target_rank     full-catalog rank of a target item per user (strictly-greater count), exclusion set optional
     srfrd::topk_merge      merge of per-shard top-k lists
     srfrd::user_labels     get_Labels (SRFR_model.py:546-570)
     srfrd::eval_rank       rank of candidate 0 (utils.py:589-597)
@@ -186,6 +188,94 @@ def _(hidden, user_label, model_key, item_lo, item_hi, k, exclude_pad):
     return [torch.empty(B, k, device=hidden.device, dtype=torch.int64), torch.empty(B, k, device=hidden.device, dtype=torch.float32)]
 
 
+def excl_csr(exclude, input_ids: Optional[torch.Tensor], B: int, device):
+    """an exclusion argument -> (excl_ptr int64 (B + 1), excl_items int32, max_row) on ``device``, or (None, None, 0).
+    ``exclude``: None; "input" (the nonzero ids of each row of ``input_ids``); a (ptr, items) CSR pair as a tuple; a list of
+    B 1-D integer tensors (one per row)."""
+    if exclude is None:
+        return None, None, 0
+    if isinstance(exclude, str):
+        if exclude != "input" or input_ids is None:
+            raise ValueError('exclude must be None, "input", a (ptr, items) pair or a list of 1-D tensors')
+        keep = input_ids != 0
+        ptr_ = torch.zeros(B + 1, device=device, dtype=torch.int64)
+        torch.cumsum(keep.sum(1), 0, out=ptr_[1:])
+        return ptr_, input_ids[keep].to(torch.int32).contiguous(), int(input_ids.shape[1])
+    if isinstance(exclude, tuple) and len(exclude) == 2:
+        ptr_, items = (torch.as_tensor(x) for x in exclude)
+    elif isinstance(exclude, list):
+        if len(exclude) != B:
+            raise ValueError(f"exclude: {len(exclude)} rows for a batch of {B}")
+        rows = [torch.as_tensor(r).reshape(-1).to(torch.int64).cpu() for r in exclude]
+        ptr_ = torch.zeros(B + 1, dtype=torch.int64)
+        torch.cumsum(torch.tensor([r.numel() for r in rows], dtype=torch.int64), 0, out=ptr_[1:])
+        items = torch.cat(rows) if rows else torch.zeros(0, dtype=torch.int64)
+    else:
+        raise ValueError('exclude must be None, "input", a (ptr, items) pair or a list of 1-D tensors')
+    if ptr_.numel() != B + 1:
+        raise ValueError(f"exclude: excl_ptr has {ptr_.numel()} entries, the batch needs {B + 1}")
+    lens = torch.diff(ptr_.to(torch.int64).cpu())
+    if bool((lens < 0).any()) or int(ptr_[0]) != 0 or int(ptr_[-1]) > items.numel():
+        raise ValueError("exclude: malformed CSR (excl_ptr must start at 0, not decrease and end within excl_items)")
+    max_row = int(lens.max()) if B > 0 else 0
+    items = items.to(device=device, dtype=torch.int32)
+    if items.numel() == 0:
+        items = torch.zeros(1, device=device, dtype=torch.int32)
+    return ptr_.to(device=device, dtype=torch.int64).contiguous(), items.contiguous(), max_row
+
+
+@torch.library.custom_op("srfrd::logits_topk_excl", mutates_args=(), device_types="cuda")
+def logits_topk_excl(hidden: torch.Tensor, user_label: Optional[torch.Tensor], model_key: int, item_lo: int, item_hi: int, k: int,
+                     exclude_pad: bool, excl_ptr: Optional[torch.Tensor], excl_items: Optional[torch.Tensor],
+                     max_row: int) -> List[torch.Tensor]:
+    m = _model(model_key)
+    lay, tab = m._table_args()
+    B, L = hidden.shape[0], hidden.shape[1]
+    dev = hidden.device
+    L_ = _lib.lib()
+    ws = torch.empty(max(L_.srfrd_topk_workspace_bytes(B, k, item_hi - item_lo), 8), device=dev, dtype=torch.uint8)
+    xws = None
+    if excl_ptr is not None:
+        xws = torch.empty(max(L_.srfrd_excl_workspace_bytes(B, min(max_row, _lib.EXCL_CAP), item_hi - item_lo), 8), device=dev,
+                          dtype=torch.uint8)
+    idx = torch.empty(B, k, device=dev, dtype=torch.int64)
+    val = torch.empty(B, k, device=dev, dtype=torch.float32)
+    check(L_.srfrd_logits_topk_excl(C.byref(lay), tab, C.c_void_p(m._flat.data_ptr() + 4 * m.n_table_pad), ptr(hidden), B, L,
+                                    item_lo, item_hi, 1 if exclude_pad else 0, ptr(user_label), k, ptr(excl_ptr), ptr(excl_items),
+                                    max_row, ptr(idx), ptr(val), ptr(ws), ptr(xws), _stream()), "srfrd_logits_topk_excl")
+    return [idx, val]
+
+
+@logits_topk_excl.register_fake
+def _(hidden, user_label, model_key, item_lo, item_hi, k, exclude_pad, excl_ptr, excl_items, max_row):
+    B = hidden.shape[0]
+    return [torch.empty(B, k, device=hidden.device, dtype=torch.int64), torch.empty(B, k, device=hidden.device, dtype=torch.float32)]
+
+
+@torch.library.custom_op("srfrd::target_rank", mutates_args=(), device_types="cuda")
+def target_rank(hidden: torch.Tensor, user_label: Optional[torch.Tensor], targets: torch.Tensor, model_key: int, item_lo: int,
+                item_hi: int, exclude_pad: bool, excl_ptr: Optional[torch.Tensor], excl_items: Optional[torch.Tensor],
+                max_row: int) -> torch.Tensor:
+    m = _model(model_key)
+    lay, tab = m._table_args()
+    B, L = hidden.shape[0], hidden.shape[1]
+    dev = hidden.device
+    L_ = _lib.lib()
+    mr = min(max_row, _lib.EXCL_CAP) if excl_ptr is not None else 0
+    ws = torch.empty(max(L_.srfrd_excl_workspace_bytes(B, mr, item_hi - item_lo), 8), device=dev, dtype=torch.uint8)
+    rank = torch.empty(B, device=dev, dtype=torch.int32)
+    targets = targets.to(device=dev, dtype=torch.int64).contiguous()
+    check(L_.srfrd_target_rank(C.byref(lay), tab, C.c_void_p(m._flat.data_ptr() + 4 * m.n_table_pad), ptr(hidden), B, L,
+                               item_lo, item_hi, 1 if exclude_pad else 0, ptr(user_label), ptr(targets), ptr(excl_ptr),
+                               ptr(excl_items), max_row, 10, ptr(rank), None, ptr(ws), _stream()), "srfrd_target_rank")
+    return rank
+
+
+@target_rank.register_fake
+def _(hidden, user_label, targets, model_key, item_lo, item_hi, exclude_pad, excl_ptr, excl_items, max_row):
+    return torch.empty(hidden.shape[0], device=hidden.device, dtype=torch.int32)
+
+
 @torch.library.custom_op("srfrd::topk_merge", mutates_args=(), device_types="cuda")
 def topk_merge(cand_idx: torch.Tensor, cand_val: torch.Tensor, k: int) -> List[torch.Tensor]:
     cand_idx, cand_val = cand_idx.contiguous(), cand_val.contiguous()
@@ -216,4 +306,5 @@ def _(logits):
     return torch.empty(logits.shape[0], device=logits.device, dtype=torch.int32)
 
 
-OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "topk_merge", "eval_rank")
+OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "target_rank", "topk_merge",
+       "eval_rank")

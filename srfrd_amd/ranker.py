@@ -57,43 +57,59 @@ class ShardedRanker:
             raise ValueError("with a process group the number of shards is the world size")
         self.shards = row_shards(model.layout.n_items + 1, self.n_shards)
 
-    def _rank_shard(self, h_last, ulab, lo, hi, k, exclude_pad):
+    def _rank_shard(self, h_last, ulab, lo, hi, k, exclude_pad, excl=None):
         from . import ops
-        idx, val = torch.ops.srfrd.logits_topk(h_last.unsqueeze(1), ulab, ops.register_model(self.model), lo, hi, k, bool(exclude_pad))
+        if excl is None:
+            idx, val = torch.ops.srfrd.logits_topk(h_last.unsqueeze(1), ulab, ops.register_model(self.model), lo, hi, k,
+                                                   bool(exclude_pad))
+        else:
+            idx, val = torch.ops.srfrd.logits_topk_excl(h_last.unsqueeze(1), ulab, ops.register_model(self.model), lo, hi, k,
+                                                        bool(exclude_pad), *excl)
         return idx, val
 
-    @torch.no_grad()
-    def topk(self, user_ids, input_ids, fake_ids, k: int = 10, exclude_pad: bool = True, check_batch: bool = True):
-        """-> (indices int64 (B,k), scores (B,k)) of this rank's users over the WHOLE catalog.  An index is -1 (score -inf) where
-        fewer than k items are rankable.  ``check_batch`` (data parallel): verify that every rank passed the same batch size
-        (one 8-byte all-gather + host read per call; pass False in a loop whose batches are known to be equal)."""
+    def _gather_excl(self, excl, B, device):
+        """data parallel: every rank's exclusion CSR -> the CSR of all world x B users (rows padded to a common width with
+        -1, an id outside every range, then re-packed)"""
+        xp, xi, mr = excl
+        width = torch.tensor([mr], device=device, dtype=torch.int64)
+        w_all = torch.empty(self.world, device=device, dtype=torch.int64)
+        _all_gather(w_all, width, self.group)
+        M = max(int(w_all.max()), 1)
+        lens = (xp[1:] - xp[:-1])
+        col = torch.arange(M, device=device)
+        src = (xp[:-1, None] + col[None, :]).clamp(max=max(xi.numel() - 1, 0))
+        pad = torch.where(col[None, :] < lens[:, None], xi[src].to(torch.int32), torch.full_like(src, -1, dtype=torch.int32))
+        pad_all = torch.empty(self.world * B, M, device=device, dtype=torch.int32)
+        _all_gather(pad_all, pad.contiguous(), self.group)
+        ptr_all = torch.arange(0, self.world * B * M + 1, M, device=device, dtype=torch.int64)
+        return ptr_all, pad_all.reshape(-1).contiguous(), M
+
+    def _users(self, input_ids, fake_ids, exclude):
+        from . import ops
         m = self.model
         ids = m._prep(input_ids, fake_ids, None, None, None, None)
         h_last = m._launch_fwd_last(ids[0], ids[1])[:, 0, :]          # (B, d_out)
         ulab = m.user_labels(ids[1]) if m._kind == "SRFRN" else None
+        excl = ops.excl_csr(exclude, ids[0], h_last.shape[0], h_last.device) if exclude is not None else None
+        return h_last, ulab, excl
+
+    @torch.no_grad()
+    def topk(self, user_ids, input_ids, fake_ids, k: int = 10, exclude_pad: bool = True, check_batch: bool = True, exclude=None):
+        """-> (indices int64 (B,k), scores (B,k)) of this rank's users over the WHOLE catalog.  An index is -1 (score -inf) where
+        fewer than k items are rankable.  ``check_batch`` (data parallel): verify that every rank passed the same batch size
+        (one 8-byte all-gather + host read per call; pass False in a loop whose batches are known to be equal).
+        ``exclude``: per-user items never to return, as in the model's ``topk``."""
+        h_last, ulab, excl = self._users(input_ids, fake_ids, exclude)
         B = h_last.shape[0]
         if not self.dist_on:
-            lists = [self._rank_shard(h_last, ulab, lo, hi, k, exclude_pad) for lo, hi in self.shards if hi > lo]
+            lists = [self._rank_shard(h_last, ulab, lo, hi, k, exclude_pad, excl) for lo, hi in self.shards if hi > lo]
             return topk_merge(torch.cat([i for i, _ in lists], 1), torch.cat([v for _, v in lists], 1), k)
         # ---- one shard per rank: gather every rank's users, rank them against the own rows, exchange the lists
-        if check_batch:
-            # every rank must bring the same number of users (the gathers below are sized world x B from the LOCAL B: a ragged
-            # last evaluation batch would hang or mis-assign rows) - one tiny all-gather, then a clear error on every rank
-            nb = torch.tensor([B], device=h_last.device, dtype=torch.int64)
-            nb_all = torch.empty(self.world, device=h_last.device, dtype=torch.int64)
-            _all_gather(nb_all, nb, self.group)
-            sizes = nb_all.tolist()
-            if any(x != B for x in sizes):
-                raise ValueError(f"ShardedRanker.topk: ranks passed different batch sizes {sizes}; pad the last batch to a common size "
-                                 "(rows of padding ids rank like any other user and can be dropped afterwards)")
-        h_all = torch.empty(self.world * B, h_last.shape[1], device=h_last.device, dtype=torch.float32)
-        _all_gather(h_all, h_last, self.group)
-        lab_all = None
-        if ulab is not None:
-            lab_all = torch.empty(self.world * B, device=h_last.device, dtype=torch.int64)
-            _all_gather(lab_all, ulab, self.group)
+        self._check_batch(B, h_last.device, check_batch)
+        h_all, lab_all = self._gather_users(h_last, ulab)
         lo, hi = self.shards[self.rank]
-        idx, val = self._rank_shard(h_all, lab_all, lo, hi, k, exclude_pad)        # (world * B, k) against the own rows
+        excl_all = self._gather_excl(excl, B, h_last.device) if excl is not None else None
+        idx, val = self._rank_shard(h_all, lab_all, lo, hi, k, exclude_pad, excl_all)   # (world * B, k) against the own rows
         idx_all = torch.empty(self.world, self.world * B, k, device=idx.device, dtype=torch.int64)
         val_all = torch.empty(self.world, self.world * B, k, device=idx.device, dtype=torch.float32)
         _all_gather(idx_all, idx, self.group)
@@ -102,6 +118,67 @@ class ShardedRanker:
         ci = idx_all[:, mine].permute(1, 0, 2).reshape(B, self.world * k)
         cv = val_all[:, mine].permute(1, 0, 2).reshape(B, self.world * k)
         return topk_merge(ci, cv, k)
+
+    @torch.no_grad()
+    def target_rank(self, user_ids, input_ids, fake_ids, targets, exclude=None, exclude_pad: bool = True, check_batch: bool = True):
+        """-> int32 (B,) full-catalog ranks of ``targets`` for this rank's users (as the model's ``target_rank``): the shards'
+        strictly-greater counts summed - one after the other on this GPU, or one shard per rank with the counts all-reduced."""
+        from . import ops
+        m = self.model
+        h_last, ulab, excl = self._users(input_ids, fake_ids, exclude)
+        B = h_last.shape[0]
+        tg = torch.as_tensor(targets).to(device=h_last.device, dtype=torch.int64).reshape(-1).contiguous()
+        if tg.numel() != B:
+            raise ValueError("targets must hold one item id per user")
+        key = ops.register_model(m)
+        xargs = excl if excl is not None else (None, None, 0)
+        if not self.dist_on:
+            rank = torch.zeros(B, device=h_last.device, dtype=torch.int32)
+            for lo, hi in self.shards:
+                if hi > lo:
+                    rank += torch.ops.srfrd.target_rank(h_last.unsqueeze(1), ulab, tg, key, lo, hi, bool(exclude_pad), *xargs)
+            return rank
+        self._check_batch(B, h_last.device, check_batch)
+        h_all, lab_all = self._gather_users(h_last, ulab)
+        t_all = torch.empty(self.world * B, device=h_last.device, dtype=torch.int64)
+        _all_gather(t_all, tg, self.group)
+        xall = self._gather_excl(excl, B, h_last.device) if excl is not None else (None, None, 0)
+        lo, hi = self.shards[self.rank]
+        if hi > lo:
+            part = torch.ops.srfrd.target_rank(h_all.unsqueeze(1), lab_all, t_all, key, lo, hi, bool(exclude_pad), *xall)
+        else:
+            part = torch.zeros(self.world * B, device=h_last.device, dtype=torch.int32)
+        part = part.to(torch.int64)
+        if dist.get_backend(self.group) == "nccl":
+            dist.all_reduce(part, group=self.group)
+        else:
+            cpu = part.cpu()
+            dist.all_reduce(cpu, group=self.group)
+            part = cpu.to(h_last.device)
+        return part[self.rank * B:(self.rank + 1) * B].to(torch.int32)
+
+    def _check_batch(self, B, device, check_batch):
+        if not check_batch:
+            return
+        # every rank must bring the same number of users (the gathers below are sized world x B from the LOCAL B: a ragged
+        # last evaluation batch would hang or mis-assign rows) - one tiny all-gather, then a clear error on every rank
+        nb = torch.tensor([B], device=device, dtype=torch.int64)
+        nb_all = torch.empty(self.world, device=device, dtype=torch.int64)
+        _all_gather(nb_all, nb, self.group)
+        sizes = nb_all.tolist()
+        if any(x != B for x in sizes):
+            raise ValueError(f"ShardedRanker: ranks passed different batch sizes {sizes}; pad the last batch to a common size "
+                             "(rows of padding ids rank like any other user and can be dropped afterwards)")
+
+    def _gather_users(self, h_last, ulab):
+        B = h_last.shape[0]
+        h_all = torch.empty(self.world * B, h_last.shape[1], device=h_last.device, dtype=torch.float32)
+        _all_gather(h_all, h_last, self.group)
+        lab_all = None
+        if ulab is not None:
+            lab_all = torch.empty(self.world * B, device=h_last.device, dtype=torch.int64)
+            _all_gather(lab_all, ulab, self.group)
+        return h_all, lab_all
 
 
 def _all_gather(out: torch.Tensor, part: torch.Tensor, group):
