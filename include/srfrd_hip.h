@@ -103,6 +103,30 @@ int64_t srfrd_aux_floats(const srfrd_layout* lay, int B, int L);
  * a function of the layout and the shape only. */
 int srfrd_bwd_grid(const srfrd_layout* lay, int B, int L);
 
+/* [host] the encoder's kernel plan, asked without a GPU: which instantiation srfrd_encoder_fwd(_sched, _last) and
+ * srfrd_encoder_bwd(_sched) launch for (lay, B, L) in `mode` (SRFRD_PLAN_* bits: what the call computes) under `switches`
+ * (SRFRD_SW_* bits: the environment switches of the same names, which the launchers read on every call), on a device with
+ * n_cu CUs, given scratch_floats of caller scratch (0: none).  For each direction, writes the instantiation's name as a
+ * kernel trace prints it, without spaces ("srfrd::encoder_fwd_ragged_kernel<0,1,50>"; at most name_len bytes with the NUL)
+ * and grids[0] (forward) / grids[1] (backward): the workgroup count, or SRFRD_E_UNSUPPORTED with an empty name where that
+ * call returns SRFRD_E_UNSUPPORTED.  Returns 0 or SRFRD_E_ARG. */
+#define SRFRD_PLAN_POS 1          /* positive target ids given (pos_logits) */
+#define SRFRD_PLAN_NEG 2          /* negative target ids given (neg_logits) */
+#define SRFRD_PLAN_CKPT 4         /* forward: training checkpoints written (save_x / save_h1 / save_aux) */
+#define SRFRD_PLAN_LOSS 8         /* forward: BCE partial sums written (loss_part) */
+#define SRFRD_PLAN_DROPOUT 16     /* dropout_p > 0 */
+#define SRFRD_PLAN_FUSED_BCE 32   /* backward: fused BCE gradient (fused_bce set, d_hidden NULL) */
+#define SRFRD_PLAN_TAPS 64        /* debug taps (dbg != NULL) */
+#define SRFRD_SW_GENERIC 1        /* the run-time-geometry instantiation for every shape the LDS holds */
+#define SRFRD_SW_NO_RAGGED 2      /* not the ragged pair at seq_len 50 */
+#define SRFRD_SW_RAGGED_FULL_ROWS 4   /* the ragged pair computes every row (same kernels) */
+#define SRFRD_SW_NO_SLOTS50 8     /* not the slot-placed backward at seq_len 50 (nor the ragged pair) */
+#define SRFRD_SW_NO_SLOTS 16      /* long sequences: neither the slot-placed nor the row-chunked backward */
+#define SRFRD_SW_NO_ROWS 32       /* long sequences: not the row-owner forward */
+#define SRFRD_SW_ROWS_ALWAYS 64   /* the row-owner forward wherever it serves (and not the ragged pair) */
+int srfrd_encoder_plan(const srfrd_layout* lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats,
+                       char* fwd_name, char* bwd_name, int name_len, int32_t* grids);
+
 /* [host] floats per debug-tap slot and number of slots (tests only). */
 int srfrd_debug_shape(const srfrd_layout* lay, int L, int64_t* slot_floats, int32_t* n_slots);
 

@@ -52,6 +52,7 @@ SIGNATURES = {
                                _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _P, _i64, _P, _i, _P]),
     "srfrd_sched_ints": (_i64, [_i]),
     "srfrd_seq_order": (_i, [_P, _i, _i, _i, _P, _P]),
+    "srfrd_encoder_plan": (_i, [_LP, _i, _i, _i, _i, _i, _i64, _P, _P, _i, _P]),
     "srfrd_encoder_fwd_sched": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
                                      _P, _P, _P, _P, _P, _P, _P, _P, _i64, _P, _i, _P]),
     "srfrd_encoder_bwd_sched": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
@@ -131,3 +132,18 @@ def scratch_floats(lay: Layout, B: int, L: int):
     f, b = _i64(0), _i64(0)
     check(lib().srfrd_scratch_floats(C.byref(lay), B, L, C.byref(f), C.byref(b)), "srfrd_scratch_floats")
     return f.value, b.value
+
+
+# srfrd_encoder_plan mode bits (SRFRD_PLAN_*) and switch bits (SRFRD_SW_*, keyed by the environment variable of that name)
+PLAN_POS, PLAN_NEG, PLAN_CKPT, PLAN_LOSS, PLAN_DROPOUT, PLAN_FUSED_BCE, PLAN_TAPS = 1, 2, 4, 8, 16, 32, 64
+SWITCHES = {"SRFRD_GENERIC": 1, "SRFRD_NO_RAGGED": 2, "SRFRD_RAGGED_FULL_ROWS": 4, "SRFRD_NO_SLOTS50": 8, "SRFRD_NO_SLOTS": 16,
+            "SRFRD_NO_ROWS": 32, "SRFRD_ROWS_ALWAYS": 64}
+
+
+def encoder_plan(lay: Layout, B: int, L: int, mode: int, switches: int = 0, n_cu: int = 256, scratch_floats: int = 0):
+    """srfrd_encoder_plan (no GPU needed) -> ((forward kernel, grid), (backward kernel, grid)); a direction the encoder
+    refuses with SRFRD_E_UNSUPPORTED reads ("", -2)."""
+    fwd, bwd, grids = C.create_string_buffer(128), C.create_string_buffer(128), (C.c_int32 * 2)()
+    check(lib().srfrd_encoder_plan(C.byref(lay), B, L, mode, switches, n_cu, scratch_floats, fwd, bwd, 128, grids),
+          "srfrd_encoder_plan")
+    return (fwd.value.decode(), grids[0]), (bwd.value.decode(), grids[1])

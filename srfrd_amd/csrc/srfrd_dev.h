@@ -12,6 +12,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "../../include/srfrd_hip.h"
 #include "srfrd_rng.h"
 
@@ -41,6 +45,41 @@ __device__ __forceinline__ void srfrd_skewed_barrier() {
 #else
 #define SRFRD_NS srfrd
 #endif
+
+// ---- host helpers shared by every launcher (one definition for both builds) ----
+namespace srfrd {
+// CU count of the CURRENT device (cached per device: one process may drive several GPUs)
+inline int num_cu() {
+  static std::mutex mu;
+  static std::map<int, int> cached;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+  std::lock_guard<std::mutex> lock(mu);
+  int& n = cached[dev];
+  if (n == 0) {
+    hipDeviceProp_t prop;
+    n = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+  }
+  return n;
+}
+
+// Raise `fn`'s dynamic-LDS limit to `bytes` (the > 64 KiB opt-in).  hipFuncSetAttribute applies to one function on the
+// CURRENT device: it is remembered per (device, function) under a mutex, so a second GPU driven from the same process, or
+// two host threads launching concurrently, each get it set before their first launch.
+inline int lds_opt_in(const void* fn, int64_t bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, int64_t> opted;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return SRFRD_E_DEVICE;
+  std::lock_guard<std::mutex> lock(mu);
+  int64_t& have = opted[{dev, fn}];
+  if (bytes > have) {
+    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return SRFRD_E_DEVICE;
+    have = bytes;
+  }
+  return 0;
+}
+}  // namespace srfrd
 
 namespace SRFRD_NS {
 using namespace srfrd;   // srfrd_rng.h

@@ -2,12 +2,10 @@
 // parameter cache, debug taps, host-side argument marshalling.
 #pragma once
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <type_traits>
-#include <utility>
 
 #include "srfrd_dev.h"
+#include "srfrd_enc_plan.h"
 
 namespace SRFRD_NS {
 
@@ -38,7 +36,6 @@ struct EncArgs {
   float* scratch;
   int64_t scratch_stride;
   int lds_floats;      // dynamic LDS (floats) the long build may carve from before falling back to `scratch`
-  int carve_mode;      // which buffers get the LDS share first (0: score matrices, 1: activation matrices)
   // debug taps
   float* dbg;
   int dbg_seq;
@@ -46,7 +43,6 @@ struct EncArgs {
   // ragged kernels (seq_len 50): sequence -> workgroup schedule from srfrd_seq_order's per-sequence lengths (NULL: b = blockIdx.x, += gridDim.x)
   const int* sched;    // int32 workspace, layout below (kSched*)
   int sched_mode;      // 0 none, 1 length order (workgroup x takes the sequence of rank perm(x): see rag_take)
-  int long_prio;       // ragged kernels: wave priority of sequences with three or four row tiles (0: none; experiment)
   int ragged_off;      // diagnostic: the ragged kernels compute every row (t0 = 0), as the full kernels do
 };
 
@@ -81,6 +77,37 @@ __host__ __device__ __forceinline__ AuxOff aux_off(int i, int b, int nb, int L, 
   f.v = blk + 4 * plane;
   f.p = blk + 5 * plane;
   return f;
+}
+
+// Scope and sizing of the long-sequence and seq_len-50 kernels (read by the kernels and by the kernel plan below).
+// Row-owner forward (srfrd_encoder_fwd_rows_kernel.inc): hidden width 50, 8 waves, seq_len <= 16 * kRowMaxTiles.
+constexpr int kRowWaves = 8;
+constexpr int kRowMaxTiles = 13;         // S^T accumulators a lane holds: key tiles of a query tile (seq_len <= 208)
+__host__ __device__ constexpr int64_t rows_lds_floats(int L, int D, int n_blocks) {
+  const int LP = (L + 15) & ~15, DS = ((D + 3) & ~3) + 2;
+  return 2ll * LP * DS + (int64_t)kRowWaves * 2 * 16 * DS + 5ll * LP + 64 + ln_cache_floats(n_blocks) + kSlack;
+}
+// Slot-placed backward (srfrd_encoder_bwd_slots_kernel.inc): seq_len 50 and 100.
+constexpr int kSlotWaves = 8;
+__host__ __device__ constexpr int slots_R(int L) { return (L + 3) & ~3; }
+__host__ __device__ constexpr int64_t slots_lds_floats(int L, int D, int n_blocks) {
+  const int LP = (L + 15) & ~15, DS = ((D + 3) & ~3) + 2;
+  return 6ll * slots_R(L) * DS + 11ll * LP + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
+}
+// Row-chunked backward (srfrd_encoder_bwd_chunks_kernel.inc): seq_len 17..208, three [L][D] intermediates in scratch.
+constexpr int kCkWaves = 8;
+constexpr int kCkRows = 48;            // rows of a chunk (three 16-row tiles)
+__host__ __device__ constexpr int64_t chunks_lds_floats(int L, int D, int n_blocks) {
+  const int LP = (L + 15) & ~15, DS = ((D + 3) & ~3) + 2, LR = (L + 3) & ~3;
+  // K | V, then a pool that is the score chunk + two chunk slots (attention pass) or five chunk slots (projection pass)
+  const int64_t pool_att = (int64_t)kCkRows * (LR + 2) + 2ll * kCkRows * DS, pool_prj = 5ll * kCkRows * DS;
+  return 2ll * LR * DS + (pool_att > pool_prj ? pool_att : pool_prj) + 11ll * LP + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
+}
+__host__ __device__ constexpr int64_t chunks_scratch_floats(int L, int D) { return 3ll * (((L + 3) & ~3) * D + 64); }
+// Ragged backward (srfrd_encoder_bwd_ragged_kernel.inc): seq_len 50, hidden 50.
+__host__ __device__ constexpr int64_t bwd_ragged_lds_floats(int n_blocks) {
+  // guard (12 rows) + six [52][54] slots + 12 per-row arrays + misc + two LayerNorm caches + slack
+  return 12ll * 54 + 6ll * 52 * 54 + 12ll * 64 + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
 }
 
 // Optimisation barrier on a wave-uniform pointer: stops LLVM from hoisting the per-call-site address arithmetic of
@@ -216,28 +243,6 @@ __device__ __forceinline__ void tap(const EncArgs& a, int b, int slot, const lds
 // ================================================================================================
 // host side
 // ================================================================================================
-// CU count of the CURRENT device (cached per device: one process may drive several GPUs)
-[[maybe_unused]] static int num_cu() {
-  static std::mutex mu;
-  static int cached[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  std::lock_guard<std::mutex> lock(mu);
-  if (cached[dev] == 0) {
-    hipDeviceProp_t prop;
-    cached[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  }
-  return cached[dev];
-}
-
-// block size override for tuning runs (multiple of 64, <= 1024)
-[[maybe_unused]] static int env_threads(const char* name, int dflt) {
-  const char* e = getenv(name);
-  if (!e) return dflt;
-  const int v = atoi(e);
-  return (v >= 64 && v <= 1024 && (v & 63) == 0) ? v : dflt;
-}
-
 [[maybe_unused]] static int fill_args(EncArgs& a, const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
                      const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids, const int64_t* pos_fake,
                      const int64_t* neg_ids, const int64_t* neg_fake, int B, int L, double dropout_p, uint32_t seed,
@@ -279,46 +284,48 @@ __device__ __forceinline__ void tap(const EncArgs& a, int b, int slot, const lds
   return 0;
 }
 
-// The ragged seq_len-50 pair (srfrd_encoder_fwd_ragged_kernel.inc + srfrd_encoder_bwd_ragged_kernel.inc) exchanges
-// checkpoints that hold only the rows of the computed tiles: a training forward may take the ragged kernel only when the
-// backward of the same (layout, length) will be the ragged one, and vice versa - ONE predicate, asked by both launchers.
-[[maybe_unused]] static bool ragged_pair(const srfrd_layout* lay, int L) {
-  if (lay->D != 50 || lay->n_heads != 1 || L != 50 || lay->n_blocks > SRFRD_MAX_BLOCKS) return false;
-  if (getenv("SRFRD_NO_RAGGED") || getenv("SRFRD_GENERIC") || getenv("SRFRD_NO_LSPEC") || getenv("SRFRD_NO_KSPEC") ||
-      getenv("SRFRD_NO_SLOTS50") || getenv("SRFRD_ROWS_ALWAYS") || getenv("SRFRD_FWD_THREADS") || getenv("SRFRD_BWD_THREADS"))
-    return false;
-  if (lay->kind == SRFRD_SASREC) return true;
-  if ((lay->kind == SRFRD_SRFR || lay->kind == SRFRD_SRFRN) && lay->d_item == 45) return true;
-  return lay->kind >= SRFRD_SRFU_B && lay->d_item == 50;
+// kind variant -> <K, DI>: f(std::integral_constant<int, v>) for a plan's variant v (kKindVariants[v] are the arguments)
+template <class F>
+static int with_variant(int v, F&& f) {
+  switch (v) {
+    case 0: return f(std::integral_constant<int, 0>());
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    default: return f(std::integral_constant<int, 3>());
+  }
 }
-// kind_variant of the ragged kernels: 0 SASRec 50 + 0, 1 SRFR 45 + 5, 2 SRFRN 45 + 5, 3 SRFU_* 50 + 0 (kind read at run time)
-[[maybe_unused]] static int ragged_variant(const srfrd_layout* lay) {
-  if (lay->kind == SRFRD_SASREC) return 0;
-  if (lay->kind == SRFRD_SRFR) return 1;
-  if (lay->kind == SRFRD_SRFRN) return 2;
-  return 3;
+template <class F>
+static int with_flag(bool b, F&& f) {
+  return b ? f(std::true_type()) : f(std::false_type());
 }
 
-// launch one instantiation.  The > 64 KiB dynamic-LDS opt-in (hipFuncSetAttribute) applies to one function on the CURRENT
-// device: it is remembered per (device, function) under a mutex, so a second GPU driven from the same process, or two
-// host threads launching concurrently, each get it set before their first launch.
+// kind variant of a layout: the hidden-50, one-head specialisations cover these kinds and width splits (-1: none)
+static inline int kind_variant(const srfrd_layout& lay) {
+  if (lay.D != 50 || lay.n_heads != 1) return -1;
+  if (lay.kind == SRFRD_SASREC) return 0;
+  if (lay.kind == SRFRD_SRFR && lay.d_item == 45) return 1;
+  if (lay.kind == SRFRD_SRFRN && lay.d_item == 45) return 2;
+  if (lay.kind >= SRFRD_SRFU_B && lay.d_item == 50) return 3;
+  return -1;
+}
+
+// launch one instantiation as the kernel plan sized it
 template <class K>
-static int launch_enc(K kernel, int grid, int threads, int64_t lds, void* stream, const EncArgs& a) {
-  static std::mutex mu;
-  static std::map<std::pair<int, const void*>, int64_t> opted;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return SRFRD_E_DEVICE;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    int64_t& have = opted[{dev, (const void*)kernel}];
-    if (lds > have) {
-      if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return SRFRD_E_DEVICE;
-      have = lds;
-    }
-  }
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), (size_t)lds, (hipStream_t)stream, a);
+static int launch_enc(K kernel, const KernelPlan& k, void* stream, const EncArgs& a) {
+  if (const int rc = lds_opt_in((const void*)kernel, k.lds)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(k.grid), dim3(k.threads), (size_t)k.lds, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
+
+#ifndef SRFRD_BUF_GLOBAL
+// one launcher per LDS-resident family, each in the translation unit that instantiates its kernels
+int launch_fwd_first(const KernelPlan& k, const EncArgs& a, void* stream);    // srfrd_encoder_fwd.hip
+int launch_fwd_rows(const KernelPlan& k, const EncArgs& a, void* stream);     // srfrd_encoder_fwd_rows.hip
+int launch_fwd_ragged(const KernelPlan& k, const EncArgs& a, void* stream);   // srfrd_encoder_fwd_ragged.hip
+int launch_bwd_first(const KernelPlan& k, const EncArgs& a, void* stream);    // srfrd_encoder_bwd.hip
+int launch_bwd_ragged(const KernelPlan& k, const EncArgs& a, void* stream);   // srfrd_encoder_bwd_ragged.hip
+int launch_bwd_slots(const KernelPlan& k, const EncArgs& a, void* stream);    // srfrd_encoder_bwd_slots.hip
+int launch_bwd_chunks(const KernelPlan& k, const EncArgs& a, void* stream);   // srfrd_encoder_bwd_chunks.hip
+#endif
 
 }  // namespace SRFRD_NS

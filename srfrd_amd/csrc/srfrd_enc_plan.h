@@ -1,0 +1,76 @@
+// Kernel plan of the fused encoder: which instantiation srfrd_encoder_fwd / srfrd_encoder_bwd launch for a (layout, B, L,
+// mode, switch set), with its grid, LDS and scratch stride.  Host only: the plan makes no HIP call (srfrd_encoder_plan asks
+// it on a machine without a GPU).  encoder_plan (srfrd_encoder_fwd.hip) is the one place that chooses; the launchers
+// launch what it names.
+#pragma once
+#include <stdint.h>
+#include <stdlib.h>
+
+#include "../../include/srfrd_hip.h"
+
+namespace srfrd {
+
+enum Family {
+  kFwdFirst,     // first-generation LDS kernel, srfrd_encoder_fwd_kernel.inc
+  kFwdRows,      // row-owner forward, srfrd_encoder_fwd_rows_kernel.inc
+  kFwdRagged,    // ragged forward, srfrd_encoder_fwd_ragged_kernel.inc
+  kFwdLong,      // global-scratch build of the first-generation forward (srfrd_long::)
+  kBwdFirst,     // first-generation LDS kernel, srfrd_encoder_bwd_kernel.inc
+  kBwdRagged,    // ragged backward, srfrd_encoder_bwd_ragged_kernel.inc
+  kBwdSlots,     // slot-placed backward, srfrd_encoder_bwd_slots_kernel.inc
+  kBwdChunks,    // row-chunked backward, srfrd_encoder_bwd_chunks_kernel.inc
+  kBwdLong,      // global-scratch build of the first-generation backward (srfrd_long::)
+};
+
+// Geometry template of the first-generation kernels (and the sequence length of the slot-placed backward)
+enum Form {
+  kGeneric,      // <0, 0, 0>: run-time geometry
+  kLP32,         // <50, 32, 8>
+  kLP64,         // <50, 64, 8>
+  kL50,          // <50, 64, 8, 50, K, T, DI>, or <50, 64, 8, 50> without a kind variant
+  kL100,         // SASRec at seq_len 100: <50, 112, 16 | 8, 100, SASREC, T, 50>
+};
+
+// Kind variants of the hidden-50, one-head specialisations: 0 SASRec 50 + 0, 1 SRFR 45 + 5, 2 SRFRN 45 + 5, 3 SRFU_* 50 + 0
+// (kind read at run time) - the <K, DI> template arguments of every specialised kernel.
+struct KindVariant {
+  int K, DI;
+};
+constexpr KindVariant kKindVariants[4] = {{SRFRD_SASREC, 50}, {SRFRD_SRFR, 45}, {SRFRD_SRFRN, 45}, {-1, 50}};
+
+struct KernelPlan {
+  int rc;                  // 0, or SRFRD_E_UNSUPPORTED: no kernel serves this call (the launcher returns it)
+  int family;              // Family
+  int form;                // Form (first-generation, global-scratch and slot-placed families)
+  int variant;             // kKindVariants index, or -1
+  bool flag;               // the family's boolean template argument: training instantiation (first-generation, ragged
+                           // forward), not plain eval (row-owner), read-modify-write slabs (ragged / slots / chunks backward)
+  int grid, threads;
+  int64_t lds;             // dynamic LDS bytes
+  int64_t scratch_stride;  // floats of the caller's scratch per workgroup (global-scratch builds, row-chunked backward), or 0
+};
+struct EncPlan {
+  KernelPlan fwd, bwd;
+};
+
+// mode: SRFRD_PLAN_* bits, switches: SRFRD_SW_* bits (read_switches), n_cu: CUs of the device, scratch_floats: the caller's
+// scratch (0 when none).  The layout is one fill_args accepted.
+EncPlan encoder_plan(const srfrd_layout& lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats);
+// the instantiation's name as a kernel trace prints it (without spaces), e.g. "srfrd::encoder_fwd_ragged_kernel<0,1,50>"
+void plan_name(const KernelPlan& k, char* buf, int len);
+// persistent workgroups of the backward (= rows of grad_slabs): a function of the layout and the shape only
+int bwd_grid(const srfrd_layout& lay, int B, int L, int n_cu);
+
+// The environment switches (tests and A/B runs; none is set in normal use), read on every call: tests flip them inside
+// one process.
+inline int read_switches() {
+  return (getenv("SRFRD_GENERIC") ? SRFRD_SW_GENERIC : 0) | (getenv("SRFRD_NO_RAGGED") ? SRFRD_SW_NO_RAGGED : 0) |
+         (getenv("SRFRD_RAGGED_FULL_ROWS") ? SRFRD_SW_RAGGED_FULL_ROWS : 0) | (getenv("SRFRD_NO_SLOTS50") ? SRFRD_SW_NO_SLOTS50 : 0) |
+         (getenv("SRFRD_NO_SLOTS") ? SRFRD_SW_NO_SLOTS : 0) | (getenv("SRFRD_NO_ROWS") ? SRFRD_SW_NO_ROWS : 0) |
+         (getenv("SRFRD_ROWS_ALWAYS") ? SRFRD_SW_ROWS_ALWAYS : 0);
+}
+
+int launch_fwd_long(const KernelPlan& k, const void* args, void* stream);   // srfrd_encoder_fwd_long.hip (args: EncArgs)
+int launch_bwd_long(const KernelPlan& k, const void* args, void* stream);   // srfrd_encoder_bwd_long.hip
+
+}  // namespace srfrd

@@ -8,34 +8,28 @@
 #include "srfrd_encoder_bwd_kernel.inc"
 
 namespace srfrd {
+
+int launch_bwd_first(const KernelPlan& k, const EncArgs& a, void* stream) {
+  switch (k.form) {
+    case kL50:
+      if (k.variant < 0) return launch_enc(encoder_bwd_kernel<50, 64, 8, 50>, k, stream, a);
+      return with_variant(k.variant, [&](auto v) {
+        constexpr KindVariant kv = kKindVariants[decltype(v)::value];
+        return with_flag(k.flag, [&](auto t) { return launch_enc(encoder_bwd_kernel<50, 64, 8, 50, kv.K, decltype(t)::value, kv.DI>, k, stream, a); });
+      });
+    case kLP64: return launch_enc(encoder_bwd_kernel<50, 64, 8>, k, stream, a);
+    case kLP32: return launch_enc(encoder_bwd_kernel<50, 32, 8>, k, stream, a);
+    default: return launch_enc(encoder_bwd_kernel<0, 0, 0>, k, stream, a);
+  }
+}
+
 }  // namespace srfrd
 
 using namespace srfrd;
 
-extern "C" int srfrd_long_launch_bwd(const void* args, int grid, int threads, int variant, void* stream);   // srfrd_encoder_bwd_long.hip
-extern "C" int srfrd_bwd_slots_launch(const void* args, int grid, int L, int kind_variant, void* stream);    // srfrd_encoder_bwd_slots.hip
-extern "C" int srfrd_bwd_chunks_launch(const void* args, int grid, int kind_variant, void* stream);          // srfrd_encoder_bwd_chunks.hip
-extern "C" int srfrd_bwd_ragged_launch(const void* args, int grid, int kind_variant, void* stream);          // srfrd_encoder_bwd_ragged.hip
-
-// kind_variant of the slot-placed / row-chunked kernels (0 SASRec 50 + 0, 1 SRFR 45 + 5, 2 SRFRN 45 + 5, 3 SRFU_* 50 + 0), or -1
-static int slots_variant(const srfrd_layout* lay) {
-  if (lay->D != 50 || lay->n_heads != 1) return -1;
-  if (lay->kind == SRFRD_SASREC) return 0;
-  if (lay->kind == SRFRD_SRFR && lay->d_item == 45) return 1;
-  if (lay->kind == SRFRD_SRFRN && lay->d_item == 45) return 2;
-  if (lay->kind >= SRFRD_SRFU_B && lay->d_item == 50) return 3;
-  return -1;
-}
-
-// The reference's default geometry (seq_len 50, hidden 50: BASELINE configs[1] / [2]) runs the slot-placed backward with its
-// six [52][54] slots = 76 KB of LDS: TWO workgroups per CU, where the first-generation kernel's ten matrices (150 KB) allow
-// one.  A function of the shape only (never of the environment switches below: callers size `grad_slabs` with it).
-static bool two_per_cu(const srfrd_layout* lay, int L) { return L == 50 && slots_variant(lay) >= 0; }
-
 extern "C" int srfrd_bwd_grid(const srfrd_layout* lay, int B, int L) {
   if (!lay || B <= 0 || L <= 0) return SRFRD_E_ARG;
-  const int wgs = num_cu() * (two_per_cu(lay, L) ? 2 : 1);
-  return B < wgs ? B : wgs;
+  return bwd_grid(*lay, B, L, num_cu());
 }
 
 static int encoder_bwd_impl(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
@@ -48,11 +42,11 @@ static int encoder_bwd_impl(const srfrd_layout* lay, const void* item_table, con
                             const float* d_neg, int fused_bce, float* grad_table, float* table_contrib, float* grad_slabs,
                             float* scratch, int64_t scratch_floats, float* dbg, int dbg_seq, const int32_t* sched, int sched_mode,
                             void* stream) {
+  const int sw = read_switches();
   EncArgs a = {};
   a.sched = sched_mode != 0 ? sched : nullptr;
   a.sched_mode = a.sched ? sched_mode : 0;
-  a.ragged_off = getenv("SRFRD_RAGGED_FULL_ROWS") != nullptr;
-  { const char* e = getenv("SRFRD_LONG_PRIO"); a.long_prio = e ? atoi(e) : 0; }
+  a.ragged_off = (sw & SRFRD_SW_RAGGED_FULL_ROWS) != 0;
   int rc = fill_args(a, lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L,
                      dropout_p, seed, seed_dev, seq_index0);
   if (rc) return rc;
@@ -63,72 +57,24 @@ static int encoder_bwd_impl(const srfrd_layout* lay, const void* item_table, con
   a.grad_table = grad_table; a.grad_slabs = grad_slabs; a.contrib = table_contrib;
   a.dbg = dbg; a.dbg_seq = dbg_seq;
   srfrd_debug_shape(lay, L, &a.dbg_slot, nullptr);
-  const Geom g = make_geom(L, lay->D);
-  const int64_t lds = bwd_lds_floats(g, lay->n_blocks) * 4;
-  const int grid = srfrd_bwd_grid(lay, B, L);
-#ifdef SRFRD_STAMPS
-  const bool taps = false;                     // (diagnostic build: `dbg` receives the phase stamps)
-#else
-  const bool taps = dbg != nullptr;
+  int mode = (pos_ids ? SRFRD_PLAN_POS : 0) | (neg_ids ? SRFRD_PLAN_NEG : 0) | (fused_bce && !d_hidden ? SRFRD_PLAN_FUSED_BCE : 0) |
+             (dropout_p > 0.0 ? SRFRD_PLAN_DROPOUT : 0);
+#ifndef SRFRD_STAMPS
+  if (dbg) mode |= SRFRD_PLAN_TAPS;            // (diagnostic build: `dbg` receives the phase stamps, not taps)
 #endif
-  if (!taps && ragged_pair(lay, L)) {
-    // seq_len 50, hidden 50: the ragged pair (the forward wrote checkpoints for the rows of the computed tiles only)
-    rc = srfrd_bwd_ragged_launch(&a, grid, ragged_variant(lay), stream);
-    if (rc != SRFRD_E_UNSUPPORTED) return rc;
-  }
-  if (two_per_cu(lay, L) && !taps && getenv("SRFRD_NO_SLOTS50") == nullptr && getenv("SRFRD_GENERIC") == nullptr &&
-      getenv("SRFRD_NO_LSPEC") == nullptr) {
-    // seq_len 50 (fused training step or autograd backward): the slot-placed kernel, two workgroups per CU.  (The switches
-    // select the first-generation kernel on the same grid - one sequence per workgroup, half of them resident at a time.)
-    rc = srfrd_bwd_slots_launch(&a, grid, L, slots_variant(lay), stream);
-    if (rc != SRFRD_E_UNSUPPORTED) return rc;
-  }
-  if (lds > kLdsLimit && !taps && lay->D == 50 && lay->n_heads == 1 &&
-      getenv("SRFRD_NO_SLOTS") == nullptr && getenv("SRFRD_GENERIC") == nullptr) {
-    // a long sequence (fused training step or autograd backward): the slot-placed, query-chunked LDS-resident kernel where
-    // one is built, the row-chunked one otherwise
-    const int kv = slots_variant(lay);
-    if (kv >= 0) {
-      rc = getenv("SRFRD_NO_SLOT_KERNEL") ? SRFRD_E_UNSUPPORTED : srfrd_bwd_slots_launch(&a, grid, L, kv, stream);
-      if (rc != SRFRD_E_UNSUPPORTED) return rc;
-      if (getenv("SRFRD_NO_CHUNKS") == nullptr && scratch) {     // other lengths up to 208: the row-chunked kernel
-        const int64_t stride = (bwd_lds_floats(g, lay->n_blocks) + 2 * kSlack + 63) & ~63ll;
-        if (scratch_floats >= stride * grid) {
-          a.scratch = scratch;
-          a.scratch_stride = stride;
-          rc = srfrd_bwd_chunks_launch(&a, grid, kv, stream);
-          if (rc != SRFRD_E_UNSUPPORTED) return rc;
-        }
-      }
-    }
-  }
-  if (lds > kLdsLimit) {                       // long sequence: working set in the caller's global scratch
-    const int64_t stride = (bwd_lds_floats(g, lay->n_blocks) + 2 * kSlack + 63) & ~63ll;
-    if (!scratch || scratch_floats < stride * grid) return SRFRD_E_UNSUPPORTED;
+  const KernelPlan k = encoder_plan(*lay, B, L, mode, sw, num_cu(), scratch ? scratch_floats : 0).bwd;
+  if (k.rc) return k.rc;
+  if (k.scratch_stride) {
     a.scratch = scratch;
-    a.scratch_stride = stride;
-    const bool c4 = lay->kind == SRFRD_SASREC && lay->D == 50 && lay->n_heads == 1 && L == 100 && pos_ids && neg_ids && fused_bce && !d_hidden &&
-                    dropout_p > 0.0 && !dbg && getenv("SRFRD_NO_LSPEC") == nullptr && getenv("SRFRD_GENERIC") == nullptr;
-    return srfrd_long_launch_bwd(&a, grid, 512, c4 ? 1 : 0, stream);
+    a.scratch_stride = k.scratch_stride;
   }
-  const int threads = env_threads("SRFRD_BWD_THREADS", 512);
-  const bool spec = getenv("SRFRD_GENERIC") == nullptr && threads == 512 && lay->D == 50 && lay->n_heads == 1;
-  if (spec && g.LP == 64 && L == 50 && getenv("SRFRD_NO_LSPEC") == nullptr)
-  {
-    const bool train = pos_ids && neg_ids && fused_bce && !d_hidden && dropout_p > 0.0 && !dbg && getenv("SRFRD_NO_TSPEC") == nullptr;
-    const bool kspec = getenv("SRFRD_NO_KSPEC") == nullptr;
-#define SRFRD_LAUNCH(K, DI) (train ? launch_enc(encoder_bwd_kernel<50, 64, 8, 50, K, 1, DI>, grid, threads, lds, stream, a) \
-                                  : launch_enc(encoder_bwd_kernel<50, 64, 8, 50, K, 0, DI>, grid, threads, lds, stream, a))
-    if (kspec && lay->kind == SRFRD_SASREC) return SRFRD_LAUNCH(SRFRD_SASREC, 50);
-    if (kspec && lay->kind >= SRFRD_SRFU_B && lay->d_item == 50) return SRFRD_LAUNCH(-1, 50);
-    if (kspec && lay->kind == SRFRD_SRFRN && lay->d_item == 45) return SRFRD_LAUNCH(SRFRD_SRFRN, 45);
-    if (kspec && lay->kind == SRFRD_SRFR && lay->d_item == 45) return SRFRD_LAUNCH(SRFRD_SRFR, 45);
-#undef SRFRD_LAUNCH
-    return launch_enc(encoder_bwd_kernel<50, 64, 8, 50>, grid, threads, lds, stream, a);
+  switch (k.family) {
+    case kBwdRagged: return launch_bwd_ragged(k, a, stream);
+    case kBwdSlots: return launch_bwd_slots(k, a, stream);
+    case kBwdChunks: return launch_bwd_chunks(k, a, stream);
+    case kBwdLong: return launch_bwd_long(k, &a, stream);
+    default: return launch_bwd_first(k, a, stream);
   }
-  if (spec && g.LP == 64) return launch_enc(encoder_bwd_kernel<50, 64, 8>, grid, threads, lds, stream, a);
-  if (spec && g.LP == 32) return launch_enc(encoder_bwd_kernel<50, 32, 8>, grid, threads, lds, stream, a);
-  return launch_enc(encoder_bwd_kernel<0, 0, 0>, grid, threads, lds, stream, a);
 }
 
 extern "C" int srfrd_encoder_bwd(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,

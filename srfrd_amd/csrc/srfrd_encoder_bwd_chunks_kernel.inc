@@ -20,16 +20,7 @@
 // debug taps.
 namespace SRFRD_NS {
 
-constexpr int kCkWaves = 8;
-constexpr int kCkRows = 48;            // rows of a chunk (three 16-row tiles)
-
-__host__ __device__ constexpr int64_t chunks_lds_floats(int L, int D, int n_blocks) {
-  const int LP = (L + 15) & ~15, DS = ((D + 3) & ~3) + 2, LR = (L + 3) & ~3;
-  // K | V, then a pool that is the score chunk + two chunk slots (attention pass) or five chunk slots (projection pass)
-  const int64_t pool_att = (int64_t)kCkRows * (LR + 2) + 2ll * kCkRows * DS, pool_prj = 5ll * kCkRows * DS;
-  return 2ll * LR * DS + (pool_att > pool_prj ? pool_att : pool_prj) + 11ll * LP + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
-}
-__host__ __device__ constexpr int64_t chunks_scratch_floats(int L, int D) { return 3ll * (((L + 3) & ~3) * D + 64); }
+// (kCkWaves, kCkRows, chunks_lds_floats, chunks_scratch_floats: srfrd_enc_common.h, where the kernel plan reads them)
 
 // the two row tiles of a (4 x 4 tile) weight gradient a wave owns (wave_tiles(8, 4, 4): strip wave % 4, tiles g, g + 2)
 struct DwAcc {

@@ -61,16 +61,9 @@ __global__ void __launch_bounds__(NW_ > 0 ? NW_ * 64 : 512) encoder_bwd_kernel(c
 #endif
   lds_f* tail = carve(tailsz);
   lds_f *bX, *bQN, *bQ, *bK, *bV, *bO, *bG, *bT, *S1, *S2;
-#ifdef SRFRD_BUF_GLOBAL
-  if (a.carve_mode == 0) { S1 = carve(szS); S2 = carve(szS + kSlack); }
-#endif
   bX = carve(szA); bQN = carve(szA); bQ = carve(szA); bK = carve(szA);
   bV = carve(szA); bO = carve(szA); bG = carve(szA); bT = carve(szA + kSlack);
-#ifdef SRFRD_BUF_GLOBAL
-  if (a.carve_mode != 0) { S1 = carve(szS); S2 = carve(szS + kSlack); }
-#else
   S1 = carve(szS); S2 = carve(szS + kSlack);
-#endif
   lds_i* s_in = (lds_i*)tail;
   lds_f* s_keep = tail + LP;
   lds_i* s_pid = (lds_i*)(tail + 2 * LP);

@@ -6,28 +6,23 @@
 
 #include <cstring>
 
-// args: the caller's srfrd::EncArgs (identical layout) with scratch / scratch_stride filled in
+namespace srfrd {
+
 template <class K>
-static int launch_long(K kernel, const srfrd_long::EncArgs& a, int grid, int threads, void* stream) {
-  static bool s_attr = false;           // one per instantiation
-  if (!s_attr) {
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, srfrd_long::kLdsLimit) != hipSuccess)
-      return SRFRD_E_DEVICE;
-    s_attr = true;
-  }
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), (size_t)a.lds_floats * 4, (hipStream_t)stream, a);
+static int launch_long(K kernel, const KernelPlan& k, const srfrd_long::EncArgs& a, void* stream) {
+  if (const int rc = lds_opt_in((const void*)kernel, srfrd_long::kLdsLimit)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(k.grid), dim3(k.threads), (size_t)k.lds, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
 
-// variant 1: SASRec, hidden 50, seq_len 100, fused training step (BASELINE configs[3] geometry) - compile-time shape
-extern "C" int srfrd_long_launch_bwd(const void* args, int grid, int threads, int variant, void* stream) {
+// args: the caller's srfrd::EncArgs (identical layout); the plan sized scratch / scratch_stride and the LDS share.
+// kL100: SASRec, hidden 50, seq_len 100, fused training step (BASELINE configs[3] geometry) - compile-time shape
+int launch_bwd_long(const KernelPlan& k, const void* args, void* stream) {
   srfrd_long::EncArgs a;
   std::memcpy(&a, args, sizeof(a));
-  // as much of the working set as fits goes to LDS (flat addressing), the rest to the caller's scratch
-  a.lds_floats = (srfrd_long::kLdsLimit / 4) - 64;
-  const char* mode = getenv("SRFRD_CARVE");
-  a.carve_mode = mode ? atoi(mode) : 1;
-  if (variant == 1 && threads == 512)
-    return launch_long(srfrd_long::encoder_bwd_kernel<50, 112, 8, 100, SRFRD_SASREC, 1, 50>, a, grid, threads, stream);
-  return launch_long(srfrd_long::encoder_bwd_kernel<0, 0, 0>, a, grid, threads, stream);
+  a.lds_floats = (int)(k.lds / 4);      // as much of the working set as fits goes to LDS (flat addressing), the rest to scratch
+  if (k.form == kL100) return launch_long(srfrd_long::encoder_bwd_kernel<50, 112, 8, 100, SRFRD_SASREC, 1, 50>, k, a, stream);
+  return launch_long(srfrd_long::encoder_bwd_kernel<0, 0, 0>, k, a, stream);
 }
+
+}  // namespace srfrd

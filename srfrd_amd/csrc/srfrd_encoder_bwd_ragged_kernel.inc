@@ -19,10 +19,7 @@
 // Same sums in another order than the full kernel: fp32 rounding-level differences, the oracle bar unchanged.
 namespace SRFRD_NS {
 
-__host__ __device__ constexpr int64_t bwd_ragged_lds_floats(int n_blocks) {
-  // guard (12 rows) + six [52][54] slots + 12 per-row arrays + misc + two LayerNorm caches + slack
-  return 12ll * 54 + 6ll * 52 * 54 + 12ll * 64 + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
-}
+// (bwd_ragged_lds_floats: srfrd_enc_common.h, where the kernel plan reads it)
 
 template <int K_, int DI_, bool RMW_>
 __global__ void __launch_bounds__(512, 4) encoder_bwd_ragged_kernel(const EncArgs a) {
@@ -154,7 +151,6 @@ __global__ void __launch_bounds__(512, 4) encoder_bwd_ragged_kernel(const EncArg
     const int mt0 = kr >> 4, r0 = mt0 << 4, mtn = MT - mt0;
     const int p0 = r0 > SH ? r0 - SH : 0;                    // first position of the computed tiles
     const int k0 = p0 + SH;                                  // first token of the token sums (tile coordinates)
-    if (a.long_prio > 0) { if (mtn >= 3) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0); }
     // head: tiles from the first position with an upstream gradient (never behind the blocks' range)
     const int hp = th < krp ? th : krp;
     const int mh0 = (hp + SH) >> 4, rh0 = mh0 << 4, mhn = MT - mh0;

@@ -23,15 +23,10 @@
 // debug taps (those run srfrd_encoder_bwd_long.hip).
 namespace SRFRD_NS {
 
-constexpr int kSlotWaves = 8;
+// (kSlotWaves, slots_R, slots_lds_floats: srfrd_enc_common.h, where the kernel plan reads them)
 constexpr int kChunkRows = 48;         // query rows of an attention-backward chunk (three 16-row tiles)
 
-__host__ __device__ constexpr int slots_R(int L) { return (L + 3) & ~3; }
 __host__ __device__ constexpr int slots_chunks(int L) { return slots_R(L) <= kChunkRows + 4 ? 1 : (slots_R(L) - 4 + kChunkRows - 1) / kChunkRows; }
-__host__ __device__ constexpr int64_t slots_lds_floats(int L, int D, int n_blocks) {
-  const int LP = (L + 15) & ~15, DS = ((D + 3) & ~3) + 2;
-  return 6ll * slots_R(L) * DS + 11ll * LP + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
-}
 
 template <int D_, int L_, int K_, int DI_, bool RMW_>
 __global__ void __launch_bounds__(kSlotWaves * 64, (L_ <= 52 ? 4 : 2)) encoder_bwd_slots_kernel(const EncArgs a) {

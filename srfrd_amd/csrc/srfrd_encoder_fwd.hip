@@ -49,10 +49,6 @@ __global__ void __launch_bounds__(256) pack_weights_kernel(const srfrd_layout ly
 
 using namespace srfrd;
 
-extern "C" int srfrd_long_launch_fwd(const void* args, int grid, int threads, void* stream);   // srfrd_encoder_fwd_long.hip
-extern "C" int srfrd_fwd_rows_launch(const void* args, int kind_variant, int mode, void* stream);   // srfrd_encoder_fwd_rows.hip
-extern "C" int srfrd_fwd_ragged_launch(const void* args, int kind_variant, int train, int grid, void* stream);   // srfrd_encoder_fwd_ragged.hip
-
 extern "C" int64_t srfrd_aux_floats(const srfrd_layout* lay, int B, int L) {
   if (!lay || B <= 0 || L <= 0) return SRFRD_E_ARG;
   const Geom g = make_geom(L, lay->D);
@@ -66,7 +62,7 @@ extern "C" int srfrd_scratch_floats(const srfrd_layout* lay, int B, int L, int64
   int gf = num_cu();
   if (gf > B) gf = B;
   if (fwd_floats) *fwd_floats = f * 4 <= kLdsLimit ? 0 : ((f + 2 * kSlack + 63) & ~63ll) * gf;
-  if (bwd_floats) *bwd_floats = bw * 4 <= kLdsLimit ? 0 : ((bw + 2 * kSlack + 63) & ~63ll) * srfrd_bwd_grid(lay, B, L);
+  if (bwd_floats) *bwd_floats = bw * 4 <= kLdsLimit ? 0 : ((bw + 2 * kSlack + 63) & ~63ll) * bwd_grid(*lay, B, L, num_cu());
   return 0;
 }
 
@@ -100,6 +96,173 @@ extern "C" int srfrd_debug_shape(const srfrd_layout* lay, int L, int64_t* slot_f
   return 0;
 }
 
+// ================================================================================================
+// kernel plan (srfrd_enc_plan.h): the one place that chooses an instantiation
+// ================================================================================================
+namespace srfrd {
+
+int bwd_grid(const srfrd_layout& lay, int B, int L, int n_cu) {
+  // The reference's default geometry (seq_len 50, hidden 50: BASELINE configs[1] / [2]) runs the slot-placed or ragged
+  // backward with six [52][54] slots = 76 KB of LDS: TWO workgroups per CU, where the first-generation kernel's ten
+  // matrices (150 KB) allow one.  A function of the shape only (never of the switches: callers size `grad_slabs` with it).
+  const int wgs = n_cu * (L == 50 && kind_variant(lay) >= 0 ? 2 : 1);
+  return B < wgs ? B : wgs;
+}
+
+static KernelPlan kernel(Family fam, int form, int variant, bool flag, int grid, int threads, int64_t lds, int64_t stride = 0) {
+  return KernelPlan{0, fam, form, variant, flag, grid, threads, lds, stride};
+}
+static KernelPlan unsupported() { return KernelPlan{SRFRD_E_UNSUPPORTED, 0, 0, -1, false, 0, 0, 0, 0}; }
+static bool fits(int64_t floats) { return floats * 4 <= kLdsLimit; }
+static int64_t scratch_stride(int64_t lds_floats) { return (lds_floats + 2 * kSlack + 63) & ~63ll; }
+
+EncPlan encoder_plan(const srfrd_layout& lay, int B, int L, int mode, int sw, int n_cu, int64_t scratch_floats) {
+  const Geom g = make_geom(L, lay.D);
+  const int nb = lay.n_blocks, kv = kind_variant(lay);
+  const bool taps = mode & SRFRD_PLAN_TAPS;
+  const bool generic = sw & SRFRD_SW_GENERIC;
+  // the hidden-50, one-head instantiations (several attention heads: the generic instantiation only)
+  const bool spec = !generic && lay.D == 50 && lay.n_heads == 1;
+  const int kFwdTrain = SRFRD_PLAN_POS | SRFRD_PLAN_NEG | SRFRD_PLAN_CKPT | SRFRD_PLAN_LOSS | SRFRD_PLAN_DROPOUT;
+  const int kBwdTrain = SRFRD_PLAN_POS | SRFRD_PLAN_NEG | SRFRD_PLAN_FUSED_BCE | SRFRD_PLAN_DROPOUT;
+  const bool fwd_train = (mode & kFwdTrain) == kFwdTrain && !taps, bwd_train = (mode & kBwdTrain) == kBwdTrain && !taps;
+  const bool plain = (mode & kFwdTrain) == 0;          // eval-mode hidden states only
+  // The ragged seq_len-50 pair exchanges checkpoints that hold only the rows of the computed tiles: the forward and the
+  // backward take it from this ONE decision.  Debug taps want every row of every intermediate: the full kernels.
+  const bool ragged = L == 50 && kv >= 0 && !taps && !(sw & (SRFRD_SW_NO_RAGGED | SRFRD_SW_GENERIC | SRFRD_SW_NO_SLOTS50 | SRFRD_SW_ROWS_ALWAYS)) &&
+                      fits(fwd_lds_floats(g, nb)) && fits(bwd_ragged_lds_floats(nb));
+  EncPlan p;
+
+  // ---- forward ----
+  const int64_t fl = fwd_lds_floats(g, nb);
+  const int fgrid_cu = n_cu < B ? n_cu : B;
+  // the row-owner kernel (K / V resident in LDS): every long sequence it covers.  (Measured against the first-generation
+  // kernel where both fit: 185 vs 170 us per 512-sequence training forward at seq_len 100, 117 vs 59 us at seq_len 50 - with
+  // 7 or 4 row tiles it runs one or two waves per SIMD and their dependent chains are exposed; SRFRD_ROWS_ALWAYS selects it
+  // anyway, for tests.)
+  if ((!fits(fl) || (sw & SRFRD_SW_ROWS_ALWAYS)) && !taps && kv >= 0 && !(sw & (SRFRD_SW_NO_ROWS | SRFRD_SW_GENERIC)) &&
+      L <= 16 * kRowMaxTiles && fits(rows_lds_floats(L, 50, nb))) {
+    p.fwd = kernel(kFwdRows, kGeneric, kv, !plain, fgrid_cu, kRowWaves * 64, rows_lds_floats(L, 50, nb) * 4);
+  } else if (!fits(fl)) {                 // long sequence: working set in the caller's global scratch
+    const int64_t stride = scratch_stride(fl);
+    p.fwd = scratch_floats < stride * fgrid_cu ? unsupported()
+                                               : kernel(kFwdLong, kGeneric, -1, false, fgrid_cu, 256, (kLdsLimit / 4 - 64) * 4ll, stride);
+  } else {
+    const int per_cu = (int)(kLdsLimit / (fl * 4)) > 2 ? 2 : (int)(kLdsLimit / (fl * 4));
+    int grid = n_cu * (per_cu < 1 ? 1 : per_cu);
+    if (grid > B) grid = B;
+    // 8 waves per workgroup measured fastest for the forward (95 vs 118 us at C2 with 4 waves)
+    if (ragged) p.fwd = kernel(kFwdRagged, kGeneric, kv, fwd_train, grid, 512, fl * 4);
+    else if (spec && L == 50) p.fwd = kernel(kFwdFirst, kL50, kv, kv >= 0 && fwd_train, grid, 512, fl * 4);
+    // BASELINE configs[3] geometry (seq_len 100): still LDS-resident in the forward, one workgroup per CU.  The training
+    // instantiation runs 16 waves (7 x 4 tiles per weight GEMM: two rounds instead of three and a half; 0.468 -> 0.462 ms
+    // per C4 step - the 128-register budget of a 1024-thread workgroup takes back most of what the extra waves give)
+    else if (spec && L == 100 && lay.kind == SRFRD_SASREC) p.fwd = kernel(kFwdFirst, kL100, 0, fwd_train, grid, fwd_train ? 1024 : 512, fl * 4);
+    else if (spec && g.LP == 64) p.fwd = kernel(kFwdFirst, kLP64, -1, false, grid, 512, fl * 4);
+    else if (spec && g.LP == 32) p.fwd = kernel(kFwdFirst, kLP32, -1, false, grid, 512, fl * 4);
+    else p.fwd = kernel(kFwdFirst, kGeneric, -1, false, grid, 512, fl * 4);
+  }
+
+  // ---- backward ----
+  const int64_t bl = bwd_lds_floats(g, nb);
+  const int grid = bwd_grid(lay, B, L, n_cu);
+  const bool rmw = B > grid;              // some workgroup takes a second sequence: its slab entries are read-modify-written
+  const int64_t stride = scratch_stride(bl);
+  const bool slots = (L == 50 || L == 100) && kv >= 0 && !taps && fits(slots_lds_floats(L, 50, nb));
+  if (ragged) {
+    p.bwd = kernel(kBwdRagged, kGeneric, kv, rmw, grid, 512, bwd_ragged_lds_floats(nb) * 4);
+  } else if (slots && L == 50 && !(sw & (SRFRD_SW_NO_SLOTS50 | SRFRD_SW_GENERIC))) {
+    // seq_len 50 (fused training step or autograd backward): the slot-placed kernel, two workgroups per CU.  (The switches
+    // select the first-generation kernel on the same grid - one sequence per workgroup, half of them resident at a time.)
+    p.bwd = kernel(kBwdSlots, kL50, kv, rmw, grid, kSlotWaves * 64, slots_lds_floats(L, 50, nb) * 4);
+  } else if (!fits(bl) && !taps && kv >= 0 && !(sw & (SRFRD_SW_NO_SLOTS | SRFRD_SW_GENERIC)) && slots) {
+    // a long sequence (fused training step or autograd backward): the slot-placed, query-chunked LDS-resident kernel where
+    // one is built, the row-chunked one for the other lengths up to 208
+    p.bwd = kernel(kBwdSlots, L == 50 ? kL50 : kL100, kv, rmw, grid, kSlotWaves * 64, slots_lds_floats(L, 50, nb) * 4);
+  } else if (!fits(bl) && !taps && kv >= 0 && !(sw & (SRFRD_SW_NO_SLOTS | SRFRD_SW_GENERIC)) && scratch_floats >= stride * grid &&
+             L >= 17 && L <= 208 && fits(chunks_lds_floats(L, 50, nb)) && stride >= chunks_scratch_floats(L, 50)) {
+    p.bwd = kernel(kBwdChunks, kGeneric, kv, rmw, grid, kCkWaves * 64, chunks_lds_floats(L, 50, nb) * 4, stride);
+  } else if (!fits(bl)) {                 // long sequence: working set in the caller's global scratch
+    const bool c4 = spec && kv == 0 && L == 100 && bwd_train;
+    p.bwd = scratch_floats < stride * grid ? unsupported()
+                                           : kernel(kBwdLong, c4 ? kL100 : kGeneric, c4 ? 0 : -1, c4, grid, 512, (kLdsLimit / 4 - 64) * 4ll, stride);
+  } else if (spec && L == 50) {
+    p.bwd = kernel(kBwdFirst, kL50, kv, kv >= 0 && bwd_train, grid, 512, bl * 4);
+  } else {
+    p.bwd = kernel(kBwdFirst, spec && g.LP == 64 ? kLP64 : spec && g.LP == 32 ? kLP32 : kGeneric, -1, false, grid, 512, bl * 4);
+  }
+  return p;
+}
+
+// template arguments of the first-generation kernels (all seven: a trace prints the defaults too)
+static void first_targs(const KernelPlan& k, int t[7]) {
+  const int gen[7] = {0, 0, 0, 0, -1, 0, 0};
+  for (int i = 0; i < 7; ++i) t[i] = gen[i];
+  if (k.form == kGeneric) return;
+  t[0] = 50; t[2] = 8;
+  t[1] = k.form == kLP32 ? 32 : k.form == kL100 ? 112 : 64;
+  if (k.form == kL50 || k.form == kL100) {
+    t[3] = k.form == kL50 ? 50 : 100;
+    if (k.variant >= 0) { t[4] = kKindVariants[k.variant].K; t[5] = k.flag; t[6] = kKindVariants[k.variant].DI; }
+    if (k.form == kL100 && k.family == kFwdFirst && k.flag) t[2] = 16;
+  }
+}
+
+void plan_name(const KernelPlan& k, char* buf, int len) {
+  if (len <= 0) return;
+  buf[0] = 0;
+  if (k.rc) return;
+  const KindVariant v = kKindVariants[k.variant < 0 ? 3 : k.variant];
+  const char* tf = k.flag ? "true" : "false";
+  int t[7];
+  switch (k.family) {
+    case kFwdFirst: case kBwdFirst: case kFwdLong: case kBwdLong:
+      first_targs(k, t);
+      snprintf(buf, len, "%s::encoder_%s_kernel<%d,%d,%d,%d,%d,%d,%d>", k.family == kFwdLong || k.family == kBwdLong ? "srfrd_long" : "srfrd",
+               k.family == kFwdFirst || k.family == kFwdLong ? "fwd" : "bwd", t[0], t[1], t[2], t[3], t[4], t[5], t[6]);
+      return;
+    case kFwdRows: snprintf(buf, len, "srfrd::encoder_fwd_rows_kernel<50,%d,%d,%d>", v.K, v.DI, (int)k.flag); return;
+    case kFwdRagged: snprintf(buf, len, "srfrd::encoder_fwd_ragged_kernel<%d,%d,%d>", v.K, (int)k.flag, v.DI); return;
+    case kBwdRagged: snprintf(buf, len, "srfrd::encoder_bwd_ragged_kernel<%d,%d,%s>", v.K, v.DI, tf); return;
+    case kBwdSlots: snprintf(buf, len, "srfrd::encoder_bwd_slots_kernel<50,%d,%d,%d,%s>", k.form == kL50 ? 50 : 100, v.K, v.DI, tf); return;
+    case kBwdChunks: snprintf(buf, len, "srfrd::encoder_bwd_chunks_kernel<50,%d,%d,%s>", v.K, v.DI, tf); return;
+  }
+}
+
+int launch_fwd_first(const KernelPlan& k, const EncArgs& a, void* stream) {
+  switch (k.form) {
+    case kL50:
+      if (k.variant < 0) return launch_enc(encoder_fwd_kernel<50, 64, 8, 50>, k, stream, a);
+      return with_variant(k.variant, [&](auto v) {
+        constexpr KindVariant kv = kKindVariants[decltype(v)::value];
+        return with_flag(k.flag, [&](auto t) { return launch_enc(encoder_fwd_kernel<50, 64, 8, 50, kv.K, decltype(t)::value, kv.DI>, k, stream, a); });
+      });
+    case kL100:
+      return k.flag ? launch_enc(encoder_fwd_kernel<50, 112, 16, 100, SRFRD_SASREC, 1, 50>, k, stream, a)
+                    : launch_enc(encoder_fwd_kernel<50, 112, 8, 100, SRFRD_SASREC, 0, 50>, k, stream, a);
+    case kLP64: return launch_enc(encoder_fwd_kernel<50, 64, 8>, k, stream, a);
+    case kLP32: return launch_enc(encoder_fwd_kernel<50, 32, 8>, k, stream, a);
+    default: return launch_enc(encoder_fwd_kernel<0, 0, 0>, k, stream, a);
+  }
+}
+
+}  // namespace srfrd
+
+extern "C" int srfrd_encoder_plan(const srfrd_layout* lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats,
+                                  char* fwd_name, char* bwd_name, int name_len, int32_t* grids) {
+  if (!lay || B <= 0 || L <= 0 || n_cu <= 0 || scratch_floats < 0 || !grids) return SRFRD_E_ARG;
+  EncPlan p;
+  if (lay->D > SRFRD_MAX_D || lay->n_heads < 1 || lay->D % lay->n_heads != 0 || lay->n_blocks > SRFRD_MAX_BLOCKS)
+    p.fwd = p.bwd = unsupported();             // (what fill_args answers)
+  else
+    p = encoder_plan(*lay, B, L, mode, switches, n_cu, scratch_floats);
+  if (fwd_name) plan_name(p.fwd, fwd_name, name_len);
+  if (bwd_name) plan_name(p.bwd, bwd_name, name_len);
+  grids[0] = p.fwd.rc ? p.fwd.rc : p.fwd.grid;
+  grids[1] = p.bwd.rc ? p.bwd.rc : p.bwd.grid;
+  return 0;
+}
+
 static int encoder_fwd_impl(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
                             const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids,
                             const int64_t* pos_fake, const int64_t* neg_ids, const int64_t* neg_fake, int B, int L,
@@ -107,12 +270,12 @@ static int encoder_fwd_impl(const srfrd_layout* lay, const void* item_table, con
                             float* hidden, float* pos_logits, float* neg_logits, float* save_x, float* save_h1,
                             float* save_aux, float* loss_part, float* scratch, int64_t scratch_floats, float* dbg, int dbg_seq,
                             int last_only, const int32_t* sched, int sched_mode, void* stream) {
+  const int sw = read_switches();
   EncArgs a = {};
   a.last_only = last_only;
   a.sched = sched_mode != 0 ? sched : nullptr;
   a.sched_mode = a.sched ? sched_mode : 0;
-  a.ragged_off = getenv("SRFRD_RAGGED_FULL_ROWS") != nullptr;
-  { const char* e = getenv("SRFRD_LONG_PRIO"); a.long_prio = e ? atoi(e) : 0; }
+  a.ragged_off = (sw & SRFRD_SW_RAGGED_FULL_ROWS) != 0;
   int rc = fill_args(a, lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L,
                      dropout_p, seed, seed_dev, seq_index0);
   if (rc) return rc;
@@ -123,81 +286,23 @@ static int encoder_fwd_impl(const srfrd_layout* lay, const void* item_table, con
   a.save_x = save_x; a.save_h1 = save_h1; a.save_aux = save_aux; a.loss_part = loss_part;
   a.dbg = dbg; a.dbg_seq = dbg_seq;
   srfrd_debug_shape(lay, L, &a.dbg_slot, nullptr);
-  const Geom g = make_geom(L, lay->D);
-  const int64_t lds = fwd_lds_floats(g, lay->n_blocks) * 4;
-  const bool plain = !pos_ids && !neg_ids && !save_x && !loss_part && dropout_p == 0.0;       // eval-mode hidden states only
-  // the row-owner kernel (K / V resident in LDS): every long sequence it covers.  (Measured against the first-generation
-  // kernel where both fit: 185 vs 170 us per 512-sequence training forward at seq_len 100, 117 vs 59 us at seq_len 50 - with
-  // 7 or 4 row tiles it runs one or two waves per SIMD and their dependent chains are exposed; SRFRD_ROWS_ALWAYS selects it
-  // anyway, for tests.)
-  const bool rows_wanted = lds > kLdsLimit || getenv("SRFRD_ROWS_ALWAYS") != nullptr;
-  if (rows_wanted && !dbg && lay->D == 50 && lay->n_heads == 1 && getenv("SRFRD_NO_ROWS") == nullptr && getenv("SRFRD_GENERIC") == nullptr) {
-    int kv = -1;
-    if (lay->kind == SRFRD_SASREC) kv = 0;
-    else if (lay->kind == SRFRD_SRFR && lay->d_item == 45) kv = 1;
-    else if (lay->kind == SRFRD_SRFRN && lay->d_item == 45) kv = 2;
-    else if (lay->kind >= SRFRD_SRFU_B && lay->d_item == 50) kv = 3;
-    if (kv >= 0) {
-      rc = srfrd_fwd_rows_launch(&a, kv, plain ? 0 : 1, stream);
-      if (rc != SRFRD_E_UNSUPPORTED) return rc;
-    }
-  }
-  if (lds > kLdsLimit) {                       // long sequence: working set in the caller's global scratch
-    int grid = num_cu();
-    if (grid > B) grid = B;
-    const int64_t stride = (fwd_lds_floats(g, lay->n_blocks) + 2 * kSlack + 63) & ~63ll;
-    if (!scratch || scratch_floats < stride * grid) return SRFRD_E_UNSUPPORTED;
-    a.scratch = scratch;
-    a.scratch_stride = stride;
-    return srfrd_long_launch_fwd(&a, grid, 256, stream);
-  }
-  const int per_cu = (int)(kLdsLimit / lds) > 2 ? 2 : (int)(kLdsLimit / lds);
-  int grid = num_cu() * (per_cu < 1 ? 1 : per_cu);
-  if (grid > B) grid = B;
-  // The reference's default geometry: the ragged kernel (rows of the left-padded sequence only).  A forward that writes
-  // training checkpoints takes it exactly when the backward of this (layout, length) will be the ragged one (ragged_pair);
-  // debug taps want every row of every intermediate: the full kernel.
-#ifdef SRFRD_STAMPS
-  const bool taps_f = false;                   // (diagnostic build: `dbg` receives the phase stamps)
-#else
-  const bool taps_f = dbg != nullptr;
+  int mode = (pos_ids ? SRFRD_PLAN_POS : 0) | (neg_ids ? SRFRD_PLAN_NEG : 0) | (save_x ? SRFRD_PLAN_CKPT : 0) |
+             (loss_part ? SRFRD_PLAN_LOSS : 0) | (dropout_p > 0.0 ? SRFRD_PLAN_DROPOUT : 0);
+#ifndef SRFRD_STAMPS
+  if (dbg) mode |= SRFRD_PLAN_TAPS;            // (diagnostic build: `dbg` receives the phase stamps, not taps)
 #endif
-  if (!taps_f && ragged_pair(lay, L)) {
-    const bool train = pos_ids && neg_ids && save_x && loss_part && dropout_p > 0.0 && getenv("SRFRD_NO_TSPEC") == nullptr;
-    rc = srfrd_fwd_ragged_launch(&a, ragged_variant(lay), train ? 1 : 0, grid, stream);
-    if (rc != SRFRD_E_UNSUPPORTED) return rc;
+  const KernelPlan k = encoder_plan(*lay, B, L, mode, sw, num_cu(), scratch ? scratch_floats : 0).fwd;
+  if (k.rc) return k.rc;
+  if (k.scratch_stride) {
+    a.scratch = scratch;
+    a.scratch_stride = k.scratch_stride;
   }
-  // 8 waves per workgroup measured fastest for the forward (95 vs 118 us at C2 with 4 waves)
-  const int threads = env_threads("SRFRD_FWD_THREADS", 512);
-  // (several attention heads: the generic instantiation only)
-  const bool spec = getenv("SRFRD_GENERIC") == nullptr && lay->D == 50 && lay->n_heads == 1;
-  if (spec && threads == 512 && g.LP == 64 && L == 50 && getenv("SRFRD_NO_LSPEC") == nullptr)
-  {
-    const bool train = pos_ids && neg_ids && save_x && loss_part && dropout_p > 0.0 && !dbg && getenv("SRFRD_NO_TSPEC") == nullptr;
-    const bool kspec = getenv("SRFRD_NO_KSPEC") == nullptr;
-#define SRFRD_LAUNCH(K, DI) (train ? launch_enc(encoder_fwd_kernel<50, 64, 8, 50, K, 1, DI>, grid, threads, lds, stream, a) \
-                                  : launch_enc(encoder_fwd_kernel<50, 64, 8, 50, K, 0, DI>, grid, threads, lds, stream, a))
-    if (kspec && lay->kind == SRFRD_SASREC) return SRFRD_LAUNCH(SRFRD_SASREC, 50);
-    if (kspec && lay->kind >= SRFRD_SRFU_B && lay->d_item == 50) return SRFRD_LAUNCH(-1, 50);
-    if (kspec && lay->kind == SRFRD_SRFRN && lay->d_item == 45) return SRFRD_LAUNCH(SRFRD_SRFRN, 45);
-    if (kspec && lay->kind == SRFRD_SRFR && lay->d_item == 45) return SRFRD_LAUNCH(SRFRD_SRFR, 45);
-#undef SRFRD_LAUNCH
-    return launch_enc(encoder_fwd_kernel<50, 64, 8, 50>, grid, threads, lds, stream, a);
+  switch (k.family) {
+    case kFwdRows: return launch_fwd_rows(k, a, stream);
+    case kFwdRagged: return launch_fwd_ragged(k, a, stream);
+    case kFwdLong: return launch_fwd_long(k, &a, stream);
+    default: return launch_fwd_first(k, a, stream);
   }
-  if (spec && threads == 512 && L == 100 && lay->kind == SRFRD_SASREC && getenv("SRFRD_NO_LSPEC") == nullptr) {
-    // BASELINE configs[3] geometry (seq_len 100): still LDS-resident in the forward, one workgroup per CU.  The training
-    // instantiation runs 16 waves (7 x 4 tiles per weight GEMM: two rounds instead of three and a half; 0.468 -> 0.462 ms
-    // per C4 step - the 128-register budget of a 1024-thread workgroup takes back most of what the extra waves give)
-    const bool train = pos_ids && neg_ids && save_x && loss_part && dropout_p > 0.0 && !dbg;
-    if (train && getenv("SRFRD_FWD_THREADS") == nullptr)
-      return launch_enc(encoder_fwd_kernel<50, 112, 16, 100, SRFRD_SASREC, 1, 50>, grid, 1024, lds, stream, a);
-    return train ? launch_enc(encoder_fwd_kernel<50, 112, 8, 100, SRFRD_SASREC, 1, 50>, grid, threads, lds, stream, a)
-                 : launch_enc(encoder_fwd_kernel<50, 112, 8, 100, SRFRD_SASREC, 0, 50>, grid, threads, lds, stream, a);
-  }
-  if (spec && threads == 512 && g.LP == 64) return launch_enc(encoder_fwd_kernel<50, 64, 8>, grid, threads, lds, stream, a);
-  if (spec && threads == 512 && g.LP == 32) return launch_enc(encoder_fwd_kernel<50, 32, 8>, grid, threads, lds, stream, a);
-  if (spec && threads == 256 && g.LP == 64) return launch_enc(encoder_fwd_kernel<50, 64, 4>, grid, threads, lds, stream, a);
-  return launch_enc(encoder_fwd_kernel<0, 0, 0>, grid, threads, lds, stream, a);
 }
 
 extern "C" int srfrd_encoder_fwd(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,

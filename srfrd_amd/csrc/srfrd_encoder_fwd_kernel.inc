@@ -43,9 +43,9 @@ __global__ void __launch_bounds__(NW_ > 0 ? NW_ * 64 : 512, NW_ == 8 ? (LP_ <= 6
   lds_f* tail = carve(tailsz);
   lds_f *bXS, *bQN, *bQ, *bK, *bV;
 #ifdef SRFRD_BUF_GLOBAL
-  if (a.carve_mode == 0) bXS = carve(szX + kSlack);
+  // (the activation matrices take the LDS share first; the scores and the input go to scratch when it runs out)
   bQN = carve(szA); bQ = carve(szA); bK = carve(szA); bV = carve(szA + kSlack);
-  if (a.carve_mode != 0) bXS = carve(szX + kSlack);
+  bXS = carve(szX + kSlack);
 #else
   bXS = carve(szX); bQN = carve(szA); bQ = carve(szA); bK = carve(szA); bV = carve(szA + kSlack);
 #endif

@@ -6,22 +6,17 @@
 
 #include <cstring>
 
-// args: the caller's srfrd::EncArgs (identical layout) with scratch / scratch_stride filled in
-extern "C" int srfrd_long_launch_fwd(const void* args, int grid, int threads, void* stream) {
+namespace srfrd {
+
+// args: the caller's srfrd::EncArgs (identical layout); the plan sized scratch / scratch_stride and the LDS share
+int launch_fwd_long(const KernelPlan& k, const void* args, void* stream) {
   srfrd_long::EncArgs a;
   std::memcpy(&a, args, sizeof(a));
-  // as much of the working set as fits goes to LDS (flat addressing), the rest to the caller's scratch
-  a.lds_floats = (srfrd_long::kLdsLimit / 4) - 64;
-  const char* mode = getenv("SRFRD_CARVE");
-  a.carve_mode = mode ? atoi(mode) : 1;
-  static bool s_attr = false;
-  if (!s_attr) {
-    if (hipFuncSetAttribute((const void*)srfrd_long::encoder_fwd_kernel<0, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            srfrd_long::kLdsLimit) != hipSuccess)
-      return SRFRD_E_DEVICE;
-    s_attr = true;
-  }
-  hipLaunchKernelGGL((srfrd_long::encoder_fwd_kernel<0, 0, 0>), dim3(grid), dim3(threads), (size_t)a.lds_floats * 4,
-                     (hipStream_t)stream, a);
+  a.lds_floats = (int)(k.lds / 4);      // as much of the working set as fits goes to LDS (flat addressing), the rest to scratch
+  const auto kernel = srfrd_long::encoder_fwd_kernel<0, 0, 0>;
+  if (const int rc = lds_opt_in((const void*)kernel, srfrd_long::kLdsLimit)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(k.grid), dim3(k.threads), (size_t)k.lds, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
+
+}  // namespace srfrd

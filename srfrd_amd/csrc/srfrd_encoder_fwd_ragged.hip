@@ -6,8 +6,6 @@
 
 #include "srfrd_encoder_fwd_ragged_kernel.inc"
 
-#include <cstring>
-
 namespace srfrd {
 
 // ---- srfrd_seq_order: first non-pad position of every sequence (what the ragged kernels rank the batch by) ----
@@ -39,26 +37,13 @@ extern "C" int srfrd_seq_order(const int64_t* input_ids, int B, int L, int pair_
   return (int)hipGetLastError();
 }
 
-// kind_variant: 0 SASRec (50 + 0), 1 SRFR (45 + 5), 2 SRFRN (45 + 5), 3 SRFU_* (50 + 0, kind read at run time); train: the
-// fused-training instantiation (targets, checkpoints, loss sums, dropout all on).  Geometry is fixed: hidden 50, seq_len 50.
-extern "C" int srfrd_fwd_ragged_launch(const void* args, int kind_variant, int train, int grid, void* stream) {
-  EncArgs a;
-  std::memcpy(&a, args, sizeof(a));
-  if (a.dm.D != 50 || a.L != 50 || a.dm.n_heads != 1 || a.dm.n_blocks > SRFRD_MAX_BLOCKS ) return SRFRD_E_UNSUPPORTED;
-#ifndef SRFRD_STAMPS
-  if (a.dbg) return SRFRD_E_UNSUPPORTED;       // debug taps want every row of every intermediate: the full kernels
-#endif
-  const Geom g = make_geom(50, 50);
-  const int64_t lds = fwd_lds_floats(g, a.dm.n_blocks) * 4;
-  if (lds > kLdsLimit) return SRFRD_E_UNSUPPORTED;
-#define SRFRD_RG(K, DI) (train ? launch_enc(encoder_fwd_ragged_kernel<K, 1, DI>, grid, 512, lds, stream, a) \
-                               : launch_enc(encoder_fwd_ragged_kernel<K, 0, DI>, grid, 512, lds, stream, a))
-  switch (kind_variant) {
-    case 0: return SRFRD_RG(SRFRD_SASREC, 50);
-    case 1: return SRFRD_RG(SRFRD_SRFR, 45);
-    case 2: return SRFRD_RG(SRFRD_SRFRN, 45);
-    case 3: return SRFRD_RG(-1, 50);
-  }
-#undef SRFRD_RG
-  return SRFRD_E_UNSUPPORTED;
+namespace srfrd {
+
+int launch_fwd_ragged(const KernelPlan& k, const EncArgs& a, void* stream) {
+  return with_variant(k.variant, [&](auto v) {
+    constexpr KindVariant kv = kKindVariants[decltype(v)::value];
+    return with_flag(k.flag, [&](auto train) { return launch_enc(encoder_fwd_ragged_kernel<kv.K, decltype(train)::value, kv.DI>, k, stream, a); });
+  });
 }
+
+}  // namespace srfrd

@@ -20,7 +20,7 @@
 // Training checkpoints are written for the rows of the computed tiles only (the ragged backward,
 // srfrd_encoder_bwd_ragged_kernel.inc, reads exactly those); the probability checkpoint of a row carries c_i P_i,rep in
 // the representative's column and t0 P_i,rep in column LP - 1 (spare: L < LP).  The launchers pair this kernel with the
-// ragged backward ONLY (srfrd_ragged_pair): every other backward reads full-row checkpoints.
+// ragged backward ONLY (encoder_plan pairs them): every other backward reads full-row checkpoints.
 //
 // Sequence -> workgroup assignment: static (b = blockIdx.x, += gridDim.x) or, when the launch carries the batch's lengths
 // (EncArgs::sched, srfrd_seq_order), by LENGTH ORDER: workgroup x takes the sequence of rank perm(x) (rag_take) so that the
@@ -458,8 +458,6 @@ __global__ void __launch_bounds__(512, 4) encoder_fwd_ragged_kernel(const EncArg
     const int kr = t0 >= 1 ? v0 - 1 : v0;
     const int mt0 = kr >> 4, r0 = mt0 << 4, mtn = MT - mt0;
     const int tstart = r0 > SH ? r0 - SH : 0;               // first position of the computed tiles
-    // (a long sequence is its CU's critical path: its waves may be given priority over the co-resident short sequence's)
-    if (a.long_prio > 0) { if (mtn >= 3) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(0); }
 
     // ---- embedding: gather + position (+ side channel) + pad mask          (SURVEY 3.4 steps 1-4)
     {

@@ -29,13 +29,7 @@
 // Scope: hidden width 50, 8 waves, seq_len <= 208.
 namespace SRFRD_NS {
 
-constexpr int kRowWaves = 8;
-constexpr int kRowMaxTiles = 13;         // S^T accumulators a lane holds: key tiles of a query tile (seq_len <= 208)
-
-__host__ __device__ constexpr int64_t rows_lds_floats(int L, int D, int n_blocks) {
-  const int LP = (L + 15) & ~15, DS = ((D + 3) & ~3) + 2;
-  return 2ll * LP * DS + (int64_t)kRowWaves * 2 * 16 * DS + 5ll * LP + 64 + ln_cache_floats(n_blocks) + kSlack;
-}
+// (kRowWaves, kRowMaxTiles, rows_lds_floats: srfrd_enc_common.h, where the kernel plan reads them)
 
 // sum / max over the 16 lanes of a DPP row (= the 16 columns a lane group holds of one accumulator row)
 __device__ __forceinline__ float row16_sum(float v) {

@@ -1,6 +1,5 @@
 // Ranking-side kernels: user labels, candidate logits (predict), full-catalog top-k, HR@10 / NDCG@10 ranks.
 // Reference: SRFR_model.py:144-152 (+ :241-259, :532-540, :668-681), :546-570; utils.py:576-598.
-#include <mutex>
 
 #include "srfrd_dev.h"
 
@@ -1287,18 +1286,7 @@ static int launch_tau(const TopkArgs& a, hipStream_t st) {
   const int wpb = 4 * row <= 64 * 1024 ? 4 : 1;
   const size_t lds = wpb * row;
   if (lds > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
-  if (lds > 64 * 1024) {
-    static std::mutex mu;
-    static size_t opted[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SRFRD_E_DEVICE;
-    std::lock_guard<std::mutex> lock(mu);
-    if (lds > opted[dev]) {
-      if (hipFuncSetAttribute((const void*)topk_tau_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return SRFRD_E_DEVICE;
-      opted[dev] = lds;
-    }
-  }
+  if (lds > 64 * 1024 && lds_opt_in((const void*)topk_tau_kernel, (int64_t)lds)) return SRFRD_E_DEVICE;
   hipLaunchKernelGGL(topk_tau_kernel, dim3((a.B + wpb - 1) / wpb), dim3(64 * wpb), lds, st, a);
   return 0;
 }
@@ -1379,35 +1367,26 @@ struct Plan16 {
   dim3 grid;
   TopkArgs h;
 };
-static int plan_stream16(const srfrd_layout* lay, const TopkArgs& a, int dev, Plan16& p, bool excl) {
+static int plan_stream16(const srfrd_layout* lay, const TopkArgs& a, Plan16& p, bool excl) {
   const bool bf16_tab = lay->table_bf16 != 0;
   p.on = getenv("SRFRD_TOPK_FP32") == nullptr &&
          (bf16_tab ? (lay->d_item <= 64 && ((lay->d_item & 1) == 0 || lay->d_item <= 51)) : lay->d_item <= 52);
   if (!p.on) return 0;
-  static std::mutex mu16;
-  static bool opted16[64] = {false};
   {
-    std::lock_guard<std::mutex> lock(mu16);
-    if (!opted16[dev]) {
-      const void* fns[] = {(const void*)topk_max16_kernel<1, false>, (const void*)topk_max16_kernel<2, false>,
-                           (const void*)topk_collect16_kernel<1, false>, (const void*)topk_collect16_kernel<2, false>,
-                           (const void*)topk_max16_kernel<1, true>, (const void*)topk_max16_kernel<2, true>,
-                           (const void*)topk_collect16_kernel<1, true>, (const void*)topk_collect16_kernel<2, true>,
-                           (const void*)target_count16_kernel<1, false, false>, (const void*)target_count16_kernel<2, false, false>,
-                           (const void*)target_count16_kernel<1, true, false>, (const void*)target_count16_kernel<2, true, false>};
-      const void* fns_x[] = {(const void*)topk_max16_kernel<1, false, true>, (const void*)topk_max16_kernel<1, true, true>,
-                             (const void*)target_count16_kernel<1, false, true>, (const void*)target_count16_kernel<1, true, true>};
-      for (const void* fn : fns)
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kStream16Lds) != hipSuccess) return SRFRD_E_DEVICE;
-      for (const void* fn : fns_x)
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kStream16LdsX) != hipSuccess) return SRFRD_E_DEVICE;
-      opted16[dev] = true;
-    }
+    const void* fns[] = {(const void*)topk_max16_kernel<1, false>, (const void*)topk_max16_kernel<2, false>,
+                         (const void*)topk_collect16_kernel<1, false>, (const void*)topk_collect16_kernel<2, false>,
+                         (const void*)topk_max16_kernel<1, true>, (const void*)topk_max16_kernel<2, true>,
+                         (const void*)topk_collect16_kernel<1, true>, (const void*)topk_collect16_kernel<2, true>,
+                         (const void*)target_count16_kernel<1, false, false>, (const void*)target_count16_kernel<2, false, false>,
+                         (const void*)target_count16_kernel<1, true, false>, (const void*)target_count16_kernel<2, true, false>};
+    const void* fns_x[] = {(const void*)topk_max16_kernel<1, false, true>, (const void*)topk_max16_kernel<1, true, true>,
+                           (const void*)target_count16_kernel<1, false, true>, (const void*)target_count16_kernel<1, true, true>};
+    for (const void* fn : fns)
+      if (lds_opt_in(fn, kStream16Lds)) return SRFRD_E_DEVICE;
+    for (const void* fn : fns_x)
+      if (lds_opt_in(fn, kStream16LdsX)) return SRFRD_E_DEVICE;
   }
-  hipDeviceProp_t prop;
-  static int cu_cached[64] = {0};
-  if (cu_cached[dev] == 0) cu_cached[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-  const int cu = cu_cached[dev];
+  const int cu = num_cu();
   const int64_t n_rows = a.item_hi - a.item_lo;
   const int user_tiles = (a.B + 15) / 16;
   int nu = user_tiles > kWaves16 ? 2 : 1;
@@ -1475,28 +1454,12 @@ static int logits_topk_impl(const srfrd_layout* lay, const void* item_table, con
   const size_t lds_stream = ((size_t)kChunk * DSi + 2 * 16 * DSi + 32 + 8 * 16 + kSlack) * sizeof(float);   // topk_stream
   const size_t lds_stream_x = lds_stream + 16 * (kChunk / 32) * sizeof(uint32_t);                          // + EXCL bits
   if (excl && lds_stream_x > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
-  static std::mutex attr_mu;
-  static size_t attr_dev[64] = {0}, attr_dev_x[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SRFRD_E_DEVICE;
-  {
-    std::lock_guard<std::mutex> attr_lock(attr_mu);
-    size_t& s_attr = attr_dev[dev];
-    if (lds > s_attr) {
-      if (hipFuncSetAttribute((const void*)topk_stage1_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)topk_max_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stream) != hipSuccess ||
-          hipFuncSetAttribute((const void*)topk_collect_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stream) != hipSuccess)
-        return SRFRD_E_DEVICE;
-      s_attr = lds;
-    }
-    size_t& x_attr = attr_dev_x[dev];
-    if (excl && lds > x_attr) {
-      if (hipFuncSetAttribute((const void*)topk_stage1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-          hipFuncSetAttribute((const void*)topk_max_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_stream_x) != hipSuccess)
-        return SRFRD_E_DEVICE;
-      x_attr = lds;
-    }
-  }
+  if (lds_opt_in((const void*)topk_stage1_kernel<false>, (int64_t)lds) || lds_opt_in((const void*)topk_max_kernel<false>, (int64_t)lds_stream) ||
+      lds_opt_in((const void*)topk_collect_kernel, (int64_t)lds_stream))
+    return SRFRD_E_DEVICE;
+  if (excl && (lds_opt_in((const void*)topk_stage1_kernel<true>, (int64_t)lds) ||
+               lds_opt_in((const void*)topk_max_kernel<true>, (int64_t)lds_stream_x)))
+    return SRFRD_E_DEVICE;
   char* ws = (char*)workspace;
   TopkArgs a = {};
   a.ly = *lay; a.table = item_table; a.dense = dense; a.hidden = hidden; a.user_label = user_label;
@@ -1523,7 +1486,7 @@ static int logits_topk_impl(const srfrd_layout* lay, const void* item_table, con
   }
   a.user_splits = splits;
   Plan16 p;
-  if (int rc = plan_stream16(lay, a, dev, p, excl)) return rc;
+  if (int rc = plan_stream16(lay, a, p, excl)) return rc;
   if (p.on) {
     // the two threshold passes on the bf16 matrix cores: a bf16 table as it is, an fp32 table split into three exact bf16
     // planes while it is staged.  The chunk-maxima array is walked with this path's chunk count, everything else (tau,
@@ -1597,19 +1560,8 @@ extern "C" int srfrd_target_rank(const srfrd_layout* lay, const void* item_table
   const size_t lds_stream_x = lds_stream + 16 * (kChunk / 32) * sizeof(uint32_t);
   if (lds_stream_x > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
   const size_t lds_score = ((size_t)2 * 16 * DSi + 16 + kSlack) * sizeof(float);
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SRFRD_E_DEVICE;
-  {
-    static std::mutex mu;
-    static bool opted[64] = {false};
-    std::lock_guard<std::mutex> lock(mu);
-    if (!opted[dev]) {
-      if (hipFuncSetAttribute((const void*)target_count_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit) != hipSuccess ||
-          hipFuncSetAttribute((const void*)target_count_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit) != hipSuccess)
-        return SRFRD_E_DEVICE;
-      opted[dev] = true;
-    }
-  }
+  if (lds_opt_in((const void*)target_count_kernel<false>, kLdsLimit) || lds_opt_in((const void*)target_count_kernel<true>, kLdsLimit))
+    return SRFRD_E_DEVICE;
   hipStream_t st = (hipStream_t)stream;
   const ExclSet ex = excl_prepare(excl_ptr, excl_items, max_row, B, item_lo, item_hi, workspace, st);
   TopkArgs a = {};
@@ -1623,7 +1575,7 @@ extern "C" int srfrd_target_rank(const srfrd_layout* lay, const void* item_table
   a.xs = ex.xs; a.xoff = ex.xoff; a.xstride = ex.xstride; a.xchunks = ex.xchunks;
   const bool excl = ex.xs != nullptr;
   Plan16 p;
-  if (int rc = plan_stream16(lay, a, dev, p, excl)) return rc;
+  if (int rc = plan_stream16(lay, a, p, excl)) return rc;
   const dim3 tiles((B + 15) / 16);
   if (p.on) {
     if (lay->table_bf16) hipLaunchKernelGGL(target_score16_kernel<false>, tiles, dim3(64), 0, st, a, targets);
@@ -1648,18 +1600,7 @@ extern "C" int srfrd_topk_merge(const int64_t* cand_idx, const float* cand_val, 
                                 float* topk_val, void* stream) {
   if (!cand_idx || !cand_val || !topk_idx || !topk_val || B <= 0 || n_cand <= 0 || k <= 0 || n_cand > 4096) return SRFRD_E_ARG;
   const size_t lds = (size_t)4 * 2 * n_cand * sizeof(float);       // 4 waves per block, (value, id) per candidate: <= 128 KiB
-  static std::mutex mu;
-  static size_t opted[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SRFRD_E_DEVICE;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (lds > 48 * 1024 && lds > opted[dev]) {
-      if (hipFuncSetAttribute((const void*)topk_merge_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return SRFRD_E_DEVICE;
-      opted[dev] = lds;
-    }
-  }
+  if (lds > 48 * 1024 && lds_opt_in((const void*)topk_merge_kernel, (int64_t)lds)) return SRFRD_E_DEVICE;
   hipLaunchKernelGGL(topk_merge_kernel, dim3((B + 3) / 4), dim3(256), lds, (hipStream_t)stream, cand_idx, cand_val, B, n_cand, k,
                      topk_idx, topk_val);
   return (int)hipGetLastError();

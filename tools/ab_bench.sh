@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B on one box: alternate two environments (given as "VAR=val" strings, "-" for none) over bench.py; prints step ms
-# and the per-kernel event times.  Usage: tools/ab_bench.sh "SRFRD_NO_LSPEC=1" "-" [rounds]
+# and the per-kernel event times.  Usage: tools/ab_bench.sh "SRFRD_NO_SLOTS50=1" "-" [rounds]
 A="$1"; B="$2"; R="${3:-2}"
 for r in $(seq 1 $R); do
   for V in "$A" "$B"; do
