@@ -124,6 +124,7 @@ int srfrd_bwd_grid(const srfrd_layout* lay, int B, int L);
 #define SRFRD_SW_NO_SLOTS 16      /* long sequences: neither the slot-placed nor the row-chunked backward */
 #define SRFRD_SW_NO_ROWS 32       /* long sequences: not the row-owner forward */
 #define SRFRD_SW_ROWS_ALWAYS 64   /* the row-owner forward wherever it serves (and not the ragged pair) */
+#define SRFRD_SW_TOPK_FP32 128    /* ranking: the fp32 stream wherever the bf16 matrix-core stream would serve (the encoder ignores it) */
 int srfrd_encoder_plan(const srfrd_layout* lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats,
                        char* fwd_name, char* bwd_name, int name_len, int32_t* grids);
 
@@ -396,6 +397,19 @@ int srfrd_target_rank(const srfrd_layout* lay, const void* item_table, const flo
                       int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad, const int64_t* user_label,
                       const int64_t* targets, const int64_t* excl_ptr, const int32_t* excl_items, int max_row,
                       int cut_k, int32_t* rank, double* metric_acc, void* workspace, void* stream);
+
+/* [host] the ranking's kernel plan, asked without a GPU: the launches srfrd_logits_topk(_excl) (op SRFRD_RANK_TOPK) or
+ * srfrd_target_rank (SRFRD_RANK_TARGET, or SRFRD_RANK_TARGET_METRIC with metric_acc != NULL) make for (lay, B, k,
+ * [item_lo, item_hi)), with an exclusion set when excl != 0, under `switches` (SRFRD_SW_* bits, as srfrd_encoder_plan) on a
+ * device with n_cu CUs.  For launch i < max_launches, in launch order: its kernel's name as a kernel trace prints it,
+ * without spaces ("srfrd::topk_max16_kernel<2,true,false>"; names + i * name_len, at most name_len bytes with the NUL)
+ * and geom[3 i ..]: workgroups, threads per workgroup, dynamic LDS bytes (names / geom may be NULL).  Returns the number of
+ * launches, SRFRD_E_UNSUPPORTED where the call refuses (it then launches nothing), or SRFRD_E_ARG. */
+#define SRFRD_RANK_TOPK 0
+#define SRFRD_RANK_TARGET 1
+#define SRFRD_RANK_TARGET_METRIC 2
+int srfrd_rank_plan(const srfrd_layout* lay, int op, int B, int k, int64_t item_lo, int64_t item_hi, int excl, int switches,
+                    int n_cu, int max_launches, char* names, int name_len, int32_t* geom);
 
 /* HR@10 / NDCG@10 inputs (reference utils.py:589-597): rank[b] = #{i >= 1 : logits[b][i] > logits[b][0]};
  * metric_acc[0] += [rank<10] / log2(rank+2), metric_acc[1] += [rank<10], metric_acc[2] += 1 (double[3]). */

@@ -77,6 +77,7 @@ SIGNATURES = {
     "srfrd_excl_workspace_bytes": (_i64, [_i, _i, _i64]),
     "srfrd_logits_topk_excl": (_i, [_LP, _P, _P, _P, _i, _i, _i64, _i64, _i, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P]),
     "srfrd_target_rank": (_i, [_LP, _P, _P, _P, _i, _i, _i64, _i64, _i, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P]),
+    "srfrd_rank_plan": (_i, [_LP, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _P, _i, _P]),
     "srfrd_eval_rank": (_i, [_P, _i, _i, _P, _P, _P]),
     "srfrd_sample_batch": (_i, [_P, _P, _P, _i, _i, _i, _i, _u32, _u32, _P, _P, _P]),
 }
@@ -147,3 +148,21 @@ def encoder_plan(lay: Layout, B: int, L: int, mode: int, switches: int = 0, n_cu
     check(lib().srfrd_encoder_plan(C.byref(lay), B, L, mode, switches, n_cu, scratch_floats, fwd, bwd, 128, grids),
           "srfrd_encoder_plan")
     return (fwd.value.decode(), grids[0]), (bwd.value.decode(), grids[1])
+
+
+# srfrd_rank_plan ops (SRFRD_RANK_*) and the ranking's switch bit (SRFRD_SW_TOPK_FP32: the environment variable SRFRD_TOPK_FP32)
+RANK_TOPK, RANK_TARGET, RANK_TARGET_METRIC = 0, 1, 2
+SW_TOPK_FP32 = 128
+
+
+def rank_plan(lay: Layout, op: int, B: int, k: int, item_lo: int, item_hi: int, excl: bool = False, switches: int = 0,
+              n_cu: int = 256):
+    """srfrd_rank_plan (no GPU needed) -> [(kernel, workgroups, threads, dynamic LDS bytes)] in launch order, or the
+    negative code the call refuses with (SRFRD_E_UNSUPPORTED, SRFRD_E_ARG)."""
+    n, w = 8, 96
+    names, geom = C.create_string_buffer(n * w), (C.c_int32 * (3 * n))()
+    rc = lib().srfrd_rank_plan(C.byref(lay), op, B, k, item_lo, item_hi, int(excl), switches, n_cu, n, names, w, geom)
+    if rc < 0:
+        return rc
+    return [(names.raw[i * w:(i + 1) * w].split(b"\0")[0].decode(), geom[3 * i], geom[3 * i + 1], geom[3 * i + 2])
+            for i in range(rc)]

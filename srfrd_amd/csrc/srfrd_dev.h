@@ -11,9 +11,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 
 #include "../../include/srfrd_hip.h"
@@ -78,6 +80,21 @@ inline int lds_opt_in(const void* fn, int64_t bytes) {
     have = bytes;
   }
   return 0;
+}
+
+// a plan's boolean template argument: f(std::true_type()) or f(std::false_type())
+template <class F>
+static int with_flag(bool b, F&& f) {
+  return b ? f(std::true_type()) : f(std::false_type());
+}
+
+// The environment switches (tests and A/B runs; none is set in normal use), read on every call: tests flip them inside
+// one process.
+inline int read_switches() {
+  return (getenv("SRFRD_GENERIC") ? SRFRD_SW_GENERIC : 0) | (getenv("SRFRD_NO_RAGGED") ? SRFRD_SW_NO_RAGGED : 0) |
+         (getenv("SRFRD_RAGGED_FULL_ROWS") ? SRFRD_SW_RAGGED_FULL_ROWS : 0) | (getenv("SRFRD_NO_SLOTS50") ? SRFRD_SW_NO_SLOTS50 : 0) |
+         (getenv("SRFRD_NO_SLOTS") ? SRFRD_SW_NO_SLOTS : 0) | (getenv("SRFRD_NO_ROWS") ? SRFRD_SW_NO_ROWS : 0) |
+         (getenv("SRFRD_ROWS_ALWAYS") ? SRFRD_SW_ROWS_ALWAYS : 0) | (getenv("SRFRD_TOPK_FP32") ? SRFRD_SW_TOPK_FP32 : 0);
 }
 }  // namespace srfrd
 

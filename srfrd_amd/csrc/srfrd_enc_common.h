@@ -294,10 +294,6 @@ static int with_variant(int v, F&& f) {
     default: return f(std::integral_constant<int, 3>());
   }
 }
-template <class F>
-static int with_flag(bool b, F&& f) {
-  return b ? f(std::true_type()) : f(std::false_type());
-}
 
 // kind variant of a layout: the hidden-50, one-head specialisations cover these kinds and width splits (-1: none)
 static inline int kind_variant(const srfrd_layout& lay) {

@@ -4,7 +4,6 @@
 // launch what it names.
 #pragma once
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/srfrd_hip.h"
 
@@ -60,15 +59,6 @@ EncPlan encoder_plan(const srfrd_layout& lay, int B, int L, int mode, int switch
 void plan_name(const KernelPlan& k, char* buf, int len);
 // persistent workgroups of the backward (= rows of grad_slabs): a function of the layout and the shape only
 int bwd_grid(const srfrd_layout& lay, int B, int L, int n_cu);
-
-// The environment switches (tests and A/B runs; none is set in normal use), read on every call: tests flip them inside
-// one process.
-inline int read_switches() {
-  return (getenv("SRFRD_GENERIC") ? SRFRD_SW_GENERIC : 0) | (getenv("SRFRD_NO_RAGGED") ? SRFRD_SW_NO_RAGGED : 0) |
-         (getenv("SRFRD_RAGGED_FULL_ROWS") ? SRFRD_SW_RAGGED_FULL_ROWS : 0) | (getenv("SRFRD_NO_SLOTS50") ? SRFRD_SW_NO_SLOTS50 : 0) |
-         (getenv("SRFRD_NO_SLOTS") ? SRFRD_SW_NO_SLOTS : 0) | (getenv("SRFRD_NO_ROWS") ? SRFRD_SW_NO_ROWS : 0) |
-         (getenv("SRFRD_ROWS_ALWAYS") ? SRFRD_SW_ROWS_ALWAYS : 0);
-}
 
 int launch_fwd_long(const KernelPlan& k, const void* args, void* stream);   // srfrd_encoder_fwd_long.hip (args: EncArgs)
 int launch_bwd_long(const KernelPlan& k, const void* args, void* stream);   // srfrd_encoder_bwd_long.hip

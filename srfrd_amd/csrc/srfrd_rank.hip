@@ -1,7 +1,10 @@
 // Ranking-side kernels: user labels, candidate logits (predict), full-catalog top-k, HR@10 / NDCG@10 ranks.
 // Reference: SRFR_model.py:144-152 (+ :241-259, :532-540, :668-681), :546-570; utils.py:576-598.
 
+#include <stdio.h>
+
 #include "srfrd_dev.h"
+#include "srfrd_rank_plan.h"
 
 namespace srfrd {
 
@@ -950,28 +953,18 @@ __device__ __forceinline__ void wave_select_topk(lds_f* sc, const int* ids, int 
   }
 }
 
+// a: 256-row chunks (n_chunks), one workgroup per chunk (user_splits 1); the overflow flag at ccnt[B]
 template <bool EXCL = false>
-__global__ void __launch_bounds__(256) topk_stage1_kernel(srfrd_layout ly, const void* __restrict__ table,
-                                                         const float* __restrict__ dense, const float* __restrict__ hidden,
-                                                         int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
-                                                         const int64_t* __restrict__ user_label, int k, int n_chunks,
-                                                         Cand* __restrict__ ws, const int32_t* __restrict__ overflow,
-                                                         const int32_t* __restrict__ xs, const int2* __restrict__ xoff,
-                                                         int xstride, int xchunks) {
-  if (*overflow == 0) return;                      // the threshold scheme succeeded: nothing to do
-  TopkArgs a = {};
-  a.ly = ly; a.table = table; a.dense = dense; a.hidden = hidden; a.user_label = user_label;
-  a.B = B; a.L = L; a.exclude_pad = exclude_pad; a.k = k; a.n_chunks = n_chunks; a.user_splits = 1;
-  a.item_lo = item_lo; a.item_hi = item_hi;
-  a.xs = xs; a.xoff = xoff; a.xstride = xstride; a.xchunks = xchunks;
+__global__ void __launch_bounds__(256) topk_stage1_kernel(const TopkArgs a, Cand* __restrict__ ws) {
+  if (a.ccnt[a.B] == 0) return;                    // the threshold scheme succeeded: nothing to do
   topk_tiles<EXCL>(a, [&](int u0, int chunk, int64_t i0, lds_f* sS, int SLD) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     for (int r = wave; r < 16; r += nw)
-      if (u0 + r < B) {
-        Cand* out = ws + ((int64_t)(u0 + r) * n_chunks + chunk) * k;
-        wave_select_topk(sS + r * SLD, nullptr, kChunk, k, out);
+      if (u0 + r < a.B) {
+        Cand* out = ws + ((int64_t)(u0 + r) * a.n_chunks + chunk) * a.k;
+        wave_select_topk(sS + r * SLD, nullptr, kChunk, a.k, out);
         if (lane == 0)
-          for (int q = 0; q < k; ++q)
+          for (int q = 0; q < a.k; ++q)
             if (out[q].i >= 0) out[q].i += (int32_t)i0;       // chunk-local position -> item id
       }
   });
@@ -1279,18 +1272,6 @@ extern "C" int srfrd_predict_logits(const srfrd_layout* lay, const void* item_ta
   return (int)hipGetLastError();
 }
 
-// tau launch: the rows of 4 users per block while they fit the default 64 KiB of dynamic LDS, else one user per block
-// (with the > 64 KiB opt-in up to the CU's 160 KiB: 40 k chunks)
-static int launch_tau(const TopkArgs& a, hipStream_t st) {
-  const size_t row = (size_t)a.n_chunks * sizeof(float);
-  const int wpb = 4 * row <= 64 * 1024 ? 4 : 1;
-  const size_t lds = wpb * row;
-  if (lds > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
-  if (lds > 64 * 1024 && lds_opt_in((const void*)topk_tau_kernel, (int64_t)lds)) return SRFRD_E_DEVICE;
-  hipLaunchKernelGGL(topk_tau_kernel, dim3((a.B + wpb - 1) / wpb), dim3(64 * wpb), lds, st, a);
-  return 0;
-}
-
 // workspace layout: [cmax B*nc f32][tau B f32][cursor B+1 i32 (+pad)][candidates B*kCandMax][fallback B*nc*k]
 static int64_t topk_off(int B, int k, int64_t nc, int which) {
   int64_t off = 0;
@@ -1305,13 +1286,6 @@ extern "C" int64_t srfrd_topk_workspace_bytes(int B, int k, int64_t n_rows) {
   const int64_t n_chunks = (n_rows + kChunk - 1) / kChunk;
   return topk_off(B, k, n_chunks, 5);
 }
-
-// exclusion sets of one launch: the pre-pass's outputs (null xs: no exclusion)
-struct ExclSet {
-  const int32_t* xs = nullptr;
-  const int2* xoff = nullptr;
-  int xstride = 0, xchunks = 0;
-};
 
 // excl workspace layout: [s_t B f32][xs B*xstride i32][xoff B*xchunks int2]
 static int excl_stride(int max_row) { return (max_row + 1 + 3) & ~3; }      // (+ the sentinel)
@@ -1328,108 +1302,233 @@ extern "C" int64_t srfrd_excl_workspace_bytes(int B, int max_row, int64_t n_rows
   return excl_off(B, max_row, n_rows, 3);
 }
 
-// host-side checks of an exclusion CSR (no device reads) and the pre-pass launch
-static int excl_args(const int64_t* excl_ptr, const int32_t* excl_items, int max_row, const void* excl_ws) {
+// host-side checks of an exclusion CSR (no device reads), then what the masked passes' 32-bit cursor arithmetic covers
+// (list positions, ids relative to a chunk start)
+static int excl_args(const int64_t* excl_ptr, const int32_t* excl_items, int max_row, const void* excl_ws, int B, int64_t item_hi) {
   if (!excl_ptr) return 0;
   if (!excl_items || !excl_ws || max_row < 0) return SRFRD_E_ARG;
   if (max_row > kExclCap) return SRFRD_E_UNSUPPORTED;
-  return 0;
-}
-// what the masked passes' 32-bit cursor arithmetic covers (list positions, ids relative to a chunk start)
-static int excl_range(int B, int max_row, int64_t item_hi) {
   if ((int64_t)B * excl_stride(max_row) >= INT32_MAX || item_hi >= (int64_t)INT32_MAX - 1024) return SRFRD_E_UNSUPPORTED;
   return 0;
 }
-static ExclSet excl_prepare(const int64_t* excl_ptr, const int32_t* excl_items, int max_row, int B, int64_t item_lo,
-                            int64_t item_hi, void* excl_ws, hipStream_t st) {
-  ExclSet x;
-  if (!excl_ptr) return x;
+
+// ---- kernel plan (srfrd_rank_plan.h) ----------------------------------------------------------------------------------
+RankPlan srfrd::rank_plan(const srfrd_layout& lay, int op, int B, int k, int64_t item_lo, int64_t item_hi, bool excl, int switches,
+                          int n_cu) {
+  RankPlan p = {};
+  const auto refuse = [&]() { p.rc = SRFRD_E_UNSUPPORTED; return p; };
+  const bool topk = op == SRFRD_RANK_TOPK, bf16_tab = lay.table_bf16 != 0;
   const int64_t n_rows = item_hi - item_lo;
-  char* ws = (char*)excl_ws;
-  x.xstride = excl_stride(max_row);
-  x.xchunks = (int)((n_rows + 255) / 256 + 1);
-  int32_t* xs = (int32_t*)(ws + excl_off(B, max_row, n_rows, 1));
-  int2* xoff = (int2*)(ws + excl_off(B, max_row, n_rows, 2));
-  int P = 1;
-  while (P < max_row) P <<= 1;
-  // (the row is sorted in a kExclCap-entry LDS array: P <= kExclCap since max_row <= kExclCap)
-  hipLaunchKernelGGL(excl_prep_kernel, dim3(B), dim3(1024), 0, st, excl_ptr, excl_items, max_row, P, item_lo, item_hi, xs,
-                     x.xstride, xoff, x.xchunks);
-  x.xs = xs;
-  x.xoff = xoff;
-  return x;
+  const int user_tiles = (B + 15) / 16;
+  p.excl = excl;
+  p.split_e = !bf16_tab;
+  p.n_chunks = (int)((n_rows + kChunk - 1) / kChunk);
+  // dynamic LDS of the fp32 stream (a chunk of item rows and two user tiles; + the EXCL bits), of the exhaustive path's
+  // tiles and of target_score_kernel
+  const int DSi = ((lay.d_item + 3) & ~3) + 2;
+  const int64_t lds_stream = ((int64_t)kChunk * DSi + 2 * 16 * DSi + 32 + 8 * 16 + kSlack) * 4;
+  const int64_t lds_stream_x = lds_stream + 16 * (kChunk / 32) * 4;
+  const int64_t lds_tiles = ((int64_t)kChunk * DSi + 16 * DSi + 16 * (kChunk + 2) + 16 + kSlack) * 4;
+  const int64_t lds_score = ((int64_t)2 * 16 * DSi + 16 + kSlack) * 4;
+  if (lay.D > SRFRD_MAX_D) return refuse();
+  if (topk ? lds_tiles > kLdsLimit || (excl && lds_stream_x > kLdsLimit) : lds_stream_x > kLdsLimit) return refuse();
+
+  // the bf16 matrix-core streams: a bf16 table up to 64 wide (odd widths up to 51), an fp32 table (three exact bf16 planes)
+  // up to 52
+  p.stream16 = !(switches & SRFRD_SW_TOPK_FP32) &&
+               (bf16_tab ? (lay.d_item <= 64 && ((lay.d_item & 1) == 0 || lay.d_item <= 51)) : lay.d_item <= 52);
+  int64_t grid;
+  if (p.stream16) {
+    int nu = user_tiles > kWaves16 ? 2 : 1;
+    int groups = (user_tiles + kWaves16 * nu - 1) / (kWaves16 * nu);
+    int crows = bf16_tab ? kChunk16 : 256;
+    if ((lay.d_item & 1) != 0 || ((n_rows + crows - 1) / crows) * groups < 2 * (int64_t)n_cu) crows = 256;
+    if (excl) {
+      // the masked forms keep 64 item bits per lane and user tile (256-row chunks) and run one user tile per wave: at two the
+      // kernel needs more than the 128 VGPRs a 1024-thread workgroup allows and spills in the tile loop
+      crows = 256;
+      nu = 1;
+      groups = (user_tiles + kWaves16 - 1) / kWaves16;
+    }
+    // a chunk is staged through kStageSlots16 registers per thread: rows x copy elements per row must fit them (a 512-row
+    // chunk of a bf16 table does up to d_item 52; wider rows take 256-row chunks - rows beyond the slots would never be copied)
+    const int64_t copy_w = bf16_tab ? ((lay.d_item & 1) == 0 ? lay.d_item >> 1 : lay.d_item) : lay.d_item;
+    if ((int64_t)crows * copy_w > (int64_t)kStageSlots16 * kWaves16 * 64) crows = 256;
+    if ((int64_t)crows * copy_w > (int64_t)kStageSlots16 * kWaves16 * 64) return refuse();
+    const int64_t nch = (n_rows + crows - 1) / crows;
+    if (nch * groups < n_cu && nu == 2) { nu = 1; groups = (user_tiles + kWaves16 - 1) / kWaves16; }
+    int per_group = n_cu / groups < 1 ? 1 : n_cu / groups;
+    if (per_group > nch) per_group = (int)nch;
+    p.nu = nu; p.crows = crows; p.stream_chunks = (int)nch; p.wg_per_group = per_group; p.user_splits = 1;
+    grid = (int64_t)groups * per_group;
+  } else {
+    p.crows = kChunk; p.stream_chunks = p.n_chunks;
+    if (topk) {
+      // user tiles are split over `splits` workgroups per chunk.  Each workgroup re-stages its chunk (~7 user tiles' worth of
+      // time), and the launch runs in rounds of `slots` resident workgroups: pick the split with the smallest
+      // rounds x (staging + tiles per workgroup).
+      const int slots = 256 * (lds_stream * 2 <= kLdsLimit ? 2 : 1);
+      double best = 1e30;
+      for (int sp = 1; sp <= user_tiles && sp <= 64; ++sp) {
+        const int64_t wgs = (int64_t)p.n_chunks * sp;
+        const double rounds = (double)((wgs + slots - 1) / slots);
+        const double cost = rounds * (7.0 + (double)((user_tiles + sp - 1) / sp));
+        if (cost < best) { best = cost; p.user_splits = sp; }
+      }
+    } else {
+      // (one user tile per workgroup and chunk: the count needs no split heuristics - the pass reads every chunk once per tile)
+      p.user_splits = user_tiles < 8 ? user_tiles : 8;
+    }
+    grid = (int64_t)p.n_chunks * p.user_splits;
+  }
+  // the streamed passes: stream16 (one user tile per wave and its item mask for EXCL) or the fp32 stream (+ the EXCL bits)
+  const int block = p.stream16 ? kWaves16 * 64 : 512, per4 = (B + 3) / 4;
+  const int64_t lds_pass = p.stream16 ? (excl ? kStream16LdsX : kStream16Lds) : (excl ? lds_stream_x : lds_stream);
+  const auto add = [&](int kernel, int64_t g, int block, int64_t lds) { p.launch[p.n_launches++] = {kernel, (int)g, block, lds}; };
+  if (excl) add(kExclPrep, B, 1024, 0);
+  if (topk) {
+    // tau: the chunk-maximum rows of 4 users per block while they fit the default 64 KiB of dynamic LDS, else one user per
+    // block (up to the CU's 160 KiB: 40 k chunks of the stream)
+    const int64_t row = (int64_t)p.stream_chunks * 4;
+    const int wpb = 4 * row <= 64 * 1024 ? 4 : 1;
+    if (wpb * row > kLdsLimit) return refuse();
+    // the two threshold passes (stream16: the chunk maxima walked with that stream's chunk count; the collection pass is
+    // unmasked, the filter drops excluded candidates), the selection, and the exhaustive path over 256-row chunks, armed
+    // on the device only if a candidate list overflowed
+    add(p.stream16 ? kTopkMax16 : kTopkMax, grid, block, lds_pass);
+    add(kTopkTau, (B + wpb - 1) / wpb, 64 * wpb, wpb * row);
+    add(p.stream16 ? kTopkCollect16 : kTopkCollect, grid, block, p.stream16 ? kStream16Lds : lds_stream);
+    if (excl) add(kTopkExclFilter, per4, 256, 0);
+    add(kTopkSelect, per4, 256, 0);
+    add(kTopkStage1, p.n_chunks, 256, lds_tiles);
+    add(kTopkStage2, per4, 256, 0);
+  } else {
+    add(p.stream16 ? kTargetScore16 : kTargetScore, user_tiles, 64, p.stream16 ? 0 : lds_score);
+    add(p.stream16 ? kTargetCount16 : kTargetCount, grid, block, lds_pass);
+    if (op == SRFRD_RANK_TARGET_METRIC) add(kTargetMetric, (B + 255) / 256, 256, 0);
+  }
+  return p;
 }
 
-// launch geometry of the bf16 matrix-core streams (users in registers, item chunks streamed through LDS)
-struct Plan16 {
-  bool on;
-  int nu;
-  dim3 grid;
-  TopkArgs h;
+// the instantiation a launch names, as a kernel trace prints it (without spaces)
+static void launch_name(const RankPlan& p, const RankLaunch& l, char* buf, int len) {
+  static const char* const names[] = {"excl_prep_kernel", "topk_max16_kernel", "topk_collect16_kernel", "topk_max_kernel", "topk_tau_kernel",
+      "topk_collect_kernel", "topk_excl_filter_kernel", "topk_select_kernel", "topk_stage1_kernel", "topk_stage2_kernel",
+      "target_score16_kernel", "target_score_kernel", "target_count16_kernel", "target_count_kernel", "target_metric_kernel"};
+  const char *se = p.split_e ? "true" : "false", *x = p.excl ? "true" : "false", *n = names[l.kernel];
+  switch (l.kernel) {
+    case kTopkMax16: case kTargetCount16: snprintf(buf, len, "srfrd::%s<%d,%s,%s>", n, p.nu, se, x); return;
+    case kTopkCollect16: snprintf(buf, len, "srfrd::%s<%d,%s>", n, p.nu, se); return;
+    case kTargetScore16: snprintf(buf, len, "srfrd::%s<%s>", n, se); return;
+    case kTopkMax: case kTopkStage1: case kTargetCount: snprintf(buf, len, "srfrd::%s<%s>", n, x); return;
+    default: snprintf(buf, len, "srfrd::%s", n);
+  }
+}
+
+extern "C" int srfrd_rank_plan(const srfrd_layout* lay, int op, int B, int k, int64_t item_lo, int64_t item_hi, int excl,
+                               int switches, int n_cu, int max_launches, char* names, int name_len, int32_t* geom) {
+  if (!lay || op < SRFRD_RANK_TOPK || op > SRFRD_RANK_TARGET_METRIC || B <= 0 || item_lo < 0 || item_hi <= item_lo ||
+      item_hi > (int64_t)lay->n_items + 1 || n_cu <= 0 || max_launches < 0 || (op == SRFRD_RANK_TOPK && (k <= 0 || k > 64)))
+    return SRFRD_E_ARG;
+  const RankPlan p = rank_plan(*lay, op, B, k, item_lo, item_hi, excl != 0, switches, n_cu);
+  if (p.rc) return p.rc;
+  for (int i = 0; i < p.n_launches && i < max_launches; ++i) {
+    const RankLaunch& l = p.launch[i];
+    if (names && name_len > 0) launch_name(p, l, names + (int64_t)i * name_len, name_len);
+    if (geom) { geom[3 * i] = l.grid; geom[3 * i + 1] = l.block; geom[3 * i + 2] = (int32_t)l.lds; }
+  }
+  return p.n_launches;
+}
+
+// ---- launchers ----------------------------------------------------------------------------------------------------------
+// what the launches of one call read and write besides TopkArgs
+struct RankIO {
+  const int64_t* excl_ptr; const int32_t* excl_items; int max_row;   // the exclusion pre-pass's CSR input
+  int64_t* topk_idx; float* topk_val;                                  // top-k outputs
+  const int64_t* targets; int cut_k; double* metric_acc;               // target rank
+  int32_t* xs; int2* xoff;                                             // the pre-pass's sorted lists / block offsets (= a.xs, a.xoff)
+  Cand* fb;                                                            // the exhaustive path's per-chunk candidates
 };
-static int plan_stream16(const srfrd_layout* lay, const TopkArgs& a, Plan16& p, bool excl) {
-  const bool bf16_tab = lay->table_bf16 != 0;
-  p.on = getenv("SRFRD_TOPK_FP32") == nullptr &&
-         (bf16_tab ? (lay->d_item <= 64 && ((lay->d_item & 1) == 0 || lay->d_item <= 51)) : lay->d_item <= 52);
-  if (!p.on) return 0;
-  {
-    const void* fns[] = {(const void*)topk_max16_kernel<1, false>, (const void*)topk_max16_kernel<2, false>,
-                         (const void*)topk_collect16_kernel<1, false>, (const void*)topk_collect16_kernel<2, false>,
-                         (const void*)topk_max16_kernel<1, true>, (const void*)topk_max16_kernel<2, true>,
-                         (const void*)topk_collect16_kernel<1, true>, (const void*)topk_collect16_kernel<2, true>,
-                         (const void*)target_count16_kernel<1, false, false>, (const void*)target_count16_kernel<2, false, false>,
-                         (const void*)target_count16_kernel<1, true, false>, (const void*)target_count16_kernel<2, true, false>};
-    const void* fns_x[] = {(const void*)topk_max16_kernel<1, false, true>, (const void*)topk_max16_kernel<1, true, true>,
-                           (const void*)target_count16_kernel<1, false, true>, (const void*)target_count16_kernel<1, true, true>};
-    for (const void* fn : fns)
-      if (lds_opt_in(fn, kStream16Lds)) return SRFRD_E_DEVICE;
-    for (const void* fn : fns_x)
-      if (lds_opt_in(fn, kStream16LdsX)) return SRFRD_E_DEVICE;
+
+// one kernel as the plan sized it: opt in exactly the dynamic LDS it uses, then launch
+template <class K, class... Args>
+static int launch_rank(K kernel, const RankLaunch& l, hipStream_t st, Args... args) {
+  if (const int rc = lds_opt_in((const void*)kernel, l.lds)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(l.grid), dim3(l.block), (size_t)l.lds, st, args...);
+  return (int)hipGetLastError();
+}
+
+// the stream16 instantiation a plan names: f(NU, SPLIT_E) as integral constants (the masked forms exist at NU = 1 only)
+template <bool EXCL, class F>
+static int with_stream16(const RankPlan& p, F&& f) {
+  return with_flag(p.split_e, [&](auto se) {
+    if constexpr (!EXCL)
+      if (p.nu == 2) return f(std::integral_constant<int, 2>(), se);
+    return f(std::integral_constant<int, 1>(), se);
+  });
+}
+
+static int launch_one(const RankPlan& p, const RankLaunch& l, const TopkArgs& a, const RankIO& io, hipStream_t st) {
+  switch (l.kernel) {
+    case kExclPrep: {                 // (a row is sorted in a kExclCap-entry LDS array: P <= kExclCap since max_row <= kExclCap)
+      int P = 1;
+      while (P < io.max_row) P <<= 1;
+      return launch_rank(excl_prep_kernel, l, st, io.excl_ptr, io.excl_items, io.max_row, P, a.item_lo, a.item_hi, io.xs,
+                         a.xstride, io.xoff, a.xchunks);
+    }
+    case kTopkMax16:
+      return with_flag(p.excl, [&](auto x) { return with_stream16<decltype(x)::value>(p, [&](auto nu, auto se) {
+        return launch_rank(topk_max16_kernel<decltype(nu)::value, decltype(se)::value, decltype(x)::value>, l, st, a); }); });
+    case kTopkCollect16:
+      return with_stream16<false>(p, [&](auto nu, auto se) {
+        return launch_rank(topk_collect16_kernel<decltype(nu)::value, decltype(se)::value>, l, st, a); });
+    case kTopkMax: return with_flag(p.excl, [&](auto x) { return launch_rank(topk_max_kernel<decltype(x)::value>, l, st, a); });
+    case kTopkTau: return launch_rank(topk_tau_kernel, l, st, a);
+    case kTopkCollect: return launch_rank(topk_collect_kernel, l, st, a);
+    case kTopkExclFilter: return launch_rank(topk_excl_filter_kernel, l, st, a);
+    case kTopkSelect: return launch_rank(topk_select_kernel, l, st, a, io.topk_idx, io.topk_val);
+    case kTopkStage1: {
+      TopkArgs e = a;                 // 256-row chunks, one workgroup each
+      e.n_chunks = p.n_chunks; e.user_splits = 1;
+      return with_flag(p.excl, [&](auto x) { return launch_rank(topk_stage1_kernel<decltype(x)::value>, l, st, e, io.fb); });
+    }
+    case kTopkStage2:
+      return launch_rank(topk_stage2_kernel, l, st, (const Cand*)io.fb, a.B, a.k, p.n_chunks, io.topk_idx, io.topk_val,
+                         (const int32_t*)(a.ccnt + a.B));
+    case kTargetScore16:
+      return with_flag(p.split_e, [&](auto se) { return launch_rank(target_score16_kernel<decltype(se)::value>, l, st, a, io.targets); });
+    case kTargetScore: return launch_rank(target_score_kernel, l, st, a, io.targets);
+    case kTargetCount16:
+      return with_flag(p.excl, [&](auto x) { return with_stream16<decltype(x)::value>(p, [&](auto nu, auto se) {
+        return launch_rank(target_count16_kernel<decltype(nu)::value, decltype(se)::value, decltype(x)::value>, l, st, a); }); });
+    case kTargetCount: return with_flag(p.excl, [&](auto x) { return launch_rank(target_count_kernel<decltype(x)::value>, l, st, a); });
+    case kTargetMetric: return launch_rank(target_metric_kernel, l, st, (const int32_t*)a.ccnt, a.B, io.cut_k, io.metric_acc);
   }
-  const int cu = num_cu();
-  const int64_t n_rows = a.item_hi - a.item_lo;
-  const int user_tiles = (a.B + 15) / 16;
-  int nu = user_tiles > kWaves16 ? 2 : 1;
-  int groups = (user_tiles + kWaves16 * nu - 1) / (kWaves16 * nu);
-  int crows = bf16_tab ? kChunk16 : 256;
-  if ((lay->d_item & 1) != 0 || ((n_rows + crows - 1) / crows) * groups < 2 * (int64_t)cu) crows = 256;
-  if (excl) {
-    // the masked forms keep 64 item bits per lane and user tile (256-row chunks) and run one user tile per wave: at two the
-    // kernel needs more than the 128 VGPRs a 1024-thread workgroup allows and spills in the tile loop
-    crows = 256;
-    nu = 1;
-    groups = (user_tiles + kWaves16 - 1) / kWaves16;
-  }
-  // a chunk is staged through kStageSlots16 registers per thread: rows x copy elements per row must fit them (a 512-row
-  // chunk of a bf16 table does up to d_item 52; wider rows take 256-row chunks - rows beyond the slots would never be copied)
-  const int64_t copy_w = bf16_tab ? ((lay->d_item & 1) == 0 ? lay->d_item >> 1 : lay->d_item) : lay->d_item;
-  if ((int64_t)crows * copy_w > (int64_t)kStageSlots16 * kWaves16 * 64) crows = 256;
-  if ((int64_t)crows * copy_w > (int64_t)kStageSlots16 * kWaves16 * 64) return SRFRD_E_UNSUPPORTED;
-  int64_t nch = (n_rows + crows - 1) / crows;
-  if (nch * groups < cu && nu == 2) { nu = 1; groups = (user_tiles + kWaves16 - 1) / kWaves16; }
-  int per_group = cu / groups < 1 ? 1 : cu / groups;
-  if (per_group > nch) per_group = (int)nch;
-  p.h = a;
-  p.h.n_chunks = (int)nch;
-  p.h.crows = crows;
-  p.h.wg_per_group = per_group;
-  p.nu = nu;
-  p.grid = dim3(groups * per_group);
+  return SRFRD_E_ARG;
+}
+// the plan's launches in order
+static int run_plan(const RankPlan& p, const TopkArgs& a, const RankIO& io, hipStream_t st) {
+  for (int i = 0; i < p.n_launches; ++i)
+    if (const int rc = launch_one(p, p.launch[i], a, io, st)) return rc;
   return 0;
 }
 
-// one launch of a stream16 kernel template at the plan's (NU, SPLIT_E); LDS = kStream16Lds, or kStream16LdsX for EXCL forms
-// SRFRD_L16X: the masked (EXCL) forms, which the plan always gives one user tile per wave
-#define SRFRD_L16X(P, KERNEL) do { \
-    const dim3 blk16(kWaves16 * 64); \
-    if ((P).h.ly.table_bf16) hipLaunchKernelGGL((KERNEL<1, false, true>), (P).grid, blk16, kStream16LdsX, st, (P).h); \
-    else hipLaunchKernelGGL((KERNEL<1, true, true>), (P).grid, blk16, kStream16LdsX, st, (P).h); } while (0)
-#define SRFRD_L16(P, LDS, KERNEL, ...) do { \
-    const dim3 blk16(kWaves16 * 64); \
-    if ((P).h.ly.table_bf16) { if ((P).nu == 2) hipLaunchKernelGGL((KERNEL<2, false __VA_ARGS__>), (P).grid, blk16, LDS, st, (P).h); \
-                               else hipLaunchKernelGGL((KERNEL<1, false __VA_ARGS__>), (P).grid, blk16, LDS, st, (P).h); } \
-    else { if ((P).nu == 2) hipLaunchKernelGGL((KERNEL<2, true __VA_ARGS__>), (P).grid, blk16, LDS, st, (P).h); \
-           else hipLaunchKernelGGL((KERNEL<1, true __VA_ARGS__>), (P).grid, blk16, LDS, st, (P).h); } } while (0)
+// the arguments every pass of a call shares, at the plan's chunking; with an exclusion set, its lists in excl_ws
+static TopkArgs rank_args(const RankPlan& p, const srfrd_layout* lay, const void* item_table, const float* dense,
+                          const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
+                          const int64_t* user_label, int k, int max_row, void* excl_ws, RankIO& io) {
+  TopkArgs a = {};
+  a.ly = *lay; a.table = item_table; a.dense = dense; a.hidden = hidden; a.user_label = user_label;
+  a.B = B; a.L = L; a.exclude_pad = exclude_pad; a.k = k; a.item_lo = item_lo; a.item_hi = item_hi;
+  a.n_chunks = p.stream_chunks; a.crows = p.crows; a.wg_per_group = p.wg_per_group; a.user_splits = p.user_splits;
+  if (p.excl) {
+    const int64_t n_rows = item_hi - item_lo;
+    a.xs = io.xs = (int32_t*)((char*)excl_ws + excl_off(B, max_row, n_rows, 1));
+    a.xoff = io.xoff = (int2*)((char*)excl_ws + excl_off(B, max_row, n_rows, 2));
+    a.xstride = excl_stride(max_row); a.xchunks = (int)((n_rows + 255) / 256 + 1);
+  }
+  return a;
+}
 
 static int topk_args_check(const srfrd_layout* lay, const void* item_table, const float* dense, const float* hidden, int B, int L,
                            int64_t item_lo, int64_t item_hi, const int64_t* user_label) {
@@ -1440,95 +1539,6 @@ static int topk_args_check(const srfrd_layout* lay, const void* item_table, cons
   return 0;
 }
 
-// the four-launch threshold scheme (+ the armed exhaustive path); ex.xs != null runs the masked instantiations
-static int logits_topk_impl(const srfrd_layout* lay, const void* item_table, const float* dense,
-                            const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
-                            const int64_t* user_label, int k, int64_t* topk_idx, float* topk_val, void* workspace,
-                            const ExclSet& ex, hipStream_t st) {
-  if (lay->D > SRFRD_MAX_D) return SRFRD_E_UNSUPPORTED;
-  const bool excl = ex.xs != nullptr;
-  const int n_chunks = (int)((item_hi - item_lo + kChunk - 1) / kChunk);
-  const int DSi = ((lay->d_item + 3) & ~3) + 2;
-  const size_t lds = ((size_t)kChunk * DSi + 16 * DSi + 16 * (kChunk + 2) + 16 + kSlack) * sizeof(float);
-  if (lds > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
-  const size_t lds_stream = ((size_t)kChunk * DSi + 2 * 16 * DSi + 32 + 8 * 16 + kSlack) * sizeof(float);   // topk_stream
-  const size_t lds_stream_x = lds_stream + 16 * (kChunk / 32) * sizeof(uint32_t);                          // + EXCL bits
-  if (excl && lds_stream_x > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
-  if (lds_opt_in((const void*)topk_stage1_kernel<false>, (int64_t)lds) || lds_opt_in((const void*)topk_max_kernel<false>, (int64_t)lds_stream) ||
-      lds_opt_in((const void*)topk_collect_kernel, (int64_t)lds_stream))
-    return SRFRD_E_DEVICE;
-  if (excl && (lds_opt_in((const void*)topk_stage1_kernel<true>, (int64_t)lds) ||
-               lds_opt_in((const void*)topk_max_kernel<true>, (int64_t)lds_stream_x)))
-    return SRFRD_E_DEVICE;
-  char* ws = (char*)workspace;
-  TopkArgs a = {};
-  a.ly = *lay; a.table = item_table; a.dense = dense; a.hidden = hidden; a.user_label = user_label;
-  a.B = B; a.L = L; a.exclude_pad = exclude_pad; a.k = k; a.n_chunks = n_chunks;
-  a.item_lo = item_lo; a.item_hi = item_hi;
-  a.cmax = (float*)(ws + topk_off(B, k, n_chunks, 0));
-  a.tau = (float*)(ws + topk_off(B, k, n_chunks, 1));
-  a.ccnt = (int32_t*)(ws + topk_off(B, k, n_chunks, 2));
-  a.cand = (Cand*)(ws + topk_off(B, k, n_chunks, 3));
-  a.xs = ex.xs; a.xoff = ex.xoff; a.xstride = ex.xstride; a.xchunks = ex.xchunks;
-  Cand* fb = (Cand*)(ws + topk_off(B, k, n_chunks, 4));
-  const int user_tiles = (B + 15) / 16;
-  // user tiles are split over `splits` workgroups per chunk.  Each workgroup re-stages its chunk (~7 user tiles' worth of
-  // time), and the launch runs in rounds of `slots` resident workgroups: pick the split with the smallest
-  // rounds x (staging + tiles per workgroup).
-  const int slots = 256 * (lds_stream * 2 <= (size_t)kLdsLimit ? 2 : 1);
-  int splits = 1;
-  double best = 1e30;
-  for (int sp = 1; sp <= user_tiles && sp <= 64; ++sp) {
-    const int64_t wgs = (int64_t)n_chunks * sp;
-    const double rounds = (double)((wgs + slots - 1) / slots);
-    const double cost = rounds * (7.0 + (double)((user_tiles + sp - 1) / sp));
-    if (cost < best) { best = cost; splits = sp; }
-  }
-  a.user_splits = splits;
-  Plan16 p;
-  if (int rc = plan_stream16(lay, a, p, excl)) return rc;
-  if (p.on) {
-    // the two threshold passes on the bf16 matrix cores: a bf16 table as it is, an fp32 table split into three exact bf16
-    // planes while it is staged.  The chunk-maxima array is walked with this path's chunk count, everything else (tau,
-    // candidate lists, selection, the armed exhaustive path with its own 256-item chunks) is shared
-    if (excl) SRFRD_L16X(p, topk_max16_kernel);
-    else SRFRD_L16(p, kStream16Lds, topk_max16_kernel, );
-    if (int trc = launch_tau(p.h, st)) return trc;
-    SRFRD_L16(p, kStream16Lds, topk_collect16_kernel, );
-  } else if (excl) {
-    hipLaunchKernelGGL(topk_max_kernel<true>, dim3(n_chunks * splits), dim3(512), lds_stream_x, st, a);
-    if (int trc = launch_tau(a, st)) return trc;
-    hipLaunchKernelGGL(topk_collect_kernel, dim3(n_chunks * splits), dim3(512), lds_stream, st, a);
-  } else {
-    hipLaunchKernelGGL(topk_max_kernel<false>, dim3(n_chunks * splits), dim3(512), lds_stream, st, a);
-    if (int trc = launch_tau(a, st)) return trc;
-    hipLaunchKernelGGL(topk_collect_kernel, dim3(n_chunks * splits), dim3(512), lds_stream, st, a);
-  }
-  if (excl) hipLaunchKernelGGL(topk_excl_filter_kernel, dim3((B + 3) / 4), dim3(256), 0, st, a);
-  hipLaunchKernelGGL(topk_select_kernel, dim3((B + 3) / 4), dim3(256), 0, st, a, topk_idx, topk_val);
-  // exhaustive path, armed only if a candidate list overflowed (device-side flag: no host synchronisation)
-  if (excl)
-    hipLaunchKernelGGL(topk_stage1_kernel<true>, dim3(n_chunks), dim3(256), lds, st, *lay, item_table, dense, hidden, B, L, item_lo,
-                       item_hi, exclude_pad, user_label, k, n_chunks, fb, (const int32_t*)(a.ccnt + B), ex.xs, ex.xoff, ex.xstride,
-                       ex.xchunks);
-  else
-    hipLaunchKernelGGL(topk_stage1_kernel<false>, dim3(n_chunks), dim3(256), lds, st, *lay, item_table, dense, hidden, B, L, item_lo,
-                       item_hi, exclude_pad, user_label, k, n_chunks, fb, (const int32_t*)(a.ccnt + B), nullptr, nullptr, 0, 0);
-  hipLaunchKernelGGL(topk_stage2_kernel, dim3((B + 3) / 4), dim3(256), 0, st, (const Cand*)fb, B, k, n_chunks, topk_idx,
-                     topk_val, (const int32_t*)(a.ccnt + B));
-  return (int)hipGetLastError();
-}
-
-extern "C" int srfrd_logits_topk(const srfrd_layout* lay, const void* item_table, const float* dense,
-                                 const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
-                                 const int64_t* user_label, int k, int64_t* topk_idx, float* topk_val, void* workspace,
-                                 void* stream) {
-  if (!topk_idx || !topk_val || !workspace || k <= 0 || k > 64) return SRFRD_E_ARG;
-  if (int rc = topk_args_check(lay, item_table, dense, hidden, B, L, item_lo, item_hi, user_label)) return rc;
-  return logits_topk_impl(lay, item_table, dense, hidden, B, L, item_lo, item_hi, exclude_pad, user_label, k, topk_idx, topk_val,
-                          workspace, ExclSet{}, (hipStream_t)stream);
-}
-
 extern "C" int srfrd_logits_topk_excl(const srfrd_layout* lay, const void* item_table, const float* dense,
                                       const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
                                       const int64_t* user_label, int k, const int64_t* excl_ptr, const int32_t* excl_items,
@@ -1536,13 +1546,28 @@ extern "C" int srfrd_logits_topk_excl(const srfrd_layout* lay, const void* item_
                                       void* stream) {
   if (!topk_idx || !topk_val || !workspace || k <= 0 || k > 64) return SRFRD_E_ARG;
   if (int rc = topk_args_check(lay, item_table, dense, hidden, B, L, item_lo, item_hi, user_label)) return rc;
-  if (int rc = excl_args(excl_ptr, excl_items, max_row, excl_workspace)) return rc;
-  if (excl_ptr)
-    if (int rc = excl_range(B, max_row, item_hi)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  const ExclSet ex = excl_prepare(excl_ptr, excl_items, max_row, B, item_lo, item_hi, excl_workspace, st);
-  return logits_topk_impl(lay, item_table, dense, hidden, B, L, item_lo, item_hi, exclude_pad, user_label, k, topk_idx, topk_val,
-                          workspace, ex, st);
+  if (int rc = excl_args(excl_ptr, excl_items, max_row, excl_workspace, B, item_hi)) return rc;
+  // the four-launch threshold scheme (+ the armed exhaustive path); an exclusion set adds its pre-pass and masks
+  const RankPlan p = rank_plan(*lay, SRFRD_RANK_TOPK, B, k, item_lo, item_hi, excl_ptr != nullptr, read_switches(), num_cu());
+  if (p.rc) return p.rc;
+  RankIO io = {excl_ptr, excl_items, max_row, topk_idx, topk_val};
+  TopkArgs a = rank_args(p, lay, item_table, dense, hidden, B, L, item_lo, item_hi, exclude_pad, user_label, k, max_row,
+                         excl_workspace, io);
+  char* ws = (char*)workspace;
+  a.cmax = (float*)(ws + topk_off(B, k, p.n_chunks, 0));
+  a.tau = (float*)(ws + topk_off(B, k, p.n_chunks, 1));
+  a.ccnt = (int32_t*)(ws + topk_off(B, k, p.n_chunks, 2));
+  a.cand = (Cand*)(ws + topk_off(B, k, p.n_chunks, 3));
+  io.fb = (Cand*)(ws + topk_off(B, k, p.n_chunks, 4));
+  return run_plan(p, a, io, (hipStream_t)stream);
+}
+
+extern "C" int srfrd_logits_topk(const srfrd_layout* lay, const void* item_table, const float* dense,
+                                 const float* hidden, int B, int L, int64_t item_lo, int64_t item_hi, int exclude_pad,
+                                 const int64_t* user_label, int k, int64_t* topk_idx, float* topk_val, void* workspace,
+                                 void* stream) {
+  return srfrd_logits_topk_excl(lay, item_table, dense, hidden, B, L, item_lo, item_hi, exclude_pad, user_label, k, nullptr, nullptr,
+                                0, topk_idx, topk_val, workspace, nullptr, stream);
 }
 
 extern "C" int srfrd_target_rank(const srfrd_layout* lay, const void* item_table, const float* dense, const float* hidden,
@@ -1551,50 +1576,16 @@ extern "C" int srfrd_target_rank(const srfrd_layout* lay, const void* item_table
                                  int cut_k, int32_t* rank, double* metric_acc, void* workspace, void* stream) {
   if (!targets || !rank || !workspace || cut_k <= 0) return SRFRD_E_ARG;
   if (int rc = topk_args_check(lay, item_table, dense, hidden, B, L, item_lo, item_hi, user_label)) return rc;
-  if (excl_ptr && (!excl_items || max_row < 0)) return SRFRD_E_ARG;
-  if (excl_ptr && max_row > kExclCap) return SRFRD_E_UNSUPPORTED;
-  if (excl_ptr)
-    if (int rc = excl_range(B, max_row, item_hi)) return rc;
-  const int DSi = ((lay->d_item + 3) & ~3) + 2;
-  const size_t lds_stream = ((size_t)kChunk * DSi + 2 * 16 * DSi + 32 + 8 * 16 + kSlack) * sizeof(float);
-  const size_t lds_stream_x = lds_stream + 16 * (kChunk / 32) * sizeof(uint32_t);
-  if (lds_stream_x > (size_t)kLdsLimit) return SRFRD_E_UNSUPPORTED;
-  const size_t lds_score = ((size_t)2 * 16 * DSi + 16 + kSlack) * sizeof(float);
-  if (lds_opt_in((const void*)target_count_kernel<false>, kLdsLimit) || lds_opt_in((const void*)target_count_kernel<true>, kLdsLimit))
-    return SRFRD_E_DEVICE;
-  hipStream_t st = (hipStream_t)stream;
-  const ExclSet ex = excl_prepare(excl_ptr, excl_items, max_row, B, item_lo, item_hi, workspace, st);
-  TopkArgs a = {};
-  a.ly = *lay; a.table = item_table; a.dense = dense; a.hidden = hidden; a.user_label = user_label;
-  a.B = B; a.L = L; a.exclude_pad = exclude_pad; a.k = 1;
-  a.item_lo = item_lo; a.item_hi = item_hi;
-  a.n_chunks = (int)((item_hi - item_lo + kChunk - 1) / kChunk);
-  a.user_splits = 1;
+  if (int rc = excl_args(excl_ptr, excl_items, max_row, workspace, B, item_hi)) return rc;
+  const RankPlan p = rank_plan(*lay, metric_acc ? SRFRD_RANK_TARGET_METRIC : SRFRD_RANK_TARGET, B, 1, item_lo, item_hi,
+                               excl_ptr != nullptr, read_switches(), num_cu());
+  if (p.rc) return p.rc;
+  RankIO io = {excl_ptr, excl_items, max_row, nullptr, nullptr, targets, cut_k, metric_acc};
+  TopkArgs a = rank_args(p, lay, item_table, dense, hidden, B, L, item_lo, item_hi, exclude_pad, user_label, 1, max_row, workspace, io);
   a.tau = (float*)workspace;                     // s_t
   a.ccnt = rank;
-  a.xs = ex.xs; a.xoff = ex.xoff; a.xstride = ex.xstride; a.xchunks = ex.xchunks;
-  const bool excl = ex.xs != nullptr;
-  Plan16 p;
-  if (int rc = plan_stream16(lay, a, p, excl)) return rc;
-  const dim3 tiles((B + 15) / 16);
-  if (p.on) {
-    if (lay->table_bf16) hipLaunchKernelGGL(target_score16_kernel<false>, tiles, dim3(64), 0, st, a, targets);
-    else hipLaunchKernelGGL(target_score16_kernel<true>, tiles, dim3(64), 0, st, a, targets);
-    if (excl) SRFRD_L16X(p, target_count16_kernel);
-    else SRFRD_L16(p, kStream16Lds, target_count16_kernel, , false);
-  } else {
-    hipLaunchKernelGGL(target_score_kernel, tiles, dim3(64), lds_score, st, a, targets);
-    // (one user tile per workgroup and chunk: the count needs no split heuristics - the pass reads every chunk once per tile)
-    a.user_splits = (B + 15) / 16 < 8 ? (B + 15) / 16 : 8;
-    if (excl) hipLaunchKernelGGL(target_count_kernel<true>, dim3(a.n_chunks * a.user_splits), dim3(512), lds_stream_x, st, a);
-    else hipLaunchKernelGGL(target_count_kernel<false>, dim3(a.n_chunks * a.user_splits), dim3(512), lds_stream, st, a);
-  }
-  if (metric_acc)
-    hipLaunchKernelGGL(target_metric_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const int32_t*)rank, B, cut_k, metric_acc);
-  return (int)hipGetLastError();
+  return run_plan(p, a, io, (hipStream_t)stream);
 }
-#undef SRFRD_L16
-#undef SRFRD_L16X
 
 extern "C" int srfrd_topk_merge(const int64_t* cand_idx, const float* cand_val, int B, int n_cand, int k, int64_t* topk_idx,
                                 float* topk_val, void* stream) {
