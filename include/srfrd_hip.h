@@ -284,7 +284,8 @@ int srfrd_step_begin(uint32_t* state, double lr, double beta1, double beta2, voi
  *   g = grad[i] * gscale;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= step_size * m / (sqrt(v)/bc2_sqrt + eps)
  * gscale = 1 / stats[2] if stats != NULL (mean over non-pad targets, trainer.py:36-38) else 1.
  * The first n_zero gradient elements (the table, accumulated by atomics) are re-zeroed in the same pass.
- * [i0, i1) = the slice this rank updates (sharded optimizer); pass 0, n for all.
+ * [i0, i1) = the slice this rank updates (sharded optimizer); pass 0, n for all.  i0 is a multiple of 4 unless the slice
+ * is empty (an empty slice launches nothing).
  * table_bf16 (may be NULL): bf16 shadow of the first n_table parameters (the item table); stepped elements below n_table
  * are also written there, rounded to nearest even.
  */
@@ -304,7 +305,8 @@ int srfrd_adam_pack_step(const srfrd_layout* lay, float* param, float* grad, flo
                          int64_t n_table_pad, int64_t n_zero, double lr, double beta1, double beta2, double eps,
                          uint32_t* state, const float* stats, float* packed, uint16_t* table_bf16, void* stream);
 
-/* bf16 shadow of an fp32 vector (round to nearest even): out[i] = bf16(src[i]), i < n.  Builds / refreshes the item-table
+/* bf16 shadow of an fp32 vector (round to nearest even; fp32 denormals are rounded, not flushed; NaN stays NaN):
+ * out[i] = bf16(src[i]), i < n.  Builds / refreshes the item-table
  * shadow that lay->table_bf16 = 1 launches gather from (the fused optimizer keeps it current by itself). */
 int srfrd_table_to_bf16(const float* src, int64_t n, uint16_t* out, void* stream);
 

@@ -391,8 +391,9 @@ extern "C" int srfrd_table_to_bf16(const float* src, int64_t n, uint16_t* out, v
 extern "C" int srfrd_adam_step(float* param, float* grad, float* m, float* v, int64_t n, int64_t i0, int64_t i1,
                                int64_t n_zero, double beta1, double beta2, double eps, const uint32_t* state,
                                const float* stats, uint16_t* table_bf16, int64_t n_table, void* stream) {
-  if (!param || !grad || !m || !v || !state || n <= 0 || i0 < 0 || i1 > n || i0 > i1 || (i0 & 3)) return SRFRD_E_ARG;
-  if (i0 == i1) return 0;
+  if (!param || !grad || !m || !v || !state || n <= 0 || i0 < 0 || i1 > n || i0 > i1) return SRFRD_E_ARG;
+  if (i0 == i1) return 0;                 // an empty slice launches nothing, wherever it sits (shard_bounds' last ranks)
+  if (i0 & 3) return SRFRD_E_ARG;
   const int64_t nvec = ((i1 - i0) >> 2) + 1;
   int64_t grid = (nvec + 255) / 256;
   if (grid > 4096) grid = 4096;

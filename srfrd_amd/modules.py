@@ -10,6 +10,7 @@ All arithmetic runs in ``libsrfrd_hip.so``; on a non-CUDA device or without the 
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import torch
 import torch.nn as nn
@@ -19,6 +20,16 @@ from ._lib import check, ptr
 
 
 FLAT_SLACK = 4096        # floats of zero padding kept behind a model's flat parameter vector
+# storage address -> the module whose flat parameter vector lives there (srfrd_amd.Adam asks which tensors the vector holds)
+_FLAT_OWNERS: "weakref.WeakValueDictionary[int, nn.Module]" = weakref.WeakValueDictionary()
+
+
+def flat_owner(storage_ptr: int):
+    """The srfrd_amd module whose current flat parameter vector starts the storage at `storage_ptr`, or None."""
+    m = _FLAT_OWNERS.get(storage_ptr)
+    if m is None or m._flat is None or m._flat.untyped_storage().data_ptr() != storage_ptr:
+        return None
+    return m
 
 
 def _stream():
@@ -237,6 +248,8 @@ class _SRFRDBase(nn.Module):
             base = flat.data_ptr()
             if all(p.data_ptr() == base + 4 * off and p.dtype == torch.float32 for p, off in slots):
                 self._slots = slots
+                if _FLAT_OWNERS.get(base) is not self:          # (a deep copy shares no storage with its original)
+                    _FLAT_OWNERS[base] = self
                 return
         # (a few KiB of zeroed slack behind the vector: the data-parallel all-gather pads it to world equal shards)
         self._flat_store = torch.zeros(self.n_flat + FLAT_SLACK, device=dev, dtype=torch.float32)
@@ -250,6 +263,7 @@ class _SRFRDBase(nn.Module):
             covered += n
         assert covered == lay.n_table + lay.n_dense, "parameter list does not match the dense layout"
         self._flat, self._slots = flat, slots
+        _FLAT_OWNERS[flat.data_ptr()] = self
 
     # ---- bf16 item-table shadow (BASELINE configs[1] / [4] "bf16"; no reference counterpart: its table is fp32)
     def use_bf16_table(self, on: bool = True, auto_refresh: bool = True):

@@ -5,10 +5,17 @@ The reference loop (trainer.py:29-41) stays as it is - ``model(...)`` -> BCE -> 
 the optimizer's constructor changes.  Every parameter of a srfrd_amd module is a view of one fp32 vector
 ``[item table | pad | dense]`` and the backward op returns every gradient as a view of one flat gradient vector, so the step
 is ``srfrd_adam_step`` over the whole vector (same arithmetic as the fused trainer's tail; torch's foreach Adam walks 31
-tensors with a handful of launches each and costs more host time than the model's kernels take).  Falls back to gathering the
-gradients into a flat buffer when they are not views of one vector (gradient accumulation over several backward calls,
-hooks that replace them).  ``state_dict()`` / ``load_state_dict()`` use torch.optim.Adam's own format, so a run can move
-between the two optimizers (and ``FusedTrainer``)."""
+tensors with a handful of launches each and costs more host time than the model's kernels take).
+
+That one in-place launch is taken when the list holds every parameter of the module, all with a gradient of the same step
+count, laid out as views of one gradient vector.  Otherwise the gradients are gathered into a flat buffer (gradient
+accumulation over several backward calls, hooks that replace them), and what must not move - tensors left out of the list
+(frozen), listed ones without a gradient (torch skips them) - is copied aside before the launch and back after it, so it
+comes out bit-unchanged: a parameter and its two moments per held tensor and step, i.e. three copies of the item table per
+step when the table is frozen (0.6 GB of traffic at 1 M x 50).  Like torch, every parameter keeps its own step count (the
+bias corrections follow it); parameters whose counts differ are stepped by one launch per count.  ``state_dict()`` /
+``load_state_dict()`` use torch.optim.Adam's own format, so a run can move between the two optimizers (and
+``FusedTrainer``)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -29,11 +36,15 @@ class Adam(torch.optim.Optimizer):
             raise ValueError("srfrd_amd.Adam takes ONE parameter group: model.parameters() of one srfrd_amd module")
         self._flat = self._m = self._v = self._gbuf = self._dev_state = None
         self._spans = None
+        self._full = False          # the list holds every parameter of the module that owns the vector (set by _resolve)
+        self._loaded = None         # load_state_dict's state, scattered into _m / _v / _counts by the next _resolve
+        self._counts = [0] * len(self.param_groups[0]["params"])     # torch's per-parameter "step"
         self._p0 = self._pl = None
-        self._steps = 0
+        self._steps = 0             # the step count the device state holds (its word 0)
 
     # ---- the flat vector behind the parameters -------------------------------------------------------------------------
     def _resolve(self):
+        from .modules import flat_owner
         ps = self.param_groups[0]["params"]
         st = ps[0].untyped_storage()
         base = st.data_ptr()
@@ -55,11 +66,28 @@ class Adam(torch.optim.Optimizer):
             self._dev_state = torch.zeros(32, device=dev, dtype=torch.int32)
             self._dev_state[0] = self._steps
         self._spans = [(p, p.storage_offset(), p.numel()) for p in ps]
+        # Whether one launch over [0, n) steps nothing but the listed tensors: the list must hold every parameter of the module
+        # whose flat vector this is (the gaps left are its alignment padding, which stays zero).  Dense tensors are packed
+        # with no alignment, so a frozen one may share a float4 with a listed one, at the tail as anywhere else.
+        owner = flat_owner(base)
+        listed = set(spans)
+        self._full = owner is not None and all((off, q.numel()) in listed for q, off in owner._slots)
+        if self._loaded is not None:
+            loaded, self._loaded = self._loaded, None
+            self._m.zero_(); self._v.zero_()
+            self._counts = [0] * len(ps)
+            for i, (p, off, k) in enumerate(self._spans):
+                s = loaded.get(i)
+                if s is not None:
+                    self._m[off:off + k] = s["exp_avg"].to(device=p.device, dtype=torch.float32).reshape(-1)
+                    self._v[off:off + k] = s["exp_avg_sq"].to(device=p.device, dtype=torch.float32).reshape(-1)
+                    self._counts[i] = int(float(s["step"]))
 
-    def _flat_grad(self):
-        """the gradients as one vector aligned with the flat parameters: in place when they already are views of one"""
+    def _flat_grad(self, in_place_ok):
+        """the gradients as one vector aligned with the flat parameters: in place when they already are views of one and
+        the launch may read all of [0, n) from there (in_place_ok: every parameter of the module is stepped)"""
         base = last = None
-        for p, off, n in self._spans:
+        for p, off, n in (self._spans if in_place_ok else ()):
             g = p.grad
             if g is None or not g.is_contiguous():
                 base = None
@@ -101,15 +129,37 @@ class Adam(torch.optim.Optimizer):
             self._p0, self._pl = ps[0].data_ptr(), ps[-1].data_ptr()
         g = self.param_groups[0]
         lr, (b1, b2), eps = g["lr"], g["betas"], g["eps"]
-        gptr, keep = self._flat_grad()
+        groups = {}                     # step count -> the listed parameters with a gradient that have taken that many steps
+        for i, (p, off, k) in enumerate(self._spans):
+            if p.grad is not None:
+                groups.setdefault(self._counts[i], []).append((off, k))
+        gptr, keep = self._flat_grad(self._full and len(groups) == 1 and sum(map(len, groups.values())) == len(ps))
+        n = self._flat.numel()
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         L_ = _lib.lib()
-        # t += 1 and the bias corrections in double precision on the device, then the step over the whole vector
-        check(L_.srfrd_step_begin(ptr(self._dev_state), lr, b1, b2, st), "srfrd_step_begin")
-        n = self._flat.numel()
-        check(L_.srfrd_adam_step(ptr(self._flat), gptr, ptr(self._m), ptr(self._v), n, 0, n, 0, b1, b2, eps,
-                                 ptr(self._dev_state), None, None, 0, st), "srfrd_adam_step")
-        self._steps += 1
+        for count, spans in sorted(groups.items()):
+            # Each launch steps all of [0, n).  Off the in-place path, what it must not step - parameters left out of the
+            # list, listed ones without a gradient or of another step count - is saved here and put back after it: the
+            # kernel's slices start on multiples of 4, parameters do not, so it cannot be launched per span.
+            held = []
+            if keep is self._gbuf:
+                lo = 0
+                for off, k in sorted(spans) + [(n, 0)]:
+                    if off > lo:
+                        held.append((lo, off, self._flat[lo:off].clone(), self._m[lo:off].clone(), self._v[lo:off].clone()))
+                    lo = max(lo, off + k)
+            if count != self._steps:
+                self._dev_state[0] = count
+            # t += 1 and the bias corrections in double precision on the device, then the step over the whole vector
+            check(L_.srfrd_step_begin(ptr(self._dev_state), lr, b1, b2, st), "srfrd_step_begin")
+            check(L_.srfrd_adam_step(ptr(self._flat), gptr, ptr(self._m), ptr(self._v), n, 0, n, 0, b1, b2, eps,
+                                     ptr(self._dev_state), None, None, 0, st), "srfrd_adam_step")
+            self._steps = count + 1
+            for lo, hi, p, m, v in held:
+                self._flat[lo:hi].copy_(p); self._m[lo:hi].copy_(m); self._v[lo:hi].copy_(v)
+        for i, (p, _, _) in enumerate(self._spans):
+            if p.grad is not None:
+                self._counts[i] += 1
         del keep
         return loss
 
@@ -118,10 +168,14 @@ class Adam(torch.optim.Optimizer):
         g = self.param_groups[0]
         ps = g["params"]
         state = {}
-        if self._spans is not None and self._steps > 0:
+        if self._loaded is not None:                   # loaded before the parameters were resolved: hand it back as it came
+            state = {i: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in s.items()} for i, s in self._loaded.items()}
+        elif self._spans is not None:
             for i, (p, off, n) in enumerate(self._spans):
-                state[i] = {"step": torch.tensor(float(self._steps)), "exp_avg": self._m[off:off + n].view(p.shape).clone(),
-                            "exp_avg_sq": self._v[off:off + n].view(p.shape).clone()}
+                if self._counts[i] > 0:                # (torch holds state only for parameters it has stepped)
+                    state[i] = {"step": torch.tensor(float(self._counts[i])),
+                                "exp_avg": self._m[off:off + n].view(p.shape).clone(),
+                                "exp_avg_sq": self._v[off:off + n].view(p.shape).clone()}
         group = {"lr": g["lr"], "betas": g["betas"], "eps": g["eps"], "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
                  "params": list(range(len(ps)))}
@@ -133,16 +187,8 @@ class Adam(torch.optim.Optimizer):
             raise ValueError("srfrd_amd.Adam implements plain Adam (no weight decay / amsgrad / maximize)")
         g = self.param_groups[0]
         g["lr"], g["betas"], g["eps"] = float(group["lr"]), (float(group["betas"][0]), float(group["betas"][1])), float(group["eps"])
-        steps = {int(float(s["step"])) for s in sd["state"].values()}
-        if len(steps) > 1:
-            raise ValueError("parameters with different step counts")
-        self._steps = steps.pop() if steps else 0
-        self._resolve()
-        self._m.zero_(); self._v.zero_()
-        for i, (p, off, n) in enumerate(self._spans):
-            s = sd["state"].get(i)
-            if s is not None:
-                self._m[off:off + n] = s["exp_avg"].to(device=p.device, dtype=torch.float32).reshape(-1)
-                self._v[off:off + n] = s["exp_avg_sq"].to(device=p.device, dtype=torch.float32).reshape(-1)
-        self._dev_state.zero_()
-        self._dev_state[0] = self._steps
+        # Kept until the next _resolve() scatters it into the moments: the parameters become views of the flat vector only
+        # at the model's first forward, so a state loaded right after construction (the usual resume order) must wait.
+        self._loaded = {int(i): {"step": s["step"], "exp_avg": s["exp_avg"].detach().clone(), "exp_avg_sq": s["exp_avg_sq"].detach().clone()}
+                        for i, s in sd["state"].items()}
+        self._spans = None

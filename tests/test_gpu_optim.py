@@ -50,6 +50,7 @@ def test_flat_adam_equals_torch_adam_and_exchanges_state(kind):
     for i in range(3):
         l1, l2 = _step(m1, o1, batches[i]), _step(m2, o2, batches[i])
         assert abs(l1 - l2) < 1e-5
+    assert o1._gbuf is None                        # every step took the one in-place launch (no gradient gather)
     sd1, sd2 = m1.state_dict(), m2.state_dict()
     _close(sd1, sd2)
     # state in torch.optim.Adam's own format, both directions
@@ -118,3 +119,97 @@ def test_replaced_parameters_and_submodules_are_picked_up_by_the_next_forward():
     assert float((m.last_layernorm.weight.detach() - before).abs().max()) > 0
     base = m.flat_parameters().data_ptr()
     assert all(base <= p.data_ptr() < base + 4 * m.flat_parameters().numel() for p in m.parameters())
+
+
+@pytest.mark.parametrize("frozen", ["item_emb.weight", "attention_layers.1.in_proj_weight", "last_layernorm.bias"])
+def test_filtered_parameter_list_leaves_frozen_tensors_alone(frozen):
+    """Adam([p for p in m.parameters() if p.requires_grad]): the backward still writes every gradient into the one flat
+    gradient vector, but a tensor left out of the list must neither move nor get state - as with torch.optim.Adam.  The last
+    one, last_layernorm.bias, starts 2 elements into a float4 at the end of the vector."""
+    import srfrd_amd
+    m1 = _model()
+    m2 = copy.deepcopy(m1)
+    for m in (m1, m2):
+        dict(m.named_parameters())[frozen].requires_grad_(False)
+    o1 = srfrd_amd.Adam([p for p in m1.parameters() if p.requires_grad], lr=1e-3, betas=(0.9, 0.98))
+    o2 = torch.optim.Adam([p for p in m2.parameters() if p.requires_grad], lr=1e-3, betas=(0.9, 0.98))
+    before = dict(m1.named_parameters())[frozen].detach().clone()
+    batches = [srfrd_amd.synthetic_batch(400, 50, 24, seed=4, index=i, device="cuda") for i in range(2)]
+    for b in batches:
+        assert abs(_step(m1, o1, b) - _step(m2, o2, b)) < 1e-5
+    assert torch.equal(dict(m1.named_parameters())[frozen].detach(), before)
+    s1, s2 = o1.state_dict(), o2.state_dict()
+    assert sorted(s1["state"]) == sorted(s2["state"]) and len(s1["state"]) == len(list(m1.parameters())) - 1
+    _close(m1.state_dict(), m2.state_dict())
+
+
+def test_listed_parameter_without_gradient_keeps_value_and_moments():
+    """a listed parameter whose .grad is None is skipped, however large its (loaded) moments - torch.optim.Adam's rule"""
+    import srfrd_amd
+    m1 = _model()
+    m2 = copy.deepcopy(m1)
+    o1 = srfrd_amd.Adam(m1.parameters(), lr=1e-3, betas=(0.9, 0.98))
+    o2 = torch.optim.Adam(m2.parameters(), lr=1e-3, betas=(0.9, 0.98))
+    batches = [srfrd_amd.synthetic_batch(400, 50, 24, seed=6, index=i, device="cuda") for i in range(2)]
+    _step(m2, o2, batches[0])
+    _step(m1, o1, batches[0])
+    o1.load_state_dict(o2.state_dict())                # non-zero moments for every parameter
+    names = [k for k, _ in m1.named_parameters()]
+    j = names.index("last_layernorm.weight")
+    p1, p2 = dict(m1.named_parameters())["last_layernorm.weight"], dict(m2.named_parameters())["last_layernorm.weight"]
+    with torch.no_grad():
+        p1.copy_(p2)
+    m_before = o1.state_dict()["state"][j]["exp_avg"].clone()
+    v_before = o1.state_dict()["state"][j]["exp_avg_sq"].clone()
+    assert float(m_before.abs().max()) > 0
+    w_before = p1.detach().clone()
+    for m, o in ((m1, o1), (m2, o2)):
+        u, seq, rsq, pos, prs, neg, nrs = batches[1]
+        h, pl, nl = m(u, seq, rsq, pos, prs, neg, nrs)
+        o.zero_grad()
+        (pl.sum() * 1e-3 - nl.sum() * 1e-3).backward()
+        dict(m.named_parameters())["last_layernorm.weight"].grad = None
+        o.step()
+    assert torch.equal(p1.detach(), w_before) and torch.equal(p2.detach(), w_before)
+    s1, s2 = o1.state_dict(), o2.state_dict()
+    assert torch.equal(s1["state"][j]["exp_avg"], m_before) and torch.equal(s1["state"][j]["exp_avg_sq"], v_before)
+    _close(m1.state_dict(), m2.state_dict())
+    # torch's per-parameter step counts: the skipped parameter is one behind, in both state dicts, and the next step corrects
+    # its bias with its own count (a second launch); the states still move between the two optimizers
+    assert sorted(s1["state"]) == sorted(s2["state"])
+    for i in s2["state"]:
+        assert float(s1["state"][i]["step"]) == float(s2["state"][i]["step"]) == (1.0 if i == j else 2.0)
+    o1.load_state_dict(s2)
+    o2.load_state_dict(s1)
+    assert abs(_step(m1, o1, batches[0]) - _step(m2, o2, batches[0])) < 1e-5
+    _close(m1.state_dict(), m2.state_dict())
+    s1, s2 = o1.state_dict(), o2.state_dict()
+    for i in s2["state"]:
+        assert float(s1["state"][i]["step"]) == float(s2["state"][i]["step"]) == (2.0 if i == j else 3.0)
+        assert float((s1["state"][i]["exp_avg"] - s2["state"][i]["exp_avg"]).abs().max()) < 1e-5
+
+
+@pytest.mark.parametrize("kind", ["SASRec", "SRFRN"])
+def test_load_state_dict_before_the_first_forward(kind):
+    """the usual resume order - build the model and the optimizer, load both state dicts, then train - continues torch's run"""
+    import srfrd_amd
+    m2 = _model(kind)
+    o2 = torch.optim.Adam(m2.parameters(), lr=1e-3, betas=(0.9, 0.98))
+    batches = [srfrd_amd.synthetic_batch(400, 50, 24, seed=3, index=i, device="cuda") for i in range(4)]
+    for i in range(3):
+        _step(m2, o2, batches[i])
+    torch.manual_seed(1)
+    m3 = (srfrd_amd.SASRec(400, 50, 50, 0.0, 2, 1, "cuda") if kind == "SASRec"
+          else srfrd_amd.SRFRN(400, 50, 45, 5, 0.0, 2, 1, "cuda")).cuda().train()
+    o3 = srfrd_amd.Adam(m3.parameters(), lr=1e-3, betas=(0.9, 0.98))
+    m3.load_state_dict(m2.state_dict())
+    o3.load_state_dict(o2.state_dict())                # before any forward of m3
+    s3 = o3.state_dict()
+    assert float(s3["state"][0]["step"]) == 3.0
+    l3, l2 = _step(m3, o3, batches[3]), _step(m2, o2, batches[3])
+    assert abs(l3 - l2) < 1e-5
+    _close(m3.state_dict(), m2.state_dict())
+    s3, s2 = o3.state_dict(), o2.state_dict()
+    for i in s2["state"]:
+        assert float(s3["state"][i]["step"]) == float(s2["state"][i]["step"]) == 4.0
+        assert float((s3["state"][i]["exp_avg"] - s2["state"][i]["exp_avg"]).abs().max()) < 1e-5
