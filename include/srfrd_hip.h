@@ -418,6 +418,31 @@ int srfrd_rank_plan(const srfrd_layout* lay, int op, int B, int k, int64_t item_
 int srfrd_eval_rank(const float* logits, int B, int n_cand, int32_t* rank, double* metric_acc, void* stream);
 
 /*
+ * Full-catalog softmax cross-entropy (no reference counterpart: the reference trains with one sampled negative per position,
+ * trainer.py:36-38).  Tokens are the positions t of the (B, L) `targets` with targets[t] != 0; the candidates are the items
+ * 1..n_items (item 0, the pad row, is excluded); s_tj = <hidden[t, :d_item], E[j]> with E = the fp32 item table
+ * (n_items + 1, d_item) and hidden (B, L, d_out) - SRFRN's fake slice is not read (it adds one constant per row, which the
+ * softmax does not see); loss_t = logsumexp_j s_tj - s_t,y.  Target ids are clamped into [0, n_items] as everywhere else.
+ * The (tokens x items) logits are never written: the forward streams the table in item tiles against tiles of tokens on
+ * the fp32 matrix cores, the backward recomputes them.  No float atomics: two identical calls give bitwise-identical results.
+ * lay->table_bf16 or lay->D > SRFRD_MAX_D -> SRFRD_E_UNSUPPORTED.
+ *
+ * srfrd_xent_workspace_floats [host]: floats of `workspace` both calls need for (B, L) (0 for arguments they refuse).
+ * srfrd_xent_fwd: token_loss (B, L) (0 where targets == 0), lse (B, L) (0 there too), stats[0..1] = {sum of the token losses,
+ *   token count} (fp32; the count stays on the device: a mean needs no host synchronisation).
+ * srfrd_xent_bwd: with the forward's lse and the upstream gradient of every token loss d_token_loss (B, L):
+ *   d_hidden (B, L, d_out) = sum_j d_t (softmax_tj - [j == y_t]) E[j] in columns < d_item, zeros elsewhere and at ignored
+ *   positions (fully overwritten); grad_table (n_items + 1, d_item) = (accumulate: +=) sum_t d_t (softmax_tj - [j == y_t])
+ *   hidden[t, :d_item]; row 0 receives 0.
+ */
+int64_t srfrd_xent_workspace_floats(const srfrd_layout* lay, int B, int L);
+int srfrd_xent_fwd(const srfrd_layout* lay, const float* table, const float* hidden, const int64_t* targets, int B, int L,
+                   float* token_loss, float* lse, float* stats, float* workspace, int64_t ws_floats, void* stream);
+int srfrd_xent_bwd(const srfrd_layout* lay, const float* table, const float* hidden, const int64_t* targets,
+                   const float* lse, const float* d_token_loss, int B, int L, float* d_hidden, float* grad_table,
+                   int accumulate, float* workspace, int64_t ws_floats, void* stream);
+
+/*
  * Device-side batch sampler with the layout and semantics of reference utils.py:21-57 (sample_function_fr /
  * WarpSampler_fr): per sampled user (uniform among users with > 1 interaction) the most recent `L` training items
  * left-padded with 0, pos[t] = the next item, neg[t] = a uniform item outside the user's history wherever pos[t] != 0,

@@ -80,6 +80,9 @@ SIGNATURES = {
     "srfrd_rank_plan": (_i, [_LP, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _P, _i, _P]),
     "srfrd_eval_rank": (_i, [_P, _i, _i, _P, _P, _P]),
     "srfrd_sample_batch": (_i, [_P, _P, _P, _i, _i, _i, _i, _u32, _u32, _P, _P, _P]),
+    "srfrd_xent_workspace_floats": (_i64, [_LP, _i, _i]),
+    "srfrd_xent_fwd": (_i, [_LP, _P, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
+    "srfrd_xent_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _P, _P, _i, _P, _i64, _P]),
 }
 
 _lib = None

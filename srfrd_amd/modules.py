@@ -129,6 +129,32 @@ class _EncoderFn(torch.autograd.Function):
         return (None,) * 9 + m._grad_views(gflat)
 
 
+class _XentFn(torch.autograd.Function):
+    """full_catalog_loss() under autograd: the launches of the registered ``srfrd::xent_fwd`` / ``srfrd::xent_bwd`` ops
+    (srfrd_amd/ops.py) without torch.library's Python glue, as _EncoderFn does for the encoder.  The reduction is applied on
+    the device from the forward's {sum, count}: no host synchronisation in either direction."""
+
+    @staticmethod
+    def forward(ctx, model, reduction, hidden, targets, table):
+        lay, tab = model.layout, ptr(table)
+        tl, lse, stats = ops.xent_launch_fwd(lay, tab, hidden, targets)
+        ctx.model, ctx.reduction = model, reduction
+        ctx.save_for_backward(hidden, targets, table, lse, stats)
+        if reduction == "none":
+            return tl
+        return stats[0].clone() if reduction == "sum" else stats[0] / stats[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        hidden, targets, table, lse, stats = ctx.saved_tensors
+        if ctx.reduction == "none":
+            d_tok = g.contiguous()
+        else:
+            d_tok = (g if ctx.reduction == "sum" else g / stats[1]).expand(targets.shape).contiguous()
+        dh, de = ops.xent_launch_bwd(ctx.model.layout, ptr(table), hidden, targets, lse, d_tok)
+        return None, None, dh, None, de
+
+
 class _SRFRDBase(nn.Module):
     """Shared machinery: flat parameter storage, kernel launches, predict."""
 
@@ -472,6 +498,34 @@ class _SRFRDBase(nn.Module):
             self._split_sizes, self._split_keep, self._split_n = sizes, keep, gflat.numel()
         parts = gflat.split_with_sizes(self._split_sizes)
         return tuple(t.view(q.shape) for (t, k), (q, _) in zip(((t, k) for t, k in zip(parts, self._split_keep) if k), self._slots))
+
+    def full_catalog_loss(self, hidden_state, positive_ids, reduction="mean"):
+        """Softmax cross-entropy of every target against the whole catalog: ``F.cross_entropy(logits[:, 1:], y - 1,
+        ignore_index=-1, reduction=...)`` over the logits ``hidden_state[..., :d_item] @ item_table.T`` of the positions with
+        ``positive_ids != 0``, without materialising them (``srfrd_xent_fwd`` / ``_bwd``).  ``hidden_state`` is the (B, L,
+        d_out) first output of ``model(...)``; autograd carries the loss into it (and so through the encoder) and into the
+        item table.  reduction: "mean" (over the targets; NaN when there are none, as torch gives), "sum" or "none" ((B, L),
+        zeros at ignored positions).  SRFRN's fake slice adds one constant per row, which the softmax does not see: it
+        gets a zero gradient."""
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
+        self._ensure_flat()
+        if self.bf16_table:
+            raise RuntimeError("full_catalog_loss needs the fp32 item table (use_bf16_table(False)); the bf16 form is not built")
+        lay = self.layout
+        dev = self._flat.device
+        if hidden_state.dim() != 3 or hidden_state.shape[2] != lay.d_out or hidden_state.device != dev:
+            raise ValueError(f"hidden_state must be the model's (B, L, {lay.d_out}) output on {dev}")
+        if hidden_state.dtype != torch.float32:
+            raise ValueError("hidden_state must be float32")
+        y = _ids(positive_ids, dev, hidden_state.shape[:2])
+        if self.validate_ids:
+            check(_lib.lib().srfrd_check_ids(ptr(y), None, None, None, None, None, y.numel(), lay.n_items, 2,
+                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
+            if self.validate_ids == "eager":
+                self.check_ids()
+        table = self._slots[0][0]
+        return _XentFn.apply(self, reduction, hidden_state.contiguous(), y, table)
 
     def user_labels(self, fake_ids):
         """get_Labels (SRFU_*) / the predict-time label (SRFRN) as an int64 (B,) tensor, computed on device."""

@@ -14,6 +14,8 @@ backward - instead of being an opaque ctypes call from Python:
     srfrd::topk_merge      merge of per-shard top-k lists
     srfrd::user_labels     get_Labels (SRFR_model.py:546-570)
     srfrd::eval_rank       rank of candidate 0 (utils.py:589-597)
+    srfrd::xent_fwd        full-catalog softmax cross-entropy per token (logits never in HBM); backward = srfrd::xent_bwd
+    srfrd::xent_bwd        its gradients into the hidden state and the item table
 
 A model's geometry (the srfrd_layout descriptor, its flat parameter vector and packed weights) is not expressible as op
 arguments one by one; the ops take ``model_key``, the registry key of a live model (``register_model``), and read
@@ -306,5 +308,87 @@ def _(logits):
     return torch.empty(logits.shape[0], device=logits.device, dtype=torch.int32)
 
 
+# ------------------------------------------------------------------------------------------------ full-catalog cross-entropy
+def xent_launch_fwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor):
+    """srfrd_xent_fwd -> (token_loss (B, L), lse (B, L), stats {sum, count})"""
+    B, L = targets.shape
+    dev = hidden.device
+    L_ = _lib.lib()
+    ws = torch.empty(L_.srfrd_xent_workspace_floats(C.byref(lay), B, L), device=dev, dtype=torch.float32)
+    tl = torch.empty(B, L, device=dev, dtype=torch.float32)
+    lse = torch.empty(B, L, device=dev, dtype=torch.float32)
+    stats = torch.empty(2, device=dev, dtype=torch.float32)
+    check(L_.srfrd_xent_fwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), B, L, ptr(tl), ptr(lse), ptr(stats), ptr(ws),
+                            ws.numel(), _stream()), "srfrd_xent_fwd")
+    return tl, lse, stats
+
+
+def xent_launch_bwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, lse: torch.Tensor, d_token_loss: torch.Tensor):
+    """srfrd_xent_bwd -> (d_hidden (B, L, d_out), d_table (n_items + 1, d_item))"""
+    B, L = targets.shape
+    dev = hidden.device
+    L_ = _lib.lib()
+    ws = torch.empty(L_.srfrd_xent_workspace_floats(C.byref(lay), B, L), device=dev, dtype=torch.float32)
+    dh = torch.empty(B, L, lay.d_out, device=dev, dtype=torch.float32)
+    de = torch.empty(lay.n_items + 1, lay.d_item, device=dev, dtype=torch.float32)
+    check(L_.srfrd_xent_bwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(lse), ptr(d_token_loss), B, L, ptr(dh),
+                            ptr(de), 0, ptr(ws), ws.numel(), _stream()), "srfrd_xent_bwd")
+    return dh, de
+
+
+def _xent_table(m, table: torch.Tensor):
+    if m.bf16_table:
+        raise RuntimeError("full-catalog cross-entropy needs the fp32 item table: call use_bf16_table(False) first")
+    lay = m.layout
+    if table.dtype != torch.float32 or not table.is_contiguous() or tuple(table.shape) != (lay.n_items + 1, lay.d_item):
+        raise ValueError("the item table must be the model's contiguous fp32 (n_items + 1, d_item) parameter")
+    return lay, ptr(table)
+
+
+@torch.library.custom_op("srfrd::xent_fwd", mutates_args=(), device_types="cuda")
+def xent_fwd(hidden: torch.Tensor, targets: torch.Tensor, table: torch.Tensor, model_key: int) -> List[torch.Tensor]:
+    """-> [token_loss (B, L), lse (B, L), stats (2) = {sum, count}]"""
+    lay, tab = _xent_table(_model(model_key), table)
+    return list(xent_launch_fwd(lay, tab, hidden.contiguous(), targets.contiguous()))
+
+
+@xent_fwd.register_fake
+def _(hidden, targets, table, model_key):
+    B, L = targets.shape
+    f = dict(device=hidden.device, dtype=torch.float32)
+    return [torch.empty(B, L, **f), torch.empty(B, L, **f), torch.empty(2, **f)]
+
+
+@torch.library.custom_op("srfrd::xent_bwd", mutates_args=(), device_types="cuda")
+def xent_bwd(hidden: torch.Tensor, targets: torch.Tensor, table: torch.Tensor, lse: torch.Tensor, d_token_loss: torch.Tensor,
+             model_key: int) -> List[torch.Tensor]:
+    """-> [d_hidden (B, L, d_out), d_table (n_items + 1, d_item)]"""
+    lay, tab = _xent_table(_model(model_key), table)
+    return list(xent_launch_bwd(lay, tab, hidden.contiguous(), targets.contiguous(), lse.contiguous(), d_token_loss.contiguous()))
+
+
+@xent_bwd.register_fake
+def _(hidden, targets, table, lse, d_token_loss, model_key):
+    return [torch.empty_like(hidden), torch.empty_like(table)]
+
+
+def _xent_setup(ctx, inputs, output):
+    hidden, targets, table, model_key = inputs
+    ctx.model_key = model_key
+    ctx.save_for_backward(hidden, targets, table, output[1])
+
+
+def _xent_backward(ctx, grads):
+    hidden, targets, table, lse = ctx.saved_tensors
+    g = grads[0]
+    if g is None:
+        return None, None, None, None
+    dh, de = torch.ops.srfrd.xent_bwd(hidden, targets, table, lse, g.contiguous(), ctx.model_key)
+    return dh, None, de, None
+
+
+xent_fwd.register_autograd(_xent_backward, setup_context=_xent_setup)
+
+
 OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "target_rank", "topk_merge",
-       "eval_rank")
+       "eval_rank", "xent_fwd", "xent_bwd")

@@ -1,0 +1,260 @@
+"""-m gpu: full-catalog softmax cross-entropy (model.full_catalog_loss, srfrd_xent_fwd / _bwd) against fp64 torch:
+F.cross_entropy(logits[..., 1:], y - 1, ignore_index=-1) on materialised fp64 logits (chunked over items at 1 M items).
+Tolerances: loss |d| <= 1e-5 max(1, |ref|); d_hidden and the table gradient ||d||_inf <= 1e-4 ||ref||_inf; whole-model
+parameter gradients 1e-4 absolute (the suite's bar); post-Adam weights by tests/helpers.assert_post_adam."""
+import pytest
+import torch
+import torch.nn.functional as F
+
+from oracle import srfrd_oracle as O
+from tests.helpers import assert_post_adam
+
+pytestmark = pytest.mark.gpu
+
+
+def _sasrec(n_items, d=50, L=20):
+    import srfrd_amd
+    return srfrd_amd.SASRec(n_items, L, d, 0.0, 2, 1, "cuda").to("cuda")
+
+
+def _targets(B, L, n_items, seed, empty_rows=(), zero_frac=0.3):
+    g = torch.Generator().manual_seed(seed)
+    y = torch.randint(1, n_items + 1, (B, L), generator=g)
+    y[torch.rand(B, L, generator=g) < zero_frac] = 0
+    for b in empty_rows:
+        y[b] = 0
+    flat = y.view(-1)
+    nz = (flat != 0).nonzero().view(-1)
+    if nz.numel() >= 2:                                 # both ends of the catalog are targets
+        flat[nz[0]] = 1
+        flat[nz[-1]] = n_items
+    return y
+
+
+def _ref(h, E, y, reduction):
+    """fp64 reference: loss and (d_hidden, dE) by autograd over materialised logits"""
+    h64 = h.detach().double().requires_grad_(True)
+    E64 = E.detach().double().requires_grad_(True)
+    d = E.shape[1]
+    logits = h64[..., :d] @ E64.T
+    n = E.shape[0] - 1
+    loss = F.cross_entropy(logits[..., 1:].reshape(-1, n), (y - 1).reshape(-1), ignore_index=-1, reduction=reduction)
+    if reduction == "none":
+        loss = loss.view(y.shape)
+    loss.backward(torch.ones_like(loss))
+    return loss.detach(), h64.grad, E64.grad
+
+
+def _rel(a, b):
+    scale = float(b.abs().max())
+    return float((a.double() - b.double()).abs().max()) / max(scale, 1e-30)
+
+
+def _run(m, h, y, reduction):
+    table = m.item_emb.weight
+    table.grad = None
+    hh = h.detach().clone().requires_grad_(True)
+    loss = m.full_catalog_loss(hh, y, reduction)
+    loss.backward(torch.ones_like(loss))
+    return loss.detach(), hh.grad, table.grad.clone()
+
+
+@pytest.mark.parametrize("n_items", [1, 15, 16, 17, 255, 257, 50_000])
+def test_op_matches_fp64_cross_entropy(n_items):
+    torch.manual_seed(n_items)
+    B, L, d = 5, 13, 50                                 # B * L = 65: not a multiple of the 64-token tile
+    m = _sasrec(n_items, d, L)
+    with torch.no_grad():
+        m.item_emb.weight.normal_(0, 0.5)
+    h = torch.randn(B, L, d, device="cuda") * 0.5
+    y = _targets(B, L, n_items, n_items, empty_rows=(2,)).cuda()
+    E = m.item_emb.weight.detach()
+    for red in ("mean", "sum", "none"):
+        loss, dh, de = _run(m, h, y, red)
+        rl, rdh, rde = _ref(h, E, y, red)
+        assert float((loss.double() - rl).abs().max()) <= 1e-5 * max(1.0, float(rl.abs().max())), (red, loss, rl)
+        assert _rel(dh, rdh) <= 1e-4, red
+        assert _rel(de, rde) <= 1e-4, red
+        assert float(de[0].abs().max()) == 0.0
+        if red == "none":
+            assert bool((loss[y == 0] == 0).all())
+            none_sum = loss.double().sum()
+    mean, _, _ = _run(m, h, y, "mean")
+    s, _, _ = _run(m, h, y, "sum")
+    cnt = int((y != 0).sum())
+    assert abs(float(s) - float(none_sum)) <= 1e-5 * max(1.0, abs(float(s)))
+    assert abs(float(mean) - float(s) / cnt) <= 1e-5 * max(1.0, abs(float(mean)))
+
+
+def test_no_targets_gives_nan_mean_and_zero_gradients():
+    m = _sasrec(100)
+    h = torch.randn(3, 7, 50, device="cuda")
+    y = torch.zeros(3, 7, dtype=torch.int64, device="cuda")
+    loss, dh, de = _run(m, h, y, "mean")
+    assert bool(torch.isnan(loss))
+    rl, _, _ = _ref(h, m.item_emb.weight, y, "mean")
+    assert bool(torch.isnan(rl))
+    s, dh, de = _run(m, h, y, "sum")
+    assert float(s) == 0.0 and float(dh.abs().max()) == 0.0 and float(de.abs().max()) == 0.0
+
+
+def test_bitwise_deterministic():
+    torch.manual_seed(0)
+    m = _sasrec(50_000, 50, 50)
+    h = torch.randn(64, 50, 50, device="cuda") * 0.3
+    y = _targets(64, 50, 50_000, 5).cuda()
+    a = _run(m, h, y, "mean")
+    b = _run(m, h, y, "mean")
+    for x, z in zip(a, b):
+        assert torch.equal(x, z)
+
+
+def _model_cfgs():
+    I, L = 300, 20
+    return [O.Cfg("SASRec", I, L, 50), O.Cfg("SRFR", I, L, 45, d_fake=5), O.Cfg("SRFRN", I, L, 45, d_fake=5),
+            O.Cfg("SRFU_B", I, L, 50, n_labels=3), O.Cfg("SASRec", I, L, 50, num_heads=2)]
+
+
+def _oracle_ce_grads(cfg, sd, batch, train=False, seed=0):
+    leaves = {k: v.detach().double().clone().requires_grad_(True) for k, v in sd.items()}
+    seq, rsq, pos = batch[0], batch[1], batch[2]
+    h, _, _ = O.forward(cfg, leaves, seq, rsq, train=train, seed=seed)
+    E = O.item_table(cfg, leaves)
+    logits = h[..., :cfg.d_item] @ E.T
+    loss = F.cross_entropy(logits[..., 1:].reshape(-1, cfg.item_number), (pos - 1).reshape(-1), ignore_index=-1)
+    loss.backward()
+    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)).clone() for k, v in leaves.items()}
+    grads[O.key_item(cfg)][0].zero_()
+    if cfg.kind in ("SRFR", "SRFRN"):
+        grads[O.key_side(cfg)][0].zero_()
+    return loss.detach(), grads, {k: v.detach().clone() for k, v in leaves.items()}
+
+
+@pytest.mark.parametrize("ci", range(5), ids=["SASRec", "SRFR", "SRFRN", "SRFU_B", "SASRec_h2"])
+def test_every_model_kind_gradients_and_adam_step(ci):
+    import srfrd_amd
+    from tests.gpu_util import build_model, cuda, maxerr, random_sd
+    cfg = _model_cfgs()[ci]
+    sd = random_sd(cfg, 7)
+    batch = srfrd_amd.synthetic_batch(cfg.item_number, cfg.max_len, 8, seed=11, device="cpu", min_len=1)[1:]
+    loss_o, grads_o, sd64 = _oracle_ce_grads(cfg, sd, batch)
+    for opt_kind in ("srfrd", "torch"):
+        model = build_model(cfg, sd).train()
+        seq, rsq, pos = cuda(*batch[:3])
+        params = list(model.parameters())
+        opt = srfrd_amd.Adam(params, lr=1e-3, betas=(0.9, 0.98)) if opt_kind == "srfrd" else \
+            torch.optim.Adam(params, lr=1e-3, betas=(0.9, 0.98))
+        hidden, _, _ = model(None, seq, rsq)
+        loss = model.full_catalog_loss(hidden, pos)
+        loss.backward()
+        assert abs(float(loss.detach()) - float(loss_o)) <= 1e-5 * max(1.0, abs(float(loss_o)))
+        for k, p in model.named_parameters():
+            assert maxerr(p.grad, grads_o[k]) < 1e-4, (k, maxerr(p.grad, grads_o[k]))
+        opt.step()
+        sd_step = {k: v.clone() for k, v in sd64.items()}
+        O.Adam(sd_step, lr=1e-3, betas=(0.9, 0.98)).step(sd_step, grads_o)
+        assert_post_adam(model.state_dict(), sd_step, [{k: g.float() for k, g in grads_o.items()}], cfg.D)
+
+
+def test_srfrn_fake_slice_gets_no_gradient():
+    """SRFRN's hidden state is [item | fake]; the loss's d_hidden is zero in the fake slice, and the fp64 cross-entropy over the
+    logits of the whole [item row | fake_embed[c]] (any c per row) has the item-slice loss and no fake_embed gradient."""
+    import srfrd_amd
+    from tests.gpu_util import build_model, random_sd
+    cfg = O.Cfg("SRFRN", 300, 20, 45, d_fake=5)
+    sd = random_sd(cfg, 2)
+    model = build_model(cfg, sd)
+    torch.manual_seed(3)
+    h = torch.randn(6, 20, cfg.d_out, device="cuda", requires_grad=True)
+    y = _targets(6, 20, 300, 4).cuda()
+    loss = model.full_catalog_loss(h, y)
+    loss.backward()
+    assert float(h.grad[..., cfg.d_item:].abs().max()) == 0.0
+    assert model.embedding_layer.fake_embed.weight.grad is None
+    E = sd["embedding_layer.item_embed.weight"].double().cuda()
+    fk = sd["embedding_layer.fake_embed.weight"].double().cuda().requires_grad_(True)
+    c = torch.randint(0, 3, (6, 20), device="cuda")
+    full = torch.cat([E.unsqueeze(0).unsqueeze(0).expand(6, 20, -1, -1),
+                      fk[c].unsqueeze(2).expand(-1, -1, E.shape[0], -1)], dim=3)        # (B, L, I + 1, d_out)
+    logits = (full * h.detach().double().unsqueeze(2)).sum(-1)
+    ref = F.cross_entropy(logits[..., 1:].reshape(-1, 300), (y - 1).reshape(-1), ignore_index=-1)
+    ref.backward()
+    assert abs(float(loss.detach()) - float(ref.detach())) <= 1e-5 * max(1.0, abs(float(ref.detach())))
+    assert float(fk.grad.abs().max()) < 1e-12
+
+
+def test_bf16_table_model_is_refused():
+    m = _sasrec(100)
+    m.use_bf16_table(True)
+    with pytest.raises(RuntimeError, match="fp32 item table"):
+        m.full_catalog_loss(torch.randn(2, 20, 50, device="cuda"), torch.ones(2, 20, dtype=torch.int64, device="cuda"))
+
+
+def test_train_mode_dropout_gradients():
+    """p = 0.5: the loss gradient flows through the dropout-masked encoder backward (oracle masks, train=True)."""
+    import srfrd_amd
+    from tests.gpu_util import build_model, cuda, maxerr, random_sd
+    cfg = O.Cfg("SASRec", 300, 20, 50, dropout=0.5)
+    sd = random_sd(cfg, 5)
+    batch = srfrd_amd.synthetic_batch(300, 20, 8, seed=12, device="cpu", min_len=1)[1:]
+    seed = 0xBEEF
+    loss_o, grads_o, _ = _oracle_ce_grads(cfg, sd, batch, train=True, seed=seed)
+    model = build_model(cfg, sd).train()
+    model._next_seed = lambda: seed
+    seq, rsq, pos = cuda(*batch[:3])
+    hidden, _, _ = model(None, seq, rsq)
+    loss = model.full_catalog_loss(hidden, pos)
+    loss.backward()
+    assert abs(float(loss.detach()) - float(loss_o)) <= 1e-5 * max(1.0, abs(float(loss_o)))
+    for k, p in model.named_parameters():
+        assert maxerr(p.grad, grads_o[k]) < 2e-4, (k, maxerr(p.grad, grads_o[k]))
+
+
+def test_c2_size_against_materialised_fp64():
+    torch.manual_seed(1)
+    import srfrd_amd
+    B, L, n = 512, 50, 50_000
+    m = _sasrec(n, 50, L)
+    with torch.no_grad():
+        m.item_emb.weight.normal_(0, 0.3)
+    _, seq, _, pos, *_ = srfrd_amd.synthetic_batch(n, L, B, seed=21, device="cuda")
+    h = torch.randn(B, L, 50, device="cuda") * 0.3
+    loss, dh, de = _run(m, h, pos, "mean")
+    rl, rdh, rde = _ref(h, m.item_emb.weight, pos, "mean")
+    assert abs(float(loss) - float(rl)) <= 1e-5 * max(1.0, abs(float(rl)))
+    assert _rel(dh, rdh) <= 1e-4 and _rel(de, rde) <= 1e-4
+
+
+def test_one_million_items_against_chunked_fp64():
+    torch.manual_seed(2)
+    B, L, n, d = 32, 200, 1_000_000, 50
+    m = _sasrec(n, d, L)
+    with torch.no_grad():
+        m.item_emb.weight.normal_(0, 0.3)
+    y = _targets(B, L, n, 9, empty_rows=(5,)).cuda()
+    h = torch.randn(B, L, d, device="cuda") * 0.3
+    loss, dh, de = _run(m, h, y, "mean")
+    # fp64 reference over 100 k-item chunks: logsumexp first, then softmax - onehot per chunk
+    tok = (y != 0).view(-1)
+    H = h.view(-1, d)[tok].double()
+    t = y.view(-1)[tok]
+    E = m.item_emb.weight.detach().double()
+    lse = torch.full((H.shape[0],), -float("inf"), device="cuda", dtype=torch.float64)
+    step = 100_000
+    for i0 in range(1, n + 1, step):
+        lse = torch.logaddexp(lse, torch.logsumexp(H @ E[i0:i0 + step].T, dim=1))
+    tl = (H * E[t]).sum(1)
+    ref = float((lse - tl).mean())
+    cnt = H.shape[0]
+    rdh = torch.zeros_like(H)
+    rde = torch.zeros_like(E)
+    for i0 in range(1, n + 1, step):
+        P = torch.exp(H @ E[i0:i0 + step].T - lse[:, None])
+        hit = (t >= i0) & (t < i0 + step)
+        P[hit.nonzero().view(-1), (t[hit] - i0)] -= 1.0
+        P /= cnt
+        rdh += P @ E[i0:i0 + step]
+        rde[i0:i0 + step] = P.T @ H
+    assert abs(float(loss) - ref) <= 1e-5 * max(1.0, abs(ref))
+    assert _rel(dh.view(-1, d)[tok], rdh) <= 1e-4 and float(dh.view(-1, d)[~tok].abs().max()) == 0.0
+    assert _rel(de, rde) <= 1e-4
