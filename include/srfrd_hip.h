@@ -127,6 +127,11 @@ int srfrd_bwd_grid(const srfrd_layout* lay, int B, int L);
 #define SRFRD_SW_TOPK_FP32 128    /* ranking: the fp32 stream wherever the bf16 matrix-core stream would serve (the encoder ignores it) */
 int srfrd_encoder_plan(const srfrd_layout* lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats,
                        char* fwd_name, char* bwd_name, int name_len, int32_t* grids);
+/* [host] the train direction of the same plan: the instantiation srfrd_encoder_train_sched launches for (lay, B, L, mode,
+ * switches, n_cu, scratch_floats) - its name in `name` and its workgroup count in *grid - or SRFRD_E_UNSUPPORTED in *grid
+ * with an empty name where that call refuses.  Returns 0 or SRFRD_E_ARG. */
+int srfrd_encoder_plan_train(const srfrd_layout* lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats,
+                             char* name, int name_len, int32_t* grid);
 
 /* [host] floats per debug-tap slot and number of slots (tests only). */
 int srfrd_debug_shape(const srfrd_layout* lay, int L, int64_t* slot_floats, int32_t* n_slots);
@@ -212,6 +217,24 @@ int srfrd_encoder_bwd_sched(const srfrd_layout* lay, const void* item_table, con
                             float* grad_table, float* table_contrib, float* grad_slabs,
                             float* scratch, int64_t scratch_floats,
                             const int32_t* sched, int sched_mode, void* stream);
+
+/* [device] one fused training step's encoder work as ONE launch: srfrd_encoder_fwd_sched (training: targets, checkpoints, loss
+ * partials) followed by srfrd_encoder_bwd_sched (fused BCE gradient) with the same arguments, each workgroup running a
+ * sequence's forward and then its backward.  Arguments: the union of the two calls' (hidden / pos_logits / neg_logits /
+ * save_* are written and read back); results are those of the two calls bit for bit.  Where the kernel plan has no train
+ * kernel for the call (srfrd_encoder_plan_train: where the ragged seq_len-50 pair serves a call with SRFRD_PLAN_POS, _NEG,
+ * _CKPT, _LOSS and _FUSED_BCE, dropout or not), returns SRFRD_E_UNSUPPORTED and launches nothing: make the two calls instead. */
+int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
+                              const int64_t* input_ids, const int64_t* fake_ids,
+                              const int64_t* pos_ids, const int64_t* pos_fake,
+                              const int64_t* neg_ids, const int64_t* neg_fake,
+                              int B, int L, double dropout_p, uint32_t seed, const uint32_t* seed_dev, int64_t seq_index0,
+                              float* hidden, float* pos_logits, float* neg_logits,
+                              float* save_x, float* save_h1, float* save_aux, float* loss_part,
+                              const float* d_hidden, const float* d_pos, const float* d_neg, int fused_bce,
+                              float* grad_table, float* table_contrib, float* grad_slabs,
+                              float* scratch, int64_t scratch_floats,
+                              const int32_t* sched, int sched_mode, void* stream);
 
 /* Inference forward for ranking: the encoder state of the LAST position only, hidden_last (B, d_out) - what the reference's
  * predict() takes from log2feats (SRFR_model.py:668-681: `log_feats[:, -1, :]`).  Same arithmetic as srfrd_encoder_fwd in

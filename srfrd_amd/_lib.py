@@ -57,6 +57,9 @@ SIGNATURES = {
                                      _P, _P, _P, _P, _P, _P, _P, _P, _i64, _P, _i, _P]),
     "srfrd_encoder_bwd_sched": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _P, _i64, _P, _i, _P]),
+    "srfrd_encoder_plan_train": (_i, [_LP, _i, _i, _i, _i, _i, _i64, _P, _i, _P]),
+    "srfrd_encoder_train_sched": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
+                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _P, _i64, _P, _i, _P]),
     "srfrd_table_reduce": (_i, [_P, _P, _P, _i64, _i, _P, _P]),
     "srfrd_aux_floats": (_i64, [_LP, _i, _i]),
     "srfrd_reduce_dense": (_i, [_P, _i, _i64, _P, _P, _i, _P, _P, _P]),
@@ -151,6 +154,20 @@ def encoder_plan(lay: Layout, B: int, L: int, mode: int, switches: int = 0, n_cu
     check(lib().srfrd_encoder_plan(C.byref(lay), B, L, mode, switches, n_cu, scratch_floats, fwd, bwd, 128, grids),
           "srfrd_encoder_plan")
     return (fwd.value.decode(), grids[0]), (bwd.value.decode(), grids[1])
+
+
+def encoder_plan_train(lay: Layout, B: int, L: int, mode: int, switches: int = 0, n_cu: int = 256, scratch_floats: int = 0):
+    """srfrd_encoder_plan_train (no GPU needed) -> (train kernel, grid): what srfrd_encoder_train_sched launches, or ("", -2)
+    where it refuses with SRFRD_E_UNSUPPORTED."""
+    name, grid = C.create_string_buffer(128), C.c_int32(0)
+    check(lib().srfrd_encoder_plan_train(C.byref(lay), B, L, mode, switches, n_cu, scratch_floats, name, 128, C.byref(grid)),
+          "srfrd_encoder_plan_train")
+    return name.value.decode(), grid.value
+
+
+def env_switches() -> int:
+    """the SRFRD_SW_* bits the launchers read from the environment right now (a switch counts when its variable is set)"""
+    return sum(bit for name, bit in SWITCHES.items() if name in os.environ)
 
 
 # srfrd_rank_plan ops (SRFRD_RANK_*) and the ranking's switch bit (SRFRD_SW_TOPK_FP32: the environment variable SRFRD_TOPK_FP32)

@@ -105,10 +105,20 @@ __host__ __device__ constexpr int64_t chunks_lds_floats(int L, int D, int n_bloc
 }
 __host__ __device__ constexpr int64_t chunks_scratch_floats(int L, int D) { return 3ll * (((L + 3) & ~3) * D + 64); }
 // Ragged backward (srfrd_encoder_bwd_ragged_kernel.inc): seq_len 50, hidden 50.
+// Per-sequence working sets (floats) of the ragged pair, without the LayerNorm caches:
+constexpr int kRagFwdWork = 64 * 66 + 4 * 64 * 54 + 4 * 64 + 64;    // scores / x [64][66], four [64][54], 4 per-row arrays, misc
+constexpr int kRagBwdWork = 12 * 54 + 6 * 52 * 54 + 12 * 64 + 64;   // guard (12 rows), six [52][54] slots, 12 per-row arrays, misc
 __host__ __device__ constexpr int64_t bwd_ragged_lds_floats(int n_blocks) {
-  // guard (12 rows) + six [52][54] slots + 12 per-row arrays + misc + two LayerNorm caches + slack
-  return 12ll * 54 + 6ll * 52 * 54 + 12ll * 64 + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
+  // working set + two LayerNorm caches + slack
+  return kRagBwdWork + 2ll * ln_cache_floats(n_blocks) + kSlack;
 }
+// Ragged train kernel (srfrd_encoder_train_ragged.hip): the forward's and the backward's working sets overlay each other,
+// then the LayerNorm parameters and the backward's gradient accumulators.  The forward's tile over-reads behind its last
+// matrix land in its own per-row arrays: no slack.  Never larger than bwd_ragged_lds_floats (two workgroups per CU).
+__host__ __device__ constexpr int64_t train_ragged_lds_floats(int n_blocks) {
+  return (kRagFwdWork > kRagBwdWork ? kRagFwdWork : kRagBwdWork) + 2ll * ln_cache_floats(n_blocks);
+}
+static_assert(kRagFwdWork <= kRagBwdWork + kSlack, "train kernel LDS within the backward's");
 
 // Optimisation barrier on a wave-uniform pointer: stops LLVM from hoisting the per-call-site address arithmetic of
 // ~35 inlined GEMMs out of the sequence / block loops (which costs > 256 VGPRs and spills).
@@ -322,6 +332,7 @@ int launch_bwd_first(const KernelPlan& k, const EncArgs& a, void* stream);    //
 int launch_bwd_ragged(const KernelPlan& k, const EncArgs& a, void* stream);   // srfrd_encoder_bwd_ragged.hip
 int launch_bwd_slots(const KernelPlan& k, const EncArgs& a, void* stream);    // srfrd_encoder_bwd_slots.hip
 int launch_bwd_chunks(const KernelPlan& k, const EncArgs& a, void* stream);   // srfrd_encoder_bwd_chunks.hip
+int launch_train_ragged(const KernelPlan& k, const EncArgs& a, void* stream); // srfrd_encoder_train_ragged.hip
 #endif
 
 }  // namespace SRFRD_NS

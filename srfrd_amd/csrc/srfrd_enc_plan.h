@@ -19,6 +19,7 @@ enum Family {
   kBwdSlots,     // slot-placed backward, srfrd_encoder_bwd_slots_kernel.inc
   kBwdChunks,    // row-chunked backward, srfrd_encoder_bwd_chunks_kernel.inc
   kBwdLong,      // global-scratch build of the first-generation backward (srfrd_long::)
+  kTrainRagged,  // ragged forward + backward in one launch, srfrd_encoder_train_ragged.hip
 };
 
 // Geometry template of the first-generation kernels (and the sequence length of the slot-placed backward)
@@ -50,6 +51,7 @@ struct KernelPlan {
 };
 struct EncPlan {
   KernelPlan fwd, bwd;
+  KernelPlan train;        // a training forward and its fused-BCE backward as ONE launch (srfrd_encoder_train_sched), or rc set
 };
 
 // mode: SRFRD_PLAN_* bits, switches: SRFRD_SW_* bits (read_switches), n_cu: CUs of the device, scratch_floats: the caller's

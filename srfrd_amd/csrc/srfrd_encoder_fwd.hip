@@ -191,6 +191,15 @@ EncPlan encoder_plan(const srfrd_layout& lay, int B, int L, int mode, int sw, in
   } else {
     p.bwd = kernel(kBwdFirst, spec && g.LP == 64 ? kLP64 : spec && g.LP == 32 ? kLP32 : kGeneric, -1, false, grid, 512, bl * 4);
   }
+
+  // ---- train: forward and backward in one launch ----
+  // Wherever the ragged pair serves a call that carries everything a fused train step computes (targets, checkpoints, loss
+  // partials and the fused BCE gradient; dropout or not): the backward's grid, schedule and slab accumulation, so the two
+  // launches and the one compute the same bits.
+  const int kTrain = SRFRD_PLAN_POS | SRFRD_PLAN_NEG | SRFRD_PLAN_CKPT | SRFRD_PLAN_LOSS | SRFRD_PLAN_FUSED_BCE;
+  p.train = ragged && (mode & kTrain) == kTrain && fits(train_ragged_lds_floats(nb))
+                ? kernel(kTrainRagged, kGeneric, kv, rmw, grid, 512, train_ragged_lds_floats(nb) * 4)
+                : unsupported();
   return p;
 }
 
@@ -226,6 +235,7 @@ void plan_name(const KernelPlan& k, char* buf, int len) {
     case kBwdRagged: snprintf(buf, len, "srfrd::encoder_bwd_ragged_kernel<%d,%d,%s>", v.K, v.DI, tf); return;
     case kBwdSlots: snprintf(buf, len, "srfrd::encoder_bwd_slots_kernel<50,%d,%d,%d,%s>", k.form == kL50 ? 50 : 100, v.K, v.DI, tf); return;
     case kBwdChunks: snprintf(buf, len, "srfrd::encoder_bwd_chunks_kernel<50,%d,%d,%s>", v.K, v.DI, tf); return;
+    case kTrainRagged: snprintf(buf, len, "srfrd::encoder_train_ragged_kernel<%d,%d,%s>", v.K, v.DI, tf); return;
   }
 }
 
@@ -260,6 +270,17 @@ extern "C" int srfrd_encoder_plan(const srfrd_layout* lay, int B, int L, int mod
   if (bwd_name) plan_name(p.bwd, bwd_name, name_len);
   grids[0] = p.fwd.rc ? p.fwd.rc : p.fwd.grid;
   grids[1] = p.bwd.rc ? p.bwd.rc : p.bwd.grid;
+  return 0;
+}
+
+extern "C" int srfrd_encoder_plan_train(const srfrd_layout* lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats,
+                                        char* name, int name_len, int32_t* grid) {
+  if (!lay || B <= 0 || L <= 0 || n_cu <= 0 || scratch_floats < 0 || !grid) return SRFRD_E_ARG;
+  KernelPlan k = unsupported();
+  if (!(lay->D > SRFRD_MAX_D || lay->n_heads < 1 || lay->D % lay->n_heads != 0 || lay->n_blocks > SRFRD_MAX_BLOCKS))
+    k = encoder_plan(*lay, B, L, mode, switches, n_cu, scratch_floats).train;
+  if (name) plan_name(k, name, name_len);
+  *grid = k.rc ? k.rc : k.grid;
   return 0;
 }
 

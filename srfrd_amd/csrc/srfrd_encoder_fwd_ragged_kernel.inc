@@ -373,40 +373,38 @@ __device__ __forceinline__ void rag_softmax(lds_f* S, int rq0, int r0, int v0, i
   }
 }
 
+// LDS working set of the ragged forward for one sequence.  The forward kernel lays it out behind its per-row arrays, the
+// train kernel (srfrd_encoder_train_ragged.hip) over the same floats as the backward's slots: see rag_fwd_seq's callers.
+struct RagFwdLds {
+  lds_f *bXS, *bQN, *bQ, *bK, *bV;  // [LP][SLD] (x, and the scores over it), then four [LP][DS]; kSlack readable behind bV
+  lds_i* s_in;                      // all four in tile coordinates (row = position + SH)
+  lds_f* s_keep;
+  lds_i *s_pid, *s_nid;
+  lds_f* s_misc;                    // 64 floats
+  lds_f* s_ln;                      // LayerNorm parameters (fill_ln_cache)
+};
+
+// The ragged forward of sequence b by the whole workgroup (512 threads), from its ids to its hidden states, logits, BCE
+// partial sums and (training) checkpoints; ends with a workgroup barrier.  tid: the laundered thread index (see launder),
+// wave: its wave (uniform).
 template <int K_, int T_, int DI_>
-__global__ void __launch_bounds__(512, 4) encoder_fwd_ragged_kernel(const EncArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
+__device__ __forceinline__ void rag_fwd_seq(const EncArgs& a, const RagFwdLds& m, int b, int& tid, int wave, uint32_t seed) {
   const Dims& ly = a.dm;
   constexpr int D = 50, L = 50, LP = 64, DK = 52, DS = 54, SLD = 66, NT = 4, MT = 4, SH = kRagSH;
   constexpr int nw = 8, nthr = 512;
   static_assert(SH + L <= LP && (SH & 3) == 0, "tile coordinates");
-  int tid = threadIdx.x;
-  const int lane0 = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int szA = LP * DS, szX = LP * SLD;
-  const int tailsz = 4 * LP + 64 + ln_cache_floats(ly.n_blocks);
-  const RagT0 t0v = rag_load_t0(a, tid);
-  lds_f* c_cur = (lds_f*)smem;
-  auto carve = [&](int64_t n) -> lds_f* { lds_f* p = c_cur; c_cur += n; return p; };
-  {
-    Geom g = make_geom(L, D);
-    const int total = (int)fwd_lds_floats(g, ly.n_blocks);
-    for (int i = tid; i < total; i += nthr) ((lds_f*)smem)[i] = 0.f;
-  }
-  lds_f* tail = carve(tailsz);
-  lds_f* bXS = carve(szX);
-  lds_f* bQN = carve(szA);
-  lds_f* bQ = carve(szA);
-  lds_f* bK = carve(szA);
-  lds_f* bV = carve(szA + kSlack);
-  lds_i* s_in = (lds_i*)tail;             // all four in tile coordinates (row = position + SH)
-  lds_f* s_keep = tail + LP;
-  lds_i* s_pid = (lds_i*)(tail + 2 * LP);
-  lds_i* s_nid = (lds_i*)(tail + 3 * LP);
-  lds_f* s_misc = tail + 4 * LP;          // 64 floats
-  lds_f* s_ln = s_misc + 64;
-  __syncthreads();
-  fill_ln_cache(s_ln, a.dense, ly);
-
+  const int lane0 = threadIdx.x & 63;
+  lds_f* bXS = m.bXS;
+  lds_f* bQN = m.bQN;
+  lds_f* bQ = m.bQ;
+  lds_f* bK = m.bK;
+  lds_f* bV = m.bV;
+  lds_i* s_in = m.s_in;
+  lds_f* s_keep = m.s_keep;
+  lds_i* s_pid = m.s_pid;
+  lds_i* s_nid = m.s_nid;
+  lds_f* s_misc = m.s_misc;
+  lds_f* s_ln = m.s_ln;
   const float* P = a.dense;
   const ItemTable table{a.table, a.table16};
   constexpr bool TR_ = T_ != 0;
@@ -420,304 +418,342 @@ __global__ void __launch_bounds__(512, 4) encoder_fwd_ragged_kernel(const EncArg
   constexpr int dout = (K_ == SRFRD_SRFR) ? DI_ : D;
   const float sqrtD = sqrtf((float)di);
   const float qscale = a.qscale;
-  const uint32_t seed = a.seed_dev ? *a.seed_dev : a.seed;
   auto pk = [&](int mat, int form) {
     return PackedB{reinterpret_cast<const float4*>(a.packed) + ((int64_t)mat * 2 + form) * (kPackFloats / 4)};
   };
 
-  STAMP_INIT
-  for (int iter = 0;; ++iter) {
-    const int b = __builtin_amdgcn_readfirstlane(rag_take(a, (lds_i*)bXS, iter, tid, t0v));      // (bXS: free between sequences)
-    if (b < 0) break;
-    asm volatile("" : "+v"(tid));
-    const int64_t rowbase = (int64_t)b * L;
-    const uint32_t seq = (uint32_t)(a.seq0 + b);
-    if (tid < LP) {
-      const int t = tid - SH;
-      const bool in = t >= 0 && t < L;
-      const int id = in ? clamp_id(a.in_ids[rowbase + t], ly.n_items) : 0;
-      s_in[tid] = id;
-      s_keep[tid] = id != 0 ? 1.f : 0.f;
-      s_pid[tid] = (in && has_pos) ? clamp_id(a.pos_ids[rowbase + t], ly.n_items) : 0;
-      s_nid[tid] = (in && has_neg) ? clamp_id(a.neg_ids[rowbase + t], ly.n_items) : 0;
-    }
-    if (is_srfu && wave == 1) {
-      const int lab = user_label_wave(kind, a.fk_ids ? a.fk_ids + rowbase : nullptr, L, ly.n_labels);
-      if (lane0 == 0) ((lds_i*)s_misc)[0] = lab;
-    }
-    __syncthreads();
-    // ---- the sequence's rows: v0 = first non-pad row, kr = first key row (the representative of the t0 leading pads)
-    int v0;
-    {
-      const unsigned long long nz = __ballot(s_in[tid & 63] != 0);
-      v0 = nz ? (int)__builtin_ctzll(nz) : SH + L;
-      if (a.ragged_off) v0 = SH;
-      v0 = __builtin_amdgcn_readfirstlane(v0);
-    }
-    const int t0 = v0 - SH;
-    const int kr = t0 >= 1 ? v0 - 1 : v0;
-    const int mt0 = kr >> 4, r0 = mt0 << 4, mtn = MT - mt0;
-    const int tstart = r0 > SH ? r0 - SH : 0;               // first position of the computed tiles
+  asm volatile("" : "+v"(tid));
+  const int64_t rowbase = (int64_t)b * L;
+  const uint32_t seq = (uint32_t)(a.seq0 + b);
+  if (tid < LP) {
+    const int t = tid - SH;
+    const bool in = t >= 0 && t < L;
+    const int id = in ? clamp_id(a.in_ids[rowbase + t], ly.n_items) : 0;
+    s_in[tid] = id;
+    s_keep[tid] = id != 0 ? 1.f : 0.f;
+    s_pid[tid] = (in && has_pos) ? clamp_id(a.pos_ids[rowbase + t], ly.n_items) : 0;
+    s_nid[tid] = (in && has_neg) ? clamp_id(a.neg_ids[rowbase + t], ly.n_items) : 0;
+  }
+  if (is_srfu && wave == 1) {
+    const int lab = user_label_wave(kind, a.fk_ids ? a.fk_ids + rowbase : nullptr, L, ly.n_labels);
+    if (lane0 == 0) ((lds_i*)s_misc)[0] = lab;
+  }
+  __syncthreads();
+  // ---- the sequence's rows: v0 = first non-pad row, kr = first key row (the representative of the t0 leading pads)
+  int v0;
+  {
+    const unsigned long long nz = __ballot(s_in[tid & 63] != 0);
+    v0 = nz ? (int)__builtin_ctzll(nz) : SH + L;
+    if (a.ragged_off) v0 = SH;
+    v0 = __builtin_amdgcn_readfirstlane(v0);
+  }
+  const int t0 = v0 - SH;
+  const int kr = t0 >= 1 ? v0 - 1 : v0;
+  const int mt0 = kr >> 4, r0 = mt0 << 4, mtn = MT - mt0;
+  const int tstart = r0 > SH ? r0 - SH : 0;               // first position of the computed tiles
 
-    // ---- embedding: gather + position (+ side channel) + pad mask          (SURVEY 3.4 steps 1-4)
-    {
-      const DropSite dsE = drop_site(drop_on && is_sas, seed, SITE_EMB, seq, a.drop_thr, a.drop_scale);
-      const int lab = is_srfu ? ((lds_i*)s_misc)[0] : 0;
-      // rows of the computed tiles that no position maps to (0 .. SH - 1 in front, SH + L .. LP - 1 behind): zeros
-      if (r0 < SH)
-        for (int i = tid; i < (SH - r0) * DS; i += nthr) bXS[r0 * DS + i] = 0.f;
-      for (int i = tid; i < (LP - SH - L) * DS; i += nthr) bXS[(SH + L) * DS + i] = 0.f;
-      int t = tstart + tid / D, c = tid - (tid / D) * D;
-      constexpr int dt = nthr / D, dc = nthr - dt * D;
-      for (; t < L;) {
-        const int id = s_in[t + SH];
-        float v;
-        if (has_fake) {
-          if (c < di) v = table((int64_t)id * di + c) + P[ly.off_pos + t * di + c];
-          else v = P[ly.off_side + ((a.fk_ids ? clamp_id(a.fk_ids[rowbase + t], 2) : 0)) * dfk + (c - di)];
-        } else {
-          v = table((int64_t)id * di + c);
-          if (is_sas) v *= sqrtD;
-          v += P[ly.off_pos + t * di + c];
-          if (is_srfu) v += P[ly.off_side + lab * D + c];
-          if (is_sas) v *= drop_mul(dsE, t, c);
-        }
-        v *= s_keep[t + SH];
-        bXS[(t + SH) * DS + c] = v;
-        if (do_save) a.save_x[x_off(0, b, ly.n_blocks, L, D) + t * D + c] = v;
-        t += dt; c += dc;
-        if (c >= D) { c -= D; ++t; }
+  // ---- embedding: gather + position (+ side channel) + pad mask          (SURVEY 3.4 steps 1-4)
+  {
+    const DropSite dsE = drop_site(drop_on && is_sas, seed, SITE_EMB, seq, a.drop_thr, a.drop_scale);
+    const int lab = is_srfu ? ((lds_i*)s_misc)[0] : 0;
+    // rows of the computed tiles that no position maps to (0 .. SH - 1 in front, SH + L .. LP - 1 behind): zeros
+    if (r0 < SH)
+      for (int i = tid; i < (SH - r0) * DS; i += nthr) bXS[r0 * DS + i] = 0.f;
+    for (int i = tid; i < (LP - SH - L) * DS; i += nthr) bXS[(SH + L) * DS + i] = 0.f;
+    int t = tstart + tid / D, c = tid - (tid / D) * D;
+    constexpr int dt = nthr / D, dc = nthr - dt * D;
+    for (; t < L;) {
+      const int id = s_in[t + SH];
+      float v;
+      if (has_fake) {
+        if (c < di) v = table((int64_t)id * di + c) + P[ly.off_pos + t * di + c];
+        else v = P[ly.off_side + ((a.fk_ids ? clamp_id(a.fk_ids[rowbase + t], 2) : 0)) * dfk + (c - di)];
+      } else {
+        v = table((int64_t)id * di + c);
+        if (is_sas) v *= sqrtD;
+        v += P[ly.off_pos + t * di + c];
+        if (is_srfu) v += P[ly.off_side + lab * D + c];
+        if (is_sas) v *= drop_mul(dsE, t, c);
       }
+      v *= s_keep[t + SH];
+      bXS[(t + SH) * DS + c] = v;
+      if (do_save) a.save_x[x_off(0, b, ly.n_blocks, L, D) + t * D + c] = v;
+      t += dt; c += dc;
+      if (c >= D) { c -= D; ++t; }
     }
-    __syncthreads();
+  }
+  __syncthreads();
 
-    for (int i = 0; i < ly.n_blocks; ++i) {
-      const BlkOff o = blk_off(ly.blk0 + i * ly.blk_stride, D);
-      launder(bXS); launder(bQN); launder(bQ); launder(bK); launder(bV);
-      // (nothing derived from the lane index may be lifted out of the block loop: hipcc otherwise precomputes every per-lane
-      // epilogue address of the block once, runs out of registers and spills them)
-      asm volatile("" : "+v"(tid));
-      const int lane = tid & 63;
-      // ranking (last_only): the LAST block computes its query-side rows for the tile of position L - 1 only
-      const bool lo = !TR_ && a.last_only != 0 && i == ly.n_blocks - 1;
-      const int mq0 = lo ? (L - 1 + SH) >> 4 : mt0, rq0 = mq0 << 4, mqn = MT - mq0;
-      const AuxOff ax = aux_off(i, b, ly.n_blocks, L, LP, D, 1);
-      float* sv_r = do_save ? a.save_aux + ax.r : nullptr;
-      float* sv_o = do_save ? a.save_aux + ax.o : nullptr;
-      float* sv_p = do_save ? a.save_aux + ax.p : nullptr;
-      float* sv_q = do_save ? a.save_aux + ax.q : nullptr;
-      float* sv_k = do_save ? a.save_aux + ax.k : nullptr;
-      float* sv_v = do_save ? a.save_aux + ax.v : nullptr;
-      // Epilogues (rgemm_packed): one lane-level branch on the column, LDS stores straight-line, checkpoint stores per row group
-      // checkpoint rows of one lane's four consecutive tile rows rb .. rb + 3 (positions rb - SH ..): scalar plane base + one
-      // 32-bit offset + immediates when all four are positions of the sequence (every row group but rows 0 .. 11 and 60 .. 63)
-      auto gstore4 = [&](float* plane, int rb, int c, const float (&v)[4]) {
-        const int p0 = rb - SH;
-        const unsigned off = (unsigned)(p0 * D + c);
-        if (p0 >= 0 && p0 + 3 < L) {
-          plane[off] = v[0]; plane[off + D] = v[1]; plane[off + 2 * D] = v[2]; plane[off + 3 * D] = v[3];
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if ((unsigned)(p0 + e) < (unsigned)L) plane[(unsigned)((p0 + e) * D + c)] = v[e];
-        }
-      };
-      const WFrag wq = load_wfrag(pk(i * 6 + 0, 0), P + o.in_b, D, NT, tid);
-      const WFrag wk = load_wfrag(pk(i * 6 + 1, 0), P + o.in_b + D, D, NT, tid);
-      const WFrag wv = load_wfrag(pk(i * 6 + 2, 0), P + o.in_b + 2 * D, D, NT, tid);
-      ln_rows(nw, bXS + rq0 * DS, bQN + rq0 * DS, LP - rq0, DS, D, s_ln + (4 * i + 0) * 64, s_ln + (4 * i + 1) * 64);
-      __syncthreads();
-      // q = (LN(x) Wq^T + bq) * sqrt(1/d_h);  k = x Wk^T + bk;  v = x Wv^T + bv       (rows of tiles mt0 .. 3)
-      rag_packed(mq0, mqn, DK >> 2, D, Mat{bQN, DS}, wq, NoPre{}, [&](int r, int c, float v, float) {
-        bQ[r * DS + c] = v * qscale;
-        return v * qscale;
-      }, lane, wave, [&](int rb, int c, const float (&gv)[4]) { if (sv_q) gstore4(sv_q, rb, c, gv); });
-      rag_packed_dual(mt0, mtn, DK >> 2, D, Mat{bXS, DS}, wk, wv, [&](int r, int c, float vk, float vv) {
-        bK[r * DS + c] = vk;
-        bV[r * DS + c] = vv;
-      }, lane, wave, [&](int rb, int c, const float (&gk)[4], const float (&gv)[4]) {
-        if (sv_k) { gstore4(sv_k, rb, c, gk); gstore4(sv_v, rb, c, gv); }
-      });
-      const WFrag wo = load_wfrag(pk(i * 6 + 3, 0), P + o.out_b, D, NT, tid);
-      const WFrag w1 = load_wfrag(pk(i * 6 + 4, 0), P + o.c1_b, D, NT, tid);
-      __syncthreads();
-      // S = q k^T on the lower-triangular tiles of [mq0, 4) x [mt0, 4) (x is dead: S overlays it), dealt round-robin
-      {
-        const int li = lane & 15, lq = lane >> 4;
-        if (lo) {
-          for (int u = wave; u < mtn; u += nw)
-            gemm_group<0, 1>(0, 1, u << 4, DK, Mat{bQ + rq0 * DS, DS}, MatT{bK + r0 * DS, DS},
-                             [&](int r, int c, float v) { bXS[(r + rq0) * SLD + c + r0] = v; }, li, lq);
-        } else {
-          const int ntri = (mtn * (mtn + 1)) >> 1;
-          for (int u = wave; u < ntri; u += nw) {
-            const int m = u >= 6 ? 3 : (u >= 3 ? 2 : (u >= 1 ? 1 : 0)), n = u - ((m * (m + 1)) >> 1);
-            gemm_group<0, 1>(m, 1, n << 4, DK, Mat{bQ + r0 * DS, DS}, MatT{bK + r0 * DS, DS},
-                             [&](int r, int c, float v) { bXS[(r + r0) * SLD + c + r0] = v; }, li, lq);
-          }
-        }
-      }
-      __syncthreads();
-      {
-        const DropSite dsA = drop_site(drop_on, seed, site_attn(i), seq, a.drop_thr, a.drop_scale);
-        rag_softmax(bXS, rq0, r0, v0, kr, t0, SH + L, dsA, sv_p, tid);
-      }
-      __syncthreads();
-      // o = P v  (q is dead: o overlays it); tile m of the queries meets key tiles <= m: the pairs {0,3}, {1,2} cost the same
-      {
-        const int li = lane & 15, lq = lane >> 4;
-        const int nt = wave & 3, g = wave >> 2;
-        auto epi_o = [&](int r_, int c, float v) {
-          const int r = r_ + rq0;
-          if (c < D) {          // (not an rgemm_packed epilogue: the column guard is its own)
-            bQ[r * DS + c] = v;
-            if (sv_o && (unsigned)(r - SH) < (unsigned)L) sv_o[(unsigned)((r - SH) * D + c)] = v;
-          }
-        };
-        if (lo) {
-          if (g == 0) {
-            const int kk0 = r0 > SH ? r0 : SH;
-            gemm_group<0, 1>(0, 1, nt << 4, LP - kk0, Mat{bXS + rq0 * SLD + kk0, SLD}, Mat{bV + kk0 * DS, DS}, epi_o, li, lq);
-          }
-        } else {
-          // (k from tile column max(r0, 12): columns 0 .. 11 of tile 0 are keys no position maps to - the softmax leaves them
-          // unwritten; with the shifted base a query tile's k-range ends up to 12 columns past its diagonal tile: exact zeros)
-          const int kk0 = r0 > SH ? r0 : SH;
-          const Mat Ap{bXS + r0 * SLD + kk0, SLD};
-          const Mat Bv{bV + kk0 * DS, DS};
-          const int kend = LP - kk0;
-          // relative query tiles of this wave: mtn 4: {0,3} | {1,2};  3: {2} | {0,1};  2: {1} | {0};  1: {0} | -
-          int ma, mb;
-          if (mtn == 4) { ma = g == 0 ? 0 : 1; mb = g == 0 ? 3 : 2; }
-          else if (mtn == 3) { ma = g == 0 ? 2 : 0; mb = g == 0 ? -1 : 1; }
-          else if (mtn == 2) { ma = g == 0 ? 1 : 0; mb = -1; }
-          else { ma = g == 0 ? 0 : -1; mb = -1; }
-          if (ma >= 0) gemm_group<2, 1>(ma, 1, nt << 4, kend, Ap, Bv, epi_o, li, lq);
-          if (mb >= 0) gemm_group<2, 1>(mb, 1, nt << 4, kend, Ap, Bv, epi_o, li, lq);
-        }
-      }
-      __syncthreads();
-      // h1 = LN(x) + (o Wo^T + bo)
-      rag_packed(mq0, mqn, DK >> 2, D, Mat{bQ, DS}, wo, [&](int r, int c) { return bQN[r * DS + c]; }, [&](int r, int c, float v, float res) {
-        const float h = res + v;
-        bXS[r * DS + c] = h;
-        return h;
-      }, lane, wave, [&](int rb, int c, const float (&gv)[4]) { if (do_save) gstore4(a.save_h1 + h1_off(i, b, ly.n_blocks, L, D), rb, c, gv); });
-      __syncthreads();
-      ln_rows(nw, bXS + rq0 * DS, bQN + rq0 * DS, LP - rq0, DS, D, s_ln + (4 * i + 2) * 64, s_ln + (4 * i + 3) * 64);
-      __syncthreads();
-      // PW-FFN: y = (drop2(relu(drop1(h2 W1^T + b1)) W2^T + b2) + h2) * keep
-      const DropSite ds1 = drop_site(drop_on, seed, site_ffn1(i), seq, a.drop_thr, a.drop_scale);
-      const DropSite ds2 = drop_site(drop_on, seed, site_ffn2(i), seq, a.drop_thr, a.drop_scale);
-      const WFrag w2 = load_wfrag(pk(i * 6 + 5, 0), P + o.c2_b, D, NT, tid);
-      rag_packed(mq0, mqn, DK >> 2, D, Mat{bQN, DS}, w1, NoPre{}, [&](int r, int c, float v, float) {
-        const float h = fmaxf(v * drop_mul(ds1, r - SH, c), 0.f);
-        bQ[r * DS + c] = h;
-        return h;
-      }, lane, wave, [&](int rb, int c, const float (&gv)[4]) { if (sv_r) gstore4(sv_r, rb, c, gv); });
-      __syncthreads();
-      rag_packed(mq0, mqn, DK >> 2, D, Mat{bQ, DS}, w2, [&](int r, int c) { return bQN[r * DS + c]; }, [&](int r, int c, float v, float res) {
-        const float y = (v * drop_mul(ds2, r - SH, c) + res) * s_keep[r];
-        bXS[r * DS + c] = y;
-        return y;
-      }, lane, wave, [&](int rb, int c, const float (&gv)[4]) { if (do_save) gstore4(a.save_x + x_off(i + 1, b, ly.n_blocks, L, D), rb, c, gv); });
-      __syncthreads();
-    }
-
-    // ---- head: (last_conv) -> last LayerNorm -> hidden, pos/neg logits, BCE partial sums        (every position: a padded
-    // row's hidden state is LayerNorm(0 or b_lc), its logits against the table's row 0 - outputs the reference has too)
-    const bool lo_h = !TR_ && a.last_only != 0;
+  for (int i = 0; i < ly.n_blocks; ++i) {
+    const BlkOff o = blk_off(ly.blk0 + i * ly.blk_stride, D);
+    launder(bXS); launder(bQN); launder(bQ); launder(bK); launder(bV);
+    // (nothing derived from the lane index may be lifted out of the block loop: hipcc otherwise precomputes every per-lane
+    // epilogue address of the block once, runs out of registers and spills them)
     asm volatile("" : "+v"(tid));
     const int lane = tid & 63;
-    if (!lo_h && r0 > SH) {                    // the positions in front of the computed tiles: exact zeros (S overlaid them)
-      for (int i = tid; i < (r0 - SH) * DS; i += nthr) bXS[SH * DS + i] = 0.f;
-      __syncthreads();
-    }
-    lds_f* xp = bXS + SH * DS;                 // position-indexed views
-    lds_f* qnp = bQN + SH * DS;
-    const lds_f* hin = xp;
-    const int p0h = lo_h ? L - 1 : 0;          // first position the head computes
-    if (kind == SRFRD_SRFR) {
-      const WFrag wl = load_wfrag(pk(ly.n_blocks * 6, 0), P + ly.off_lc_b, di, (di + 15) >> 4, tid);
-      const int mh0 = lo_h ? MT - 1 : 0;
-      // (three strips of 45 columns: load_wfrag dealt strip wave % 3 to this wave; waves 0 .. 5 = 3 strips x 2 row-tile groups)
-      {
-        constexpr int nst = (di + 15) >> 4;
-        const int nt = wave % nst, g = wave / nst;
-        const int mtn_h = MT - mh0;
-        auto epi = [&](int r_, int c, float v) { if (c < di) bQ[(r_ + (mh0 << 4)) * DS + c] = v; };
-        if (g < 2) {
-          if (g + 2 < mtn_h) gemm_group_packed<2>(g, 2, nt, DK >> 2, Mat{bXS + (mh0 << 4) * DS, DS}, wl, epi, lane);
-          else if (g < mtn_h) gemm_group_packed<1>(g, 2, nt, DK >> 2, Mat{bXS + (mh0 << 4) * DS, DS}, wl, epi, lane);
-        }
-      }
-      __syncthreads();
-      hin = bQ + SH * DS;
-    }
-    ln_rows(nw, hin + p0h * DS, qnp + p0h * DS, L - p0h, DS, dout, s_ln + (4 * ly.n_blocks) * 64, s_ln + (4 * ly.n_blocks + 1) * 64);
-    __syncthreads();
-    if (lo_h) {
-      for (int c = tid; c < dout; c += nthr) a.hidden[(int64_t)b * dout + c] = qnp[(L - 1) * DS + c];
-    } else {
-      const bool srfrn = kind == SRFRD_SRFRN;
-      lds_f* kp = bK + SH * DS;
-      lds_f* vp = bV + SH * DS;
-      {
-        int t = tid / dout, c = tid - t * dout;
-        constexpr int dt = nthr / dout, dc = nthr - dt * dout;
-        for (; t < L;) {
-          const float h = qnp[t * DS + c];
-          a.hidden[(rowbase + t) * dout + c] = h;
-          if (has_pos)
-            kp[t * DS + c] = h * (c < di ? table((int64_t)s_pid[t + SH] * di + c)
-                                         : (srfrn ? P[ly.off_side + clamp_id(a.pos_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f));
-          if (has_neg)
-            vp[t * DS + c] = h * (c < di ? table((int64_t)s_nid[t + SH] * di + c)
-                                         : (srfrn ? P[ly.off_side + clamp_id(a.neg_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f));
-          t += dt; c += dc;
-          if (c >= dout) { c -= dout; ++t; }
-        }
-      }
-      __syncthreads();
-      float sp = 0.f, sn = 0.f, cnt = 0.f;
-      const int q = tid & (kRL - 1);
-      for (int t = tid / kRL; t < L; t += nthr / kRL) {
-        float ap = 0.f, an = 0.f;
+    // ranking (last_only): the LAST block computes its query-side rows for the tile of position L - 1 only
+    const bool lo = !TR_ && a.last_only != 0 && i == ly.n_blocks - 1;
+    const int mq0 = lo ? (L - 1 + SH) >> 4 : mt0, rq0 = mq0 << 4, mqn = MT - mq0;
+    const AuxOff ax = aux_off(i, b, ly.n_blocks, L, LP, D, 1);
+    float* sv_r = do_save ? a.save_aux + ax.r : nullptr;
+    float* sv_o = do_save ? a.save_aux + ax.o : nullptr;
+    float* sv_p = do_save ? a.save_aux + ax.p : nullptr;
+    float* sv_q = do_save ? a.save_aux + ax.q : nullptr;
+    float* sv_k = do_save ? a.save_aux + ax.k : nullptr;
+    float* sv_v = do_save ? a.save_aux + ax.v : nullptr;
+    // Epilogues (rgemm_packed): one lane-level branch on the column, LDS stores straight-line, checkpoint stores per row group
+    // checkpoint rows of one lane's four consecutive tile rows rb .. rb + 3 (positions rb - SH ..): scalar plane base + one
+    // 32-bit offset + immediates when all four are positions of the sequence (every row group but rows 0 .. 11 and 60 .. 63)
+    auto gstore4 = [&](float* plane, int rb, int c, const float (&v)[4]) {
+      const int p0 = rb - SH;
+      const unsigned off = (unsigned)(p0 * D + c);
+      if (p0 >= 0 && p0 + 3 < L) {
+        plane[off] = v[0]; plane[off + D] = v[1]; plane[off + 2 * D] = v[2]; plane[off + 3 * D] = v[3];
+      } else {
 #pragma unroll
-        for (int j = 0; j < kQC; ++j) {
-          const int c = q + kRL * j;
-          if (c < dout) {
-            if (has_pos) ap += kp[t * DS + c];
-            if (has_neg) an += vp[t * DS + c];
-          }
-        }
-        const float pl = row_sum(ap), nl = row_sum(an);
-        if (q == 0) {
-          if (has_pos) a.pos_logits[rowbase + t] = pl;
-          if (has_neg) a.neg_logits[rowbase + t] = nl;
-          if (do_loss && s_pid[t + SH] != 0) {     // trainer.py:36-38: both terms indexed by pos != 0
-            sp += softplus_fast(-pl);
-            sn += softplus_fast(nl);
-            cnt += 1.f;
-          }
-        }
+        for (int e = 0; e < 4; ++e)
+          if ((unsigned)(p0 + e) < (unsigned)L) plane[(unsigned)((p0 + e) * D + c)] = v[e];
       }
-      if (do_loss) {
-        sp = wave_sum(sp); sn = wave_sum(sn); cnt = wave_sum(cnt);
-        if (lane == 0) {
-          s_misc[8 + wave * 3 + 0] = sp;
-          s_misc[8 + wave * 3 + 1] = sn;
-          s_misc[8 + wave * 3 + 2] = cnt;
-        }
-        __syncthreads();
-        if (tid < 3) {
-          float s = 0.f;
-          for (int w = 0; w < nw; ++w) s += s_misc[8 + w * 3 + tid];
-          a.loss_part[(int64_t)b * 3 + tid] = s;
+    };
+    const WFrag wq = load_wfrag(pk(i * 6 + 0, 0), P + o.in_b, D, NT, tid);
+    const WFrag wk = load_wfrag(pk(i * 6 + 1, 0), P + o.in_b + D, D, NT, tid);
+    const WFrag wv = load_wfrag(pk(i * 6 + 2, 0), P + o.in_b + 2 * D, D, NT, tid);
+    ln_rows(nw, bXS + rq0 * DS, bQN + rq0 * DS, LP - rq0, DS, D, s_ln + (4 * i + 0) * 64, s_ln + (4 * i + 1) * 64);
+    __syncthreads();
+    // q = (LN(x) Wq^T + bq) * sqrt(1/d_h);  k = x Wk^T + bk;  v = x Wv^T + bv       (rows of tiles mt0 .. 3)
+    rag_packed(mq0, mqn, DK >> 2, D, Mat{bQN, DS}, wq, NoPre{}, [&](int r, int c, float v, float) {
+      bQ[r * DS + c] = v * qscale;
+      return v * qscale;
+    }, lane, wave, [&](int rb, int c, const float (&gv)[4]) { if (sv_q) gstore4(sv_q, rb, c, gv); });
+    rag_packed_dual(mt0, mtn, DK >> 2, D, Mat{bXS, DS}, wk, wv, [&](int r, int c, float vk, float vv) {
+      bK[r * DS + c] = vk;
+      bV[r * DS + c] = vv;
+    }, lane, wave, [&](int rb, int c, const float (&gk)[4], const float (&gv)[4]) {
+      if (sv_k) { gstore4(sv_k, rb, c, gk); gstore4(sv_v, rb, c, gv); }
+    });
+    const WFrag wo = load_wfrag(pk(i * 6 + 3, 0), P + o.out_b, D, NT, tid);
+    const WFrag w1 = load_wfrag(pk(i * 6 + 4, 0), P + o.c1_b, D, NT, tid);
+    __syncthreads();
+    // S = q k^T on the lower-triangular tiles of [mq0, 4) x [mt0, 4) (x is dead: S overlays it), dealt round-robin
+    {
+      const int li = lane & 15, lq = lane >> 4;
+      if (lo) {
+        for (int u = wave; u < mtn; u += nw)
+          gemm_group<0, 1>(0, 1, u << 4, DK, Mat{bQ + rq0 * DS, DS}, MatT{bK + r0 * DS, DS},
+                           [&](int r, int c, float v) { bXS[(r + rq0) * SLD + c + r0] = v; }, li, lq);
+      } else {
+        const int ntri = (mtn * (mtn + 1)) >> 1;
+        for (int u = wave; u < ntri; u += nw) {
+          const int m = u >= 6 ? 3 : (u >= 3 ? 2 : (u >= 1 ? 1 : 0)), n = u - ((m * (m + 1)) >> 1);
+          gemm_group<0, 1>(m, 1, n << 4, DK, Mat{bQ + r0 * DS, DS}, MatT{bK + r0 * DS, DS},
+                           [&](int r, int c, float v) { bXS[(r + r0) * SLD + c + r0] = v; }, li, lq);
         }
       }
     }
     __syncthreads();
+    {
+      const DropSite dsA = drop_site(drop_on, seed, site_attn(i), seq, a.drop_thr, a.drop_scale);
+      rag_softmax(bXS, rq0, r0, v0, kr, t0, SH + L, dsA, sv_p, tid);
+    }
+    __syncthreads();
+    // o = P v  (q is dead: o overlays it); tile m of the queries meets key tiles <= m: the pairs {0,3}, {1,2} cost the same
+    {
+      const int li = lane & 15, lq = lane >> 4;
+      const int nt = wave & 3, g = wave >> 2;
+      auto epi_o = [&](int r_, int c, float v) {
+        const int r = r_ + rq0;
+        if (c < D) {          // (not an rgemm_packed epilogue: the column guard is its own)
+          bQ[r * DS + c] = v;
+          if (sv_o && (unsigned)(r - SH) < (unsigned)L) sv_o[(unsigned)((r - SH) * D + c)] = v;
+        }
+      };
+      if (lo) {
+        if (g == 0) {
+          const int kk0 = r0 > SH ? r0 : SH;
+          gemm_group<0, 1>(0, 1, nt << 4, LP - kk0, Mat{bXS + rq0 * SLD + kk0, SLD}, Mat{bV + kk0 * DS, DS}, epi_o, li, lq);
+        }
+      } else {
+        // (k from tile column max(r0, 12): columns 0 .. 11 of tile 0 are keys no position maps to - the softmax leaves them
+        // unwritten; with the shifted base a query tile's k-range ends up to 12 columns past its diagonal tile: exact zeros)
+        const int kk0 = r0 > SH ? r0 : SH;
+        const Mat Ap{bXS + r0 * SLD + kk0, SLD};
+        const Mat Bv{bV + kk0 * DS, DS};
+        const int kend = LP - kk0;
+        // relative query tiles of this wave: mtn 4: {0,3} | {1,2};  3: {2} | {0,1};  2: {1} | {0};  1: {0} | -
+        int ma, mb;
+        if (mtn == 4) { ma = g == 0 ? 0 : 1; mb = g == 0 ? 3 : 2; }
+        else if (mtn == 3) { ma = g == 0 ? 2 : 0; mb = g == 0 ? -1 : 1; }
+        else if (mtn == 2) { ma = g == 0 ? 1 : 0; mb = -1; }
+        else { ma = g == 0 ? 0 : -1; mb = -1; }
+        if (ma >= 0) gemm_group<2, 1>(ma, 1, nt << 4, kend, Ap, Bv, epi_o, li, lq);
+        if (mb >= 0) gemm_group<2, 1>(mb, 1, nt << 4, kend, Ap, Bv, epi_o, li, lq);
+      }
+    }
+    __syncthreads();
+    // h1 = LN(x) + (o Wo^T + bo)
+    rag_packed(mq0, mqn, DK >> 2, D, Mat{bQ, DS}, wo, [&](int r, int c) { return bQN[r * DS + c]; }, [&](int r, int c, float v, float res) {
+      const float h = res + v;
+      bXS[r * DS + c] = h;
+      return h;
+    }, lane, wave, [&](int rb, int c, const float (&gv)[4]) { if (do_save) gstore4(a.save_h1 + h1_off(i, b, ly.n_blocks, L, D), rb, c, gv); });
+    __syncthreads();
+    ln_rows(nw, bXS + rq0 * DS, bQN + rq0 * DS, LP - rq0, DS, D, s_ln + (4 * i + 2) * 64, s_ln + (4 * i + 3) * 64);
+    __syncthreads();
+    // PW-FFN: y = (drop2(relu(drop1(h2 W1^T + b1)) W2^T + b2) + h2) * keep
+    const DropSite ds1 = drop_site(drop_on, seed, site_ffn1(i), seq, a.drop_thr, a.drop_scale);
+    const DropSite ds2 = drop_site(drop_on, seed, site_ffn2(i), seq, a.drop_thr, a.drop_scale);
+    const WFrag w2 = load_wfrag(pk(i * 6 + 5, 0), P + o.c2_b, D, NT, tid);
+    rag_packed(mq0, mqn, DK >> 2, D, Mat{bQN, DS}, w1, NoPre{}, [&](int r, int c, float v, float) {
+      const float h = fmaxf(v * drop_mul(ds1, r - SH, c), 0.f);
+      bQ[r * DS + c] = h;
+      return h;
+    }, lane, wave, [&](int rb, int c, const float (&gv)[4]) { if (sv_r) gstore4(sv_r, rb, c, gv); });
+    __syncthreads();
+    rag_packed(mq0, mqn, DK >> 2, D, Mat{bQ, DS}, w2, [&](int r, int c) { return bQN[r * DS + c]; }, [&](int r, int c, float v, float res) {
+      const float y = (v * drop_mul(ds2, r - SH, c) + res) * s_keep[r];
+      bXS[r * DS + c] = y;
+      return y;
+    }, lane, wave, [&](int rb, int c, const float (&gv)[4]) { if (do_save) gstore4(a.save_x + x_off(i + 1, b, ly.n_blocks, L, D), rb, c, gv); });
+    __syncthreads();
+  }
+
+  // ---- head: (last_conv) -> last LayerNorm -> hidden, pos/neg logits, BCE partial sums        (every position: a padded
+  // row's hidden state is LayerNorm(0 or b_lc), its logits against the table's row 0 - outputs the reference has too)
+  const bool lo_h = !TR_ && a.last_only != 0;
+  asm volatile("" : "+v"(tid));
+  const int lane = tid & 63;
+  if (!lo_h && r0 > SH) {                    // the positions in front of the computed tiles: exact zeros (S overlaid them)
+    for (int i = tid; i < (r0 - SH) * DS; i += nthr) bXS[SH * DS + i] = 0.f;
+    __syncthreads();
+  }
+  lds_f* xp = bXS + SH * DS;                 // position-indexed views
+  lds_f* qnp = bQN + SH * DS;
+  const lds_f* hin = xp;
+  const int p0h = lo_h ? L - 1 : 0;          // first position the head computes
+  if (kind == SRFRD_SRFR) {
+    const WFrag wl = load_wfrag(pk(ly.n_blocks * 6, 0), P + ly.off_lc_b, di, (di + 15) >> 4, tid);
+    const int mh0 = lo_h ? MT - 1 : 0;
+    // (three strips of 45 columns: load_wfrag dealt strip wave % 3 to this wave; waves 0 .. 5 = 3 strips x 2 row-tile groups)
+    {
+      constexpr int nst = (di + 15) >> 4;
+      const int nt = wave % nst, g = wave / nst;
+      const int mtn_h = MT - mh0;
+      auto epi = [&](int r_, int c, float v) { if (c < di) bQ[(r_ + (mh0 << 4)) * DS + c] = v; };
+      if (g < 2) {
+        if (g + 2 < mtn_h) gemm_group_packed<2>(g, 2, nt, DK >> 2, Mat{bXS + (mh0 << 4) * DS, DS}, wl, epi, lane);
+        else if (g < mtn_h) gemm_group_packed<1>(g, 2, nt, DK >> 2, Mat{bXS + (mh0 << 4) * DS, DS}, wl, epi, lane);
+      }
+    }
+    __syncthreads();
+    hin = bQ + SH * DS;
+  }
+  ln_rows(nw, hin + p0h * DS, qnp + p0h * DS, L - p0h, DS, dout, s_ln + (4 * ly.n_blocks) * 64, s_ln + (4 * ly.n_blocks + 1) * 64);
+  __syncthreads();
+  if (lo_h) {
+    for (int c = tid; c < dout; c += nthr) a.hidden[(int64_t)b * dout + c] = qnp[(L - 1) * DS + c];
+  } else {
+    const bool srfrn = kind == SRFRD_SRFRN;
+    lds_f* kp = bK + SH * DS;
+    lds_f* vp = bV + SH * DS;
+    {
+      int t = tid / dout, c = tid - t * dout;
+      constexpr int dt = nthr / dout, dc = nthr - dt * dout;
+      for (; t < L;) {
+        const float h = qnp[t * DS + c];
+        a.hidden[(rowbase + t) * dout + c] = h;
+        if (has_pos)
+          kp[t * DS + c] = h * (c < di ? table((int64_t)s_pid[t + SH] * di + c)
+                                       : (srfrn ? P[ly.off_side + clamp_id(a.pos_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f));
+        if (has_neg)
+          vp[t * DS + c] = h * (c < di ? table((int64_t)s_nid[t + SH] * di + c)
+                                       : (srfrn ? P[ly.off_side + clamp_id(a.neg_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f));
+        t += dt; c += dc;
+        if (c >= dout) { c -= dout; ++t; }
+      }
+    }
+    __syncthreads();
+    float sp = 0.f, sn = 0.f, cnt = 0.f;
+    const int q = tid & (kRL - 1);
+    for (int t = tid / kRL; t < L; t += nthr / kRL) {
+      float ap = 0.f, an = 0.f;
+#pragma unroll
+      for (int j = 0; j < kQC; ++j) {
+        const int c = q + kRL * j;
+        if (c < dout) {
+          if (has_pos) ap += kp[t * DS + c];
+          if (has_neg) an += vp[t * DS + c];
+        }
+      }
+      const float pl = row_sum(ap), nl = row_sum(an);
+      if (q == 0) {
+        if (has_pos) a.pos_logits[rowbase + t] = pl;
+        if (has_neg) a.neg_logits[rowbase + t] = nl;
+        if (do_loss && s_pid[t + SH] != 0) {     // trainer.py:36-38: both terms indexed by pos != 0
+          sp += softplus_fast(-pl);
+          sn += softplus_fast(nl);
+          cnt += 1.f;
+        }
+      }
+    }
+    if (do_loss) {
+      sp = wave_sum(sp); sn = wave_sum(sn); cnt = wave_sum(cnt);
+      if (lane == 0) {
+        s_misc[8 + wave * 3 + 0] = sp;
+        s_misc[8 + wave * 3 + 1] = sn;
+        s_misc[8 + wave * 3 + 2] = cnt;
+      }
+      __syncthreads();
+      if (tid < 3) {
+        float s = 0.f;
+        for (int w = 0; w < nw; ++w) s += s_misc[8 + w * 3 + tid];
+        a.loss_part[(int64_t)b * 3 + tid] = s;
+      }
+    }
+  }
+  __syncthreads();
+}
+
+template <int K_, int T_, int DI_>
+__global__ void __launch_bounds__(512, 4) encoder_fwd_ragged_kernel(const EncArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const Dims& ly = a.dm;
+  constexpr int D = 50, L = 50, LP = 64, DS = 54, SLD = 66;
+  constexpr int nthr = 512;
+  int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  constexpr int szA = LP * DS, szX = LP * SLD;
+  const int tailsz = 4 * LP + 64 + ln_cache_floats(ly.n_blocks);
+  const RagT0 t0v = rag_load_t0(a, tid);
+  lds_f* c_cur = (lds_f*)smem;
+  auto carve = [&](int64_t n) -> lds_f* { lds_f* p = c_cur; c_cur += n; return p; };
+  {
+    Geom g = make_geom(L, D);
+    const int total = (int)fwd_lds_floats(g, ly.n_blocks);
+    for (int i = tid; i < total; i += nthr) ((lds_f*)smem)[i] = 0.f;
+  }
+  lds_f* tail = carve(tailsz);
+  RagFwdLds m;
+  m.bXS = carve(szX);
+  m.bQN = carve(szA);
+  m.bQ = carve(szA);
+  m.bK = carve(szA);
+  m.bV = carve(szA + kSlack);
+  m.s_in = (lds_i*)tail;
+  m.s_keep = tail + LP;
+  m.s_pid = (lds_i*)(tail + 2 * LP);
+  m.s_nid = (lds_i*)(tail + 3 * LP);
+  m.s_misc = tail + 4 * LP;
+  lds_f* s_ln = m.s_misc + 64;
+  m.s_ln = s_ln;
+  __syncthreads();
+  fill_ln_cache(s_ln, a.dense, ly);
+  const uint32_t seed = a.seed_dev ? *a.seed_dev : a.seed;
+
+  STAMP_INIT
+  for (int iter = 0;; ++iter) {
+    const int b = __builtin_amdgcn_readfirstlane(rag_take(a, (lds_i*)m.bXS, iter, tid, t0v));      // (bXS: free between sequences)
+    if (b < 0) break;
+    rag_fwd_seq<K_, T_, DI_>(a, m, b, tid, wave, seed);
   }
 }
 

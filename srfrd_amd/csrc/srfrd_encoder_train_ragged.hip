@@ -1,0 +1,113 @@
+// Ragged train kernel (seq_len 50, hidden 50): the training forward of srfrd_encoder_fwd_ragged_kernel.inc and the fused-BCE
+// backward of srfrd_encoder_bwd_ragged_kernel.inc as ONE launch.  Each workgroup runs, for the sequence its schedule slot
+// names, the forward, a workgroup barrier, then the backward - which reads only what the same workgroup has just written
+// (checkpoints, hidden states, logits): a workgroup-scope fence is all the hand-off needs, no workgroup waits for another.
+// The BCE normaliser (the global target count) enters later, in the Adam step, so nothing in here needs the whole batch.
+//
+// Against the two launches: a long sequence's backward no longer waits for the slowest forward on the chip, and once its
+// short partner on the CU has finished, it runs alone.  Results are those of the two launches bit for bit: same
+// arithmetic, the same sequence -> workgroup schedule (so the same per-workgroup slab sums), and every phase starts from
+// the zeroed working set a fresh launch starts from.
+#include "srfrd_enc_common.h"
+
+#include "srfrd_encoder_fwd_ragged_kernel.inc"
+#include "srfrd_encoder_bwd_ragged_kernel.inc"
+
+namespace srfrd {
+
+// LDS: [ working set (forward and backward overlaid) | LayerNorm parameters | LayerNorm gradient accumulators ]
+template <int K_, int DI_, bool RMW_>
+__global__ void __launch_bounds__(512, 4) encoder_train_ragged_kernel(const EncArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const Dims& ly = a.dm;
+  constexpr int LP = 64, DS = 54, SLD = 66, nthr = 512;
+  constexpr int W = kRagFwdWork > kRagBwdWork ? kRagFwdWork : kRagBwdWork;
+  int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const RagT0 t0v = rag_load_t0(a, tid);
+  lds_f* base = (lds_f*)smem;
+  {
+    const int total = (int)train_ragged_lds_floats(ly.n_blocks);
+    for (int i = tid; i < total; i += nthr) base[i] = 0.f;
+  }
+  RagFwdLds fm;
+  fm.bXS = base;
+  fm.bQN = base + LP * SLD;
+  fm.bQ = fm.bQN + LP * DS;
+  fm.bK = fm.bQ + LP * DS;
+  fm.bV = fm.bK + LP * DS;
+  lds_f* ftail = fm.bV + LP * DS;         // (the forward's per-row arrays: its over-reads behind bV stay in the allocation)
+  fm.s_in = (lds_i*)ftail;
+  fm.s_keep = ftail + LP;
+  fm.s_pid = (lds_i*)(ftail + 2 * LP);
+  fm.s_nid = (lds_i*)(ftail + 3 * LP);
+  fm.s_misc = ftail + 4 * LP;
+  static_assert(LP * SLD + 4 * LP * DS + 5 * LP == kRagFwdWork, "forward working set");
+  lds_f* s_ln = base + W;
+  fm.s_ln = s_ln;
+  const RagBwdLds bm{base, s_ln, s_ln + ln_cache_floats(ly.n_blocks)};
+  __syncthreads();
+  fill_ln_cache(s_ln, a.dense, ly);
+  const uint32_t seed = a.seed_dev ? *a.seed_dev : a.seed;
+
+  for (int iter = 0;; ++iter) {
+    if (iter > 0) {                       // the previous backward's leftovers: the forward starts from zeros, as in its own launch
+      for (int i = tid; i < W; i += nthr) base[i] = 0.f;
+      __syncthreads();
+    }
+    const int b = __builtin_amdgcn_readfirstlane(rag_take(a, (lds_i*)fm.bXS, iter, tid, t0v));
+    if (b < 0) break;
+    rag_fwd_seq<K_, 1, DI_>(a, fm, b, tid, wave, seed);
+    // (rag_fwd_seq ended with a workgroup barrier: its checkpoint stores are visible to every wave of the workgroup)
+    for (int i = tid; i < W; i += nthr) base[i] = 0.f;
+    __syncthreads();
+    rag_bwd_seq<K_, DI_, RMW_>(a, bm, b, iter, tid, wave, seed);
+  }
+}
+
+int launch_train_ragged(const KernelPlan& k, const EncArgs& a, void* stream) {
+  return with_variant(k.variant, [&](auto v) {
+    constexpr KindVariant kv = kKindVariants[decltype(v)::value];
+    return with_flag(k.flag, [&](auto rmw) { return launch_enc(encoder_train_ragged_kernel<kv.K, kv.DI, decltype(rmw)::value>, k, stream, a); });
+  });
+}
+
+}  // namespace srfrd
+
+using namespace srfrd;
+
+extern "C" int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
+                                         const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids,
+                                         const int64_t* pos_fake, const int64_t* neg_ids, const int64_t* neg_fake, int B, int L,
+                                         double dropout_p, uint32_t seed, const uint32_t* seed_dev, int64_t seq_index0,
+                                         float* hidden, float* pos_logits, float* neg_logits, float* save_x, float* save_h1,
+                                         float* save_aux, float* loss_part, const float* d_hidden, const float* d_pos,
+                                         const float* d_neg, int fused_bce, float* grad_table, float* table_contrib,
+                                         float* grad_slabs, float* scratch, int64_t scratch_floats, const int32_t* sched,
+                                         int sched_mode, void* stream) {
+  if (sched_mode < 0 || sched_mode > 1 || (sched_mode != 0 && !sched)) return SRFRD_E_ARG;
+  const int sw = read_switches();
+  EncArgs a = {};
+  a.sched = sched_mode != 0 ? sched : nullptr;
+  a.sched_mode = a.sched ? sched_mode : 0;
+  a.ragged_off = (sw & SRFRD_SW_RAGGED_FULL_ROWS) != 0;
+  const int rc = fill_args(a, lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L,
+                           dropout_p, seed, seed_dev, seq_index0);
+  if (rc) return rc;
+  // what srfrd_encoder_fwd_sched and srfrd_encoder_bwd_sched each refuse
+  if (!hidden || (pos_ids && !pos_logits) || (neg_ids && !neg_logits)) return SRFRD_E_ARG;
+  if (loss_part && !(pos_ids && neg_ids)) return SRFRD_E_ARG;
+  if ((save_x != nullptr) != (save_h1 != nullptr) || (save_x != nullptr) != (save_aux != nullptr)) return SRFRD_E_ARG;
+  if (!save_x || !grad_table || !grad_slabs) return SRFRD_E_ARG;
+  if (fused_bce && !(pos_ids && neg_ids)) return SRFRD_E_ARG;
+  const int mode = (pos_ids ? SRFRD_PLAN_POS : 0) | (neg_ids ? SRFRD_PLAN_NEG : 0) | SRFRD_PLAN_CKPT | (loss_part ? SRFRD_PLAN_LOSS : 0) |
+                   (dropout_p > 0.0 ? SRFRD_PLAN_DROPOUT : 0) | (fused_bce && !d_hidden ? SRFRD_PLAN_FUSED_BCE : 0);
+  const KernelPlan k = encoder_plan(*lay, B, L, mode, sw, num_cu(), scratch ? scratch_floats : 0).train;
+  if (k.rc) return k.rc;
+  a.hidden = hidden; a.pos_logits = pos_logits; a.neg_logits = neg_logits;
+  a.save_x = save_x; a.save_h1 = save_h1; a.save_aux = save_aux; a.loss_part = loss_part;
+  a.c_hidden = hidden; a.c_pl = pos_logits; a.c_nl = neg_logits; a.c_save_x = save_x; a.c_save_h1 = save_h1; a.c_save_aux = save_aux;
+  a.fused_bce = 1;
+  a.grad_table = grad_table; a.grad_slabs = grad_slabs; a.contrib = table_contrib;
+  return launch_train_ragged(k, a, stream);
+}

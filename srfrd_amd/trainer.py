@@ -3,7 +3,8 @@
     forward -> masked BCE(pos, 1) + BCE(neg, 0) over pos != 0 -> backward -> Adam(lr, betas=(0.9, 0.98))
 
 as five stream-ordered launches on persistent buffers (encoder_fwd, encoder_bwd, reduce_dense [+ loss], adam_step,
-pack_weights [+ optimizer-state advance for the next step]), captured into one HIP graph when no collective sits in the middle.  Differences from the reference
+pack_weights [+ optimizer-state advance for the next step]; single rank at seq_len 50: encoder_fwd and encoder_bwd are ONE
+launch, srfrd_encoder_train_sched), captured into one HIP graph when no collective sits in the middle.  Differences from the reference
 loop, all behaviour-preserving: the loss is never synchronised to the host (``loss`` stays a device scalar), the
 ``l2_emb * ||p||`` terms (trainer.py:39: one Frobenius norm per parameter tensor) cost two small launches and one pass over
 the gradient when l2_emb != 0 and nothing at the reference's 0.0, and dropout masks come from the coordinate hash of csrc/srfrd_rng.h instead of torch's Bernoulli stream.
@@ -140,6 +141,10 @@ class FusedTrainer:
         self.sched_mode = min(1, int(os.environ.get("SRFRD_SCHED", "1"))) if ragged else 0
         self.sched = torch.zeros(int(_lib.lib().srfrd_sched_ints(B)), device=dev, dtype=torch.int32) if self.sched_mode else None
         self.pair_stride = max(1, _lib.lib().srfrd_bwd_grid(C.byref(lay), 1 << 30, L) // 2)      # CUs: workgroups of the first round
+        # single rank: forward + backward as one launch where the plan has a train kernel (srfrd_encoder_train_sched), asked
+        # at every enqueue under the environment's switches then; False: always the two launches (A/B comparisons)
+        self._train_mode = fused
+        self.train_launch = True
         self.packed = model.pack_weights()
         check(_lib.lib().srfrd_step_begin(ptr(self.state), self.lr, self.betas[0], self.betas[1],
                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "srfrd_step_begin")
@@ -170,7 +175,8 @@ class FusedTrainer:
         check(_lib.lib().srfrd_l2_apply(grad_ptr, ptr(param), i0, min(i1, self.n_flat), self.n_tab, ptr(self.l2buf),
                                         ptr(self.l2_dense), ptr(self.stats), self._stream()), "srfrd_l2_apply")
 
-    def _enqueue_fwd(self, slot: int = 0):
+    def _enqueue_fwd(self, slot: int = 0, train: bool = False):
+        """the forward (train: the forward and the backward, one srfrd_encoder_train_sched launch)"""
         L_, lay, st = _lib.lib(), self.lay, self._stream()
         if self.l2 != 0.0:               # norms of the parameters this step's forward uses
             check(L_.srfrd_l2_norms(ptr(self.flat), ptr(self.seg_off), ptr(self.seg_len), self.seg_off.numel(), self.n_tab,
@@ -179,6 +185,15 @@ class FusedTrainer:
         lay_t, tab = self.model._table_args()
         if self.sched_mode:
             check(L_.srfrd_seq_order(ptr(ids[0]), self.B, self.L, self.pair_stride, ptr(self.sched), st), "srfrd_seq_order")
+        if train:
+            check(L_.srfrd_encoder_train_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk),
+                                               ptr(ids[2]), ptr(pfk), ptr(ids[4]), ptr(nfk), self.B, self.L, p, 0, seed_dev, seq0,
+                                               ptr(self.hidden), ptr(self.pl), ptr(self.nl), ptr(self.save_x), ptr(self.save_h1),
+                                               ptr(self.save_aux), ptr(self.loss_part), None, None, None, 1, ptr(self.grad),
+                                               ptr(self.contrib), ptr(self.slabs), ptr(self.scratch), self.n_scratch, ptr(self.sched),
+                                               self.sched_mode, st), "srfrd_encoder_train_sched")
+            self._enqueue_grad_tail(slot)
+            return
         check(L_.srfrd_encoder_fwd_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk), ptr(ids[2]),
                                          ptr(pfk), ptr(ids[4]), ptr(nfk), self.B, self.L, p, 0, seed_dev, seq0, ptr(self.hidden),
                                          ptr(self.pl), ptr(self.nl), ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), ptr(self.loss_part),
@@ -195,6 +210,12 @@ class FusedTrainer:
                                          ptr(self.pl), ptr(self.nl), ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), None, None, None, 1,
                                          ptr(self.grad), ptr(self.contrib), ptr(self.slabs), ptr(self.scratch), self.n_scratch,
                                          ptr(self.sched), self.sched_mode, st), "srfrd_encoder_bwd_sched")
+        self._enqueue_grad_tail(slot)
+
+    def _enqueue_grad_tail(self, slot: int = 0):
+        """after the backward: the deterministic item-table reduction, then the dense-gradient slab reduction (+ loss)"""
+        L_, lay, st = _lib.lib(), self.lay, self._stream()
+        ids = self.ids_ring[slot]
         if self.contrib is not None:
             # deterministic item-table scatter: stable sort of the 3 B L row keys (pos, neg, input ids - the row order of
             # `contrib`), then one wave per item adds its rows in that order
@@ -210,8 +231,18 @@ class FusedTrainer:
                                     ptr(self.loss) if self.mode == "single" else None, st), "srfrd_reduce_dense")
 
     def _enqueue_compute(self, slot: int = 0):
+        """forward and backward as their two launches (the data-parallel step, per-launch timing)"""
         self._enqueue_fwd(slot)
         self._enqueue_bwd(slot)
+
+    def _enqueue_step_compute(self, slot: int = 0):
+        """the single-rank step's compute: forward and backward as ONE launch where the kernel plan offers a train kernel (each
+        workgroup runs its sequence's backward right after its forward; the same bits as the two launches), else the two"""
+        if self.mode == "single" and self.train_launch and _lib.encoder_plan_train(
+                self.lay, self.B, self.L, self._train_mode, _lib.env_switches())[0]:
+            self._enqueue_fwd(slot, train=True)
+        else:
+            self._enqueue_compute(slot)
 
     def _enqueue_update(self):
         """single rank / all-reduce form: Adam over the whole flat vector + re-pack + optimizer-state advance, one launch"""
@@ -305,7 +336,7 @@ class FusedTrainer:
                 # graph will hold has then run once on this communicator (lazy channel / buffer set-up cannot be captured)
                 self._enqueue_dp_step()
             else:
-                self._enqueue_compute()
+                self._enqueue_step_compute()
                 if self.mode == "sharded":
                     self._enqueue_shard_update()
                     self._enqueue_shard_finish()
@@ -349,7 +380,7 @@ class FusedTrainer:
         if self.graph_form == "one" and self.mode != "single":
             pass
         elif self.mode == "single":
-            self._graph_a = [graph_of(lambda k=k: (self._enqueue_compute(k), self._enqueue_update())) for k in range(self.slots)]
+            self._graph_a = [graph_of(lambda k=k: (self._enqueue_step_compute(k), self._enqueue_update())) for k in range(self.slots)]
         elif self.mode == "allreduce":
             self._graph_a = [graph_of(lambda k=k: self._enqueue_compute(k)) for k in range(self.slots)]
             self._graph_b = graph_of(self._enqueue_update)
@@ -533,7 +564,7 @@ class FusedTrainer:
             self._capture()
         if not g:
             if self.mode == "single":
-                self._enqueue_compute(slot)
+                self._enqueue_step_compute(slot)
                 self._enqueue_update()
             else:
                 self._enqueue_dp_step(slot)
