@@ -466,6 +466,38 @@ int srfrd_xent_bwd(const srfrd_layout* lay, const float* table, const float* hid
                    int accumulate, float* workspace, int64_t ws_floats, void* stream);
 
 /*
+ * Sampled softmax cross-entropy with shared negatives (no reference counterpart either).  Tokens are the positions t of the
+ * (B, L) `targets` with targets[t] != 0, as in srfrd_xent_*.  `negatives` (K) int64 is one set of sampled item ids shared by
+ * every token: id 0 marks an unused slot, duplicates are allowed (each occurrence is its own candidate).  `log_q` (K) fp32
+ * may be NULL.  s_t+ = <hidden[t, :d_item], E[y_t]>; slot j has s_tj = <hidden[t, :d_item], E[n_j]> - log_q[j] (nothing
+ * subtracted without log_q); loss_t = logsumexp({s_t+} u {s_tj : n_j != 0, and n_j != y_t if remove_hits}) - s_t+, which is
+ * 0 with a zero gradient when no slot takes part.  negatives = 1..n_items without log_q and with remove_hits is the full-
+ * catalog loss.  SRFRN's fake slice is not read (one constant per row: the softmax does not see it).  Ids are clamped into
+ * [0, n_items].  The (tokens x (1 + K)) logits are never written: the forward streams 64-slot chunks of gathered rows E[n_j]
+ * against tiles of tokens on the fp32 matrix cores, the backward recomputes them.  No float atomics: two identical calls
+ * give bitwise-identical results.  lay->table_bf16 or lay->D > SRFRD_MAX_D -> SRFRD_E_UNSUPPORTED; K <= 0 -> SRFRD_E_ARG.
+ *
+ * srfrd_sxent_workspace_floats [host]: floats of `workspace` both calls need for (B, L, K) (0 for arguments they refuse).
+ * srfrd_sxent_fwd: token_loss (B, L) (0 where targets == 0), lse (B, L) (0 there too; the log of the sampled partition
+ *   function, target term included), stats[0..1] = {sum of the token losses, token count} (fp32, on the device).
+ * srfrd_sxent_bwd: with the forward's lse and the upstream gradient of every token loss d_token_loss (B, L):
+ *   d_hidden (B, L, d_out) = sum_j d_t softmax_tj E[n_j] + d_t (softmax_t+ - 1) E[y_t] in columns < d_item, zeros elsewhere
+ *   and at ignored positions (fully overwritten).  The table gradient is left unsummed, in the srfrd_table_reduce contract:
+ *   table_contrib (K + B L, d_item) and contrib_keys (K + B L) int64, fully overwritten.  Row j < K is slot j's
+ *   sum_t d_t softmax_tj hidden[t, :d_item] with key n_j; row K + t is d_t (softmax_t+ - 1) hidden[t, :d_item] with key
+ *   y_t.  Unused slots and positions without a target have key 0 and a zero row.  A stable sort of the keys followed by
+ *   srfrd_table_reduce into a zeroed (n_items + 1, d_item) gradient gives dE with every item's rows summed in a fixed order.
+ */
+int64_t srfrd_sxent_workspace_floats(const srfrd_layout* lay, int B, int L, int K);
+int srfrd_sxent_fwd(const srfrd_layout* lay, const float* table, const float* hidden, const int64_t* targets,
+                    const int64_t* negatives, const float* log_q, int K, int remove_hits, int B, int L, float* token_loss,
+                    float* lse, float* stats, float* workspace, int64_t ws_floats, void* stream);
+int srfrd_sxent_bwd(const srfrd_layout* lay, const float* table, const float* hidden, const int64_t* targets,
+                    const int64_t* negatives, const float* log_q, int K, int remove_hits, const float* lse,
+                    const float* d_token_loss, int B, int L, float* d_hidden, float* table_contrib, int64_t* contrib_keys,
+                    float* workspace, int64_t ws_floats, void* stream);
+
+/*
  * Device-side batch sampler with the layout and semantics of reference utils.py:21-57 (sample_function_fr /
  * WarpSampler_fr): per sampled user (uniform among users with > 1 interaction) the most recent `L` training items
  * left-padded with 0, pos[t] = the next item, neg[t] = a uniform item outside the user's history wherever pos[t] != 0,

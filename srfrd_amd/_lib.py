@@ -86,6 +86,9 @@ SIGNATURES = {
     "srfrd_xent_workspace_floats": (_i64, [_LP, _i, _i]),
     "srfrd_xent_fwd": (_i, [_LP, _P, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
     "srfrd_xent_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _P, _P, _i, _P, _i64, _P]),
+    "srfrd_sxent_workspace_floats": (_i64, [_LP, _i, _i, _i]),
+    "srfrd_sxent_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _P, _i64, _P]),
+    "srfrd_sxent_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
 }
 
 _lib = None

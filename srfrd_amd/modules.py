@@ -155,6 +155,32 @@ class _XentFn(torch.autograd.Function):
         return None, None, dh, None, de
 
 
+class _SxentFn(torch.autograd.Function):
+    """sampled_softmax_loss() under autograd: the launches of the registered ``srfrd::sxent_fwd`` / ``srfrd::sxent_bwd`` ops
+    without torch.library's Python glue, as _XentFn.  The reduction is applied on the device from the forward's
+    {sum, count}: no host synchronisation in either direction.  log_q is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, model, reduction, remove_hits, hidden, targets, negatives, log_q, table):
+        lay, tab = model.layout, ptr(table)
+        tl, lse, stats = ops.sxent_launch_fwd(lay, tab, hidden, targets, negatives, log_q, remove_hits)
+        ctx.model, ctx.reduction, ctx.remove_hits = model, reduction, remove_hits
+        ctx.save_for_backward(hidden, targets, negatives, log_q, table, lse, stats)
+        if reduction == "none":
+            return tl
+        return stats[0].clone() if reduction == "sum" else stats[0] / stats[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        hidden, targets, negatives, log_q, table, lse, stats = ctx.saved_tensors
+        if ctx.reduction == "none":
+            d_tok = g.contiguous()
+        else:
+            d_tok = (g if ctx.reduction == "sum" else g / stats[1]).expand(targets.shape).contiguous()
+        dh, de = ops.sxent_launch_bwd(ctx.model.layout, ptr(table), hidden, targets, negatives, log_q, ctx.remove_hits, lse, d_tok)
+        return None, None, None, dh, None, None, None, de
+
+
 class _SRFRDBase(nn.Module):
     """Shared machinery: flat parameter storage, kernel launches, predict."""
 
@@ -526,6 +552,49 @@ class _SRFRDBase(nn.Module):
                 self.check_ids()
         table = self._slots[0][0]
         return _XentFn.apply(self, reduction, hidden_state.contiguous(), y, table)
+
+    def sampled_softmax_loss(self, hidden_state, positive_ids, negative_ids, log_q=None, remove_accidental_hits=True,
+                             reduction="mean"):
+        """Sampled softmax cross-entropy with negatives shared by the whole batch (``srfrd_sxent_fwd`` / ``_bwd``): every
+        position with ``positive_ids != 0`` is scored against its own target and the K items of ``negative_ids``,
+        ``loss_t = logsumexp({s_t+} u {s_tj}) - s_t+`` with ``s_t+ = <h_t[:d_item], E[y_t]>`` and ``s_tj = <h_t[:d_item],
+        E[n_j]> - log_q[j]``.  ``negative_ids`` (K,): id 0 marks an unused slot, duplicates count once each;
+        ``log_q`` (K,) float32 or None (e.g. the second output of ``srfrd_amd.sample_negatives``), not differentiable;
+        ``remove_accidental_hits`` drops, per token, the slots equal to its target.  The (tokens x (1 + K)) logits are
+        never materialised.  reduction: "mean" (over the targets; NaN when there are none), "sum" or "none" ((B, L), zeros
+        at ignored positions).  Autograd carries the loss into ``hidden_state`` and into the item table, whose gradient is
+        reduced per item in a fixed order (bitwise reproducible).  SRFRN's fake slice gets a zero gradient, as in
+        full_catalog_loss; ``negative_ids = arange(1, n_items + 1)`` without log_q is full_catalog_loss."""
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
+        self._ensure_flat()
+        if self.bf16_table:
+            raise RuntimeError("sampled_softmax_loss needs the fp32 item table (use_bf16_table(False)); the bf16 form is not built")
+        lay = self.layout
+        dev = self._flat.device
+        if hidden_state.dim() != 3 or hidden_state.shape[2] != lay.d_out or hidden_state.device != dev:
+            raise ValueError(f"hidden_state must be the model's (B, L, {lay.d_out}) output on {dev}")
+        if hidden_state.dtype != torch.float32:
+            raise ValueError("hidden_state must be float32")
+        y = _ids(positive_ids, dev, hidden_state.shape[:2])
+        neg = torch.as_tensor(negative_ids)
+        if neg.dim() != 1 or neg.numel() == 0 or neg.is_floating_point() or neg.is_complex() or neg.dtype == torch.bool:
+            raise ValueError(f"negative_ids must be a non-empty 1-D integer tensor (got shape {tuple(neg.shape)}, {neg.dtype})")
+        neg = _ids(neg, dev)
+        K = neg.numel()
+        if log_q is not None:
+            if not isinstance(log_q, torch.Tensor) or log_q.dtype != torch.float32 or tuple(log_q.shape) != (K,):
+                raise ValueError(f"log_q must be a float32 tensor of shape ({K},) or None")
+            log_q = log_q.detach().to(dev).contiguous()
+        if self.validate_ids:
+            check(_lib.lib().srfrd_check_ids(ptr(y), None, None, None, None, None, y.numel(), lay.n_items, 2,
+                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
+            check(_lib.lib().srfrd_check_ids(ptr(neg), None, None, None, None, None, K, lay.n_items, 2,
+                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
+            if self.validate_ids == "eager":
+                self.check_ids()
+        table = self._slots[0][0]
+        return _SxentFn.apply(self, reduction, bool(remove_accidental_hits), hidden_state.contiguous(), y, neg, log_q, table)
 
     def user_labels(self, fake_ids):
         """get_Labels (SRFU_*) / the predict-time label (SRFRN) as an int64 (B,) tensor, computed on device."""

@@ -16,6 +16,8 @@ backward - instead of being an opaque ctypes call from Python:
     srfrd::eval_rank       rank of candidate 0 (utils.py:589-597)
     srfrd::xent_fwd        full-catalog softmax cross-entropy per token (logits never in HBM); backward = srfrd::xent_bwd
     srfrd::xent_bwd        its gradients into the hidden state and the item table
+    srfrd::sxent_fwd       sampled softmax cross-entropy with shared negatives per token; backward = srfrd::sxent_bwd
+    srfrd::sxent_bwd       its gradients into the hidden state and the item table (deterministic table reduction)
 
 A model's geometry (the srfrd_layout descriptor, its flat parameter vector and packed weights) is not expressible as op
 arguments one by one; the ops take ``model_key``, the registry key of a live model (``register_model``), and read
@@ -390,5 +392,96 @@ def _xent_backward(ctx, grads):
 xent_fwd.register_autograd(_xent_backward, setup_context=_xent_setup)
 
 
+# ------------------------------------------------------------------------------------------------ sampled softmax cross-entropy
+def sxent_launch_fwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor,
+                     log_q: Optional[torch.Tensor], remove_hits: bool):
+    """srfrd_sxent_fwd -> (token_loss (B, L), lse (B, L), stats {sum, count})"""
+    B, L = targets.shape
+    K = negatives.numel()
+    dev = hidden.device
+    L_ = _lib.lib()
+    ws = torch.empty(L_.srfrd_sxent_workspace_floats(C.byref(lay), B, L, K), device=dev, dtype=torch.float32)
+    tl = torch.empty(B, L, device=dev, dtype=torch.float32)
+    lse = torch.empty(B, L, device=dev, dtype=torch.float32)
+    stats = torch.empty(2, device=dev, dtype=torch.float32)
+    check(L_.srfrd_sxent_fwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(negatives), ptr(log_q), K, int(remove_hits),
+                             B, L, ptr(tl), ptr(lse), ptr(stats), ptr(ws), ws.numel(), _stream()), "srfrd_sxent_fwd")
+    return tl, lse, stats
+
+
+def sxent_launch_bwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor,
+                     log_q: Optional[torch.Tensor], remove_hits: bool, lse: torch.Tensor, d_token_loss: torch.Tensor):
+    """srfrd_sxent_bwd, then the stable key sort and srfrd_table_reduce -> (d_hidden (B, L, d_out), d_table (n_items + 1,
+    d_item)): every item's contribution rows (its negative slots in slot order, then its target tokens in position order)
+    summed in that fixed order"""
+    B, L = targets.shape
+    K = negatives.numel()
+    dev = hidden.device
+    L_ = _lib.lib()
+    ws = torch.empty(L_.srfrd_sxent_workspace_floats(C.byref(lay), B, L, K), device=dev, dtype=torch.float32)
+    dh = torch.empty(B, L, lay.d_out, device=dev, dtype=torch.float32)
+    contrib = torch.empty(K + B * L, lay.d_item, device=dev, dtype=torch.float32)
+    keys = torch.empty(K + B * L, device=dev, dtype=torch.int64)
+    check(L_.srfrd_sxent_bwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(negatives), ptr(log_q), K, int(remove_hits),
+                             ptr(lse), ptr(d_token_loss), B, L, ptr(dh), ptr(contrib), ptr(keys), ptr(ws), ws.numel(), _stream()),
+          "srfrd_sxent_bwd")
+    skeys, order = torch.sort(keys, stable=True)
+    de = torch.zeros(lay.n_items + 1, lay.d_item, device=dev, dtype=torch.float32)
+    check(L_.srfrd_table_reduce(ptr(skeys), ptr(order), ptr(contrib), skeys.numel(), lay.d_item, ptr(de), _stream()),
+          "srfrd_table_reduce")
+    return dh, de
+
+
+@torch.library.custom_op("srfrd::sxent_fwd", mutates_args=(), device_types="cuda")
+def sxent_fwd(hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor, log_q: Optional[torch.Tensor],
+              table: torch.Tensor, remove_hits: bool, model_key: int) -> List[torch.Tensor]:
+    """-> [token_loss (B, L), lse (B, L), stats (2) = {sum, count}]"""
+    lay, tab = _xent_table(_model(model_key), table)
+    return list(sxent_launch_fwd(lay, tab, hidden.contiguous(), targets.contiguous(), negatives.contiguous(),
+                                 None if log_q is None else log_q.contiguous(), remove_hits))
+
+
+@sxent_fwd.register_fake
+def _(hidden, targets, negatives, log_q, table, remove_hits, model_key):
+    B, L = targets.shape
+    f = dict(device=hidden.device, dtype=torch.float32)
+    return [torch.empty(B, L, **f), torch.empty(B, L, **f), torch.empty(2, **f)]
+
+
+@torch.library.custom_op("srfrd::sxent_bwd", mutates_args=(), device_types="cuda")
+def sxent_bwd(hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor, log_q: Optional[torch.Tensor],
+              table: torch.Tensor, remove_hits: bool, lse: torch.Tensor, d_token_loss: torch.Tensor,
+              model_key: int) -> List[torch.Tensor]:
+    """-> [d_hidden (B, L, d_out), d_table (n_items + 1, d_item)]"""
+    lay, tab = _xent_table(_model(model_key), table)
+    return list(sxent_launch_bwd(lay, tab, hidden.contiguous(), targets.contiguous(), negatives.contiguous(),
+                                 None if log_q is None else log_q.contiguous(), remove_hits, lse.contiguous(),
+                                 d_token_loss.contiguous()))
+
+
+@sxent_bwd.register_fake
+def _(hidden, targets, negatives, log_q, table, remove_hits, lse, d_token_loss, model_key):
+    return [torch.empty_like(hidden), torch.empty_like(table)]
+
+
+def _sxent_setup(ctx, inputs, output):
+    hidden, targets, negatives, log_q, table, remove_hits, model_key = inputs
+    ctx.model_key, ctx.remove_hits = model_key, remove_hits
+    ctx.save_for_backward(hidden, targets, negatives, log_q, table, output[1])
+
+
+def _sxent_backward(ctx, grads):
+    hidden, targets, negatives, log_q, table, lse = ctx.saved_tensors
+    g = grads[0]
+    if g is None:
+        return None, None, None, None, None, None, None
+    dh, de = torch.ops.srfrd.sxent_bwd(hidden, targets, negatives, log_q, table, ctx.remove_hits, lse, g.contiguous(),
+                                       ctx.model_key)
+    return dh, None, None, None, de, None, None
+
+
+sxent_fwd.register_autograd(_sxent_backward, setup_context=_sxent_setup)
+
+
 OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "target_rank", "topk_merge",
-       "eval_rank", "xent_fwd", "xent_bwd")
+       "eval_rank", "xent_fwd", "xent_bwd", "sxent_fwd", "sxent_bwd")

@@ -10,6 +10,8 @@ and it runs on the target device so the timed loop never waits for a host sample
 """
 from __future__ import annotations
 
+import math
+
 import torch
 
 
@@ -43,6 +45,31 @@ def synthetic_batch(n_items: int, max_len: int, batch: int, *, seed: int = 1, in
     if packed:
         return user.to(device), torch.stack([seq, rsq, pos, prs, neg, nrs]).to(device=device, dtype=torch.int64)
     return tuple(t.to(device=device, dtype=torch.int64) for t in (user, seq, rsq, pos, prs, neg, nrs))
+
+
+def sample_negatives(n_items: int, num: int, counts=None, alpha: float = 1.0, generator=None, device="cuda"):
+    """Shared negatives for ``model.sampled_softmax_loss``: ``num`` item ids drawn with replacement from 1..n_items, uniformly
+    or with probability q_j proportional to ``counts[j] ** alpha`` (``counts`` indexed by item id, shape (n_items + 1,);
+    entry 0, the padding id, is ignored).  Returns ``(ids, log_q)``: ids int64 (num,) and ``log_q = log(num * q_ids)`` float32
+    (num,), the log-Q correction under which the sampled sum of exps estimates the full partition function.  Drawn with
+    torch on ``device`` (``generator``, if given, must live there)."""
+    if n_items < 1 or num < 1:
+        raise ValueError(f"n_items and num must be positive (got {n_items}, {num})")
+    if counts is None:
+        ids = torch.randint(1, n_items + 1, (num,), generator=generator, device=device)
+        log_q = torch.full((num,), math.log(num / n_items), device=device, dtype=torch.float32)
+        return ids, log_q
+    c = torch.as_tensor(counts, device=device, dtype=torch.float64)
+    if tuple(c.shape) != (n_items + 1,):
+        raise ValueError(f"counts must have shape ({n_items + 1},) (indexed by item id), got {tuple(c.shape)}")
+    w = c[1:].clamp_min(0) ** alpha
+    total = w.sum()
+    if not bool(total > 0):
+        raise ValueError("counts ** alpha has no positive weight")
+    q = w / total
+    ids = torch.multinomial(q, num, replacement=True, generator=generator) + 1
+    log_q = torch.log(num * q[ids - 1]).to(torch.float32)
+    return ids, log_q
 
 
 def eval_candidates(n_items: int, seq: torch.Tensor, target: torch.Tensor, n_neg: int = 100, *, seed: int = 7):
