@@ -498,6 +498,20 @@ int srfrd_sxent_bwd(const srfrd_layout* lay, const float* table, const float* hi
                     float* workspace, int64_t ws_floats, void* stream);
 
 /*
+ * Shared negatives of one sampled-softmax train step, drawn on the device (FusedTrainer(loss="sampled_softmax") captures it
+ * into the step graph).  Slot j < K: h1 = fmix32(base ^ j), h2 = fmix32(base ^ (j | 2^31)) with base = fmix32(state[2] +
+ * SITE_NEG * 0x9E3779B9) (srfrd_rng.h; state[2] is the step seed word srfrd_step_begin / srfrd_adam_pack_step advance), then
+ *   uniform (alias_prob == alias_idx == NULL): out_ids[j] = 1 + mulhi32(h1, n_items);
+ *   alias (Walker / Vose table over buckets 0..n_items-1, alias_prob fp32 and alias_idx int32 (n_items)): b = mulhi32(h1,
+ *     n_items), out_ids[j] = 1 + (u < alias_prob[b] ? b : alias_idx[b]) with u = (h2 >> 8) * 2^-24.
+ * out_log_q[j] = item_log_q[out_ids[j]] (item_log_q fp32 (n_items + 1), e.g. log(K q)), or log(K / n_items) when item_log_q is
+ * NULL (uniform only).  mulhi32(a, b) = (a * b) >> 32 in 64 bits.  K <= 0, n_items < 1, a NULL output, one of the two alias
+ * arrays without the other, or an alias table without item_log_q -> SRFRD_E_ARG.
+ */
+int srfrd_shared_negatives(const uint32_t* state, int n_items, int K, const float* alias_prob, const int32_t* alias_idx,
+                           const float* item_log_q, int64_t* out_ids, float* out_log_q, void* stream);
+
+/*
  * Device-side batch sampler with the layout and semantics of reference utils.py:21-57 (sample_function_fr /
  * WarpSampler_fr): per sampled user (uniform among users with > 1 interaction) the most recent `L` training items
  * left-padded with 0, pos[t] = the next item, neg[t] = a uniform item outside the user's history wherever pos[t] != 0,

@@ -89,6 +89,7 @@ SIGNATURES = {
     "srfrd_sxent_workspace_floats": (_i64, [_LP, _i, _i, _i]),
     "srfrd_sxent_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _P, _i64, _P]),
     "srfrd_sxent_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
+    "srfrd_shared_negatives": (_i, [_P, _i, _i, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

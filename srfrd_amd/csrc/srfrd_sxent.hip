@@ -526,7 +526,7 @@ extern "C" int srfrd_sxent_bwd(const srfrd_layout* lay, const float* table, cons
   const int64_t T = (int64_t)B * L;
   const hipStream_t st = (hipStream_t)stream;
   if (int rc = sxent_tokens(w, targets, T, workspace, nullptr, nullptr, st)) return rc;
-  if (hipError_t e = hipMemsetAsync(d_hidden, 0, (size_t)T * lay->d_out * sizeof(float), st)) return (int)e;
+  if (int rc = zero_floats(d_hidden, T * lay->d_out, st)) return rc;
   const SArgs a = sxent_args(lay, w, table, hidden, targets, negatives, log_q, K, remove_hits, T, workspace);
   hipLaunchKernelGGL(sxent_target_kernel, dim3((unsigned)((T + kTargetBlock - 1) / kTargetBlock)), dim3(kTargetBlock), 0, st, a,
                      lse, d_token_loss, workspace + w.tpos, table_contrib, contrib_keys);

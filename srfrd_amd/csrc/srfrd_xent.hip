@@ -437,7 +437,7 @@ extern "C" int srfrd_xent_bwd(const srfrd_layout* lay, const float* table, const
   const int64_t T = (int64_t)B * L;
   const hipStream_t st = (hipStream_t)stream;
   if (int rc = xent_tokens(w, targets, T, workspace, nullptr, nullptr, st)) return rc;
-  if (hipError_t e = hipMemsetAsync(d_hidden, 0, (size_t)T * lay->d_out * sizeof(float), st)) return (int)e;
+  if (int rc = zero_floats(d_hidden, T * lay->d_out, st)) return rc;
   const int tiles = (int)((T + kTok - 1) / kTok);
   const int n_chunks = (lay->n_items + 1 + kItems - 1) / kItems;
   const SplitArgs a{table, hidden, targets, (const int*)(workspace + w.idx), (const int*)(workspace + w.count), lay->d_item,

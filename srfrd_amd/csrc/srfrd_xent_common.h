@@ -116,6 +116,18 @@ __device__ __forceinline__ void merge(float& m, float& s, float m2, float s2) {
   s = a + b;
 }
 
+// d_hidden = 0 before the backward writes the token rows: a kernel, not hipMemsetAsync - inside a captured HIP graph the
+// memset node left some of these floats non-zero (the fused cross-entropy train step replays these launchers from a graph)
+__global__ void __launch_bounds__(256) zero_floats_kernel(float* __restrict__ p, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = 0.f;
+}
+inline int zero_floats(float* p, int64_t n, hipStream_t st) {
+  int64_t grid = (n + 255) / 256;
+  if (grid > 2048) grid = 2048;
+  if (grid > 0) hipLaunchKernelGGL(zero_floats_kernel, dim3((unsigned)grid), dim3(256), 0, st, p, n);
+  return (int)hipGetLastError();
+}
+
 __global__ void __launch_bounds__(256) xent_stats_kernel(const float* __restrict__ bsum, int nb, const int* __restrict__ count,
                                                          float* __restrict__ stats) {
   __shared__ float sw[4];

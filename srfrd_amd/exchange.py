@@ -46,12 +46,17 @@ def shard_size(n: int, world: int, align: int = 4) -> int:
     return (per + align - 1) // align * align
 
 
+def exchange_active(group=None) -> bool:
+    """True where the fused step takes the data-parallel paths: a process group of more than one rank, or a forced exchange."""
+    return dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or exchange_forced())
+
+
 class GradExchange:
     """Shard arithmetic + collectives for one flat vector of ``n`` floats (padded to ``n_pad = per * world``)."""
 
     def __init__(self, n: int, group=None):
         self.group = group
-        self.on = dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or exchange_forced())
+        self.on = exchange_active(group)
         self.world = dist.get_world_size(group) if self.on else 1
         self.rank = dist.get_rank(group) if self.on else 0
         self.n = int(n)

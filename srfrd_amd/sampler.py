@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 
@@ -70,6 +71,39 @@ def sample_negatives(n_items: int, num: int, counts=None, alpha: float = 1.0, ge
     ids = torch.multinomial(q, num, replacement=True, generator=generator) + 1
     log_q = torch.log(num * q[ids - 1]).to(torch.float32)
     return ids, log_q
+
+
+def negative_q(n_items: int, counts, alpha: float = 1.0):
+    """The sampling distribution of ``sample_negatives`` as fp64 numpy (n_items,): q[i] for item id i + 1, proportional to
+    ``counts[i + 1] ** alpha`` (entry 0, the padding id, ignored; negative counts taken as 0)."""
+    c = np.asarray(torch.as_tensor(counts).detach().cpu().to(torch.float64))
+    if c.shape != (n_items + 1,):
+        raise ValueError(f"counts must have shape ({n_items + 1},) (indexed by item id), got {tuple(c.shape)}")
+    w = np.maximum(c[1:], 0.0) ** float(alpha)
+    total = w.sum()
+    if not total > 0 or not np.isfinite(total):
+        raise ValueError("counts ** alpha has no positive (finite) weight")
+    return w / total
+
+
+def alias_table(q):
+    """Walker / Vose alias table of the distribution q (n,) (fp64, summing to 1): (alias_prob float32 (n,), alias_idx int32
+    (n,)).  Drawing bucket b uniformly, then keeping b with probability alias_prob[b] and otherwise taking alias_idx[b],
+    gives b' with probability q[b'].  Built in fp64; only the stored probabilities are rounded to fp32."""
+    q = np.asarray(q, dtype=np.float64)
+    n = q.size
+    p = q * n
+    prob = np.ones(n, dtype=np.float64)
+    alias = np.arange(n, dtype=np.int32)
+    small = [i for i in range(n) if p[i] < 1.0]
+    large = [i for i in range(n) if p[i] >= 1.0]
+    while small and large:
+        s, g = small.pop(), large.pop()
+        prob[s], alias[s] = p[s], g
+        p[g] = (p[g] + p[s]) - 1.0
+        (small if p[g] < 1.0 else large).append(g)
+    # what is left has p == 1 up to rounding: kept with probability 1 (prob and alias already say so)
+    return prob.astype(np.float32), alias
 
 
 def eval_candidates(n_items: int, seq: torch.Tensor, target: torch.Tensor, n_neg: int = 100, *, seed: int = 7):

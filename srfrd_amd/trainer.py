@@ -26,9 +26,14 @@ import os
 import torch
 import torch.distributed as dist
 
+import numpy as np
+
 from . import _lib
 from ._lib import check, ptr
-from .exchange import GradExchange, shard_bounds  # noqa: F401  (shard_bounds re-exported)
+from .exchange import GradExchange, exchange_active, shard_bounds  # noqa: F401  (shard_bounds re-exported)
+from .sampler import alias_table, negative_q
+
+LOSSES = ("bce", "sampled_softmax", "softmax")
 
 
 def flat_allreduce(flat: torch.Tensor, group=None):
@@ -38,12 +43,38 @@ def flat_allreduce(flat: torch.Tensor, group=None):
     return flat
 
 
+def _loss_config(model, loss, num_negatives, neg_counts, neg_alpha, process_group):
+    """The refusals of FusedTrainer's loss arguments, made before anything is allocated; -> q (fp64 numpy (n_items,)) of the
+    popularity sampler, or None"""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES} (got {loss!r})")
+    if loss != "sampled_softmax" and neg_counts is not None:
+        raise ValueError("neg_counts belongs to loss='sampled_softmax'")
+    if loss == "bce":
+        return None
+    q = None
+    if loss == "sampled_softmax":
+        if int(num_negatives) < 1:
+            raise ValueError(f"num_negatives must be at least 1 (got {num_negatives})")
+        if neg_counts is not None:
+            q = negative_q(model.layout.n_items, neg_counts, neg_alpha)
+    if model.layout.D > _lib.MAX_D:
+        raise ValueError(f"loss={loss!r}: the cross-entropy kernels cover hidden width <= {_lib.MAX_D} (got {model.layout.D})")
+    if model.bf16_table:
+        raise ValueError(f"loss={loss!r} reads the fp32 item table: call model.use_bf16_table(False) first")
+    if exchange_active(process_group):
+        raise ValueError(f"loss={loss!r} trains on a single rank: the data-parallel step supports loss='bce' only")
+    return q
+
+
 class FusedTrainer:
     """Owns optimizer state and step buffers for one model on one GPU (one rank of a DP job)."""
 
     def __init__(self, model, batch_size: int, seq_len: int | None = None, lr: float = 1e-3, betas=(0.9, 0.98),
                  eps: float = 1e-8, l2_emb: float = 0.0, seed: int = 42, process_group=None, use_graph: bool = True,
-                 slots: int = 1, exchange: str = "sharded", deterministic: bool = False, shadow_gather: bool = False):
+                 slots: int = 1, exchange: str = "sharded", deterministic: bool = False, shadow_gather: bool = False,
+                 loss: str = "bce", num_negatives: int = 1024, neg_counts=None, neg_alpha: float = 1.0,
+                 logq_correction: bool = True, remove_accidental_hits: bool = True):
         """``shadow_gather`` (sharded exchange over a bf16 item-table shadow, ``model.use_bf16_table()``; SURVEY 8e's alternative
         for BASELINE configs[4]): the fp32 master of an item row and its Adam moments live on the OWNER rank only; after the
         sharded Adam step the all-gather carries the bf16 SHADOW of the table (2 bytes per element: 90 MB instead of 180 MB at
@@ -52,7 +83,17 @@ class FusedTrainer:
         all-gather) before reading ``model.state_dict()`` / saving a checkpoint.
         ``deterministic``: the item-table gradient is scattered by a stable sort + per-item ordered sums instead of float
         atomics - every step bitwise reproducible (the dense gradients already are: fixed slab tree), at the cost of one
-        sort of 3 B L keys per step."""
+        sort of 3 B L keys per step.
+        ``loss``: "bce" (the reference's masked BCE on the positive / negative ids), or a softmax cross-entropy over the
+        positive ids, mean over the positions with a target: "sampled_softmax" against ``num_negatives``
+        shared negatives that every step draws on the device (``srfrd_shared_negatives``), uniformly or by
+        ``neg_counts ** neg_alpha`` (``neg_counts`` (n_items + 1,), indexed by item id), with the log-Q correction
+        (``logq_correction``) and accidental-hit removal (``remove_accidental_hits``) of ``model.sampled_softmax_loss``;
+        "softmax": the full catalog, as ``model.full_catalog_loss``.  The negative-id planes of a batch are not read under
+        a cross-entropy loss.  ``negatives`` / ``log_q`` show what the last step drew.  The cross-entropy steps run on one
+        rank with the fp32 item table; the sampled step's table gradient is always reduced in a fixed order (bitwise
+        reproducible, whatever ``deterministic`` says)."""
+        q = _loss_config(model, loss, num_negatives, neg_counts, neg_alpha, process_group)
         self.model = model
         model._ensure_flat()
         self.lay = model.layout
@@ -112,7 +153,10 @@ class FusedTrainer:
         self.state = torch.zeros(32, device=dev, dtype=torch.int32)
         self.state[1] = int(seed) & 0x7FFFFFFF
         self.deterministic = bool(deterministic)
-        self.contrib = torch.zeros(3, B, L, lay.d_item, **f32) if self.deterministic else None
+        self.loss_kind = loss
+        self.sampled = loss == "sampled_softmax"
+        # (the sampled step keeps the encoder's contribution rows in its own merged buffer, below)
+        self.contrib = torch.zeros(3, B, L, lay.d_item, **f32) if self.deterministic and not self.sampled else None
         self.keys = torch.zeros(3, B, L, device=dev, dtype=torch.int64) if self.deterministic else None
         self.n_slabs = _lib.lib().srfrd_bwd_grid(C.byref(lay), B, L)
         self.slabs = torch.empty(self.n_slabs, lay.n_dense, **f32)
@@ -137,7 +181,9 @@ class FusedTrainer:
         # Built where the kernel plan runs the ragged pair for this shape without switches (a test may set one later; the
         # other kernels ignore the schedule).  SRFRD_SCHED = 0 (off: workgroup x takes sequence x) | 1 (length order; default)
         fused = _lib.PLAN_POS | _lib.PLAN_NEG | _lib.PLAN_CKPT | _lib.PLAN_LOSS | _lib.PLAN_FUSED_BCE
-        ragged = _lib.encoder_plan(lay, B, L, fused)[0][0].startswith("srfrd::encoder_fwd_ragged_kernel<")
+        # (a cross-entropy step runs the encoder without targets: checkpoints only, and its own head after the forward)
+        plan_mode = fused if loss == "bce" else _lib.PLAN_CKPT
+        ragged = _lib.encoder_plan(lay, B, L, plan_mode)[0][0].startswith("srfrd::encoder_fwd_ragged_kernel<")
         self.sched_mode = min(1, int(os.environ.get("SRFRD_SCHED", "1"))) if ragged else 0
         self.sched = torch.zeros(int(_lib.lib().srfrd_sched_ints(B)), device=dev, dtype=torch.int32) if self.sched_mode else None
         self.pair_stride = max(1, _lib.lib().srfrd_bwd_grid(C.byref(lay), 1 << 30, L) // 2)      # CUs: workgroups of the first round
@@ -145,6 +191,8 @@ class FusedTrainer:
         # at every enqueue under the environment's switches then; False: always the two launches (A/B comparisons)
         self._train_mode = fused
         self.train_launch = True
+        if loss != "bce":
+            self._init_ce(q, num_negatives, logq_correction, remove_accidental_hits)
         self.packed = model.pack_weights()
         check(_lib.lib().srfrd_step_begin(ptr(self.state), self.lr, self.betas[0], self.betas[1],
                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "srfrd_step_begin")
@@ -155,6 +203,54 @@ class FusedTrainer:
         self.steps_done = 0
         self.err = torch.zeros(1, device=dev, dtype=torch.int32)   # srfrd_check_ids word of step() / step_packed() inputs
         self._fresh = False      # packed weights known to match the parameters (see refresh())
+
+    def _init_ce(self, q, num_negatives, logq_correction, remove_hits):
+        """buffers of the cross-entropy step"""
+        lay, B, L, dev = self.lay, self.B, self.L, self.flat.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        T = B * L
+        self.remove_hits = bool(remove_hits)
+        self.token_loss = torch.zeros(B, L, **f32)
+        self.lse = torch.zeros(B, L, **f32)
+        self.d_token = torch.ones(B, L, **f32)               # d loss / d token loss = 1: SUM, the Adam tail divides by the count
+        self.d_hidden = torch.zeros(B, L, lay.d_out, **f32)
+        if self.sampled:
+            K = self.K = int(num_negatives)
+            self.logq_correction = bool(logq_correction)
+            self._negatives = torch.zeros(K, device=dev, dtype=torch.int64)
+            self._log_q = torch.zeros(K, **f32)
+            if q is None:
+                self.alias_prob = self.alias_idx = self.item_log_q = None
+            else:
+                prob, idx = alias_table(q)
+                with np.errstate(divide="ignore"):                    # (an item of weight 0 is never drawn: its -inf is not read)
+                    lq = np.concatenate([[0.0], np.log(K * q)]).astype(np.float32)
+                self.alias_prob = torch.from_numpy(prob).to(dev)
+                self.alias_idx = torch.from_numpy(idx).to(dev)
+                self.item_log_q = torch.from_numpy(lq).to(dev)
+            n_ws = _lib.lib().srfrd_sxent_workspace_floats(C.byref(lay), B, L, K)
+            # one contribution buffer for the whole table gradient: rows [0, 3T) the encoder's (pos, neg, input planes; only
+            # the input plane carries anything here), rows [3T, 3T + K + T) the loss head's; keys of rows [2T, 4T + K)
+            self.contrib_ce = torch.zeros(4 * T + K, lay.d_item, **f32)
+            self.keys_ce = torch.zeros(2 * T + K, device=dev, dtype=torch.int64)
+        else:
+            n_ws = _lib.lib().srfrd_xent_workspace_floats(C.byref(lay), B, L)
+            if self.deterministic:
+                self.keys_in = torch.zeros(T, device=dev, dtype=torch.int64)
+                self.de_ce = torch.zeros(lay.n_items + 1, lay.d_item, **f32)
+        if n_ws <= 0:
+            raise ValueError(f"loss={self.loss_kind!r}: the cross-entropy kernels refuse this model / shape")
+        self.ce_ws = torch.zeros(n_ws, **f32)
+
+    @property
+    def negatives(self):
+        """(K,) int64: the shared negatives the last sampled-softmax step drew (None under another loss); read-only view"""
+        return self._negatives.detach().clone() if self.sampled else None
+
+    @property
+    def log_q(self):
+        """(K,) float32: log(K q) of those negatives, whether or not the loss subtracts it (None under another loss)"""
+        return self._log_q.detach().clone() if self.sampled else None
 
     # ---- pieces -------------------------------------------------------------------------------
     def _stream(self):
@@ -230,6 +326,70 @@ class FusedTrainer:
                                     ptr(self.loss_part) if fuse_stats else None, self.B, ptr(self.stats) if fuse_stats else None,
                                     ptr(self.loss) if self.mode == "single" else None, st), "srfrd_reduce_dense")
 
+    def _enqueue_ce_compute(self, slot: int = 0):
+        """the cross-entropy step's compute (single rank): [shared negatives] -> encoder forward (checkpoints,
+        hidden) -> loss head forward, {sum, count} into stats[1..2] -> loss head backward with d token loss = 1 -> encoder
+        backward from d_hidden -> table gradient -> dense slab reduction.  stats[0] stays 0, so the Adam tail's 1 / stats[2]
+        and srfrd_loss_finalize give the gradient of the mean and the mean."""
+        L_, lay, st = _lib.lib(), self.lay, self._stream()
+        B, L, T, di = self.B, self.L, self.B * self.L, lay.d_item
+        if self.l2 != 0.0:
+            check(L_.srfrd_l2_norms(ptr(self.flat), ptr(self.seg_off), ptr(self.seg_len), self.seg_off.numel(), self.n_tab,
+                                    self.l2, ptr(self.l2_partial), ptr(self.l2buf), ptr(self.l2_dense), st), "srfrd_l2_norms")
+        ids, fk, pfk, nfk, p, seed_dev, seq0 = self._ids_of(slot)
+        lay_t, tab = self.model._table_args()
+        if self.sched_mode:
+            check(L_.srfrd_seq_order(ptr(ids[0]), B, L, self.pair_stride, ptr(self.sched), st), "srfrd_seq_order")
+        if self.sampled:
+            check(L_.srfrd_shared_negatives(ptr(self.state), lay.n_items, self.K, ptr(self.alias_prob), ptr(self.alias_idx),
+                                            ptr(self.item_log_q), ptr(self._negatives), ptr(self._log_q), st),
+                  "srfrd_shared_negatives")
+        check(L_.srfrd_encoder_fwd_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk),
+                                         None, None, None, None, B, L, p, 0, seed_dev, seq0, ptr(self.hidden), None, None,
+                                         ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), None, ptr(self.scratch),
+                                         self.n_scratch, ptr(self.sched), self.sched_mode, st), "srfrd_encoder_fwd_sched")
+        table, tgt = ptr(self.flat), ptr(ids[2])                     # (the fp32 item table is the flat vector's head)
+        stats_sc = C.c_void_p(self.stats.data_ptr() + 4)             # {sum, count} -> stats[1], stats[2]
+        ws, n_ws = ptr(self.ce_ws), self.ce_ws.numel()
+        if self.sampled:
+            neg, K, rh = ptr(self._negatives), self.K, int(self.remove_hits)
+            lq = ptr(self._log_q) if self.logq_correction else None
+            check(L_.srfrd_sxent_fwd(C.byref(lay), table, ptr(self.hidden), tgt, neg, lq, K, rh, B, L, ptr(self.token_loss),
+                                     ptr(self.lse), stats_sc, ws, n_ws, st), "srfrd_sxent_fwd")
+            check(L_.srfrd_sxent_bwd(C.byref(lay), table, ptr(self.hidden), tgt, neg, lq, K, rh, ptr(self.lse), ptr(self.d_token),
+                                     B, L, ptr(self.d_hidden), C.c_void_p(self.contrib_ce.data_ptr() + 4 * 3 * T * di),
+                                     C.c_void_p(self.keys_ce.data_ptr() + 8 * T), ws, n_ws, st), "srfrd_sxent_bwd")
+            table_grad, contrib = ptr(self.grad), ptr(self.contrib_ce)
+        else:
+            det = self.contrib is not None
+            # xent_bwd writes a dense table gradient; the deterministic encoder table reduction below STORES its rows, so
+            # there the head's part waits in de_ce and is added afterwards
+            check(L_.srfrd_xent_fwd(C.byref(lay), table, ptr(self.hidden), tgt, B, L, ptr(self.token_loss), ptr(self.lse),
+                                    stats_sc, ws, n_ws, st), "srfrd_xent_fwd")
+            check(L_.srfrd_xent_bwd(C.byref(lay), table, ptr(self.hidden), tgt, ptr(self.lse), ptr(self.d_token), B, L,
+                                    ptr(self.d_hidden), ptr(self.de_ce) if det else ptr(self.grad), 0 if det else 1, ws, n_ws, st),
+                  "srfrd_xent_bwd")
+            table_grad, contrib = ptr(self.grad), ptr(self.contrib)
+        check(L_.srfrd_encoder_bwd_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk),
+                                         None, None, None, None, B, L, p, 0, seed_dev, seq0, ptr(self.hidden), None, None,
+                                         ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), ptr(self.d_hidden), None, None, 0,
+                                         table_grad, contrib, ptr(self.slabs), ptr(self.scratch), self.n_scratch, ptr(self.sched),
+                                         self.sched_mode, st), "srfrd_encoder_bwd_sched")
+        if self.sampled:
+            # one stable sort of [input ids (T) | the head's keys (K + T)]; the rows they key are contrib_ce[2T:]
+            torch.clamp(ids[0].reshape(-1), 0, lay.n_items, out=self.keys_ce[:T])
+            skeys, order = torch.sort(self.keys_ce, stable=True)
+            check(L_.srfrd_table_reduce(ptr(skeys), ptr(order), C.c_void_p(self.contrib_ce.data_ptr() + 4 * 2 * T * di),
+                                        skeys.numel(), di, ptr(self.grad), st), "srfrd_table_reduce")
+        elif self.contrib is not None:
+            torch.clamp(ids[0].reshape(-1), 0, lay.n_items, out=self.keys_in)
+            skeys, order = torch.sort(self.keys_in, stable=True)
+            check(L_.srfrd_table_reduce(ptr(skeys), ptr(order), C.c_void_p(self.contrib.data_ptr() + 4 * 2 * T * di),
+                                        skeys.numel(), di, ptr(self.grad), st), "srfrd_table_reduce")
+            self.grad[:lay.n_table].add_(self.de_ce.view(-1))
+        check(L_.srfrd_reduce_dense(ptr(self.slabs), self.n_slabs, lay.n_dense, self._dense_ptr(self.grad), None, B, None, None, st),
+              "srfrd_reduce_dense")
+
     def _enqueue_compute(self, slot: int = 0):
         """forward and backward as their two launches (the data-parallel step, per-launch timing)"""
         self._enqueue_fwd(slot)
@@ -238,7 +398,9 @@ class FusedTrainer:
     def _enqueue_step_compute(self, slot: int = 0):
         """the single-rank step's compute: forward and backward as ONE launch where the kernel plan offers a train kernel (each
         workgroup runs its sequence's backward right after its forward; the same bits as the two launches), else the two"""
-        if self.mode == "single" and self.train_launch and _lib.encoder_plan_train(
+        if self.loss_kind != "bce":
+            self._enqueue_ce_compute(slot)
+        elif self.mode == "single" and self.train_launch and _lib.encoder_plan_train(
                 self.lay, self.B, self.L, self._train_mode, _lib.env_switches())[0]:
             self._enqueue_fwd(slot, train=True)
         else:
@@ -253,7 +415,7 @@ class FusedTrainer:
                                       self.n_flat, self.n_tab, self.n_tab, self.lr, self.betas[0], self.betas[1], self.eps,
                                       ptr(self.state), ptr(self.stats), ptr(self.packed), ptr(self.model._table16), st),
               "srfrd_adam_pack_step")
-        if self.mode != "single":
+        if self.mode != "single" or self.loss_kind != "bce":      # (single-rank BCE: the slab reduction wrote the loss)
             check(L_.srfrd_loss_finalize(ptr(self.stats), ptr(self.loss), st), "srfrd_loss_finalize")
         if self.l2 != 0.0:
             self.loss.add_(self.l2buf[1:2])
@@ -473,8 +635,17 @@ class FusedTrainer:
         group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
                  "params": list(range(len(params)))}
-        return {"state": state, "param_groups": [group],
-                "srfrd": {"seed": int(self.state[1].item()), "steps_done": int(self.steps_done)}}
+        extra = {"seed": int(self.state[1].item()), "steps_done": int(self.steps_done)}
+        if self.loss_kind != "bce":
+            extra["loss"] = self._loss_signature()
+        return {"state": state, "param_groups": [group], "srfrd": extra}
+
+    def _loss_signature(self):
+        """the loss configuration a resumed run must share (state_dict()["srfrd"]["loss"]; absent: "bce")"""
+        if not self.sampled:
+            return {"kind": self.loss_kind}
+        return {"kind": self.loss_kind, "num_negatives": self.K, "popularity": self.alias_prob is not None,
+                "logq_correction": self.logq_correction, "remove_accidental_hits": self.remove_hits}
 
     def load_state_dict(self, sd):
         """Inverse of state_dict(); also takes the state_dict of a torch.optim.Adam that stepped the same model's
@@ -489,6 +660,11 @@ class FusedTrainer:
         steps = {int(float(st["step"])) for st in sd["state"].values()}
         if len(steps) > 1:
             raise ValueError("parameters with different step counts")
+        if "srfrd" in sd:          # (a torch.optim.Adam state carries no loss: it may continue under any)
+            saved = (sd["srfrd"] or {}).get("loss", {"kind": "bce"})
+            mine = self._loss_signature() if self.loss_kind != "bce" else {"kind": "bce"}
+            if saved != mine:
+                raise ValueError(f"optimizer state was saved under loss {saved}; this trainer trains {mine}")
         self.lr, self.betas, self.eps = float(group["lr"]), (float(group["betas"][0]), float(group["betas"][1])), float(group["eps"])
         dev = self.flat.device
         m = torch.zeros(self.ex.n_pad if self.mode == "sharded" else self.n_flat, device=dev, dtype=torch.float32)
@@ -541,8 +717,12 @@ class FusedTrainer:
         return self._run()
 
     def step(self, user_ids, input_ids, fake_ids, positive_ids, positive_fake_ids, negative_ids, negative_fake_ids):
-        """Same argument order as the reference model call at trainer.py:30 (``user_ids`` is unused there too)."""
+        """Same argument order as the reference model call at trainer.py:30 (``user_ids`` is unused there too).  Under a
+        cross-entropy loss ``negative_ids`` / ``negative_fake_ids`` are not read and may be None."""
         for k, t in enumerate((input_ids, fake_ids, positive_ids, positive_fake_ids, negative_ids, negative_fake_ids)):
+            if t is None and k >= 4 and self.loss_kind != "bce":
+                self.ids[k].zero_()
+                continue
             self.ids[k].copy_(t, non_blocking=True)
         self._check_slot(0)
         return self._run()
