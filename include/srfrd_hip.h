@@ -498,6 +498,60 @@ int srfrd_sxent_bwd(const srfrd_layout* lay, const float* table, const float* hi
                     float* workspace, int64_t ws_floats, void* stream);
 
 /*
+ * Losses with K negatives PER POSITION (the form the reference samples in, utils.py:27-46, with more than one of them):
+ * sampled softmax with per-position negatives, and BCE with K negatives generalised to gBCE (gSASRec, Petrov & Macdonald,
+ * RecSys 2023).  Tokens are the positions t of the (B, L) `targets` with targets[t] != 0.  `negatives` (B, L, K) int64: id 0
+ * marks an unused slot, duplicates count once each, ids are clamped into [0, n_items].  s_t+ = <hidden[t, :d_item], E[y_t]>,
+ * s_tk = <hidden[t, :d_item], E[n_tk]>; slot k takes part when n_tk != 0 and, with remove_hits, n_tk != y_t.
+ *   SRFRD_TNEG_SOFTMAX  loss_t = logsumexp({s_t+} u {s_tk - log_q[t, k]}) - s_t+; log_q (B, L, K) fp32 or NULL.  A token
+ *                       without a participating slot has loss 0 and a zero gradient, exactly.  SRFRN's fake slice is not
+ *                       read (one constant per row: the softmax does not see it).
+ *   SRFRD_TNEG_GBCE     loss_t = beta softplus(-s_t+) + sum_k softplus(s_tk), beta >= 0 finite (1: plain BCE with K
+ *                       negatives; K = 1 too: the reference's loss, trainer.py:36-38, before its division by the count).
+ *                       log_q must be NULL.  lay->kind == SRFRD_SRFRN -> SRFRD_E_UNSUPPORTED: its logits include the fake
+ *                       slice, and BCE, unlike the softmax, is not invariant to that per-row term.
+ * No row is shared between tokens: the logits are gathered rows against one hidden row on the vector ALU, a wave per
+ * position, never written to memory; the backward recomputes them.  No float atomics: two identical calls give bitwise-
+ * identical results.  lay->table_bf16 or lay->D > SRFRD_MAX_D -> SRFRD_E_UNSUPPORTED; a null pointer, K <= 0, B L (1 + K)
+ * >= 2^31, an unknown objective, log_q with gbce, a negative or non-finite beta -> SRFRD_E_ARG.
+ *
+ * srfrd_tneg_workspace_floats [host]: floats of `workspace` the three calls need for (B, L, K) (0 for arguments they refuse).
+ * srfrd_tneg_fwd: token_loss (B, L) (0 where targets == 0), lse (B, L) (softmax: the log of the sampled partition function,
+ *   target term included; gbce and ignored positions: 0), stats[0..1] = {sum of the token losses, token count} (fp32, on the
+ *   device: the contract of srfrd_sxent_fwd).
+ * srfrd_tneg_bwd: with the forward's lse and the upstream gradient of every token loss d_token_loss (B, L): d_hidden
+ *   (B, L, d_out) = g_t+ E[y_t] + sum_k g_tk E[n_tk] in columns < d_item, zeros elsewhere and at ignored positions (fully
+ *   overwritten, by the kernel itself); softmax: g_t+ = d_t (softmax_t+ - 1), g_tk = d_t softmax_tk; gbce: g_t+ = -d_t beta
+ *   sigmoid(-s_t+), g_tk = d_t sigmoid(s_tk).  The table gradient is left as a list of RANK-1 rows, never written out: row
+ *   r = t (1 + K) + j is contrib_coef[r] * hidden[t, :d_item] with key contrib_keys[r]; j = 0 is the target (key y_t), j =
+ *   1..K the negatives (key n_tk); slots that take no part and ignored positions have key 0 and coefficient 0.  contrib_coef
+ *   (B, L, 1 + K) fp32 and contrib_keys (B, L, 1 + K) int64 are fully overwritten.
+ * srfrd_table_reduce_rank1: the second half, as srfrd_table_reduce is for contribution rows: `sorted_keys` (n) the keys
+ *   sorted ascending by a STABLE sort, order[i] the list row sorted position i came from; sums, per run of equal keys and in
+ *   sorted order, contrib_coef[order[i]] * hidden[order[i] / rows_per_token, :d_item] into grad_table[key] (caller-zeroed
+ *   (n_items + 1, d_item); rows without contributions are not touched; keys <= 0 are skipped, the segments that lie inside
+ *   that run without being walked).  The sorted list is cut into segments of SRFRD_TNEG_SPLIT_ROWS rows summed by a wave
+ *   each, so a popular item's long run costs no more than its share; a run that crosses segments has its per-segment
+ *   partials added in segment order by a second launch.  The cut depends on the keys alone: bitwise reproducible.
+ *   `workspace`: 2 ceil(n / SRFRD_TNEG_SPLIT_ROWS) d_item floats rounded up to 64 (srfrd_tneg_workspace_floats covers it
+ *   for n = B L (1 + K)); n must be below 2^31.
+ */
+#define SRFRD_TNEG_SOFTMAX 0
+#define SRFRD_TNEG_GBCE 1
+#define SRFRD_TNEG_SPLIT_ROWS 256
+int64_t srfrd_tneg_workspace_floats(const srfrd_layout* lay, int B, int L, int K);
+int srfrd_tneg_fwd(const srfrd_layout* lay, const float* table, const float* hidden, const int64_t* targets,
+                   const int64_t* negatives, const float* log_q, int K, int objective, double beta, int remove_hits, int B,
+                   int L, float* token_loss, float* lse, float* stats, float* workspace, int64_t ws_floats, void* stream);
+int srfrd_tneg_bwd(const srfrd_layout* lay, const float* table, const float* hidden, const int64_t* targets,
+                   const int64_t* negatives, const float* log_q, int K, int objective, double beta, int remove_hits,
+                   const float* lse, const float* d_token_loss, int B, int L, float* d_hidden, float* contrib_coef,
+                   int64_t* contrib_keys, float* workspace, int64_t ws_floats, void* stream);
+int srfrd_table_reduce_rank1(const int64_t* sorted_keys, const int64_t* order, const float* contrib_coef,
+                             const float* hidden, int d_out, int rows_per_token, int64_t n, int d_item, float* grad_table,
+                             float* workspace, int64_t ws_floats, void* stream);
+
+/*
  * Shared negatives of one sampled-softmax train step, drawn on the device (FusedTrainer(loss="sampled_softmax") captures it
  * into the step graph).  Slot j < K: h1 = fmix32(base ^ j), h2 = fmix32(base ^ (j | 2^31)) with base = fmix32(state[2] +
  * SITE_NEG * 0x9E3779B9) (srfrd_rng.h; state[2] is the step seed word srfrd_step_begin / srfrd_adam_pack_step advance), then

@@ -90,6 +90,10 @@ SIGNATURES = {
     "srfrd_sxent_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _P, _i64, _P]),
     "srfrd_sxent_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
     "srfrd_shared_negatives": (_i, [_P, _i, _i, _P, _P, _P, _P, _P, _P]),
+    "srfrd_tneg_workspace_floats": (_i64, [_LP, _i, _i, _i]),
+    "srfrd_tneg_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _d, _i, _i, _i, _P, _P, _P, _P, _i64, _P]),
+    "srfrd_tneg_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _d, _i, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
+    "srfrd_table_reduce_rank1": (_i, [_P, _P, _P, _P, _i, _i, _i64, _i, _P, _P, _i64, _P]),
 }
 
 _lib = None
@@ -173,6 +177,10 @@ def env_switches() -> int:
     """the SRFRD_SW_* bits the launchers read from the environment right now (a switch counts when its variable is set)"""
     return sum(bit for name, bit in SWITCHES.items() if name in os.environ)
 
+
+# objectives of srfrd_tneg_fwd / _bwd (SRFRD_TNEG_*) and the segment length of srfrd_table_reduce_rank1 (SRFRD_TNEG_SPLIT_ROWS)
+TNEG_OBJECTIVES = {"softmax": 0, "gbce": 1}
+TNEG_SPLIT_ROWS = 256
 
 # srfrd_rank_plan ops (SRFRD_RANK_*) and the ranking's switch bit (SRFRD_SW_TOPK_FP32: the environment variable SRFRD_TOPK_FP32)
 RANK_TOPK, RANK_TARGET, RANK_TARGET_METRIC = 0, 1, 2

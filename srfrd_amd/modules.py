@@ -181,6 +181,32 @@ class _SxentFn(torch.autograd.Function):
         return None, None, None, dh, None, None, None, de
 
 
+class _TnegFn(torch.autograd.Function):
+    """token_negatives_loss() under autograd: the launches of the registered ``srfrd::tneg_fwd`` / ``srfrd::tneg_bwd`` ops
+    without torch.library's Python glue, as _SxentFn.  The reduction is applied on the device from the forward's
+    {sum, count}: no host synchronisation in either direction.  log_q is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, model, reduction, objective, beta, remove_hits, hidden, targets, negatives, log_q, table):
+        lay, tab = model.layout, ptr(table)
+        tl, lse, stats = ops.tneg_launch_fwd(lay, tab, hidden, targets, negatives, log_q, objective, beta, remove_hits)
+        ctx.model, ctx.reduction, ctx.meta = model, reduction, (objective, beta, remove_hits)
+        ctx.save_for_backward(hidden, targets, negatives, log_q, table, lse, stats)
+        if reduction == "none":
+            return tl
+        return stats[0].clone() if reduction == "sum" else stats[0] / stats[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        hidden, targets, negatives, log_q, table, lse, stats = ctx.saved_tensors
+        if ctx.reduction == "none":
+            d_tok = g.contiguous()
+        else:
+            d_tok = (g if ctx.reduction == "sum" else g / stats[1]).expand(targets.shape).contiguous()
+        dh, de = ops.tneg_launch_bwd(ctx.model.layout, ptr(table), hidden, targets, negatives, log_q, *ctx.meta, lse, d_tok)
+        return None, None, None, None, None, dh, None, None, None, de
+
+
 class _SRFRDBase(nn.Module):
     """Shared machinery: flat parameter storage, kernel launches, predict."""
 
@@ -595,6 +621,75 @@ class _SRFRDBase(nn.Module):
                 self.check_ids()
         table = self._slots[0][0]
         return _SxentFn.apply(self, reduction, bool(remove_accidental_hits), hidden_state.contiguous(), y, neg, log_q, table)
+
+    def token_negatives_loss(self, hidden_state, positive_ids, negative_ids, objective="softmax", log_q=None, beta=1.0,
+                             remove_accidental_hits=True, reduction="mean"):
+        """A loss with K negatives PER POSITION (``srfrd_tneg_fwd`` / ``_bwd``): ``negative_ids`` is (B, L, K), the form the
+        reference's sampler draws in with K = 1 (``srfrd_amd.sample_token_negatives`` draws K).  Every position with
+        ``positive_ids != 0`` is scored against its target, ``s_t+ = <h_t[:d_item], E[y_t]>``, and its own K items, ``s_tk =
+        <h_t[:d_item], E[n_tk]>``; id 0 marks an unused slot, duplicates count once each, and ``remove_accidental_hits``
+        drops the slots equal to the position's target.
+
+        objective="softmax": ``loss_t = logsumexp({s_t+} u {s_tk - log_q[t, k]}) - s_t+``; ``log_q`` (B, L, K) float32 or
+        None, not differentiable.  A position none of whose slots takes part has loss 0 and a zero gradient.  SRFRN's fake
+        slice gets a zero gradient, as in full_catalog_loss.
+
+        objective="gbce": ``loss_t = beta * softplus(-s_t+) + sum_k softplus(s_tk)``, gSASRec's generalised BCE (Petrov &
+        Macdonald, RecSys 2023; ``srfrd_amd.gbce_beta`` gives beta from the sampling rate and the calibration t); beta = 1
+        is plain BCE with K negatives, and with K = 1, ``remove_accidental_hits=False`` and reduction="mean" it is the
+        reference's loss.  ``log_q`` must be None.  SRFRN is refused (ValueError): its logits include the fake slice, and
+        BCE, unlike the softmax, is not invariant to that per-row term; that form is not built.
+
+        The (tokens x (1 + K)) logits are never materialised.  reduction: "mean" (over the targets; NaN when there are
+        none), "sum" or "none" ((B, L), zeros at ignored positions).  Autograd carries the loss into ``hidden_state`` and
+        into the item table, whose gradient is reduced per item in a fixed order (bitwise reproducible)."""
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
+        if objective not in _lib.TNEG_OBJECTIVES:
+            raise ValueError(f"objective must be 'softmax' or 'gbce' (got {objective!r})")
+        beta = float(beta)
+        if not (beta >= 0.0) or beta == float("inf"):
+            raise ValueError(f"beta must be finite and >= 0 (got {beta})")
+        if objective == "gbce":
+            if log_q is not None:
+                raise ValueError("log_q belongs to the softmax objective: pass None with objective='gbce'")
+            if self._kind == "SRFRN":
+                raise ValueError("objective='gbce' is not built for SRFRN: its logits include the fake slice, which BCE "
+                                 "(unlike the softmax) is not invariant to")
+        self._ensure_flat()
+        if self.bf16_table:
+            raise RuntimeError("token_negatives_loss needs the fp32 item table (use_bf16_table(False)); the bf16 form is not built")
+        lay = self.layout
+        dev = self._flat.device
+        if hidden_state.dim() != 3 or hidden_state.shape[2] != lay.d_out or hidden_state.device != dev:
+            raise ValueError(f"hidden_state must be the model's (B, L, {lay.d_out}) output on {dev}")
+        if hidden_state.dtype != torch.float32:
+            raise ValueError("hidden_state must be float32")
+        y = _ids(positive_ids, dev, hidden_state.shape[:2])
+        neg = torch.as_tensor(negative_ids)
+        B, L = hidden_state.shape[:2]
+        if (neg.dim() != 3 or tuple(neg.shape[:2]) != (B, L) or neg.shape[2] == 0 or neg.is_floating_point() or neg.is_complex()
+                or neg.dtype == torch.bool):
+            raise ValueError(f"negative_ids must be a ({B}, {L}, K) integer tensor with K >= 1 (got shape {tuple(neg.shape)}, "
+                             f"{neg.dtype})")
+        neg = _ids(neg, dev)
+        K = neg.shape[2]
+        if B * L * (1 + K) >= 2 ** 31:
+            raise ValueError(f"B * L * (1 + K) = {B * L * (1 + K)} must stay below 2^31")
+        if log_q is not None:
+            if not isinstance(log_q, torch.Tensor) or log_q.dtype != torch.float32 or tuple(log_q.shape) != (B, L, K):
+                raise ValueError(f"log_q must be a float32 tensor of shape ({B}, {L}, {K}) or None")
+            log_q = log_q.detach().to(dev).contiguous()
+        if self.validate_ids:
+            check(_lib.lib().srfrd_check_ids(ptr(y), None, None, None, None, None, y.numel(), lay.n_items, 2,
+                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
+            check(_lib.lib().srfrd_check_ids(ptr(neg), None, None, None, None, None, neg.numel(), lay.n_items, 2,
+                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
+            if self.validate_ids == "eager":
+                self.check_ids()
+        table = self._slots[0][0]
+        return _TnegFn.apply(self, reduction, _lib.TNEG_OBJECTIVES[objective], beta, bool(remove_accidental_hits),
+                             hidden_state.contiguous(), y, neg, log_q, table)
 
     def user_labels(self, fake_ids):
         """get_Labels (SRFU_*) / the predict-time label (SRFRN) as an int64 (B,) tensor, computed on device."""

@@ -18,6 +18,8 @@ backward - instead of being an opaque ctypes call from Python:
     srfrd::xent_bwd        its gradients into the hidden state and the item table
     srfrd::sxent_fwd       sampled softmax cross-entropy with shared negatives per token; backward = srfrd::sxent_bwd
     srfrd::sxent_bwd       its gradients into the hidden state and the item table (deterministic table reduction)
+    srfrd::tneg_fwd        sampled softmax / gBCE with K negatives per position, per token; backward = srfrd::tneg_bwd
+    srfrd::tneg_bwd        its gradients into the hidden state and the item table (rank-1 contribution list, deterministic)
 
 A model's geometry (the srfrd_layout descriptor, its flat parameter vector and packed weights) is not expressible as op
 arguments one by one; the ops take ``model_key``, the registry key of a live model (``register_model``), and read
@@ -482,6 +484,99 @@ def _sxent_backward(ctx, grads):
 
 sxent_fwd.register_autograd(_sxent_backward, setup_context=_sxent_setup)
 
+# ------------------------------------------------------------------------------------------------ K negatives per position
+def tneg_launch_fwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor,
+                    log_q: Optional[torch.Tensor], objective: int, beta: float, remove_hits: bool):
+    """srfrd_tneg_fwd -> (token_loss (B, L), lse (B, L), stats {sum, count}); negatives (B, L, K)"""
+    B, L = targets.shape
+    K = negatives.shape[2]
+    dev = hidden.device
+    L_ = _lib.lib()
+    ws = torch.empty(max(L_.srfrd_tneg_workspace_floats(C.byref(lay), B, L, K), 1), device=dev, dtype=torch.float32)
+    tl = torch.empty(B, L, device=dev, dtype=torch.float32)
+    lse = torch.empty(B, L, device=dev, dtype=torch.float32)
+    stats = torch.empty(2, device=dev, dtype=torch.float32)
+    check(L_.srfrd_tneg_fwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(negatives), ptr(log_q), K, objective, beta,
+                            int(remove_hits), B, L, ptr(tl), ptr(lse), ptr(stats), ptr(ws), ws.numel(), _stream()),
+          "srfrd_tneg_fwd")
+    return tl, lse, stats
+
+
+def tneg_launch_bwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor,
+                    log_q: Optional[torch.Tensor], objective: int, beta: float, remove_hits: bool, lse: torch.Tensor,
+                    d_token_loss: torch.Tensor):
+    """srfrd_tneg_bwd, then the stable key sort and srfrd_table_reduce_rank1 -> (d_hidden (B, L, d_out), d_table (n_items + 1,
+    d_item)): every item's rank-1 rows coef * hidden[t] summed in list order (position-major, the target before its
+    negatives)"""
+    B, L = targets.shape
+    K = negatives.shape[2]
+    dev = hidden.device
+    L_ = _lib.lib()
+    ws = torch.empty(max(L_.srfrd_tneg_workspace_floats(C.byref(lay), B, L, K), 1), device=dev, dtype=torch.float32)
+    dh = torch.empty(B, L, lay.d_out, device=dev, dtype=torch.float32)
+    coef = torch.empty(B * L * (1 + K), device=dev, dtype=torch.float32)
+    keys = torch.empty(B * L * (1 + K), device=dev, dtype=torch.int64)
+    check(L_.srfrd_tneg_bwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(negatives), ptr(log_q), K, objective, beta,
+                            int(remove_hits), ptr(lse), ptr(d_token_loss), B, L, ptr(dh), ptr(coef), ptr(keys), ptr(ws),
+                            ws.numel(), _stream()), "srfrd_tneg_bwd")
+    skeys, order = torch.sort(keys, stable=True)
+    de = torch.zeros(lay.n_items + 1, lay.d_item, device=dev, dtype=torch.float32)
+    check(L_.srfrd_table_reduce_rank1(ptr(skeys), ptr(order), ptr(coef), ptr(hidden), lay.d_out, 1 + K, skeys.numel(),
+                                      lay.d_item, ptr(de), ptr(ws), ws.numel(), _stream()), "srfrd_table_reduce_rank1")
+    return dh, de
+
+
+@torch.library.custom_op("srfrd::tneg_fwd", mutates_args=(), device_types="cuda")
+def tneg_fwd(hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor, log_q: Optional[torch.Tensor],
+             table: torch.Tensor, objective: int, beta: float, remove_hits: bool, model_key: int) -> List[torch.Tensor]:
+    """-> [token_loss (B, L), lse (B, L), stats (2) = {sum, count}]; objective: _lib.TNEG_OBJECTIVES"""
+    lay, tab = _xent_table(_model(model_key), table)
+    return list(tneg_launch_fwd(lay, tab, hidden.contiguous(), targets.contiguous(), negatives.contiguous(),
+                                None if log_q is None else log_q.contiguous(), objective, beta, remove_hits))
+
+
+@tneg_fwd.register_fake
+def _(hidden, targets, negatives, log_q, table, objective, beta, remove_hits, model_key):
+    B, L = targets.shape
+    f = dict(device=hidden.device, dtype=torch.float32)
+    return [torch.empty(B, L, **f), torch.empty(B, L, **f), torch.empty(2, **f)]
+
+
+@torch.library.custom_op("srfrd::tneg_bwd", mutates_args=(), device_types="cuda")
+def tneg_bwd(hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor, log_q: Optional[torch.Tensor],
+             table: torch.Tensor, objective: int, beta: float, remove_hits: bool, lse: torch.Tensor, d_token_loss: torch.Tensor,
+             model_key: int) -> List[torch.Tensor]:
+    """-> [d_hidden (B, L, d_out), d_table (n_items + 1, d_item)]"""
+    lay, tab = _xent_table(_model(model_key), table)
+    return list(tneg_launch_bwd(lay, tab, hidden.contiguous(), targets.contiguous(), negatives.contiguous(),
+                                None if log_q is None else log_q.contiguous(), objective, beta, remove_hits, lse.contiguous(),
+                                d_token_loss.contiguous()))
+
+
+@tneg_bwd.register_fake
+def _(hidden, targets, negatives, log_q, table, objective, beta, remove_hits, lse, d_token_loss, model_key):
+    return [torch.empty_like(hidden), torch.empty_like(table)]
+
+
+def _tneg_setup(ctx, inputs, output):
+    hidden, targets, negatives, log_q, table, objective, beta, remove_hits, model_key = inputs
+    ctx.meta = (objective, beta, remove_hits, model_key)
+    ctx.save_for_backward(hidden, targets, negatives, log_q, table, output[1])
+
+
+def _tneg_backward(ctx, grads):
+    hidden, targets, negatives, log_q, table, lse = ctx.saved_tensors
+    g = grads[0]
+    if g is None:
+        return (None,) * 9
+    objective, beta, remove_hits, model_key = ctx.meta
+    dh, de = torch.ops.srfrd.tneg_bwd(hidden, targets, negatives, log_q, table, objective, beta, remove_hits, lse, g.contiguous(),
+                                      model_key)
+    return dh, None, None, None, de, None, None, None, None
+
+
+tneg_fwd.register_autograd(_tneg_backward, setup_context=_tneg_setup)
+
 
 OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "target_rank", "topk_merge",
-       "eval_rank", "xent_fwd", "xent_bwd", "sxent_fwd", "sxent_bwd")
+       "eval_rank", "xent_fwd", "xent_bwd", "sxent_fwd", "sxent_bwd", "tneg_fwd", "tneg_bwd")

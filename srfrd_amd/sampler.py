@@ -73,6 +73,43 @@ def sample_negatives(n_items: int, num: int, counts=None, alpha: float = 1.0, ge
     return ids, log_q
 
 
+def sample_token_negatives(n_items: int, positive_ids, num: int, counts=None, alpha: float = 1.0, generator=None):
+    """Per-position negatives for ``model.token_negatives_loss``: for every position of ``positive_ids`` (B, L) with a target,
+    ``num`` item ids drawn with replacement from 1..n_items, uniformly or with probability q_j proportional to
+    ``counts[j] ** alpha`` (``counts`` as in ``sample_negatives``); id 0 in every slot of a position without a target.
+    Returns ``(negative_ids (B, L, num) int64, log_q (B, L, num) float32)`` with ``log_q = log(num * q_ids)`` (0 in the
+    id-0 slots).  Drawn with torch on the device of ``positive_ids`` (``generator``, if given, must live there).  The draws
+    do not avoid the user's history: accidental hits on the position's own target are dropped by the loss."""
+    pos = torch.as_tensor(positive_ids)
+    if pos.dim() != 2:
+        raise ValueError(f"positive_ids must be (batch, seq_len) (got shape {tuple(pos.shape)})")
+    if n_items < 1 or num < 1:
+        raise ValueError(f"n_items and num must be positive (got {n_items}, {num})")
+    dev = pos.device
+    B, L = pos.shape
+    if counts is None:
+        ids = torch.randint(1, n_items + 1, (B, L, num), generator=generator, device=dev)
+        log_q = torch.full((B, L, num), math.log(num / n_items), device=dev, dtype=torch.float32)
+    else:
+        q = torch.as_tensor(negative_q(n_items, counts, alpha), device=dev)
+        ids = torch.multinomial(q, B * L * num, replacement=True, generator=generator).view(B, L, num) + 1
+        log_q = torch.log(num * q[ids - 1]).to(torch.float32)
+    live = (pos != 0).unsqueeze(-1)
+    return torch.where(live, ids, torch.zeros_like(ids)), torch.where(live, log_q, torch.zeros_like(log_q))
+
+
+def gbce_beta(n_items: int, num_negatives: int, t: float) -> float:
+    """gSASRec's beta for ``token_negatives_loss(objective="gbce")``: with the sampling rate ``alpha = K / (n_items - 1)``,
+    ``beta = alpha * (t * (1 - 1 / alpha) + 1 / alpha)``; the calibration t = 0 gives 1.0 (plain BCE), t = 1 gives alpha (the
+    fully calibrated loss)."""
+    if not 0.0 <= t <= 1.0:
+        raise ValueError(f"t must lie in [0, 1] (got {t})")
+    if not 1 <= num_negatives <= n_items - 1:
+        raise ValueError(f"num_negatives must lie in [1, n_items - 1] (got {num_negatives} for {n_items} items)")
+    a = num_negatives / (n_items - 1)
+    return a * (t * (1.0 - 1.0 / a) + 1.0 / a)
+
+
 def negative_q(n_items: int, counts, alpha: float = 1.0):
     """The sampling distribution of ``sample_negatives`` as fp64 numpy (n_items,): q[i] for item id i + 1, proportional to
     ``counts[i + 1] ** alpha`` (entry 0, the padding id, ignored; negative counts taken as 0)."""
