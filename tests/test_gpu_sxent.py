@@ -11,6 +11,10 @@ import torch
 
 from oracle import srfrd_oracle as O
 from tests.helpers import assert_post_adam
+from tests.loss_refs import rel as _rel
+from tests.loss_refs import shared_negatives as _negatives
+from tests.loss_refs import sxent_logits_ref as _logits_ref
+from tests.loss_refs import sxent_ref as _ref
 
 pytestmark = pytest.mark.gpu
 
@@ -27,78 +31,6 @@ def _targets(B, L, n_items, seed, empty_rows=(), zero_frac=0.3):
     for b in empty_rows:
         y[b] = 0
     return y
-
-
-def _negatives(K, n_items, y, seed):
-    """ids in 0..n_items with id-0 slots, duplicates and accidental hits (targets of the batch)"""
-    g = torch.Generator().manual_seed(seed)
-    neg = torch.randint(1, n_items + 1, (K,), generator=g)
-    if K >= 4:
-        neg[1::5] = 0                                   # unused slots
-        neg[2::7] = neg[0]                              # duplicates
-        tg = y[y != 0].view(-1).cpu()
-        if tg.numel():
-            neg[3::6] = tg[torch.randint(0, tg.numel(), (len(range(3, K, 6)),), generator=g)]   # accidental hits
-    return neg
-
-
-def _logits_ref(h64, E64, y, neg, log_q, remove):
-    """-> (token mask, s+ (T,), masked negative logits (T, K)) in the dtype of h64 / E64"""
-    d = E64.shape[1]
-    hs = h64[..., :d].reshape(-1, d)
-    yy = y.reshape(-1)
-    tok = yy != 0
-    H, t = hs[tok], yy[tok]
-    sp = (H * E64[t]).sum(1)
-    sn = H @ E64[neg].T
-    if log_q is not None:
-        sn = sn - log_q.to(sn.dtype)
-    mask = (neg == 0).unsqueeze(0).expand_as(sn)
-    if remove:
-        mask = mask | (neg.unsqueeze(0) == t.unsqueeze(1))
-    return tok, sp, sn.masked_fill(mask, -float("inf"))
-
-
-def _reduce(lt, tok, shape, reduction):
-    if reduction == "mean":
-        return lt.mean()
-    if reduction == "sum":
-        return lt.sum()
-    full = torch.zeros(tok.numel(), dtype=lt.dtype, device=lt.device)
-    return full.index_put((tok.nonzero().view(-1),), lt).view(shape)
-
-
-def _ref(h, E, y, neg, log_q, remove, reduction, with_abs=False):
-    """fp64 reference: loss and (d_hidden, dE) by autograd over materialised logits; with_abs: also the inf-norms of the
-    two gradients summed over the absolute values of their terms"""
-    h64 = h.detach().double().requires_grad_(True)
-    E64 = E.detach().double().requires_grad_(True)
-    tok, sp, sn = _logits_ref(h64, E64, y, neg, log_q, remove)
-    lse = torch.logsumexp(torch.cat([sp.unsqueeze(1), sn], 1), 1)
-    loss = _reduce(lse - sp, tok, y.shape, reduction)
-    loss.backward(torch.ones_like(loss))
-    gh = h64.grad if h64.grad is not None else torch.zeros_like(h64)
-    ge = E64.grad if E64.grad is not None else torch.zeros_like(E64)
-    if not with_abs:
-        return loss.detach(), gh, ge
-    with torch.no_grad():
-        c = 1.0 / max(int(tok.sum()), 1) if reduction == "mean" else 1.0
-        d = E.shape[1]
-        H = h64.detach()[..., :d].reshape(-1, d)[tok].abs()
-        Ea = E64.detach().abs()
-        P = torch.exp(sn.detach() - lse.detach().unsqueeze(1)) * c
-        gp = (torch.exp(sp.detach() - lse.detach()) - 1.0).abs() * c
-        t = y.reshape(-1)[tok]
-        ah = P @ Ea[neg] + gp.unsqueeze(1) * Ea[t]
-        ae = torch.zeros_like(Ea).index_add_(0, neg, P.T @ H).index_add_(0, t, gp.unsqueeze(1) * H)
-    return loss.detach(), gh, ge, float(ah.max()) if ah.numel() else 0.0, float(ae.max())
-
-
-def _rel(a, b, abs_norm=0.0):
-    scale = max(float(b.abs().max()), 0.1 * abs_norm)
-    if scale == 0.0:
-        return float(a.abs().max())
-    return float((a.double() - b.double()).abs().max()) / scale
 
 
 def _run(m, h, y, neg, log_q=None, remove=True, reduction="mean"):

@@ -12,6 +12,9 @@ import torch
 from oracle import srfrd_oracle as O
 from tests.helpers import KINDS as GOLDEN_KINDS
 from tests.helpers import assert_post_adam, golden_cfg, load_golden, sub
+from tests.loss_refs import make_inputs
+from tests.loss_refs import rel as _rel
+from tests.loss_refs import tneg_ref as _ref
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4                      # tests/test_gpu_train.py
@@ -26,30 +29,6 @@ def _model(kind, n_items, L=20):
 
 def _table(m):
     return m.item_emb.weight if hasattr(m, "item_emb") else m.embedding_layer.item_embed.weight
-
-
-def make_inputs(B, L, K, n_items, seed, empty_rows=(2,), zero_frac=0.3):
-    """(targets (B, L), negatives (B, L, K)) on the CPU with id-0 slots, duplicate ids inside one position, accidental hits,
-    rows of the batch without any target, every tenth token with all slots unused and every tenth (offset 1) with every
-    slot unused or the target's own id: those tokens have no participating slot (under hit removal, for the second kind)"""
-    g = torch.Generator().manual_seed(seed)
-    y = torch.randint(1, n_items + 1, (B, L), generator=g)
-    y[torch.rand(B, L, generator=g) < zero_frac] = 0
-    for b in empty_rows:
-        y[b] = 0
-    neg = torch.randint(1, n_items + 1, (B, L, K), generator=g)
-    neg[torch.rand(B, L, K, generator=g) < 0.2] = 0                                  # unused slots
-    hit = torch.rand(B, L, K, generator=g) < 0.15                                    # accidental hits
-    neg = torch.where(hit, y.unsqueeze(-1).expand_as(neg), neg)
-    if K >= 3:
-        neg[..., 2] = neg[..., 0]                                                    # duplicates inside a position
-    flat, yy = neg.view(-1, K), y.view(-1)
-    live = (yy != 0).nonzero().view(-1)
-    flat[live[0::10]] = 0
-    mix = live[1::10]
-    flat[mix] = torch.where(torch.rand(mix.numel(), K, generator=g) < 0.5, yy[mix].unsqueeze(1).expand(-1, K),
-                            torch.zeros(mix.numel(), K, dtype=torch.int64))
-    return y, neg
 
 
 def degenerate_fraction(y, neg, remove):
@@ -67,69 +46,6 @@ def test_input_generator_keeps_the_degenerate_branch_a_minority():
         y, neg = make_inputs(5, 13, K, 1000, 1000 * 1009 + K)
         for remove in (True, False):
             assert 0.0 < degenerate_fraction(y, neg, remove) < 0.5, (K, remove)
-
-
-def _ref(h, E, y, neg, log_q=None, remove=True, reduction="mean", objective="softmax", beta=1.0, with_abs=False, chunk=2048):
-    """fp64 reference over materialised logits, in token chunks: loss and (d_hidden, dE) by autograd; with_abs: also the
-    inf-norms of the two gradients summed over the absolute values of their terms"""
-    d, K = E.shape[1], neg.shape[-1]
-    h64 = h.detach().double().requires_grad_(True)
-    E64 = E.detach().double().requires_grad_(True)
-    yy = y.reshape(-1)
-    idx = (yy != 0).nonzero().view(-1)
-    n_tok = idx.numel()
-    c = 1.0 / n_tok if (reduction == "mean" and n_tok) else 1.0
-    hs, N_all = h64.view(-1, h64.shape[-1]), neg.reshape(-1, K)
-    lq_all = None if log_q is None else log_q.reshape(-1, K).double()
-    losses, ah = [], 0.0
-    ae = torch.zeros(E.shape, dtype=torch.float64, device=E.device)
-    for i0 in range(0, n_tok, chunk):
-        ii = idx[i0:i0 + chunk]
-        H, t, N = hs[ii, :d], yy[ii], N_all[ii]
-        sp = (H * E64[t]).sum(1)
-        sn = torch.einsum("td,tkd->tk", H, E64[N])
-        mask = N == 0
-        if remove:
-            mask = mask | (N == t.unsqueeze(1))
-        if objective == "softmax":
-            if lq_all is not None:
-                sn = sn - lq_all[ii]
-            sn = sn.masked_fill(mask, -float("inf"))
-            lse = torch.logsumexp(torch.cat([sp.unsqueeze(1), sn], 1), 1)
-            lt = lse - sp
-        else:
-            lt = beta * torch.nn.functional.softplus(-sp) + torch.nn.functional.softplus(sn).masked_fill(mask, 0.0).sum(1)
-        (lt.sum() * c).backward()
-        losses.append(lt.detach())
-        if with_abs:
-            with torch.no_grad():
-                if objective == "softmax":
-                    P, gp = torch.exp(sn - lse.unsqueeze(1)) * c, (torch.exp(sp - lse) - 1.0).abs() * c
-                else:
-                    P, gp = torch.sigmoid(sn).masked_fill(mask, 0.0) * c, beta * torch.sigmoid(-sp) * c
-                Ha, Ea = H.abs(), E64.abs()
-                ah = max(ah, float((torch.einsum("tk,tkd->td", P, Ea[N]) + gp.unsqueeze(1) * Ea[t]).max()))
-                ae.index_add_(0, N.reshape(-1), (P.unsqueeze(2) * Ha.unsqueeze(1)).reshape(-1, d))
-                ae.index_add_(0, t, gp.unsqueeze(1) * Ha)
-    lt = torch.cat(losses) if losses else torch.zeros(0, dtype=torch.float64, device=h.device)
-    if reduction == "mean":
-        loss = lt.mean()
-    elif reduction == "sum":
-        loss = lt.sum()
-    else:
-        loss = torch.zeros(yy.numel(), dtype=torch.float64, device=h.device).index_put((idx,), lt).view(y.shape)
-    gh = h64.grad if h64.grad is not None else torch.zeros_like(h64)
-    ge = E64.grad if E64.grad is not None else torch.zeros_like(E64)
-    if with_abs:
-        return loss, gh, ge, ah, float(ae.max())
-    return loss, gh, ge
-
-
-def _rel(a, b, abs_norm=0.0):
-    scale = max(float(b.abs().max()), 0.1 * abs_norm)
-    if scale == 0.0:
-        return float(a.abs().max())
-    return float((a.double() - b.double()).abs().max()) / scale
 
 
 def _run(m, h, y, neg, objective="softmax", log_q=None, beta=1.0, remove=True, reduction="mean"):

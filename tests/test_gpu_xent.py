@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 from oracle import srfrd_oracle as O
 from tests.helpers import assert_post_adam
+from tests.loss_refs import xent_ref as _ref
 
 pytestmark = pytest.mark.gpu
 
@@ -29,20 +30,6 @@ def _targets(B, L, n_items, seed, empty_rows=(), zero_frac=0.3):
         flat[nz[0]] = 1
         flat[nz[-1]] = n_items
     return y
-
-
-def _ref(h, E, y, reduction):
-    """fp64 reference: loss and (d_hidden, dE) by autograd over materialised logits"""
-    h64 = h.detach().double().requires_grad_(True)
-    E64 = E.detach().double().requires_grad_(True)
-    d = E.shape[1]
-    logits = h64[..., :d] @ E64.T
-    n = E.shape[0] - 1
-    loss = F.cross_entropy(logits[..., 1:].reshape(-1, n), (y - 1).reshape(-1), ignore_index=-1, reduction=reduction)
-    if reduction == "none":
-        loss = loss.view(y.shape)
-    loss.backward(torch.ones_like(loss))
-    return loss.detach(), h64.grad, E64.grad
 
 
 def _rel(a, b):
