@@ -376,6 +376,11 @@ int srfrd_predict_logits(const srfrd_layout* lay, const void* item_table, const 
  * Full-catalog ranking: top-k items of <hidden[b, L-1, :], E[i]> over i in [item_lo, item_hi) with the logits
  * never written to HBM.  Ties break to the lower item id (stable descending sort).  topk_idx int64 (B,k),
  * topk_val (B,k).  workspace: srfrd_topk_workspace_bytes().  exclude_pad != 0 skips item 0.
+ * A returned score is fp32-grade, not one fixed rounding: a candidate list that overflows (more than 2048 scores at or above
+ * the k-th largest chunk maximum: mass ties, or fewer chunks than k over more than 2048 rows) is re-ranked by the exhaustive
+ * path, whose fp32 matrix-core sum and the bf16 stream's six-product sum can round the same (user, item) score to
+ * neighbouring floats.  Within one call all scores come from one arithmetic, so the order law holds exactly; across calls
+ * (another k, another item range) two items whose scores lie within that rounding of each other may change places.
  */
 int64_t srfrd_topk_workspace_bytes(int B, int k, int64_t n_rows);
 int srfrd_logits_topk(const srfrd_layout* lay, const void* item_table, const float* dense,
@@ -387,8 +392,11 @@ int srfrd_logits_topk(const srfrd_layout* lay, const void* item_table, const flo
  * Merge of per-shard top-k lists: the catalog's rows split into shards (one per GPU for the row-sharded table of BASELINE
  * configs[4], or just to bound the ranking workspace), each ranked by srfrd_logits_topk over its [item_lo, item_hi).
  * cand_idx int64 / cand_val (B, n_cand) hold the shards' lists side by side (n_cand = shards * k <= 4096; idx < 0 marks an
- * empty slot); topk_idx / topk_val (B, k) receive the k best in stable descending order (value desc, item id asc): what
- * ONE srfrd_logits_topk over the whole catalog returns, ties across shard boundaries included.
+ * empty slot); topk_idx / topk_val (B, k) receive the k best in stable descending order (value desc, item id asc), exact
+ * ties across shard boundaries included.  That is what ONE srfrd_logits_topk over the whole catalog returns, bit for bit,
+ * when the shards and the whole catalog are scored by the same arithmetic (see srfrd_logits_topk: every list on the
+ * threshold scheme, e.g. k = 10); otherwise the ids agree wherever two scores differ by more than their rounding, and the
+ * values agree to that rounding.
  */
 int srfrd_topk_merge(const int64_t* cand_idx, const float* cand_val, int B, int n_cand, int k,
                      int64_t* topk_idx, float* topk_val, void* stream);

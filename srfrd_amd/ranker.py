@@ -5,7 +5,9 @@ candidate) is the one part of the path whose cost grows with the catalog: 2 B I 
 reference would materialise.  Here the item rows are split into contiguous shards; each shard is ranked by
 ``srfrd_logits_topk`` over its own ``[lo, hi)`` (logits never reach HBM) and the per-shard top-k lists are merged by
 ``srfrd_topk_merge`` into the order one unsharded ranking returns (value desc, item id asc - ties across shard boundaries
-included).
+included).  The merged list equals the unsharded one bit for bit when both are scored by the same arithmetic; a call whose
+candidate lists overflow (include/srfrd_hip.h, ``srfrd_logits_topk``) is re-ranked on the fp32 matrix cores, and then the
+ids agree wherever two scores differ by more than an fp32 rounding and the values agree to that rounding.
 
 * one process (``n_shards`` given, no process group): the shards are ranked one after the other on this GPU - bounds the
   ranking workspace at 1M+ items and is what the single-GPU tests exercise;
@@ -99,7 +101,13 @@ class ShardedRanker:
         fewer than k items are rankable.  ``check_batch`` (data parallel): verify that every rank passed the same batch size
         (one 8-byte all-gather + host read per call; pass False in a loop whose batches are known to be equal).
         ``exclude``: per-user items never to return, as in the model's ``topk``."""
-        h_last, ulab, excl = self._users(input_ids, fake_ids, exclude)
+        return self.topk_hidden(*self._users(input_ids, fake_ids, exclude), k=k, exclude_pad=exclude_pad, check_batch=check_batch)
+
+    @torch.no_grad()
+    def topk_hidden(self, h_last, ulab=None, excl=None, k: int = 10, exclude_pad: bool = True, check_batch: bool = True):
+        """``topk`` from the users' last-position states themselves: ``h_last`` (B, d_out) fp32, ``ulab`` the int64 (B,) user
+        labels of SRFRN (else None), ``excl`` an ``ops.excl_csr`` triple or None.  What ``topk`` calls after its encoder pass;
+        also the entry for states computed elsewhere."""
         B = h_last.shape[0]
         if not self.dist_on:
             lists = [self._rank_shard(h_last, ulab, lo, hi, k, exclude_pad, excl) for lo, hi in self.shards if hi > lo]

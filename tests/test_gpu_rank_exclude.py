@@ -39,9 +39,32 @@ def _batch(I, L, B, seed):
 
 
 def _scores(m, seq, rsq, I):
-    """(B, I + 1) fp64 scores of every item (the predict kernel: one fp32 dot product per (user, item))"""
+    """(B, I + 1) fp64 scores of every item (the predict kernel: one fp32 dot product per (user, item)).  The tests of this
+    file trust these; _check_predict_chain holds them to the host's fp64 scores of the same hidden states, and
+    tests/test_gpu_rank_widths.py pins predict_logits itself at every width."""
     with torch.no_grad():
-        return m.predict(None, seq, rsq, torch.arange(I + 1, device="cuda")).double().reshape(seq.shape[0], I + 1)
+        s = m.predict(None, seq, rsq, torch.arange(I + 1, device="cuda")).double().reshape(seq.shape[0], I + 1)
+    _check_predict_chain(m, seq, rsq, s)
+    return s
+
+
+def _check_predict_chain(m, seq, rsq, s):
+    """the predict-derived scores agree with scores64 of tests/rank_refs.py (fp64 on the host from the encoder's last hidden
+    state and the table the kernels read) within that file's value bound, 4 max(E32, 2^-23) A"""
+    from tests import rank_refs as R
+    with torch.no_grad():
+        ids = m._prep(seq, rsq, None, None, None, None)
+        hidden = m._launch_fwd_last(ids[0], ids[1]).cpu()
+        rows, d = m.layout.n_items + 1, m.layout.d_item
+        if m.bf16_table:
+            table = ((m._table16.cpu().to(torch.int32) & 0xFFFF) << 16).view(torch.float32).reshape(rows, d)
+        else:
+            table = m._item_param().detach().cpu()
+        side = None
+        if m._kind == "SRFRN":
+            side = (m.embedding_layer.fake_embed.weight.detach().cpu(), m.user_labels(ids[1]).cpu().clamp(0, 2))
+    ref = R.Ref(hidden, table, side)
+    assert (np.abs(s.cpu().numpy() - ref.s) <= ref.eps * ref.A).all()
 
 
 def _mask(scores, rows, exclude_pad=True):
