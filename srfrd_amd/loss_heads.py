@@ -1,0 +1,134 @@
+"""The launches of the three fused loss heads over the item table, written once  (DESIGN sections 12-15).
+
+    XENT    full-catalog softmax                     srfrd_xent_fwd / _bwd     head arguments: none
+    SXENT   sampled softmax, shared negatives (K,)   srfrd_sxent_fwd / _bwd    (negatives, log_q, remove_hits)
+    TNEG    K negatives per position (B, L, K)       srfrd_tneg_fwd / _bwd     (negatives, log_q, objective, beta, remove_hits)
+
+The C entry points of a head differ from one another in two places only, and a ``Head`` names both.  Between the targets and
+the lse / shape arguments sit the head's own arguments (none, or negatives, log_q, K and the scalars in the order above).
+Between d_hidden and the workspace sits the table gradient in one of three forms: a dense (n_items + 1, d_item) write with
+an accumulate flag (XENT); K + T contribution rows and their item keys, summed per item by srfrd_table_reduce (SXENT); or
+T (1 + K) coefficients and keys, summed per item as coef * hidden[t] by srfrd_table_reduce_rank1 (TNEG).  Both reduces run
+over a stable sort of the keys, so every item's rows are added in list order: bitwise reproducible.
+
+``launch_fwd`` / ``launch_bwd`` are what the ``srfrd::{xent,sxent,tneg}_{fwd,bwd}`` library ops (ops.py), the modules'
+autograd function (modules.py) and FusedTrainer's cross-entropy step (trainer.py) all call.  Every buffer they would
+allocate may be handed in instead (a persistent-buffer step allocates nothing); tensors must be contiguous.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Callable, NamedTuple, Optional
+
+import torch
+
+from . import _lib
+from ._lib import check, ptr
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def table_dense(lay, hidden, K, rows, keys, ws, d_table):
+    """the backward kernel wrote (or accumulated into) the dense table gradient itself"""
+    return d_table
+
+
+def _sorted_keys(lay, keys, d_table):
+    skeys, order = torch.sort(keys, stable=True)
+    if d_table is None:
+        d_table = torch.zeros(lay.n_items + 1, lay.d_item, device=keys.device, dtype=torch.float32)
+    return skeys, order, d_table
+
+
+def table_rows(lay, hidden, K, rows, keys, ws, d_table):
+    """every item's contribution rows (its negative slots in slot order, then its target tokens in position order) summed in
+    that fixed order"""
+    skeys, order, d_table = _sorted_keys(lay, keys, d_table)
+    check(_lib.lib().srfrd_table_reduce(ptr(skeys), ptr(order), ptr(rows), skeys.numel(), lay.d_item, ptr(d_table), _stream()),
+          "srfrd_table_reduce")
+    return d_table
+
+
+def table_rank1(lay, hidden, K, rows, keys, ws, d_table):
+    """every item's rank-1 rows coef * hidden[t] summed in list order (position-major, the target before its negatives)"""
+    skeys, order, d_table = _sorted_keys(lay, keys, d_table)
+    check(_lib.lib().srfrd_table_reduce_rank1(ptr(skeys), ptr(order), ptr(rows), ptr(hidden), lay.d_out, 1 + K, skeys.numel(),
+                                              lay.d_item, ptr(d_table), ptr(ws), ws.numel(), _stream()),
+          "srfrd_table_reduce_rank1")
+    return d_table
+
+
+class Head(NamedTuple):
+    fwd: str                        # the C entry points
+    bwd: str
+    n_neg: Optional[Callable]       # negatives tensor -> K (None: the head takes no arguments of its own)
+    workspace: Callable             # (lib, layout, B, L, K) -> workspace floats
+    rows: Optional[Callable]        # (layout, T, K) -> shape of the backward's contribution list (None: dense table gradient)
+    finish: Callable                # table_dense | table_rows | table_rank1
+
+
+XENT = Head("srfrd_xent_fwd", "srfrd_xent_bwd", None,
+            lambda L_, lay, B, L, K: L_.srfrd_xent_workspace_floats(C.byref(lay), B, L), None, table_dense)
+SXENT = Head("srfrd_sxent_fwd", "srfrd_sxent_bwd", lambda neg: neg.numel(),
+             lambda L_, lay, B, L, K: L_.srfrd_sxent_workspace_floats(C.byref(lay), B, L, K),
+             lambda lay, T, K: (K + T, lay.d_item), table_rows)
+TNEG = Head("srfrd_tneg_fwd", "srfrd_tneg_bwd", lambda neg: neg.shape[2],
+            lambda L_, lay, B, L, K: max(L_.srfrd_tneg_workspace_floats(C.byref(lay), B, L, K), 1),
+            lambda lay, T, K: (T * (1 + K),), table_rank1)
+
+
+def _head_args(head, args):
+    """(negatives, log_q, *scalars) -> (K, the C arguments between the targets and lse / B)"""
+    if head.n_neg is None:
+        return 0, ()
+    negatives, log_q, *scalars = args
+    K = head.n_neg(negatives)
+    return K, (ptr(negatives), ptr(log_q), K, *(int(s) if isinstance(s, bool) else s for s in scalars))
+
+
+def launch_fwd(head: Head, lay, table_ptr, hidden, targets, args=(), *, out=None, ws=None):
+    """the head's forward -> (token_loss (B, L), lse (B, L), stats {sum, count}); ``args``: the head's own arguments (see the
+    module docstring); ``out``: those three tensors, ``ws``: the workspace, where the caller keeps them"""
+    B, L = targets.shape
+    f32 = dict(device=hidden.device, dtype=torch.float32)
+    L_ = _lib.lib()
+    K, cargs = _head_args(head, args)
+    if ws is None:
+        ws = torch.empty(head.workspace(L_, lay, B, L, K), **f32)
+    tl, lse, stats = out if out is not None else (torch.empty(B, L, **f32), torch.empty(B, L, **f32), torch.empty(2, **f32))
+    check(getattr(L_, head.fwd)(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), *cargs, B, L, ptr(tl), ptr(lse), ptr(stats),
+                                ptr(ws), ws.numel(), _stream()), head.fwd)
+    return tl, lse, stats
+
+
+def launch_bwd(head: Head, lay, table_ptr, hidden, targets, args, lse, d_token_loss, *, d_hidden=None, ws=None, rows=None,
+               keys=None, d_table=None, accumulate=False, finish=True):
+    """the head's backward, then the head's table-gradient finisher -> (d_hidden (B, L, d_out), d_table (n_items + 1, d_item)).
+    ``d_hidden``, ``ws``, ``rows`` / ``keys`` (the contribution list) and ``d_table`` (where the table gradient goes; a
+    reducing finisher stores into it as it is) are the caller's buffers where given.  ``accumulate``: the dense form adds to
+    ``d_table``.  ``finish=False`` leaves the contribution list unreduced (-> (d_hidden, None)): the caller merges it with
+    rows of its own."""
+    B, L = targets.shape
+    f32 = dict(device=hidden.device, dtype=torch.float32)
+    L_ = _lib.lib()
+    K, cargs = _head_args(head, args)
+    if ws is None:
+        ws = torch.empty(head.workspace(L_, lay, B, L, K), **f32)
+    if d_hidden is None:
+        d_hidden = torch.empty(B, L, lay.d_out, **f32)
+    if head.rows is None:
+        if d_table is None:
+            d_table = torch.empty(lay.n_items + 1, lay.d_item, **f32)
+        grad_args = (ptr(d_table), int(accumulate))
+    else:
+        shape = head.rows(lay, B * L, K)
+        if rows is None:
+            rows = torch.empty(shape, **f32)
+        if keys is None:
+            keys = torch.empty(shape[0], device=hidden.device, dtype=torch.int64)
+        grad_args = (ptr(rows), ptr(keys))
+    check(getattr(L_, head.bwd)(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), *cargs, ptr(lse), ptr(d_token_loss), B, L,
+                                ptr(d_hidden), *grad_args, ptr(ws), ws.numel(), _stream()), head.bwd)
+    return d_hidden, (head.finish(lay, hidden, K, rows, keys, ws, d_table) if finish else None)

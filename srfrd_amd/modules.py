@@ -15,7 +15,7 @@ import weakref
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
+from . import _lib, loss_heads, ops
 from ._lib import check, ptr
 
 
@@ -129,82 +129,31 @@ class _EncoderFn(torch.autograd.Function):
         return (None,) * 9 + m._grad_views(gflat)
 
 
-class _XentFn(torch.autograd.Function):
-    """full_catalog_loss() under autograd: the launches of the registered ``srfrd::xent_fwd`` / ``srfrd::xent_bwd`` ops
-    (srfrd_amd/ops.py) without torch.library's Python glue, as _EncoderFn does for the encoder.  The reduction is applied on
-    the device from the forward's {sum, count}: no host synchronisation in either direction."""
+class _LossHeadFn(torch.autograd.Function):
+    """full_catalog_loss() / sampled_softmax_loss() / token_negatives_loss() under autograd: the launches of the registered
+    ``srfrd::{xent,sxent,tneg}_fwd`` / ``_bwd`` ops (srfrd_amd/loss_heads.py) without torch.library's Python glue, as _EncoderFn
+    does for the encoder.  ``head``: loss_heads.XENT / SXENT / TNEG; ``scalars``: its non-tensor arguments; ``ids``: () or
+    (negatives, log_q).  The reduction is applied on the device from the forward's {sum, count}: no host synchronisation in
+    either direction.  log_q is not differentiable."""
 
     @staticmethod
-    def forward(ctx, model, reduction, hidden, targets, table):
-        lay, tab = model.layout, ptr(table)
-        tl, lse, stats = ops.xent_launch_fwd(lay, tab, hidden, targets)
-        ctx.model, ctx.reduction = model, reduction
-        ctx.save_for_backward(hidden, targets, table, lse, stats)
+    def forward(ctx, model, head, reduction, scalars, hidden, table, targets, *ids):
+        tl, lse, stats = loss_heads.launch_fwd(head, model.layout, ptr(table), hidden, targets, (*ids, *scalars))
+        ctx.model, ctx.head, ctx.reduction, ctx.scalars = model, head, reduction, scalars
+        ctx.save_for_backward(hidden, table, targets, lse, stats, *ids)
         if reduction == "none":
             return tl
         return stats[0].clone() if reduction == "sum" else stats[0] / stats[1]
 
     @staticmethod
     def backward(ctx, g):
-        hidden, targets, table, lse, stats = ctx.saved_tensors
+        hidden, table, targets, lse, stats, *ids = ctx.saved_tensors
         if ctx.reduction == "none":
             d_tok = g.contiguous()
         else:
             d_tok = (g if ctx.reduction == "sum" else g / stats[1]).expand(targets.shape).contiguous()
-        dh, de = ops.xent_launch_bwd(ctx.model.layout, ptr(table), hidden, targets, lse, d_tok)
-        return None, None, dh, None, de
-
-
-class _SxentFn(torch.autograd.Function):
-    """sampled_softmax_loss() under autograd: the launches of the registered ``srfrd::sxent_fwd`` / ``srfrd::sxent_bwd`` ops
-    without torch.library's Python glue, as _XentFn.  The reduction is applied on the device from the forward's
-    {sum, count}: no host synchronisation in either direction.  log_q is not differentiable."""
-
-    @staticmethod
-    def forward(ctx, model, reduction, remove_hits, hidden, targets, negatives, log_q, table):
-        lay, tab = model.layout, ptr(table)
-        tl, lse, stats = ops.sxent_launch_fwd(lay, tab, hidden, targets, negatives, log_q, remove_hits)
-        ctx.model, ctx.reduction, ctx.remove_hits = model, reduction, remove_hits
-        ctx.save_for_backward(hidden, targets, negatives, log_q, table, lse, stats)
-        if reduction == "none":
-            return tl
-        return stats[0].clone() if reduction == "sum" else stats[0] / stats[1]
-
-    @staticmethod
-    def backward(ctx, g):
-        hidden, targets, negatives, log_q, table, lse, stats = ctx.saved_tensors
-        if ctx.reduction == "none":
-            d_tok = g.contiguous()
-        else:
-            d_tok = (g if ctx.reduction == "sum" else g / stats[1]).expand(targets.shape).contiguous()
-        dh, de = ops.sxent_launch_bwd(ctx.model.layout, ptr(table), hidden, targets, negatives, log_q, ctx.remove_hits, lse, d_tok)
-        return None, None, None, dh, None, None, None, de
-
-
-class _TnegFn(torch.autograd.Function):
-    """token_negatives_loss() under autograd: the launches of the registered ``srfrd::tneg_fwd`` / ``srfrd::tneg_bwd`` ops
-    without torch.library's Python glue, as _SxentFn.  The reduction is applied on the device from the forward's
-    {sum, count}: no host synchronisation in either direction.  log_q is not differentiable."""
-
-    @staticmethod
-    def forward(ctx, model, reduction, objective, beta, remove_hits, hidden, targets, negatives, log_q, table):
-        lay, tab = model.layout, ptr(table)
-        tl, lse, stats = ops.tneg_launch_fwd(lay, tab, hidden, targets, negatives, log_q, objective, beta, remove_hits)
-        ctx.model, ctx.reduction, ctx.meta = model, reduction, (objective, beta, remove_hits)
-        ctx.save_for_backward(hidden, targets, negatives, log_q, table, lse, stats)
-        if reduction == "none":
-            return tl
-        return stats[0].clone() if reduction == "sum" else stats[0] / stats[1]
-
-    @staticmethod
-    def backward(ctx, g):
-        hidden, targets, negatives, log_q, table, lse, stats = ctx.saved_tensors
-        if ctx.reduction == "none":
-            d_tok = g.contiguous()
-        else:
-            d_tok = (g if ctx.reduction == "sum" else g / stats[1]).expand(targets.shape).contiguous()
-        dh, de = ops.tneg_launch_bwd(ctx.model.layout, ptr(table), hidden, targets, negatives, log_q, *ctx.meta, lse, d_tok)
-        return None, None, None, None, None, dh, None, None, None, de
+        dh, de = loss_heads.launch_bwd(ctx.head, ctx.model.layout, ptr(table), hidden, targets, (*ids, *ctx.scalars), lse, d_tok)
+        return (None,) * 4 + (dh, de, None) + (None,) * len(ids)
 
 
 class _SRFRDBase(nn.Module):
@@ -551,6 +500,31 @@ class _SRFRDBase(nn.Module):
         parts = gflat.split_with_sizes(self._split_sizes)
         return tuple(t.view(q.shape) for (t, k), (q, _) in zip(((t, k) for t, k in zip(parts, self._split_keep) if k), self._slots))
 
+    def _loss_inputs(self, name, hidden_state, positive_ids, reduction):
+        """the checks the three loss methods share -> (contiguous hidden state, targets as int64 ids on the model's device)"""
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
+        self._ensure_flat()
+        if self.bf16_table:
+            raise RuntimeError(f"{name} needs the fp32 item table (use_bf16_table(False)); the bf16 form is not built")
+        lay = self.layout
+        dev = self._flat.device
+        if hidden_state.dim() != 3 or hidden_state.shape[2] != lay.d_out or hidden_state.device != dev:
+            raise ValueError(f"hidden_state must be the model's (B, L, {lay.d_out}) output on {dev}")
+        if hidden_state.dtype != torch.float32:
+            raise ValueError("hidden_state must be float32")
+        return hidden_state.contiguous(), _ids(positive_ids, dev, hidden_state.shape[:2])
+
+    def _check_item_ids(self, *ids):
+        """validate_ids: one srfrd_check_ids launch per tensor of item ids; "eager" raises here (IndexError, one host sync)"""
+        if not self.validate_ids:
+            return
+        for t in ids:
+            check(_lib.lib().srfrd_check_ids(ptr(t), None, None, None, None, None, t.numel(), self.layout.n_items, 2,
+                                             ptr(self._err_word(t.device)), _stream()), "srfrd_check_ids")
+        if self.validate_ids == "eager":
+            self.check_ids()
+
     def full_catalog_loss(self, hidden_state, positive_ids, reduction="mean"):
         """Softmax cross-entropy of every target against the whole catalog: ``F.cross_entropy(logits[:, 1:], y - 1,
         ignore_index=-1, reduction=...)`` over the logits ``hidden_state[..., :d_item] @ item_table.T`` of the positions with
@@ -559,25 +533,9 @@ class _SRFRDBase(nn.Module):
         item table.  reduction: "mean" (over the targets; NaN when there are none, as torch gives), "sum" or "none" ((B, L),
         zeros at ignored positions).  SRFRN's fake slice adds one constant per row, which the softmax does not see: it
         gets a zero gradient."""
-        if reduction not in ("mean", "sum", "none"):
-            raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
-        self._ensure_flat()
-        if self.bf16_table:
-            raise RuntimeError("full_catalog_loss needs the fp32 item table (use_bf16_table(False)); the bf16 form is not built")
-        lay = self.layout
-        dev = self._flat.device
-        if hidden_state.dim() != 3 or hidden_state.shape[2] != lay.d_out or hidden_state.device != dev:
-            raise ValueError(f"hidden_state must be the model's (B, L, {lay.d_out}) output on {dev}")
-        if hidden_state.dtype != torch.float32:
-            raise ValueError("hidden_state must be float32")
-        y = _ids(positive_ids, dev, hidden_state.shape[:2])
-        if self.validate_ids:
-            check(_lib.lib().srfrd_check_ids(ptr(y), None, None, None, None, None, y.numel(), lay.n_items, 2,
-                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
-            if self.validate_ids == "eager":
-                self.check_ids()
-        table = self._slots[0][0]
-        return _XentFn.apply(self, reduction, hidden_state.contiguous(), y, table)
+        h, y = self._loss_inputs("full_catalog_loss", hidden_state, positive_ids, reduction)
+        self._check_item_ids(y)
+        return _LossHeadFn.apply(self, loss_heads.XENT, reduction, (), h, self._slots[0][0], y)
 
     def sampled_softmax_loss(self, hidden_state, positive_ids, negative_ids, log_q=None, remove_accidental_hits=True,
                              reduction="mean"):
@@ -591,18 +549,8 @@ class _SRFRDBase(nn.Module):
         at ignored positions).  Autograd carries the loss into ``hidden_state`` and into the item table, whose gradient is
         reduced per item in a fixed order (bitwise reproducible).  SRFRN's fake slice gets a zero gradient, as in
         full_catalog_loss; ``negative_ids = arange(1, n_items + 1)`` without log_q is full_catalog_loss."""
-        if reduction not in ("mean", "sum", "none"):
-            raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
-        self._ensure_flat()
-        if self.bf16_table:
-            raise RuntimeError("sampled_softmax_loss needs the fp32 item table (use_bf16_table(False)); the bf16 form is not built")
-        lay = self.layout
-        dev = self._flat.device
-        if hidden_state.dim() != 3 or hidden_state.shape[2] != lay.d_out or hidden_state.device != dev:
-            raise ValueError(f"hidden_state must be the model's (B, L, {lay.d_out}) output on {dev}")
-        if hidden_state.dtype != torch.float32:
-            raise ValueError("hidden_state must be float32")
-        y = _ids(positive_ids, dev, hidden_state.shape[:2])
+        h, y = self._loss_inputs("sampled_softmax_loss", hidden_state, positive_ids, reduction)
+        dev = h.device
         neg = torch.as_tensor(negative_ids)
         if neg.dim() != 1 or neg.numel() == 0 or neg.is_floating_point() or neg.is_complex() or neg.dtype == torch.bool:
             raise ValueError(f"negative_ids must be a non-empty 1-D integer tensor (got shape {tuple(neg.shape)}, {neg.dtype})")
@@ -612,15 +560,8 @@ class _SRFRDBase(nn.Module):
             if not isinstance(log_q, torch.Tensor) or log_q.dtype != torch.float32 or tuple(log_q.shape) != (K,):
                 raise ValueError(f"log_q must be a float32 tensor of shape ({K},) or None")
             log_q = log_q.detach().to(dev).contiguous()
-        if self.validate_ids:
-            check(_lib.lib().srfrd_check_ids(ptr(y), None, None, None, None, None, y.numel(), lay.n_items, 2,
-                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
-            check(_lib.lib().srfrd_check_ids(ptr(neg), None, None, None, None, None, K, lay.n_items, 2,
-                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
-            if self.validate_ids == "eager":
-                self.check_ids()
-        table = self._slots[0][0]
-        return _SxentFn.apply(self, reduction, bool(remove_accidental_hits), hidden_state.contiguous(), y, neg, log_q, table)
+        self._check_item_ids(y, neg)
+        return _LossHeadFn.apply(self, loss_heads.SXENT, reduction, (bool(remove_accidental_hits),), h, self._slots[0][0], y, neg, log_q)
 
     def token_negatives_loss(self, hidden_state, positive_ids, negative_ids, objective="softmax", log_q=None, beta=1.0,
                              remove_accidental_hits=True, reduction="mean"):
@@ -643,8 +584,6 @@ class _SRFRDBase(nn.Module):
         The (tokens x (1 + K)) logits are never materialised.  reduction: "mean" (over the targets; NaN when there are
         none), "sum" or "none" ((B, L), zeros at ignored positions).  Autograd carries the loss into ``hidden_state`` and
         into the item table, whose gradient is reduced per item in a fixed order (bitwise reproducible)."""
-        if reduction not in ("mean", "sum", "none"):
-            raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
         if objective not in _lib.TNEG_OBJECTIVES:
             raise ValueError(f"objective must be 'softmax' or 'gbce' (got {objective!r})")
         beta = float(beta)
@@ -656,16 +595,8 @@ class _SRFRDBase(nn.Module):
             if self._kind == "SRFRN":
                 raise ValueError("objective='gbce' is not built for SRFRN: its logits include the fake slice, which BCE "
                                  "(unlike the softmax) is not invariant to")
-        self._ensure_flat()
-        if self.bf16_table:
-            raise RuntimeError("token_negatives_loss needs the fp32 item table (use_bf16_table(False)); the bf16 form is not built")
-        lay = self.layout
-        dev = self._flat.device
-        if hidden_state.dim() != 3 or hidden_state.shape[2] != lay.d_out or hidden_state.device != dev:
-            raise ValueError(f"hidden_state must be the model's (B, L, {lay.d_out}) output on {dev}")
-        if hidden_state.dtype != torch.float32:
-            raise ValueError("hidden_state must be float32")
-        y = _ids(positive_ids, dev, hidden_state.shape[:2])
+        h, y = self._loss_inputs("token_negatives_loss", hidden_state, positive_ids, reduction)
+        dev = h.device
         neg = torch.as_tensor(negative_ids)
         B, L = hidden_state.shape[:2]
         if (neg.dim() != 3 or tuple(neg.shape[:2]) != (B, L) or neg.shape[2] == 0 or neg.is_floating_point() or neg.is_complex()
@@ -680,16 +611,9 @@ class _SRFRDBase(nn.Module):
             if not isinstance(log_q, torch.Tensor) or log_q.dtype != torch.float32 or tuple(log_q.shape) != (B, L, K):
                 raise ValueError(f"log_q must be a float32 tensor of shape ({B}, {L}, {K}) or None")
             log_q = log_q.detach().to(dev).contiguous()
-        if self.validate_ids:
-            check(_lib.lib().srfrd_check_ids(ptr(y), None, None, None, None, None, y.numel(), lay.n_items, 2,
-                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
-            check(_lib.lib().srfrd_check_ids(ptr(neg), None, None, None, None, None, neg.numel(), lay.n_items, 2,
-                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
-            if self.validate_ids == "eager":
-                self.check_ids()
-        table = self._slots[0][0]
-        return _TnegFn.apply(self, reduction, _lib.TNEG_OBJECTIVES[objective], beta, bool(remove_accidental_hits),
-                             hidden_state.contiguous(), y, neg, log_q, table)
+        self._check_item_ids(y, neg)
+        scalars = (_lib.TNEG_OBJECTIVES[objective], beta, bool(remove_accidental_hits))
+        return _LossHeadFn.apply(self, loss_heads.TNEG, reduction, scalars, h, self._slots[0][0], y, neg, log_q)
 
     def user_labels(self, fake_ids):
         """get_Labels (SRFU_*) / the predict-time label (SRFRN) as an int64 (B,) tensor, computed on device."""
@@ -718,11 +642,7 @@ class _SRFRDBase(nn.Module):
         if cand.dim() == 2 and cand.shape[0] != B:
             raise ValueError("per-user candidates must be (B, I_c)")
         ulab = self.user_labels(fake_ids) if self._kind == "SRFRN" else None
-        if self.validate_ids:
-            check(_lib.lib().srfrd_check_ids(ptr(cand), None, None, None, None, None, cand.numel(), lay.n_items, 2,
-                                             ptr(self._err_word(dev)), _stream()), "srfrd_check_ids")
-            if self.validate_ids == "eager":
-                self.check_ids()
+        self._check_item_ids(cand)
         return torch.ops.srfrd.predict_logits(hidden.contiguous(), cand.contiguous(), ulab, ops.register_model(self))
 
     def topk(self, user_ids, input_ids, fake_ids, k=10, exclude_pad=True, item_range=None, exclude=None):

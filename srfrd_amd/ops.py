@@ -1,8 +1,10 @@
 """PyTorch-ROCm custom ops (namespace ``srfrd::``) over the C ABI of include/srfrd_hip.h  (SURVEY.md 8b).
 
 Every launcher the drop-in modules use is registered with ``torch.library`` - visible to the dispatcher as
-``torch.ops.srfrd.<name>``, with a fake (meta) implementation for shape propagation and, for the encoder, a registered
-backward - instead of being an opaque ctypes call from Python:
+``torch.ops.srfrd.<name>``, with a fake (meta) implementation for shape propagation and, for the encoder and the loss
+heads, a registered backward - instead of being an opaque ctypes call from Python.  The six loss-head ops are thin: their
+launches live in loss_heads.py (one ``launch_fwd`` / ``launch_bwd`` over a description per head, shared with the modules'
+autograd function and FusedTrainer), and their fakes and autograd are registered once, by ``_register_head``:
 
     srfrd::encoder_fwd     embedding gather -> n_blocks x {LN, causal self-attention, FFN} -> last LN -> pos / neg logits
                            (reference SRFR_model.py:92-142 and twins); backward = srfrd::encoder_bwd + srfrd_reduce_dense
@@ -35,7 +37,7 @@ from typing import List, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, loss_heads
 from ._lib import check, ptr
 
 _MODELS: "weakref.WeakValueDictionary[int, torch.nn.Module]" = weakref.WeakValueDictionary()
@@ -312,34 +314,7 @@ def _(logits):
     return torch.empty(logits.shape[0], device=logits.device, dtype=torch.int32)
 
 
-# ------------------------------------------------------------------------------------------------ full-catalog cross-entropy
-def xent_launch_fwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor):
-    """srfrd_xent_fwd -> (token_loss (B, L), lse (B, L), stats {sum, count})"""
-    B, L = targets.shape
-    dev = hidden.device
-    L_ = _lib.lib()
-    ws = torch.empty(L_.srfrd_xent_workspace_floats(C.byref(lay), B, L), device=dev, dtype=torch.float32)
-    tl = torch.empty(B, L, device=dev, dtype=torch.float32)
-    lse = torch.empty(B, L, device=dev, dtype=torch.float32)
-    stats = torch.empty(2, device=dev, dtype=torch.float32)
-    check(L_.srfrd_xent_fwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), B, L, ptr(tl), ptr(lse), ptr(stats), ptr(ws),
-                            ws.numel(), _stream()), "srfrd_xent_fwd")
-    return tl, lse, stats
-
-
-def xent_launch_bwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, lse: torch.Tensor, d_token_loss: torch.Tensor):
-    """srfrd_xent_bwd -> (d_hidden (B, L, d_out), d_table (n_items + 1, d_item))"""
-    B, L = targets.shape
-    dev = hidden.device
-    L_ = _lib.lib()
-    ws = torch.empty(L_.srfrd_xent_workspace_floats(C.byref(lay), B, L), device=dev, dtype=torch.float32)
-    dh = torch.empty(B, L, lay.d_out, device=dev, dtype=torch.float32)
-    de = torch.empty(lay.n_items + 1, lay.d_item, device=dev, dtype=torch.float32)
-    check(L_.srfrd_xent_bwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(lse), ptr(d_token_loss), B, L, ptr(dh),
-                            ptr(de), 0, ptr(ws), ws.numel(), _stream()), "srfrd_xent_bwd")
-    return dh, de
-
-
+# ------------------------------------------------------------------------------------------------ the three loss heads
 def _xent_table(m, table: torch.Tensor):
     if m.bf16_table:
         raise RuntimeError("full-catalog cross-entropy needs the fp32 item table: call use_bf16_table(False) first")
@@ -349,233 +324,93 @@ def _xent_table(m, table: torch.Tensor):
     return lay, ptr(table)
 
 
-@torch.library.custom_op("srfrd::xent_fwd", mutates_args=(), device_types="cuda")
-def xent_fwd(hidden: torch.Tensor, targets: torch.Tensor, table: torch.Tensor, model_key: int) -> List[torch.Tensor]:
+def _contiguous(args):
+    return tuple(a.contiguous() if isinstance(a, torch.Tensor) else a for a in args)
+
+
+def _head_fwd(head, model_key, table, hidden, targets, *args):
     """-> [token_loss (B, L), lse (B, L), stats (2) = {sum, count}]"""
     lay, tab = _xent_table(_model(model_key), table)
-    return list(xent_launch_fwd(lay, tab, hidden.contiguous(), targets.contiguous()))
+    return list(loss_heads.launch_fwd(head, lay, tab, hidden.contiguous(), targets.contiguous(), _contiguous(args)))
 
 
-@xent_fwd.register_fake
-def _(hidden, targets, table, model_key):
-    B, L = targets.shape
-    f = dict(device=hidden.device, dtype=torch.float32)
-    return [torch.empty(B, L, **f), torch.empty(B, L, **f), torch.empty(2, **f)]
+def _head_bwd(head, model_key, table, lse, d_token_loss, hidden, targets, *args):
+    """-> [d_hidden (B, L, d_out), d_table (n_items + 1, d_item)]"""
+    lay, tab = _xent_table(_model(model_key), table)
+    return list(loss_heads.launch_bwd(head, lay, tab, hidden.contiguous(), targets.contiguous(), _contiguous(args),
+                                      lse.contiguous(), d_token_loss.contiguous()))
+
+
+@torch.library.custom_op("srfrd::xent_fwd", mutates_args=(), device_types="cuda")
+def xent_fwd(hidden: torch.Tensor, targets: torch.Tensor, table: torch.Tensor, model_key: int) -> List[torch.Tensor]:
+    return _head_fwd(loss_heads.XENT, model_key, table, hidden, targets)
 
 
 @torch.library.custom_op("srfrd::xent_bwd", mutates_args=(), device_types="cuda")
 def xent_bwd(hidden: torch.Tensor, targets: torch.Tensor, table: torch.Tensor, lse: torch.Tensor, d_token_loss: torch.Tensor,
              model_key: int) -> List[torch.Tensor]:
-    """-> [d_hidden (B, L, d_out), d_table (n_items + 1, d_item)]"""
-    lay, tab = _xent_table(_model(model_key), table)
-    return list(xent_launch_bwd(lay, tab, hidden.contiguous(), targets.contiguous(), lse.contiguous(), d_token_loss.contiguous()))
-
-
-@xent_bwd.register_fake
-def _(hidden, targets, table, lse, d_token_loss, model_key):
-    return [torch.empty_like(hidden), torch.empty_like(table)]
-
-
-def _xent_setup(ctx, inputs, output):
-    hidden, targets, table, model_key = inputs
-    ctx.model_key = model_key
-    ctx.save_for_backward(hidden, targets, table, output[1])
-
-
-def _xent_backward(ctx, grads):
-    hidden, targets, table, lse = ctx.saved_tensors
-    g = grads[0]
-    if g is None:
-        return None, None, None, None
-    dh, de = torch.ops.srfrd.xent_bwd(hidden, targets, table, lse, g.contiguous(), ctx.model_key)
-    return dh, None, de, None
-
-
-xent_fwd.register_autograd(_xent_backward, setup_context=_xent_setup)
-
-
-# ------------------------------------------------------------------------------------------------ sampled softmax cross-entropy
-def sxent_launch_fwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor,
-                     log_q: Optional[torch.Tensor], remove_hits: bool):
-    """srfrd_sxent_fwd -> (token_loss (B, L), lse (B, L), stats {sum, count})"""
-    B, L = targets.shape
-    K = negatives.numel()
-    dev = hidden.device
-    L_ = _lib.lib()
-    ws = torch.empty(L_.srfrd_sxent_workspace_floats(C.byref(lay), B, L, K), device=dev, dtype=torch.float32)
-    tl = torch.empty(B, L, device=dev, dtype=torch.float32)
-    lse = torch.empty(B, L, device=dev, dtype=torch.float32)
-    stats = torch.empty(2, device=dev, dtype=torch.float32)
-    check(L_.srfrd_sxent_fwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(negatives), ptr(log_q), K, int(remove_hits),
-                             B, L, ptr(tl), ptr(lse), ptr(stats), ptr(ws), ws.numel(), _stream()), "srfrd_sxent_fwd")
-    return tl, lse, stats
-
-
-def sxent_launch_bwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor,
-                     log_q: Optional[torch.Tensor], remove_hits: bool, lse: torch.Tensor, d_token_loss: torch.Tensor):
-    """srfrd_sxent_bwd, then the stable key sort and srfrd_table_reduce -> (d_hidden (B, L, d_out), d_table (n_items + 1,
-    d_item)): every item's contribution rows (its negative slots in slot order, then its target tokens in position order)
-    summed in that fixed order"""
-    B, L = targets.shape
-    K = negatives.numel()
-    dev = hidden.device
-    L_ = _lib.lib()
-    ws = torch.empty(L_.srfrd_sxent_workspace_floats(C.byref(lay), B, L, K), device=dev, dtype=torch.float32)
-    dh = torch.empty(B, L, lay.d_out, device=dev, dtype=torch.float32)
-    contrib = torch.empty(K + B * L, lay.d_item, device=dev, dtype=torch.float32)
-    keys = torch.empty(K + B * L, device=dev, dtype=torch.int64)
-    check(L_.srfrd_sxent_bwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(negatives), ptr(log_q), K, int(remove_hits),
-                             ptr(lse), ptr(d_token_loss), B, L, ptr(dh), ptr(contrib), ptr(keys), ptr(ws), ws.numel(), _stream()),
-          "srfrd_sxent_bwd")
-    skeys, order = torch.sort(keys, stable=True)
-    de = torch.zeros(lay.n_items + 1, lay.d_item, device=dev, dtype=torch.float32)
-    check(L_.srfrd_table_reduce(ptr(skeys), ptr(order), ptr(contrib), skeys.numel(), lay.d_item, ptr(de), _stream()),
-          "srfrd_table_reduce")
-    return dh, de
+    return _head_bwd(loss_heads.XENT, model_key, table, lse, d_token_loss, hidden, targets)
 
 
 @torch.library.custom_op("srfrd::sxent_fwd", mutates_args=(), device_types="cuda")
 def sxent_fwd(hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor, log_q: Optional[torch.Tensor],
               table: torch.Tensor, remove_hits: bool, model_key: int) -> List[torch.Tensor]:
-    """-> [token_loss (B, L), lse (B, L), stats (2) = {sum, count}]"""
-    lay, tab = _xent_table(_model(model_key), table)
-    return list(sxent_launch_fwd(lay, tab, hidden.contiguous(), targets.contiguous(), negatives.contiguous(),
-                                 None if log_q is None else log_q.contiguous(), remove_hits))
-
-
-@sxent_fwd.register_fake
-def _(hidden, targets, negatives, log_q, table, remove_hits, model_key):
-    B, L = targets.shape
-    f = dict(device=hidden.device, dtype=torch.float32)
-    return [torch.empty(B, L, **f), torch.empty(B, L, **f), torch.empty(2, **f)]
+    return _head_fwd(loss_heads.SXENT, model_key, table, hidden, targets, negatives, log_q, remove_hits)
 
 
 @torch.library.custom_op("srfrd::sxent_bwd", mutates_args=(), device_types="cuda")
 def sxent_bwd(hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor, log_q: Optional[torch.Tensor],
               table: torch.Tensor, remove_hits: bool, lse: torch.Tensor, d_token_loss: torch.Tensor,
               model_key: int) -> List[torch.Tensor]:
-    """-> [d_hidden (B, L, d_out), d_table (n_items + 1, d_item)]"""
-    lay, tab = _xent_table(_model(model_key), table)
-    return list(sxent_launch_bwd(lay, tab, hidden.contiguous(), targets.contiguous(), negatives.contiguous(),
-                                 None if log_q is None else log_q.contiguous(), remove_hits, lse.contiguous(),
-                                 d_token_loss.contiguous()))
-
-
-@sxent_bwd.register_fake
-def _(hidden, targets, negatives, log_q, table, remove_hits, lse, d_token_loss, model_key):
-    return [torch.empty_like(hidden), torch.empty_like(table)]
-
-
-def _sxent_setup(ctx, inputs, output):
-    hidden, targets, negatives, log_q, table, remove_hits, model_key = inputs
-    ctx.model_key, ctx.remove_hits = model_key, remove_hits
-    ctx.save_for_backward(hidden, targets, negatives, log_q, table, output[1])
-
-
-def _sxent_backward(ctx, grads):
-    hidden, targets, negatives, log_q, table, lse = ctx.saved_tensors
-    g = grads[0]
-    if g is None:
-        return None, None, None, None, None, None, None
-    dh, de = torch.ops.srfrd.sxent_bwd(hidden, targets, negatives, log_q, table, ctx.remove_hits, lse, g.contiguous(),
-                                       ctx.model_key)
-    return dh, None, None, None, de, None, None
-
-
-sxent_fwd.register_autograd(_sxent_backward, setup_context=_sxent_setup)
-
-# ------------------------------------------------------------------------------------------------ K negatives per position
-def tneg_launch_fwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor,
-                    log_q: Optional[torch.Tensor], objective: int, beta: float, remove_hits: bool):
-    """srfrd_tneg_fwd -> (token_loss (B, L), lse (B, L), stats {sum, count}); negatives (B, L, K)"""
-    B, L = targets.shape
-    K = negatives.shape[2]
-    dev = hidden.device
-    L_ = _lib.lib()
-    ws = torch.empty(max(L_.srfrd_tneg_workspace_floats(C.byref(lay), B, L, K), 1), device=dev, dtype=torch.float32)
-    tl = torch.empty(B, L, device=dev, dtype=torch.float32)
-    lse = torch.empty(B, L, device=dev, dtype=torch.float32)
-    stats = torch.empty(2, device=dev, dtype=torch.float32)
-    check(L_.srfrd_tneg_fwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(negatives), ptr(log_q), K, objective, beta,
-                            int(remove_hits), B, L, ptr(tl), ptr(lse), ptr(stats), ptr(ws), ws.numel(), _stream()),
-          "srfrd_tneg_fwd")
-    return tl, lse, stats
-
-
-def tneg_launch_bwd(lay, table_ptr, hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor,
-                    log_q: Optional[torch.Tensor], objective: int, beta: float, remove_hits: bool, lse: torch.Tensor,
-                    d_token_loss: torch.Tensor):
-    """srfrd_tneg_bwd, then the stable key sort and srfrd_table_reduce_rank1 -> (d_hidden (B, L, d_out), d_table (n_items + 1,
-    d_item)): every item's rank-1 rows coef * hidden[t] summed in list order (position-major, the target before its
-    negatives)"""
-    B, L = targets.shape
-    K = negatives.shape[2]
-    dev = hidden.device
-    L_ = _lib.lib()
-    ws = torch.empty(max(L_.srfrd_tneg_workspace_floats(C.byref(lay), B, L, K), 1), device=dev, dtype=torch.float32)
-    dh = torch.empty(B, L, lay.d_out, device=dev, dtype=torch.float32)
-    coef = torch.empty(B * L * (1 + K), device=dev, dtype=torch.float32)
-    keys = torch.empty(B * L * (1 + K), device=dev, dtype=torch.int64)
-    check(L_.srfrd_tneg_bwd(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), ptr(negatives), ptr(log_q), K, objective, beta,
-                            int(remove_hits), ptr(lse), ptr(d_token_loss), B, L, ptr(dh), ptr(coef), ptr(keys), ptr(ws),
-                            ws.numel(), _stream()), "srfrd_tneg_bwd")
-    skeys, order = torch.sort(keys, stable=True)
-    de = torch.zeros(lay.n_items + 1, lay.d_item, device=dev, dtype=torch.float32)
-    check(L_.srfrd_table_reduce_rank1(ptr(skeys), ptr(order), ptr(coef), ptr(hidden), lay.d_out, 1 + K, skeys.numel(),
-                                      lay.d_item, ptr(de), ptr(ws), ws.numel(), _stream()), "srfrd_table_reduce_rank1")
-    return dh, de
+    return _head_bwd(loss_heads.SXENT, model_key, table, lse, d_token_loss, hidden, targets, negatives, log_q, remove_hits)
 
 
 @torch.library.custom_op("srfrd::tneg_fwd", mutates_args=(), device_types="cuda")
 def tneg_fwd(hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor, log_q: Optional[torch.Tensor],
              table: torch.Tensor, objective: int, beta: float, remove_hits: bool, model_key: int) -> List[torch.Tensor]:
-    """-> [token_loss (B, L), lse (B, L), stats (2) = {sum, count}]; objective: _lib.TNEG_OBJECTIVES"""
-    lay, tab = _xent_table(_model(model_key), table)
-    return list(tneg_launch_fwd(lay, tab, hidden.contiguous(), targets.contiguous(), negatives.contiguous(),
-                                None if log_q is None else log_q.contiguous(), objective, beta, remove_hits))
-
-
-@tneg_fwd.register_fake
-def _(hidden, targets, negatives, log_q, table, objective, beta, remove_hits, model_key):
-    B, L = targets.shape
-    f = dict(device=hidden.device, dtype=torch.float32)
-    return [torch.empty(B, L, **f), torch.empty(B, L, **f), torch.empty(2, **f)]
+    """objective: _lib.TNEG_OBJECTIVES"""
+    return _head_fwd(loss_heads.TNEG, model_key, table, hidden, targets, negatives, log_q, objective, beta, remove_hits)
 
 
 @torch.library.custom_op("srfrd::tneg_bwd", mutates_args=(), device_types="cuda")
 def tneg_bwd(hidden: torch.Tensor, targets: torch.Tensor, negatives: torch.Tensor, log_q: Optional[torch.Tensor],
              table: torch.Tensor, objective: int, beta: float, remove_hits: bool, lse: torch.Tensor, d_token_loss: torch.Tensor,
              model_key: int) -> List[torch.Tensor]:
-    """-> [d_hidden (B, L, d_out), d_table (n_items + 1, d_item)]"""
-    lay, tab = _xent_table(_model(model_key), table)
-    return list(tneg_launch_bwd(lay, tab, hidden.contiguous(), targets.contiguous(), negatives.contiguous(),
-                                None if log_q is None else log_q.contiguous(), objective, beta, remove_hits, lse.contiguous(),
-                                d_token_loss.contiguous()))
+    return _head_bwd(loss_heads.TNEG, model_key, table, lse, d_token_loss, hidden, targets, negatives, log_q, objective, beta,
+                     remove_hits)
 
 
-@tneg_bwd.register_fake
-def _(hidden, targets, negatives, log_q, table, objective, beta, remove_hits, lse, d_token_loss, model_key):
-    return [torch.empty_like(hidden), torch.empty_like(table)]
+def _head_fwd_fake(hidden, targets, *rest):
+    B, L = targets.shape
+    f = dict(device=hidden.device, dtype=torch.float32)
+    return [torch.empty(B, L, **f), torch.empty(B, L, **f), torch.empty(2, **f)]
 
 
-def _tneg_setup(ctx, inputs, output):
-    hidden, targets, negatives, log_q, table, objective, beta, remove_hits, model_key = inputs
-    ctx.meta = (objective, beta, remove_hits, model_key)
-    ctx.save_for_backward(hidden, targets, negatives, log_q, table, output[1])
+def _register_head(fwd, bwd, i_table):
+    """fakes and autograd of one head's op pair.  Both ops take (hidden, targets, [negatives, log_q,] table, *scalars, ...) with
+    the table at ``i_table``; the forward ends in model_key, the backward in (lse, d_token_loss, model_key)."""
+    def bwd_fake(*args):
+        return [torch.empty_like(args[0]), torch.empty_like(args[i_table])]
+
+    def setup_context(ctx, inputs, output):
+        ctx.rest = inputs[i_table + 1:]                                   # (*scalars, model_key)
+        ctx.save_for_backward(*inputs[:i_table + 1], output[1])
+
+    def backward(ctx, grads):
+        *tensors, lse = ctx.saved_tensors
+        out = [None] * (len(tensors) + len(ctx.rest))
+        if grads[0] is not None:
+            out[0], out[i_table] = bwd(*tensors, *ctx.rest[:-1], lse, grads[0].contiguous(), ctx.rest[-1])
+        return tuple(out)
+
+    fwd.register_fake(_head_fwd_fake)
+    bwd.register_fake(bwd_fake)
+    fwd.register_autograd(backward, setup_context=setup_context)
 
 
-def _tneg_backward(ctx, grads):
-    hidden, targets, negatives, log_q, table, lse = ctx.saved_tensors
-    g = grads[0]
-    if g is None:
-        return (None,) * 9
-    objective, beta, remove_hits, model_key = ctx.meta
-    dh, de = torch.ops.srfrd.tneg_bwd(hidden, targets, negatives, log_q, table, objective, beta, remove_hits, lse, g.contiguous(),
-                                      model_key)
-    return dh, None, None, None, de, None, None, None, None
-
-
-tneg_fwd.register_autograd(_tneg_backward, setup_context=_tneg_setup)
+_register_head(xent_fwd, xent_bwd, 2)
+_register_head(sxent_fwd, sxent_bwd, 4)
+_register_head(tneg_fwd, tneg_bwd, 4)
 
 
 OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "target_rank", "topk_merge",

@@ -28,7 +28,7 @@ import torch.distributed as dist
 
 import numpy as np
 
-from . import _lib
+from . import _lib, loss_heads
 from ._lib import check, ptr
 from .exchange import GradExchange, exchange_active, shard_bounds  # noqa: F401  (shard_bounds re-exported)
 from .sampler import alias_table, negative_q
@@ -228,16 +228,15 @@ class FusedTrainer:
                 self.alias_prob = torch.from_numpy(prob).to(dev)
                 self.alias_idx = torch.from_numpy(idx).to(dev)
                 self.item_log_q = torch.from_numpy(lq).to(dev)
-            n_ws = _lib.lib().srfrd_sxent_workspace_floats(C.byref(lay), B, L, K)
             # one contribution buffer for the whole table gradient: rows [0, 3T) the encoder's (pos, neg, input planes; only
             # the input plane carries anything here), rows [3T, 3T + K + T) the loss head's; keys of rows [2T, 4T + K)
             self.contrib_ce = torch.zeros(4 * T + K, lay.d_item, **f32)
             self.keys_ce = torch.zeros(2 * T + K, device=dev, dtype=torch.int64)
-        else:
-            n_ws = _lib.lib().srfrd_xent_workspace_floats(C.byref(lay), B, L)
-            if self.deterministic:
-                self.keys_in = torch.zeros(T, device=dev, dtype=torch.int64)
-                self.de_ce = torch.zeros(lay.n_items + 1, lay.d_item, **f32)
+        elif self.deterministic:
+            self.keys_in = torch.zeros(T, device=dev, dtype=torch.int64)
+            self.de_ce = torch.zeros(lay.n_items + 1, lay.d_item, **f32)
+        head = loss_heads.SXENT if self.sampled else loss_heads.XENT
+        n_ws = head.workspace(_lib.lib(), lay, B, L, self.K if self.sampled else 0)
         if n_ws <= 0:
             raise ValueError(f"loss={self.loss_kind!r}: the cross-entropy kernels refuse this model / shape")
         self.ce_ws = torch.zeros(n_ws, **f32)
@@ -348,32 +347,28 @@ class FusedTrainer:
                                          None, None, None, None, B, L, p, 0, seed_dev, seq0, ptr(self.hidden), None, None,
                                          ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), None, ptr(self.scratch),
                                          self.n_scratch, ptr(self.sched), self.sched_mode, st), "srfrd_encoder_fwd_sched")
-        table, tgt = ptr(self.flat), ptr(ids[2])                     # (the fp32 item table is the flat vector's head)
-        stats_sc = C.c_void_p(self.stats.data_ptr() + 4)             # {sum, count} -> stats[1], stats[2]
-        ws, n_ws = ptr(self.ce_ws), self.ce_ws.numel()
+        # the loss head (loss_heads.py) on the step's own buffers; the fp32 item table is the flat vector's head
         if self.sampled:
-            neg, K, rh = ptr(self._negatives), self.K, int(self.remove_hits)
-            lq = ptr(self._log_q) if self.logq_correction else None
-            check(L_.srfrd_sxent_fwd(C.byref(lay), table, ptr(self.hidden), tgt, neg, lq, K, rh, B, L, ptr(self.token_loss),
-                                     ptr(self.lse), stats_sc, ws, n_ws, st), "srfrd_sxent_fwd")
-            check(L_.srfrd_sxent_bwd(C.byref(lay), table, ptr(self.hidden), tgt, neg, lq, K, rh, ptr(self.lse), ptr(self.d_token),
-                                     B, L, ptr(self.d_hidden), C.c_void_p(self.contrib_ce.data_ptr() + 4 * 3 * T * di),
-                                     C.c_void_p(self.keys_ce.data_ptr() + 8 * T), ws, n_ws, st), "srfrd_sxent_bwd")
-            table_grad, contrib = ptr(self.grad), ptr(self.contrib_ce)
+            # its contribution rows and keys land behind the encoder's in the merged buffers, unreduced: the one sort below
+            head, args = loss_heads.SXENT, (self._negatives, self._log_q if self.logq_correction else None, self.remove_hits)
+            grad_to = dict(rows=self.contrib_ce[3 * T:], keys=self.keys_ce[T:], finish=False)
+            contrib = ptr(self.contrib_ce)
         else:
-            det = self.contrib is not None
             # xent_bwd writes a dense table gradient; the deterministic encoder table reduction below STORES its rows, so
             # there the head's part waits in de_ce and is added afterwards
-            check(L_.srfrd_xent_fwd(C.byref(lay), table, ptr(self.hidden), tgt, B, L, ptr(self.token_loss), ptr(self.lse),
-                                    stats_sc, ws, n_ws, st), "srfrd_xent_fwd")
-            check(L_.srfrd_xent_bwd(C.byref(lay), table, ptr(self.hidden), tgt, ptr(self.lse), ptr(self.d_token), B, L,
-                                    ptr(self.d_hidden), ptr(self.de_ce) if det else ptr(self.grad), 0 if det else 1, ws, n_ws, st),
-                  "srfrd_xent_bwd")
-            table_grad, contrib = ptr(self.grad), ptr(self.contrib)
+            det = self.contrib is not None
+            head, args = loss_heads.XENT, ()
+            grad_to = dict(d_table=self.de_ce if det else self.grad, accumulate=not det)
+            contrib = ptr(self.contrib)
+        table, tgt = ptr(self.flat), ids[2]
+        loss_heads.launch_fwd(head, lay, table, self.hidden, tgt, args, ws=self.ce_ws,
+                              out=(self.token_loss, self.lse, self.stats[1:]))       # {sum, count} -> stats[1], stats[2]
+        loss_heads.launch_bwd(head, lay, table, self.hidden, tgt, args, self.lse, self.d_token, ws=self.ce_ws,
+                              d_hidden=self.d_hidden, **grad_to)
         check(L_.srfrd_encoder_bwd_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk),
                                          None, None, None, None, B, L, p, 0, seed_dev, seq0, ptr(self.hidden), None, None,
                                          ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), ptr(self.d_hidden), None, None, 0,
-                                         table_grad, contrib, ptr(self.slabs), ptr(self.scratch), self.n_scratch, ptr(self.sched),
+                                         ptr(self.grad), contrib, ptr(self.slabs), ptr(self.scratch), self.n_scratch, ptr(self.sched),
                                          self.sched_mode, st), "srfrd_encoder_bwd_sched")
         if self.sampled:
             # one stable sort of [input ids (T) | the head's keys (K + T)]; the rows they key are contrib_ce[2T:]

@@ -161,7 +161,8 @@ def test_tneg_gather_shapes_of_a_misaligned_table(d_item):
     """with_shape narrows the row loads when the table does not start on a 16- or 8-byte boundary.  torch's allocations always
     do, so the launch-level functions the srfrd::tneg_* ops call are given a table that starts 0, 1 and 2 floats into a larger
     buffer.  The three results agree to the tolerances, not bitwise: the shapes group the dot product's sum differently."""
-    from srfrd_amd import _lib, ops
+    from srfrd_amd import _lib
+    from srfrd_amd.loss_heads import TNEG, launch_bwd, launch_fwd
     n_items, K = 257, 65
     torch.manual_seed(4000 + d_item)
     m = _model(d_item, 0, n_items)
@@ -187,8 +188,8 @@ def test_tneg_gather_shapes_of_a_misaligned_table(d_item):
             shapes.add(tneg_shape(d_item, addr))
             out = []
             for _ in range(2):
-                tl, lse, stats = ops.tneg_launch_fwd(lay, C.c_void_p(addr), h, y, neg, lq, code, beta, True)
-                dh, de = ops.tneg_launch_bwd(lay, C.c_void_p(addr), h, y, neg, lq, code, beta, True, lse, ones)
+                tl, lse, stats = launch_fwd(TNEG, lay, C.c_void_p(addr), h, y, (neg, lq, code, beta, True))
+                dh, de = launch_bwd(TNEG, lay, C.c_void_p(addr), h, y, (neg, lq, code, beta, True), lse, ones)
                 out.append((tl, stats, dh, de))
             for a, b in zip(*out):
                 assert torch.equal(a, b), (objective, off)

@@ -33,7 +33,7 @@ def child(name: str, reps: int) -> dict:
     sys.path.insert(0, ROOT)
     import torch
     import srfrd_amd
-    from srfrd_amd import ops
+    from srfrd_amd.loss_heads import SXENT, launch_bwd, launch_fwd
     from srfrd_amd._lib import ptr
     cfg = CONFIGS[name]
     I, L, B, K = cfg["I"], cfg["L"], cfg["B"], cfg["K"]
@@ -49,10 +49,10 @@ def child(name: str, reps: int) -> dict:
     neg, log_q = srfrd_amd.sample_negatives(I, K, generator=torch.Generator(device="cuda").manual_seed(2))
     lay, tab = m.layout, ptr(m.flat_parameters())
     tokens = int((pos != 0).sum())
-    tl, lse, stats = ops.sxent_launch_fwd(lay, tab, h, pos, neg, log_q, True)
+    tl, lse, stats = launch_fwd(SXENT, lay, tab, h, pos, (neg, log_q, True))
     g = (torch.ones((), device="cuda") / stats[1]).expand(B, L).contiguous()
-    runs = {"fwd": lambda: ops.sxent_launch_fwd(lay, tab, h, pos, neg, log_q, True),
-            "bwd": lambda: ops.sxent_launch_bwd(lay, tab, h, pos, neg, log_q, True, lse, g)}
+    runs = {"fwd": lambda: launch_fwd(SXENT, lay, tab, h, pos, (neg, log_q, True)),
+            "bwd": lambda: launch_bwd(SXENT, lay, tab, h, pos, (neg, log_q, True), lse, g)}
     if 4.0 * tokens * (K + 1) * 4 <= TORCH_LIMIT_BYTES:
         E = m.item_emb.weight.detach().clone().requires_grad_(True)
         hv = h.detach().clone().requires_grad_(True)

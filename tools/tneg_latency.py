@@ -33,7 +33,8 @@ def child(name: str, reps: int, only: str | None = None) -> list:
     import ctypes as C
     import torch
     import srfrd_amd
-    from srfrd_amd import _lib, ops
+    from srfrd_amd import _lib
+    from srfrd_amd.loss_heads import TNEG, launch_bwd, launch_fwd
     from srfrd_amd._lib import check, ptr
     cfg = CONFIGS[name]
     I, L, B, K = cfg["I"], cfg["L"], cfg["B"], cfg["K"]
@@ -58,7 +59,7 @@ def child(name: str, reps: int, only: str | None = None) -> list:
             continue
         code = _lib.TNEG_OBJECTIVES[objective]
         lq = log_q if objective == "softmax" else None
-        tl, lse, stats = ops.tneg_launch_fwd(lay, tab, h, pos, neg, lq, code, beta, True)
+        tl, lse, stats = launch_fwd(TNEG, lay, tab, h, pos, (neg, lq, code, beta, True))
         g = (torch.ones((), device="cuda") / stats[1]).expand(B, L).contiguous()
         # the backward's three parts on buffers of their own
         ws = torch.empty(L_.srfrd_tneg_workspace_floats(C.byref(lay), B, L, K), device="cuda", dtype=torch.float32)
@@ -95,8 +96,8 @@ def child(name: str, reps: int, only: str | None = None) -> list:
                 f = torch.nn.functional.softplus
                 loss = (beta * f(-sp) + f(sn).masked_fill(mask, 0.0).sum(1)).mean()
             loss.backward()
-        runs = {"fwd": lambda: ops.tneg_launch_fwd(lay, tab, h, pos, neg, lq, code, beta, True),
-                "bwd": lambda: ops.tneg_launch_bwd(lay, tab, h, pos, neg, lq, code, beta, True, lse, g),
+        runs = {"fwd": lambda: launch_fwd(TNEG, lay, tab, h, pos, (neg, lq, code, beta, True)),
+                "bwd": lambda: launch_bwd(TNEG, lay, tab, h, pos, (neg, lq, code, beta, True), lse, g),
                 "bwd_kernel": bwd_kernel, "sort": lambda: torch.sort(keys, stable=True), "reduce": reduce,
                 "torch_fp32_fwd_bwd": torch_step}
         out = _time(runs, {"config": name, "objective": objective, **cfg, "tokens": tokens, "reps": reps}, reps)

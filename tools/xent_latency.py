@@ -30,7 +30,7 @@ def child(name: str, reps: int) -> dict:
     import torch
     import torch.nn.functional as F
     import srfrd_amd
-    from srfrd_amd import ops
+    from srfrd_amd.loss_heads import XENT, launch_bwd, launch_fwd
     from srfrd_amd._lib import ptr
     cfg = CONFIGS[name]
     I, L, B = cfg["I"], cfg["L"], cfg["B"]
@@ -45,10 +45,10 @@ def child(name: str, reps: int) -> dict:
         h, _, _ = m(None, seq, rsq)
     lay, tab = m.layout, ptr(m.flat_parameters())
     tokens = int((pos != 0).sum())
-    tl, lse, stats = ops.xent_launch_fwd(lay, tab, h, pos)
+    tl, lse, stats = launch_fwd(XENT, lay, tab, h, pos)
     g = (torch.ones((), device="cuda") / stats[1]).expand(B, L).contiguous()
-    runs = {"fwd": lambda: ops.xent_launch_fwd(lay, tab, h, pos),
-            "bwd": lambda: ops.xent_launch_bwd(lay, tab, h, pos, lse, g)}
+    runs = {"fwd": lambda: launch_fwd(XENT, lay, tab, h, pos),
+            "bwd": lambda: launch_bwd(XENT, lay, tab, h, pos, (), lse, g)}
     if 4.0 * tokens * I * 4 <= TORCH_LIMIT_BYTES:
         E = m.item_emb.weight.detach().clone().requires_grad_(True)
         hv = h.detach().clone().requires_grad_(True)
