@@ -223,7 +223,10 @@ int srfrd_encoder_bwd_sched(const srfrd_layout* lay, const void* item_table, con
  * sequence's forward and then its backward.  Arguments: the union of the two calls' (hidden / pos_logits / neg_logits /
  * save_* are written and read back); results are those of the two calls bit for bit.  Where the kernel plan has no train
  * kernel for the call (srfrd_encoder_plan_train: where the ragged seq_len-50 pair serves a call with SRFRD_PLAN_POS, _NEG,
- * _CKPT, _LOSS and _FUSED_BCE, dropout or not), returns SRFRD_E_UNSUPPORTED and launches nothing: make the two calls instead. */
+ * _CKPT, _LOSS and _FUSED_BCE, dropout or not), returns SRFRD_E_UNSUPPORTED and launches nothing: make the two calls instead.
+ * scratch: srfrd_train_scratch_floats(lay, B, L) floats or more (SRFRD_E_ARG otherwise) - where a workgroup's forward leaves
+ * the head's hidden-state gradient for its backward; contents are of no use to the caller. */
+int64_t srfrd_train_scratch_floats(const srfrd_layout* lay, int B, int L);
 int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
                               const int64_t* input_ids, const int64_t* fake_ids,
                               const int64_t* pos_ids, const int64_t* pos_fake,

@@ -58,6 +58,7 @@ SIGNATURES = {
     "srfrd_encoder_bwd_sched": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _P, _i64, _P, _i, _P]),
     "srfrd_encoder_plan_train": (_i, [_LP, _i, _i, _i, _i, _i, _i64, _P, _i, _P]),
+    "srfrd_train_scratch_floats": (_i64, [_LP, _i, _i]),
     "srfrd_encoder_train_sched": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
                                        _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _P, _i64, _P, _i, _P]),
     "srfrd_table_reduce": (_i, [_P, _P, _P, _i64, _i, _P, _P]),

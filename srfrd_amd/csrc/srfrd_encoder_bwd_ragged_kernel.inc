@@ -33,8 +33,11 @@ struct RagBwdLds {
 // The ragged backward of sequence b (the workgroup's iter-th) by the whole workgroup (512 threads): reads the checkpoints
 // of the ragged forward, scatters item-row gradients, accumulates the dense ones into this workgroup's slab and s_lng; ends
 // with a workgroup barrier.  tid: the laundered thread index (see launder), wave: its wave (uniform).
-template <int K_, int DI_, bool RMW_>
-__device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m, int b, int iter, int& tid, int wave, uint32_t seed) {
+// SEAM_ (the train kernel): rag_fwd_seq<.., SEAM_> of the same workgroup has done the head's first part - d hidden comes from
+// a.head_dh in one coalesced read, the target rows' item-table contributions are out already; seam_th is the th it returned.
+template <int K_, int DI_, bool RMW_, bool SEAM_ = false>
+__device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m, int b, int iter, int& tid, int wave, uint32_t seed,
+                                            int seam_th = 0) {
   const Dims& ly = a.dm;
   constexpr int nw = 8, nthr = 512;
   constexpr int L = 50, D = 50, LP = 64, DK = 52, DS = 54, NT = 4, MT = 4;
@@ -109,13 +112,17 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
     s_pfk[t] = (in && a.pos_fk) ? clamp_id(a.pos_fk[rowbase + t], 2) : 0;
     s_nfk[t] = (in && a.neg_fk) ? clamp_id(a.neg_fk[rowbase + t], 2) : 0;
     float dp = 0.f, dn = 0.f;
-    if (in) {
-      if (a.fused_bce) {                   // fused masked BCE (trainer.py:36-38): both terms indexed by pos != 0
-        const float pl = a.c_pl[rowbase + t], nl = a.c_nl[rowbase + t];
-        if (pid != 0) {
-          dp = sigmoid_f(pl) - 1.0f;
-          dn = sigmoid_f(nl);
+    if constexpr (SEAM_) {                 // (only SRFRN's side-channel sums still read the logit gradients)
+      if constexpr (K_ == SRFRD_SRFRN)
+        if (in) {
+          const float* dl = a.head_dh + (int64_t)B * L * dout + rowbase * 2;
+          dp = dl[t];
+          dn = dl[L + t];
         }
+    } else if (in) {
+      if (a.fused_bce) {                   // fused masked BCE
+        const float pl = a.c_pl[rowbase + t], nl = a.c_nl[rowbase + t];
+        bce_dlogits(pid, pl, nl, dp, dn);
       } else {                             // upstream logit gradients (the autograd path)
         if (a.d_pos && a.pos_ids) dp = a.d_pos[rowbase + t];
         if (a.d_neg && a.neg_ids) dn = a.d_neg[rowbase + t];
@@ -139,6 +146,7 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
     th = ng ? (int)__builtin_ctzll(ng) : L;
     if (a.ragged_off) t0 = 0;
     if (a.d_hidden != nullptr || a.ragged_off) th = 0;
+    if constexpr (SEAM_) th = seam_th;
     t0 = __builtin_amdgcn_readfirstlane(t0);
     th = __builtin_amdgcn_readfirstlane(th);
   }
@@ -148,9 +156,9 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
   const int p0 = r0 > SH ? r0 - SH : 0;                    // first position of the computed tiles
   const int k0 = p0 + SH;                                  // first token of the token sums (tile coordinates)
   // head: tiles from the first position with an upstream gradient (never behind the blocks' range)
-  const int hp = th < krp ? th : krp;
-  const int mh0 = (hp + SH) >> 4, rh0 = mh0 << 4, mhn = MT - mh0;
-  const int ph0 = rh0 > SH ? rh0 - SH : 0, kh0 = ph0 + SH;
+  const RagHead hr = rag_head_range(th, krp);
+  const int mh0 = hr.tile0, mhn = MT - mh0;
+  const int ph0 = hr.pos0, kh0 = ph0 + SH;
 
   lds_f *sX = slot[0], *sQ = slot[1], *sG = slot[2], *sT = slot[3], *sK = slot[4], *sO = slot[5];
   // GEMM epilogues are BRANCH-FREE: an element outside the matrix (column >= D of the last strip, or a tile row in front of
@@ -164,6 +172,22 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
   g_last.load(a.c_save_x + x_off(ly.n_blocks, b, ly.n_blocks, L, D) + p0 * D, L - p0, D, nthr);
   g_h1.load(a.c_save_h1 + h1_off(ly.n_blocks - 1, b, ly.n_blocks, L, D) + p0 * D, L - p0, D, nthr);
   g_r.load(a.c_save_aux + aux_off(ly.n_blocks - 1, b, ly.n_blocks, L, LP, D).r + p0 * D, L - p0, D, nthr);
+  if constexpr (SEAM_) {                // d hidden of the head range -> sG (SRFRN: the hidden rows -> sT for the side-channel sums)
+    constexpr bool V2 = dout % 2 == 0;    // (8-byte accesses: every head range starts at an even float offset)
+    constexpr int HIT = (L * (V2 ? dout / 2 : dout) + nthr - 1) / nthr;
+    G2L<HIT, V2> g_dh;
+    g_dh.load(a.head_dh + (rowbase + ph0) * dout, L - ph0, dout, nthr);
+    g_dh.store(sG + ph0 * DS, DS, L - ph0, dout, nthr);
+    if constexpr (K_ == SRFRD_SRFRN) {
+      g_dh.load(a.c_hidden + (rowbase + ph0) * dout, L - ph0, dout, nthr);
+      g_dh.store(sT + ph0 * DS, DS, L - ph0, dout, nthr);
+    }
+    if (dout < D)
+      for (int idx = tid; idx < (L - ph0) * (D - dout); idx += nthr) {
+        const int tt = idx / (D - dout), cc = dout + idx - tt * (D - dout);
+        sG[(ph0 + tt) * DS + cc] = 0.f;
+      }
+  }
   g_last.store(sX + p0 * DS, DS, L - p0, D, nthr);
   // (head rows in front of the blocks' range - pad positions that carry an upstream gradient - are exact zeros: the
   // forward did not write them)
@@ -234,7 +258,7 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
     lnin = sQ;
   }
   // ---- logits backward.  Pass 1: dh -> sG and the hidden rows -> sT (positions ph0 .. L - 1, coalesced row gathers)
-  {
+  if constexpr (!SEAM_) {
     const bool srfrn = K_ == SRFRD_SRFRN;
     const int n = (L - ph0) * dout;
     constexpr int GIT = (LP * D + nthr - 1) / nthr;
@@ -274,7 +298,7 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
           if (i < n) {
             const int tt = i / dout, c = i - tt * dout, t = ph0 + tt;
             float dh = dhid ? dhid[i] : 0.f;
-            if (c < di || srfrn) dh += s_dpl[t] * pv[u] + s_dnl[t] * nv[u];
+            if (c < di || srfrn) dh = head_dh(dh, s_dpl[t], pv[u], s_dnl[t], nv[u]);
             sT[t * DS + c] = hv[u];
             sG[t * DS + c] = dh;
           }
@@ -289,9 +313,9 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
         sG[(ph0 + tt) * DS + cc] = 0.f;
       }
   }
-  __syncthreads();
+  if constexpr (!SEAM_) __syncthreads();
   // Pass 2: item-table scatter (float atomics, no return): at most two contiguous row segments per wave-instruction
-  {
+  if constexpr (!SEAM_) {
     int t = ph0 + tid / di, c = tid - (tid / di) * di;
     constexpr int dt = nthr / di, dc = nthr - dt * di;
     for (; t < L;) {
@@ -299,11 +323,11 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
       const float dp = s_dpl[t], dn = s_dnl[t];
       const int pid = s_pid[t], nid = s_nid[t];
       if (a.contrib != nullptr) {          // deterministic mode: see srfrd_encoder_bwd_kernel.inc
-        a.contrib[(((int64_t)0 * B + b) * L + t) * di + c] = pid != 0 ? dp * h : 0.f;
-        a.contrib[(((int64_t)1 * B + b) * L + t) * di + c] = nid != 0 ? dn * h : 0.f;
+        a.contrib[(((int64_t)0 * B + b) * L + t) * di + c] = pid != 0 ? head_contrib(dp, h) : 0.f;
+        a.contrib[(((int64_t)1 * B + b) * L + t) * di + c] = nid != 0 ? head_contrib(dn, h) : 0.f;
       } else {
-        if (pid != 0 && dp != 0.f) atomicAdd(&a.grad_table[(int64_t)pid * di + c], dp * h);
-        if (nid != 0 && dn != 0.f) atomicAdd(&a.grad_table[(int64_t)nid * di + c], dn * h);
+        if (pid != 0 && dp != 0.f) atomicAdd(&a.grad_table[(int64_t)pid * di + c], head_contrib(dp, h));
+        if (nid != 0 && dn != 0.f) atomicAdd(&a.grad_table[(int64_t)nid * di + c], head_contrib(dn, h));
       }
       t += dt; c += dc;
       if (c >= di) { c -= di; ++t; }

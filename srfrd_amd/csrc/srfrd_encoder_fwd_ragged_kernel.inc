@@ -122,6 +122,50 @@ __device__ __forceinline__ int rag_take(const EncArgs& a, lds_i* scr, int iter, 
 // that every lane of the head pass executes)
 __device__ __forceinline__ float softplus_fast(float z) { return fmaxf(z, 0.f) + __logf(1.0f + __expf(-fabsf(z))); }
 
+// The fused masked BCE's logit gradients (trainer.py:36-38: both terms indexed by pos != 0) and what they send back into the
+// head: one definition for the backward's head and the train kernel's forward head (SEAM_), so that both contract the same way.
+__device__ __forceinline__ void bce_dlogits(int pid, float pl, float nl, float& dp, float& dn) {
+  if (pid != 0) {
+    dp = sigmoid_f(pl) - 1.0f;
+    dn = sigmoid_f(nl);
+  }
+}
+// d hidden[t][c] of a column with target rows: the upstream gradient (0 under the fused BCE) plus dp * (positive row) +
+// dn * (negative row)
+__device__ __forceinline__ float head_dh(float up, float dp, float pv, float dn, float nv) {
+  up += dp * pv + dn * nv;
+  return up;
+}
+// head_dh(0, ...) as the backward's instantiation of kind K_ computes it.  Under -ffp-contract=fast hipcc contracts the
+// expression above by its surroundings: in SRFRN's backward to fma(dn, nv, fma(dp, pv, up)), in the other kinds' to two rounded
+// products and their sum.  The train kernel's forward head stands elsewhere, so it pins the form (the empty asm keeps a rounded
+// product from being fused again); tests/test_gpu_fused_train.py and tests/test_gpu_train_seam.py hold the one-launch step to
+// the two-launch step bit for bit, for every kind.
+template <int K_>
+__device__ __forceinline__ float head_dh_as_backward(float dp, float pv, float dn, float nv) {
+  float a = dp * pv;
+  asm volatile("" : "+v"(a));
+  if constexpr (K_ == SRFRD_SRFRN) return __builtin_fmaf(dn, nv, a);
+  float b = dn * nv;
+  asm volatile("" : "+v"(b));
+  return a + b;
+}
+// ... and the two rows' item-table contributions: dp * h, dn * h
+__device__ __forceinline__ float head_contrib(float dl, float h) { return dl * h; }
+// Head range of the backward: the first position of the 16-row tiles that hold position min(th, krp), th the first position
+// with an upstream gradient, krp the representative key.  tile0: the first tile, pos0: its first position.
+struct RagHead {
+  int tile0, pos0;
+};
+__device__ __forceinline__ RagHead rag_head_range(int th, int krp) {
+  const int hp = th < krp ? th : krp;
+  RagHead r;
+  r.tile0 = (hp + kRagSH) >> 4;
+  const int rh0 = r.tile0 << 4;
+  r.pos0 = rh0 > kRagSH ? rh0 - kRagSH : 0;
+  return r;
+}
+
 // Packed-weight GEMM group for the ragged kernels: gemm_group_packed (srfrd_dev.h) with
 //   * an optional SECOND product accumulated into the same tiles (C = A1 W1 + A2 W2: the backward's dx = dk Wk + dv Wv without
 //     a store and a read-modify-write in between),
@@ -387,8 +431,13 @@ struct RagFwdLds {
 // The ragged forward of sequence b by the whole workgroup (512 threads), from its ids to its hidden states, logits, BCE
 // partial sums and (training) checkpoints; ends with a workgroup barrier.  tid: the laundered thread index (see launder),
 // wave: its wave (uniform).
-template <int K_, int T_, int DI_>
-__device__ __forceinline__ void rag_fwd_seq(const EncArgs& a, const RagFwdLds& m, int b, int& tid, int wave, uint32_t seed) {
+// SEAM_ (the train kernel, fused BCE): the head also does the first part of the backward's head while the target rows, the
+// hidden rows and the logits are at hand - the logit gradients, d hidden -> a.head_dh (the backward's head range, [L][d_out] per
+// sequence; SRFRN: the logit gradients behind it) and, as its last action, the target rows' item-table contributions (float
+// atomics, or the rows of a.contrib).  Returns th, the first position with an upstream gradient (0 without SEAM_).
+template <int K_, int T_, int DI_, bool SEAM_ = false>
+__device__ __forceinline__ int rag_fwd_seq(const EncArgs& a, const RagFwdLds& m, int b, int& tid, int wave, uint32_t seed) {
+  static_assert(!SEAM_ || T_ != 0, "the head seam belongs to the training forward");
   const Dims& ly = a.dm;
   constexpr int D = 50, L = 50, LP = 64, DK = 52, DS = 54, SLD = 66, NT = 4, MT = 4, SH = kRagSH;
   constexpr int nw = 8, nthr = 512;
@@ -620,6 +669,7 @@ __device__ __forceinline__ void rag_fwd_seq(const EncArgs& a, const RagFwdLds& m
   // ---- head: (last_conv) -> last LayerNorm -> hidden, pos/neg logits, BCE partial sums        (every position: a padded
   // row's hidden state is LayerNorm(0 or b_lc), its logits against the table's row 0 - outputs the reference has too)
   const bool lo_h = !TR_ && a.last_only != 0;
+  int seam_th = 0;
   asm volatile("" : "+v"(tid));
   const int lane = tid & 63;
   if (!lo_h && r0 > SH) {                    // the positions in front of the computed tiles: exact zeros (S overlaid them)
@@ -655,18 +705,27 @@ __device__ __forceinline__ void rag_fwd_seq(const EncArgs& a, const RagFwdLds& m
     const bool srfrn = kind == SRFRD_SRFRN;
     lds_f* kp = bK + SH * DS;
     lds_f* vp = bV + SH * DS;
+    lds_f* s_dp = bXS + LP * DS;               // SEAM_: the logit gradients by position, behind the [LP][DS] view of x
+    lds_f* s_dn = s_dp + LP;
+    static_assert(LP * DS + 2 * LP <= LP * SLD, "logit gradients inside the x / scores matrix");
     {
       int t = tid / dout, c = tid - t * dout;
       constexpr int dt = nthr / dout, dc = nthr - dt * dout;
       for (; t < L;) {
         const float h = qnp[t * DS + c];
         a.hidden[(rowbase + t) * dout + c] = h;
-        if (has_pos)
-          kp[t * DS + c] = h * (c < di ? table((int64_t)s_pid[t + SH] * di + c)
-                                       : (srfrn ? P[ly.off_side + clamp_id(a.pos_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f));
-        if (has_neg)
-          vp[t * DS + c] = h * (c < di ? table((int64_t)s_nid[t + SH] * di + c)
-                                       : (srfrn ? P[ly.off_side + clamp_id(a.neg_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f));
+        if (has_pos) {
+          const float pv = c < di ? table((int64_t)s_pid[t + SH] * di + c)
+                                  : (srfrn ? P[ly.off_side + clamp_id(a.pos_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f);
+          kp[t * DS + c] = h * pv;
+          if constexpr (SEAM_) xp[t * DS + c] = pv;           // (x and, below, the last_conv output are dead: the rows wait there)
+        }
+        if (has_neg) {
+          const float nv = c < di ? table((int64_t)s_nid[t + SH] * di + c)
+                                  : (srfrn ? P[ly.off_side + clamp_id(a.neg_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f);
+          vp[t * DS + c] = h * nv;
+          if constexpr (SEAM_) bQ[(t + SH) * DS + c] = nv;
+        }
         t += dt; c += dc;
         if (c >= dout) { c -= dout; ++t; }
       }
@@ -688,6 +747,12 @@ __device__ __forceinline__ void rag_fwd_seq(const EncArgs& a, const RagFwdLds& m
       if (q == 0) {
         if (has_pos) a.pos_logits[rowbase + t] = pl;
         if (has_neg) a.neg_logits[rowbase + t] = nl;
+        if constexpr (SEAM_) {
+          float dp = 0.f, dn = 0.f;
+          bce_dlogits(s_pid[t + SH], pl, nl, dp, dn);
+          s_dp[t] = dp;
+          s_dn[t] = dn;
+        }
         if (do_loss && s_pid[t + SH] != 0) {     // trainer.py:36-38: both terms indexed by pos != 0
           sp += softplus_fast(-pl);
           sn += softplus_fast(nl);
@@ -709,8 +774,52 @@ __device__ __forceinline__ void rag_fwd_seq(const EncArgs& a, const RagFwdLds& m
         a.loss_part[(int64_t)b * 3 + tid] = s;
       }
     }
+    if constexpr (SEAM_) {
+      // (the barrier of the loss sums stands between the logit gradients' stores and these reads)
+      const int l0 = tid & 63;
+      const unsigned long long ng = __ballot(l0 < L && (s_in[l0 + SH] != 0 || s_dp[l0] != 0.f || s_dn[l0] != 0.f));
+      seam_th = ng ? (int)__builtin_ctzll(ng) : L;
+      if (a.ragged_off) seam_th = 0;
+      seam_th = __builtin_amdgcn_readfirstlane(seam_th);
+      const int ph0 = rag_head_range(seam_th, t0 >= 1 ? t0 - 1 : 0).pos0;
+      float* dhb = a.head_dh + (rowbase + ph0) * dout;
+      const int B = a.B;
+      int t = ph0 + tid / dout, c = tid - (tid / dout) * dout, i = tid;
+      constexpr int dt = nthr / dout, dc = nthr - dt * dout;
+      for (; t < L;) {
+        const float dp = s_dp[t], dn = s_dn[t];
+        float dh = 0.f;
+        if (c < di || srfrn) dh = head_dh_as_backward<K_>(dp, xp[t * DS + c], dn, bQ[(t + SH) * DS + c]);
+        dhb[i] = dh;
+        if (c < di) {
+          const float h = qnp[t * DS + c];
+          const int pid = s_pid[t + SH], nid = s_nid[t + SH];
+          if (a.contrib != nullptr) {          // deterministic mode: see srfrd_encoder_bwd_kernel.inc
+            a.contrib[(((int64_t)0 * B + b) * L + t) * di + c] = pid != 0 ? head_contrib(dp, h) : 0.f;
+            a.contrib[(((int64_t)1 * B + b) * L + t) * di + c] = nid != 0 ? head_contrib(dn, h) : 0.f;
+          } else {
+            if (pid != 0 && dp != 0.f) atomicAdd(&a.grad_table[(int64_t)pid * di + c], head_contrib(dp, h));
+            if (nid != 0 && dn != 0.f) atomicAdd(&a.grad_table[(int64_t)nid * di + c], head_contrib(dn, h));
+          }
+        }
+        t += dt; c += dc; i += nthr;
+        if (c >= dout) { c -= dout; ++t; }
+      }
+      if (a.contrib != nullptr)              // (the sorted reduction reads every row of the batch: rows in front of the head are zeros)
+        for (int idx = tid; idx < ph0 * di; idx += nthr) {
+          a.contrib[(((int64_t)0 * B + b) * L) * di + idx] = 0.f;
+          a.contrib[(((int64_t)1 * B + b) * L) * di + idx] = 0.f;
+        }
+      if constexpr (K_ == SRFRD_SRFRN)       // the side-channel sums of the backward's head weigh the hidden rows by these
+        if (tid < L) {
+          float* dl = a.head_dh + (int64_t)B * L * dout + rowbase * 2;
+          dl[tid] = s_dp[tid];
+          dl[L + tid] = s_dn[tid];
+        }
+    }
   }
   __syncthreads();
+  return seam_th;
 }
 
 template <int K_, int T_, int DI_>

@@ -3,6 +3,8 @@
 // names, the forward, a workgroup barrier, then the backward - which reads only what the same workgroup has just written
 // (checkpoints, hidden states, logits): a workgroup-scope fence is all the hand-off needs, no workgroup waits for another.
 // The BCE normaliser (the global target count) enters later, in the Adam step, so nothing in here needs the whole batch.
+// The forward's head also does the first part of the backward's head (SEAM_ of rag_fwd_seq / rag_bwd_seq): logit gradients,
+// d hidden -> a.head_dh, the target rows' item-table contributions; the backward starts from d hidden.
 //
 // Against the two launches: a long sequence's backward no longer waits for the slowest forward on the chip, and once its
 // short partner on the CU has finished, it runs alone.  Results are those of the two launches bit for bit: same
@@ -57,11 +59,11 @@ __global__ void __launch_bounds__(512, 4) encoder_train_ragged_kernel(const EncA
     }
     const int b = __builtin_amdgcn_readfirstlane(rag_take(a, (lds_i*)fm.bXS, iter, tid, t0v));
     if (b < 0) break;
-    rag_fwd_seq<K_, 1, DI_>(a, fm, b, tid, wave, seed);
+    const int th = rag_fwd_seq<K_, 1, DI_, true>(a, fm, b, tid, wave, seed);
     // (rag_fwd_seq ended with a workgroup barrier: its checkpoint stores are visible to every wave of the workgroup)
     for (int i = tid; i < W; i += nthr) base[i] = 0.f;
     __syncthreads();
-    rag_bwd_seq<K_, DI_, RMW_>(a, bm, b, iter, tid, wave, seed);
+    rag_bwd_seq<K_, DI_, RMW_, true>(a, bm, b, iter, tid, wave, seed, th);
   }
 }
 
@@ -75,6 +77,12 @@ int launch_train_ragged(const KernelPlan& k, const EncArgs& a, void* stream) {
 }  // namespace srfrd
 
 using namespace srfrd;
+
+// d hidden of every position, and SRFRN's logit gradients (see EncArgs::head_dh)
+extern "C" int64_t srfrd_train_scratch_floats(const srfrd_layout* lay, int B, int L) {
+  if (!lay || B <= 0 || L <= 0) return 0;
+  return (int64_t)B * L * (lay->d_out + (lay->kind == SRFRD_SRFRN ? 2 : 0));
+}
 
 extern "C" int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
                                          const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids,
@@ -104,6 +112,8 @@ extern "C" int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* it
                    (dropout_p > 0.0 ? SRFRD_PLAN_DROPOUT : 0) | (fused_bce && !d_hidden ? SRFRD_PLAN_FUSED_BCE : 0);
   const KernelPlan k = encoder_plan(*lay, B, L, mode, sw, num_cu(), scratch ? scratch_floats : 0).train;
   if (k.rc) return k.rc;
+  if (!scratch || scratch_floats < srfrd_train_scratch_floats(lay, B, L)) return SRFRD_E_ARG;
+  a.head_dh = scratch;
   a.hidden = hidden; a.pos_logits = pos_logits; a.neg_logits = neg_logits;
   a.save_x = save_x; a.save_h1 = save_h1; a.save_aux = save_aux; a.loss_part = loss_part;
   a.c_hidden = hidden; a.c_pl = pos_logits; a.c_nl = neg_logits; a.c_save_x = save_x; a.c_save_h1 = save_h1; a.c_save_aux = save_aux;

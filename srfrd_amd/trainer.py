@@ -101,8 +101,13 @@ class FusedTrainer:
         dev = self.flat.device
         self.B, self.L = int(batch_size), int(seq_len or self.lay.max_len)
         n_f, n_b = _lib.scratch_floats(self.lay, self.B, self.L)      # 0 when the working set fits LDS
-        self.scratch = torch.empty(max(n_f, n_b), device=dev, dtype=torch.float32) if max(n_f, n_b) else None
-        self.n_scratch = max(n_f, n_b)
+        # (where the plan has the one-launch train kernel, its forward hands the head's hidden-state gradient to its backward
+        # through the scratch: srfrd_train_scratch_floats)
+        fused = _lib.PLAN_POS | _lib.PLAN_NEG | _lib.PLAN_CKPT | _lib.PLAN_LOSS | _lib.PLAN_FUSED_BCE
+        has_train = bool(_lib.encoder_plan_train(self.lay, self.B, self.L, fused)[0])
+        n_t = int(_lib.lib().srfrd_train_scratch_floats(C.byref(self.lay), self.B, self.L)) if has_train else 0
+        self.n_scratch = max(n_f, n_b, n_t)
+        self.scratch = torch.empty(self.n_scratch, device=dev, dtype=torch.float32) if self.n_scratch else None
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.group = process_group
         self.n_tab, self.n_flat = model.n_table_pad, model.n_flat
@@ -180,7 +185,6 @@ class FusedTrainer:
         # launch per step ranks the batch by length, forward and backward pair a long with a short sequence on every CU.
         # Built where the kernel plan runs the ragged pair for this shape without switches (a test may set one later; the
         # other kernels ignore the schedule).  SRFRD_SCHED = 0 (off: workgroup x takes sequence x) | 1 (length order; default)
-        fused = _lib.PLAN_POS | _lib.PLAN_NEG | _lib.PLAN_CKPT | _lib.PLAN_LOSS | _lib.PLAN_FUSED_BCE
         # (a cross-entropy step runs the encoder without targets: checkpoints only, and its own head after the forward)
         plan_mode = fused if loss == "bce" else _lib.PLAN_CKPT
         ragged = _lib.encoder_plan(lay, B, L, plan_mode)[0][0].startswith("srfrd::encoder_fwd_ragged_kernel<")
