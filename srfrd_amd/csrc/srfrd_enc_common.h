@@ -44,8 +44,8 @@ struct EncArgs {
   const int* sched;    // int32 workspace, layout below (kSched*)
   int sched_mode;      // 0 none, 1 length order (workgroup x takes the sequence of rank perm(x): see rag_take)
   int ragged_off;      // diagnostic: the ragged kernels compute every row (t0 = 0), as the full kernels do
-  // ragged train kernel: what its forward's head leaves for its backward's - d hidden (B, L, d_out), then (SRFRN) the logit
-  // gradients (B, 2, L); see srfrd_head_dh_floats
+  // (was the ragged train kernel's forward -> backward buffer for d hidden; that hand-off stays in LDS now and no kernel reads
+  // this.  The field keeps the argument block's size, and with it every kernel's implicit-argument offsets, as they were.)
   float* head_dh;
 };
 

@@ -33,11 +33,13 @@ struct RagBwdLds {
 // The ragged backward of sequence b (the workgroup's iter-th) by the whole workgroup (512 threads): reads the checkpoints
 // of the ragged forward, scatters item-row gradients, accumulates the dense ones into this workgroup's slab and s_lng; ends
 // with a workgroup barrier.  tid: the laundered thread index (see launder), wave: its wave (uniform).
-// SEAM_ (the train kernel): rag_fwd_seq<.., SEAM_> of the same workgroup has done the head's first part - d hidden comes from
-// a.head_dh in one coalesced read, the target rows' item-table contributions are out already; seam_th is the th it returned.
+// SEAM_ (the train kernel): rag_fwd_seq<.., SEAM_> of the same workgroup has done the head's first part and rag_seam_handoff
+// has left the working set as this function's own first phase would: the last block's output in sX, d hidden in sG (slot
+// kRagSeamG), the ids in the per-position arrays - nothing of it is read from global memory again; the target rows'
+// item-table contributions are out already.  hs: what the forward returned.
 template <int K_, int DI_, bool RMW_, bool SEAM_ = false>
 __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m, int b, int iter, int& tid, int wave, uint32_t seed,
-                                            int seam_th = 0) {
+                                            const RagSeam& hs = RagSeam{}) {
   const Dims& ly = a.dm;
   constexpr int nw = 8, nthr = 512;
   constexpr int L = 50, D = 50, LP = 64, DK = 52, DS = 54, NT = 4, MT = 4;
@@ -98,7 +100,7 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
   const int64_t rowbase = (int64_t)b * L;
   const uint32_t seq = (uint32_t)(a.seq0 + b);
   const int lane0 = tid & 63;
-  if (tid < LP) {
+  if (!SEAM_ && tid < LP) {
     const int t = tid;
     const bool in = t < L;
     const int id = in ? clamp_id(a.in_ids[rowbase + t], ly.n_items) : 0;
@@ -112,14 +114,7 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
     s_pfk[t] = (in && a.pos_fk) ? clamp_id(a.pos_fk[rowbase + t], 2) : 0;
     s_nfk[t] = (in && a.neg_fk) ? clamp_id(a.neg_fk[rowbase + t], 2) : 0;
     float dp = 0.f, dn = 0.f;
-    if constexpr (SEAM_) {                 // (only SRFRN's side-channel sums still read the logit gradients)
-      if constexpr (K_ == SRFRD_SRFRN)
-        if (in) {
-          const float* dl = a.head_dh + (int64_t)B * L * dout + rowbase * 2;
-          dp = dl[t];
-          dn = dl[L + t];
-        }
-    } else if (in) {
+    if (in) {
       if (a.fused_bce) {                   // fused masked BCE
         const float pl = a.c_pl[rowbase + t], nl = a.c_nl[rowbase + t];
         bce_dlogits(pid, pl, nl, dp, dn);
@@ -133,12 +128,15 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
   }
   if (is_srfu && wave == 1) {
     const int lab = user_label_wave(rkind, a.fk_ids ? a.fk_ids + rowbase : nullptr, L, ly.n_labels);
-    if (lane0 == 0) ((lds_i*)s_misc)[0] = lab;
+    if (lane0 == 0) ((lds_i*)s_misc)[0] = lab;       // (read after the blocks: any later barrier orders it)
   }
-  __syncthreads();
+  if constexpr (!SEAM_) __syncthreads();
   // ---- the sequence's rows (wave-uniform): t0 leading pads; head range from the first position with an upstream gradient
   int t0, th;
-  {
+  if constexpr (SEAM_) {
+    t0 = hs.t0;
+    th = hs.th;
+  } else {
     const bool inr = lane0 < L;
     const unsigned long long nz = __ballot(inr && s_in[lane0] != 0);
     const unsigned long long ng = __ballot(inr && (s_in[lane0] != 0 || s_dpl[lane0] != 0.f || s_dnl[lane0] != 0.f));
@@ -146,7 +144,6 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
     th = ng ? (int)__builtin_ctzll(ng) : L;
     if (a.ragged_off) t0 = 0;
     if (a.d_hidden != nullptr || a.ragged_off) th = 0;
-    if constexpr (SEAM_) th = seam_th;
     t0 = __builtin_amdgcn_readfirstlane(t0);
     th = __builtin_amdgcn_readfirstlane(th);
   }
@@ -160,7 +157,9 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
   const int mh0 = hr.tile0, mhn = MT - mh0;
   const int ph0 = hr.pos0, kh0 = ph0 + SH;
 
-  lds_f *sX = slot[0], *sQ = slot[1], *sG = slot[2], *sT = slot[3], *sK = slot[4], *sO = slot[5];
+  // (SEAM_: d hidden arrives in slot kRagSeamG, whose floats the forward's head no longer needs when it writes them)
+  static_assert(kRagSlot == SZ && kRagSeamG == 3, "hand-off slot");
+  lds_f *sX = slot[0], *sQ = slot[1], *sG = slot[SEAM_ ? 3 : 2], *sT = slot[SEAM_ ? 2 : 3], *sK = slot[4], *sO = slot[5];
   // GEMM epilogues are BRANCH-FREE: an element outside the matrix (column >= D of the last strip, or a tile row in front of
   // row 12 that aliases the previous slot) is stored to this scratch word instead of being skipped - with a branch per element
   // hipcc wraps each of a tile's eight stores (and the LDS read some of them need) in its own exec-mask region and waits for
@@ -169,37 +168,32 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
   // (tile-coordinate view of a slot: tile row r = slot row r - SH)
 #define TB(p) ((p) - SH * DS)
   G2L<CIT, CV2> g_last, g_h1, g_r;
-  g_last.load(a.c_save_x + x_off(ly.n_blocks, b, ly.n_blocks, L, D) + p0 * D, L - p0, D, nthr);
+  if constexpr (!SEAM_) g_last.load(a.c_save_x + x_off(ly.n_blocks, b, ly.n_blocks, L, D) + p0 * D, L - p0, D, nthr);
   g_h1.load(a.c_save_h1 + h1_off(ly.n_blocks - 1, b, ly.n_blocks, L, D) + p0 * D, L - p0, D, nthr);
   g_r.load(a.c_save_aux + aux_off(ly.n_blocks - 1, b, ly.n_blocks, L, LP, D).r + p0 * D, L - p0, D, nthr);
-  if constexpr (SEAM_) {                // d hidden of the head range -> sG (SRFRN: the hidden rows -> sT for the side-channel sums)
-    constexpr bool V2 = dout % 2 == 0;    // (8-byte accesses: every head range starts at an even float offset)
-    constexpr int HIT = (L * (V2 ? dout / 2 : dout) + nthr - 1) / nthr;
-    G2L<HIT, V2> g_dh;
-    g_dh.load(a.head_dh + (rowbase + ph0) * dout, L - ph0, dout, nthr);
-    g_dh.store(sG + ph0 * DS, DS, L - ph0, dout, nthr);
+  if constexpr (SEAM_) {                // SRFRN: the hidden rows -> sT for the side-channel sums (everything else is in place)
     if constexpr (K_ == SRFRD_SRFRN) {
-      g_dh.load(a.c_hidden + (rowbase + ph0) * dout, L - ph0, dout, nthr);
-      g_dh.store(sT + ph0 * DS, DS, L - ph0, dout, nthr);
+      constexpr bool V2 = dout % 2 == 0;    // (8-byte accesses: every head range starts at an even float offset)
+      constexpr int HIT = (L * (V2 ? dout / 2 : dout) + nthr - 1) / nthr;
+      G2L<HIT, V2> g_hid;
+      g_hid.load(a.c_hidden + (rowbase + ph0) * dout, L - ph0, dout, nthr);
+      g_hid.store(sT + ph0 * DS, DS, L - ph0, dout, nthr);
+      __syncthreads();
     }
-    if (dout < D)
-      for (int idx = tid; idx < (L - ph0) * (D - dout); idx += nthr) {
-        const int tt = idx / (D - dout), cc = dout + idx - tt * (D - dout);
-        sG[(ph0 + tt) * DS + cc] = 0.f;
-      }
+  } else {
+    g_last.store(sX + p0 * DS, DS, L - p0, D, nthr);
+    // (head rows in front of the blocks' range - pad positions that carry an upstream gradient - are exact zeros: the
+    // forward did not write them)
+    // (column D, the ones column, is left to ones_col below: eight rows x 64 columns per pass, no division)
+    for (int r = ph0 + (tid >> 6); r < p0; r += nthr >> 6) {
+      const int c = tid & 63;
+      if (c < DS && c != D) sX[r * DS + c] = 0.f;
+    }
+    zero_pad_rows(sX);
+    ones_col(sX);
+    zero_pad_rows(sG);
+    __syncthreads();
   }
-  g_last.store(sX + p0 * DS, DS, L - p0, D, nthr);
-  // (head rows in front of the blocks' range - pad positions that carry an upstream gradient - are exact zeros: the
-  // forward did not write them)
-  // (column D, the ones column, is left to ones_col below: eight rows x 64 columns per pass, no division)
-  for (int r = ph0 + (tid >> 6); r < p0; r += nthr >> 6) {
-    const int c = tid & 63;
-    if (c < DS && c != D) sX[r * DS + c] = 0.f;
-  }
-  zero_pad_rows(sX);
-  ones_col(sX);
-  zero_pad_rows(sG);
-  __syncthreads();
 
   // (per-lane indices are re-derived from the laundered thread index per block: nothing computed from them may be lifted out
   // of the block loop - hipcc otherwise precomputes hundreds of per-lane addresses, spills them and reloads each before use)
@@ -686,6 +680,55 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
   __syncthreads();
 #undef TB
 #undef RG_RELANE
+}
+
+// Between rag_fwd_seq<.., SEAM_> and rag_bwd_seq<.., SEAM_> of one sequence (the train kernel; a workgroup barrier on either
+// side): every word of the working set (W floats) gets the value the backward's own first phase would have left in a
+// zeroed one, except the rows the forward hands over, which stay:
+//   * slot 0 (sX): rows p0 .. L - 1, columns < D - the last block's output, position-indexed at this very address.  The
+//     forward left score data in its columns D .. DS - 1 and in rows L, L + 1: the ones column, zeros; rows in front of p0
+//     (the head's rows ph0 .. p0 - 1 among them) are zeros, as a pad's row is;
+//   * slot kRagSeamG (sG): rows ph0 .. L - 1, columns < d_out - d hidden, written by the forward's last pass;
+//   * the nine per-position arrays (rag_bwd_seq's first nine, in its order) from hs, whole.
+// So each word has one writer here, and the backward reads what a launch of its own would read.
+template <int K_, int DI_>
+__device__ __forceinline__ void rag_seam_handoff(const RagBwdLds& m, const RagSeam& hs, int W, int tid) {
+  constexpr int nthr = 512, L = 50, D = 50, LP = 64, DS = 54, R = 52, SZ = R * DS, SH = kRagSH;
+  constexpr int dout = (K_ == SRFRD_SRFR) ? DI_ : D;
+  constexpr int oX = SH * DS, oG = oX + kRagSeamG * SZ, oT = oX + 6 * SZ, nT = 9 * LP;
+  lds_f* base = m.base;
+  const int krp = hs.t0 >= 1 ? hs.t0 - 1 : 0;
+  const int r0 = ((krp + SH) >> 4) << 4;
+  const int p0 = r0 > SH ? r0 - SH : 0;
+  const int ph0 = rag_head_range(hs.th, krp).pos0;
+  auto zero = [&](int lo, int hi) {
+    for (int i = lo + tid; i < hi; i += nthr) base[i] = 0.f;
+  };
+  zero(0, oX);
+  zero(oX + SZ, oG);
+  zero(oG + SZ, oT);
+  zero(oT + nT, W);
+  {                                      // the two slots with rows that stay: eight rows x 64 columns per pass, no division
+    const int c = tid & 63;
+    if (c < DS)
+      for (int r = tid >> 6; r < R; r += nthr >> 6) {
+        if (!(r >= p0 && r < L && c < D)) base[oX + r * DS + c] = (c == D && r < L) ? 1.0f : 0.f;
+        if (!(r >= ph0 && r < L && c < dout)) base[oG + r * DS + c] = 0.f;
+      }
+  }
+  if (tid < LP) {
+    lds_f* tail = base + oT;
+    lds_i* ti = (lds_i*)tail;
+    ti[tid] = hs.id;
+    tail[LP + tid] = hs.id != 0 ? 1.f : 0.f;
+    ti[2 * LP + tid] = hs.pid;
+    ti[3 * LP + tid] = hs.nid;
+    ti[4 * LP + tid] = hs.fk;
+    ti[5 * LP + tid] = hs.pfk;
+    ti[6 * LP + tid] = hs.nfk;
+    tail[7 * LP + tid] = hs.dp;
+    tail[8 * LP + tid] = hs.dn;
+  }
 }
 
 template <int K_, int DI_, bool RMW_>

@@ -150,6 +150,13 @@ __device__ __forceinline__ float head_dh_as_backward(float dp, float pv, float d
   asm volatile("" : "+v"(b));
   return a + b;
 }
+// h * (target row element) as the stand-alone forward rounds it into LDS before the logit sums read it: the train kernel keeps
+// the row there instead and multiplies in the sum (the empty asm keeps the product out of an fma with the running sum)
+__device__ __forceinline__ float seam_product(float h, float v) {
+  float p = h * v;
+  asm volatile("" : "+v"(p));
+  return p;
+}
 // ... and the two rows' item-table contributions: dp * h, dn * h
 __device__ __forceinline__ float head_contrib(float dl, float h) { return dl * h; }
 // Head range of the backward: the first position of the 16-row tiles that hold position min(th, krp), th the first position
@@ -417,6 +424,18 @@ __device__ __forceinline__ void rag_softmax(lds_f* S, int rq0, int r0, int v0, i
   }
 }
 
+// What the train kernel's forward hands its backward in registers (SEAM_), beside the LDS rows it leaves in place: the head's
+// first position, the leading pads, and - in lane t < 64 of the first wave - the ids and SRFRN's logit gradients of position t.
+struct RagSeam {
+  int th, t0;
+  int id, pid, nid, fk, pfk, nfk;
+  float dp, dn;
+};
+// ... and in LDS: the last block's output stays in the backward's slot 0 (the forward's position-indexed x is that address
+// range), d hidden is written to the backward's slot kRagSeamG, which rag_bwd_seq<.., SEAM_> takes for sG.
+constexpr int kRagSlot = 52 * 54;   // floats of one backward slot
+constexpr int kRagSeamG = 3;
+
 // LDS working set of the ragged forward for one sequence.  The forward kernel lays it out behind its per-row arrays, the
 // train kernel (srfrd_encoder_train_ragged.hip) over the same floats as the backward's slots: see rag_fwd_seq's callers.
 struct RagFwdLds {
@@ -431,12 +450,13 @@ struct RagFwdLds {
 // The ragged forward of sequence b by the whole workgroup (512 threads), from its ids to its hidden states, logits, BCE
 // partial sums and (training) checkpoints; ends with a workgroup barrier.  tid: the laundered thread index (see launder),
 // wave: its wave (uniform).
-// SEAM_ (the train kernel, fused BCE): the head also does the first part of the backward's head while the target rows, the
-// hidden rows and the logits are at hand - the logit gradients, d hidden -> a.head_dh (the backward's head range, [L][d_out] per
-// sequence; SRFRN: the logit gradients behind it) and, as its last action, the target rows' item-table contributions (float
-// atomics, or the rows of a.contrib).  Returns th, the first position with an upstream gradient (0 without SEAM_).
+// SEAM_ (the train kernel, fused BCE; m laid over the backward's slots as encoder_train_ragged_kernel does): the head also does
+// the first part of the backward's head while the target rows, the hidden rows and the logits are at hand - the logit
+// gradients, d hidden -> the backward's LDS slot kRagSeamG (its head range) and, as its last action, the target rows'
+// item-table contributions (float atomics, or the rows of a.contrib) - and leaves the last block's output where it is.
+// Returns what the backward takes over in registers (RagSeam; zeros without SEAM_).
 template <int K_, int T_, int DI_, bool SEAM_ = false>
-__device__ __forceinline__ int rag_fwd_seq(const EncArgs& a, const RagFwdLds& m, int b, int& tid, int wave, uint32_t seed) {
+__device__ __forceinline__ RagSeam rag_fwd_seq(const EncArgs& a, const RagFwdLds& m, int b, int& tid, int wave, uint32_t seed) {
   static_assert(!SEAM_ || T_ != 0, "the head seam belongs to the training forward");
   const Dims& ly = a.dm;
   constexpr int D = 50, L = 50, LP = 64, DK = 52, DS = 54, SLD = 66, NT = 4, MT = 4, SH = kRagSH;
@@ -670,6 +690,7 @@ __device__ __forceinline__ int rag_fwd_seq(const EncArgs& a, const RagFwdLds& m,
   // row's hidden state is LayerNorm(0 or b_lc), its logits against the table's row 0 - outputs the reference has too)
   const bool lo_h = !TR_ && a.last_only != 0;
   int seam_th = 0;
+  RagSeam hs = {};
   asm volatile("" : "+v"(tid));
   const int lane = tid & 63;
   if (!lo_h && r0 > SH) {                    // the positions in front of the computed tiles: exact zeros (S overlaid them)
@@ -717,14 +738,13 @@ __device__ __forceinline__ int rag_fwd_seq(const EncArgs& a, const RagFwdLds& m,
         if (has_pos) {
           const float pv = c < di ? table((int64_t)s_pid[t + SH] * di + c)
                                   : (srfrn ? P[ly.off_side + clamp_id(a.pos_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f);
-          kp[t * DS + c] = h * pv;
-          if constexpr (SEAM_) xp[t * DS + c] = pv;           // (x and, below, the last_conv output are dead: the rows wait there)
+          // (SEAM_: the row itself waits there - the logit pass forms the product - and x stays whole for the backward)
+          kp[t * DS + c] = SEAM_ ? pv : h * pv;
         }
         if (has_neg) {
           const float nv = c < di ? table((int64_t)s_nid[t + SH] * di + c)
                                   : (srfrn ? P[ly.off_side + clamp_id(a.neg_fk[rowbase + t], 2) * dfk + (c - di)] : 0.f);
-          vp[t * DS + c] = h * nv;
-          if constexpr (SEAM_) bQ[(t + SH) * DS + c] = nv;
+          vp[t * DS + c] = SEAM_ ? nv : h * nv;
         }
         t += dt; c += dc;
         if (c >= dout) { c -= dout; ++t; }
@@ -739,8 +759,14 @@ __device__ __forceinline__ int rag_fwd_seq(const EncArgs& a, const RagFwdLds& m,
       for (int j = 0; j < kQC; ++j) {
         const int c = q + kRL * j;
         if (c < dout) {
-          if (has_pos) ap += kp[t * DS + c];
-          if (has_neg) an += vp[t * DS + c];
+          if constexpr (SEAM_) {               // the stand-alone forward's rounded products, summed as it sums them
+            const float h = qnp[t * DS + c];
+            ap += seam_product(h, kp[t * DS + c]);
+            an += seam_product(h, vp[t * DS + c]);
+          } else {
+            if (has_pos) ap += kp[t * DS + c];
+            if (has_neg) an += vp[t * DS + c];
+          }
         }
       }
       const float pl = row_sum(ap), nl = row_sum(an);
@@ -782,15 +808,24 @@ __device__ __forceinline__ int rag_fwd_seq(const EncArgs& a, const RagFwdLds& m,
       if (a.ragged_off) seam_th = 0;
       seam_th = __builtin_amdgcn_readfirstlane(seam_th);
       const int ph0 = rag_head_range(seam_th, t0 >= 1 ? t0 - 1 : 0).pos0;
-      float* dhb = a.head_dh + (rowbase + ph0) * dout;
+      hs.th = seam_th;
+      hs.t0 = t0;
+      if (has_fake && tid < L) {             // (requested in front of the atomics: the memory queue retires in order)
+        hs.fk = a.fk_ids ? clamp_id(a.fk_ids[rowbase + tid], 2) : 0;
+        hs.pfk = a.pos_fk ? clamp_id(a.pos_fk[rowbase + tid], 2) : 0;
+        hs.nfk = a.neg_fk ? clamp_id(a.neg_fk[rowbase + tid], 2) : 0;
+      }
+      // d hidden of the head range goes where the backward reads it: its slot kRagSeamG, position-indexed like xp - over the
+      // last_conv output / q matrix, which is dead (the rows it reads wait in kp / vp, the hidden rows in qnp)
+      lds_f* sgp = xp + kRagSeamG * kRagSlot;
       const int B = a.B;
-      int t = ph0 + tid / dout, c = tid - (tid / dout) * dout, i = tid;
+      int t = ph0 + tid / dout, c = tid - (tid / dout) * dout;
       constexpr int dt = nthr / dout, dc = nthr - dt * dout;
       for (; t < L;) {
         const float dp = s_dp[t], dn = s_dn[t];
         float dh = 0.f;
-        if (c < di || srfrn) dh = head_dh_as_backward<K_>(dp, xp[t * DS + c], dn, bQ[(t + SH) * DS + c]);
-        dhb[i] = dh;
+        if (c < di || srfrn) dh = head_dh_as_backward<K_>(dp, kp[t * DS + c], dn, vp[t * DS + c]);
+        sgp[t * DS + c] = dh;
         if (c < di) {
           const float h = qnp[t * DS + c];
           const int pid = s_pid[t + SH], nid = s_nid[t + SH];
@@ -802,7 +837,7 @@ __device__ __forceinline__ int rag_fwd_seq(const EncArgs& a, const RagFwdLds& m,
             if (nid != 0 && dn != 0.f) atomicAdd(&a.grad_table[(int64_t)nid * di + c], head_contrib(dn, h));
           }
         }
-        t += dt; c += dc; i += nthr;
+        t += dt; c += dc;
         if (c >= dout) { c -= dout; ++t; }
       }
       if (a.contrib != nullptr)              // (the sorted reduction reads every row of the batch: rows in front of the head are zeros)
@@ -810,16 +845,20 @@ __device__ __forceinline__ int rag_fwd_seq(const EncArgs& a, const RagFwdLds& m,
           a.contrib[(((int64_t)0 * B + b) * L) * di + idx] = 0.f;
           a.contrib[(((int64_t)1 * B + b) * L) * di + idx] = 0.f;
         }
-      if constexpr (K_ == SRFRD_SRFRN)       // the side-channel sums of the backward's head weigh the hidden rows by these
-        if (tid < L) {
-          float* dl = a.head_dh + (int64_t)B * L * dout + rowbase * 2;
-          dl[tid] = s_dp[tid];
-          dl[L + tid] = s_dn[tid];
+      // the ids, position-indexed as the backward holds them (lanes 0 .. L - 1 of the first wave; zeros behind)
+      if (tid < L) {
+        hs.id = s_in[tid + SH];
+        hs.pid = s_pid[tid + SH];
+        hs.nid = s_nid[tid + SH];
+        if constexpr (K_ == SRFRD_SRFRN) {   // (only its side-channel sums still read the logit gradients)
+          hs.dp = s_dp[tid];
+          hs.dn = s_dn[tid];
         }
+      }
     }
   }
   __syncthreads();
-  return seam_th;
+  return hs;
 }
 
 template <int K_, int T_, int DI_>

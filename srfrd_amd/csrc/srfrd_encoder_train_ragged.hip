@@ -4,7 +4,9 @@
 // (checkpoints, hidden states, logits): a workgroup-scope fence is all the hand-off needs, no workgroup waits for another.
 // The BCE normaliser (the global target count) enters later, in the Adam step, so nothing in here needs the whole batch.
 // The forward's head also does the first part of the backward's head (SEAM_ of rag_fwd_seq / rag_bwd_seq): logit gradients,
-// d hidden -> a.head_dh, the target rows' item-table contributions; the backward starts from d hidden.
+// d hidden, the target rows' item-table contributions; the backward starts from d hidden.  What the backward's head needs
+// first - the last block's output, d hidden, the ids - stays in LDS and registers across the barrier (rag_seam_handoff): its
+// first arithmetic waits for no global load, and the loads it does issue stand behind no id round trip.
 //
 // Against the two launches: a long sequence's backward no longer waits for the slowest forward on the chip, and once its
 // short partner on the CU has finished, it runs alone.  Results are those of the two launches bit for bit: same
@@ -45,6 +47,10 @@ __global__ void __launch_bounds__(512, 4) encoder_train_ragged_kernel(const EncA
   fm.s_nid = (lds_i*)(ftail + 3 * LP);
   fm.s_misc = ftail + 4 * LP;
   static_assert(LP * SLD + 4 * LP * DS + 5 * LP == kRagFwdWork, "forward working set");
+  // The hand-off (rag_seam_handoff): the forward's position-indexed x IS the backward's slot 0, and d hidden's slot lies inside
+  // bQ and the unused rows in front of bK's position 0 - the one matrix the forward's head has no use for
+  constexpr int oG = (kRagSH + kRagSeamG * 52) * DS;
+  static_assert(oG >= LP * SLD + LP * DS && oG + 50 * DS <= LP * SLD + 2 * LP * DS + kRagSH * DS, "d hidden lands in dead floats");
   lds_f* s_ln = base + W;
   fm.s_ln = s_ln;
   const RagBwdLds bm{base, s_ln, s_ln + ln_cache_floats(ly.n_blocks)};
@@ -59,11 +65,12 @@ __global__ void __launch_bounds__(512, 4) encoder_train_ragged_kernel(const EncA
     }
     const int b = __builtin_amdgcn_readfirstlane(rag_take(a, (lds_i*)fm.bXS, iter, tid, t0v));
     if (b < 0) break;
-    const int th = rag_fwd_seq<K_, 1, DI_, true>(a, fm, b, tid, wave, seed);
-    // (rag_fwd_seq ended with a workgroup barrier: its checkpoint stores are visible to every wave of the workgroup)
-    for (int i = tid; i < W; i += nthr) base[i] = 0.f;
+    const RagSeam hs = rag_fwd_seq<K_, 1, DI_, true>(a, fm, b, tid, wave, seed);
+    // (rag_fwd_seq ended with a workgroup barrier: its checkpoint stores are visible to every wave of the workgroup, and
+    // nobody reads the forward's matrices any more)
+    rag_seam_handoff<K_, DI_>(bm, hs, W, tid);
     __syncthreads();
-    rag_bwd_seq<K_, DI_, RMW_, true>(a, bm, b, iter, tid, wave, seed, th);
+    rag_bwd_seq<K_, DI_, RMW_, true>(a, bm, b, iter, tid, wave, seed, hs);
   }
 }
 
@@ -78,7 +85,9 @@ int launch_train_ragged(const KernelPlan& k, const EncArgs& a, void* stream) {
 
 using namespace srfrd;
 
-// d hidden of every position, and SRFRN's logit gradients (see EncArgs::head_dh)
+// The step's scratch as srfrd_encoder_train_sched demands it: d hidden of every position, and SRFRN's logit gradients.  (The
+// kernel handed these from its forward to its backward through this buffer; they stay in LDS now and nothing touches it,
+// but the entry point's argument list and its refusals are pinned.)
 extern "C" int64_t srfrd_train_scratch_floats(const srfrd_layout* lay, int B, int L) {
   if (!lay || B <= 0 || L <= 0) return 0;
   return (int64_t)B * L * (lay->d_out + (lay->kind == SRFRD_SRFRN ? 2 : 0));
@@ -113,7 +122,6 @@ extern "C" int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* it
   const KernelPlan k = encoder_plan(*lay, B, L, mode, sw, num_cu(), scratch ? scratch_floats : 0).train;
   if (k.rc) return k.rc;
   if (!scratch || scratch_floats < srfrd_train_scratch_floats(lay, B, L)) return SRFRD_E_ARG;
-  a.head_dh = scratch;
   a.hidden = hidden; a.pos_logits = pos_logits; a.neg_logits = neg_logits;
   a.save_x = save_x; a.save_h1 = save_h1; a.save_aux = save_aux; a.loss_part = loss_part;
   a.c_hidden = hidden; a.c_pl = pos_logits; a.c_nl = neg_logits; a.c_save_x = save_x; a.c_save_h1 = save_h1; a.c_save_aux = save_aux;
