@@ -577,6 +577,48 @@ int srfrd_shared_negatives(const uint32_t* state, int n_items, int K, const floa
                            const float* item_log_q, int64_t* out_ids, float* out_log_q, void* stream);
 
 /*
+ * K negatives PER POSITION for srfrd_tneg_fwd / _bwd, drawn on the device outside the row user's history (the reference's
+ * random_neq, utils.py:14-19, used at :27-46, with K slots per position).  user_ptr / items are the CSR histories of
+ * srfrd_sample_batch (user_ptr int64 (usernum + 2), items int32; time-ordered, duplicates allowed).  users (B) are the rows'
+ * user ids, clamped into [0, usernum]; targets is (B, L) int64.  out_ids (B, L, K) int64, out_log_q (B, L, K) fp32 or NULL.
+ *   - A position with targets == 0 gets id 0 and log_q 0 in all K slots.
+ *   - A slot at a live position makes up to SRFRD_TNEG_TRIES draws and keeps the first candidate that is not among the
+ *     user's training items: the WHOLE history, not only the last L (the position's own target is in it).  The kernel reads
+ *     at most the first max_hist items of a history.
+ *   - If all SRFRD_TNEG_TRIES draws clash, the slot is written as id 0 with log_q 0, which the loss treats as unused: a
+ *     history item is never emitted (unlike the 256-try fallback of srfrd_sample_batch's one negative).
+ *   - exclude_history == 0: the first draw is kept.
+ *   - Slots of one position are independent: sampling is with replacement.
+ * Stream (integer-exact, wrapping in uint32; fmix32 and SITE_TNEG = 0x4E470002 of srfrd_rng.h; mulhi32(a, b) = (a * b) >> 32
+ * in 64 bits):
+ *   s0 = fmix32(seed ^ batch_index * 0x9E3779B9)
+ *   s1 = fmix32(s0 + SITE_TNEG * 0x9E3779B9 + (state ? state[2] : 0))     state: the optimizer's uint32 state words, state[2]
+ *                                                                        the step seed: a captured graph draws afresh per replay
+ *   s2 = fmix32(s1 + b),  e = fmix32(s2 ^ (t * K + k))
+ *   try r: h1 = fmix32(e + 2r), h2 = fmix32(e + 2r + 1), bucket = mulhi32(h1, n_items)
+ *   alias table given (as for srfrd_shared_negatives): u = (h2 >> 8) * 2^-24; if !(u < alias_prob[bucket]) bucket =
+ *     clamp(alias_idx[bucket], 0, n_items - 1)
+ *   id = bucket + 1
+ * out_log_q[b, t, k] = (item_log_q ? item_log_q[id] : (float)log((double)K / n_items)) - (user_log_keep ? user_log_keep[u] : 0),
+ * one fp32 subtraction.  item_log_q fp32 (n_items + 1) is log(K q); user_log_keep fp32 (usernum + 1) is log(1 - the sum of q
+ * over the distinct items of u's history), the renormalisation that rejection imposes on q.
+ * One 256-thread workgroup per sequence; with exclusion the user's items go into an open-addressing set in dynamic LDS
+ * (4 bytes x the power of two >= 2 max(max_hist, 32)); plain stores only, every output element written exactly once by the
+ * kernel, two identical calls give identical bits.
+ * Refused before any launch: a NULL user_ptr, items, users, targets or out_ids, B, L, K, usernum or n_items <= 0, B L (1 + K)
+ * >= 2^31, one of the two alias arrays without the other, an alias table without item_log_q, max_hist < 0 -> SRFRD_E_ARG;
+ * exclude_history with max_hist > SRFRD_TNEG_MAX_HIST -> SRFRD_E_UNSUPPORTED.
+ */
+#define SRFRD_TNEG_TRIES 32
+#define SRFRD_TNEG_MAX_HIST 16384
+int srfrd_token_negatives(const int64_t* user_ptr, const int32_t* items, int usernum, int n_items, int max_hist,
+                          const int64_t* users, const int64_t* targets, int B, int L, int K,
+                          uint32_t seed, uint32_t batch_index, const uint32_t* state,
+                          const float* alias_prob, const int32_t* alias_idx, const float* item_log_q,
+                          const float* user_log_keep, int exclude_history,
+                          int64_t* out_ids, float* out_log_q, void* stream);
+
+/*
  * Device-side batch sampler with the layout and semantics of reference utils.py:21-57 (sample_function_fr /
  * WarpSampler_fr): per sampled user (uniform among users with > 1 interaction) the most recent `L` training items
  * left-padded with 0, pos[t] = the next item, neg[t] = a uniform item outside the user's history wherever pos[t] != 0,

@@ -91,6 +91,7 @@ SIGNATURES = {
     "srfrd_sxent_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _P, _i64, _P]),
     "srfrd_sxent_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
     "srfrd_shared_negatives": (_i, [_P, _i, _i, _P, _P, _P, _P, _P, _P]),
+    "srfrd_token_negatives": (_i, [_P, _P, _i, _i, _i, _P, _P, _i, _i, _i, _u32, _u32, _P, _P, _P, _P, _P, _i, _P, _P, _P]),
     "srfrd_tneg_workspace_floats": (_i64, [_LP, _i, _i, _i]),
     "srfrd_tneg_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _d, _i, _i, _i, _P, _P, _P, _P, _i64, _P]),
     "srfrd_tneg_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _d, _i, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
@@ -182,6 +183,9 @@ def env_switches() -> int:
 # objectives of srfrd_tneg_fwd / _bwd (SRFRD_TNEG_*) and the segment length of srfrd_table_reduce_rank1 (SRFRD_TNEG_SPLIT_ROWS)
 TNEG_OBJECTIVES = {"softmax": 0, "gbce": 1}
 TNEG_SPLIT_ROWS = 256
+# srfrd_token_negatives: draws per slot (SRFRD_TNEG_TRIES) and the longest history its LDS set holds (SRFRD_TNEG_MAX_HIST)
+TNEG_TRIES = 32
+TNEG_MAX_HIST = 16384
 
 # srfrd_rank_plan ops (SRFRD_RANK_*) and the ranking's switch bit (SRFRD_SW_TOPK_FP32: the environment variable SRFRD_TOPK_FP32)
 RANK_TOPK, RANK_TARGET, RANK_TARGET_METRIC = 0, 1, 2

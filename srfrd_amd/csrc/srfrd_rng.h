@@ -22,6 +22,8 @@ SRFRD_HD uint32_t fmix32(uint32_t h) {
 enum { SITE_EMB = 0 };
 // the shared negatives of a sampled-softmax step (srfrd_negs.hip): far above every dropout site (< 1024 * heads + 3 * blocks + 4)
 enum : uint32_t { SITE_NEG = 0x4E470001u };
+// the K negatives per position of srfrd_token_negatives (srfrd_tneg_sample.hip)
+enum : uint32_t { SITE_TNEG = 0x4E470002u };
 SRFRD_HD int site_attn(int blk, int head = 0) { return 1 + 3 * blk + 1024 * head; }   // (one mask per attention head)
 SRFRD_HD int site_ffn1(int blk) { return 2 + 3 * blk; }
 SRFRD_HD int site_ffn2(int blk) { return 3 + 3 * blk; }

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .sampler import alias_table, history_log_keep, negative_q
 
 
 @dataclass
@@ -185,12 +186,29 @@ def evaluation(model, data: InteractionData, maxlen: int, batch: int = 2048, n_n
 
 class DeviceSampler:
     """``WarpSampler_fr`` replacement: ``next_batch()`` returns the same 7-tuple, already on the device, generated by one
-    kernel launch from the CSR histories (no worker processes, reproducible)."""
+    kernel launch from the CSR histories (no worker processes, reproducible).
+
+    ``num_negatives=K > 0``: every ``next_batch()`` also draws K negatives per position for ``model.token_negatives_loss``
+    (srfrd_token_negatives: one more launch, from the batch's user and pos planes and the same ``(seed, index)``), outside
+    the user's whole training history unless ``exclude_history=False``; ``sampler.negatives`` (B, L, K) int64 and
+    ``sampler.log_q`` (B, L, K) float32 then hold the last batch's draw.  ``neg_counts`` (itemnum + 1,), indexed by item
+    id, draws with probability proportional to ``neg_counts ** neg_alpha`` instead of uniformly."""
 
     def __init__(self, data: InteractionData, batch_size: int = 64, maxlen: int = 10, seed: int = 0, device="cuda",
-                 model=None):
+                 model=None, *, num_negatives: int = 0, neg_counts=None, neg_alpha: float = 1.0, exclude_history: bool = True):
         """``model``: the module (or FusedTrainer) the batches will feed - its item table must cover ``data.itemnum``
         (checked once here; the reference would fail at the first nn.Embedding lookup of a larger id)."""
+        self.K, self.exclude_history = int(num_negatives), bool(exclude_history)
+        if self.K < 0:
+            raise ValueError(f"num_negatives must not be negative (got {num_negatives})")
+        q = None
+        if self.K > 0:
+            if neg_counts is not None:
+                q = negative_q(data.itemnum, neg_counts, neg_alpha)       # (refuses a shape other than (itemnum + 1,))
+            self.max_hist = int(data.train_len().max()) if data.train_len().size else 0
+            if self.exclude_history and self.max_hist > _lib.TNEG_MAX_HIST:
+                raise ValueError(f"the longest training history holds {self.max_hist} items; the per-position sampler excludes "
+                                 f"histories of up to {_lib.TNEG_MAX_HIST}: pass exclude_history=False to draw without exclusion")
         self.data, self.B, self.L, self.seed, self.device = data, int(batch_size), int(maxlen), int(seed), torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DeviceSampler generates batches on the ROCm GPU; there is no CPU fallback")
@@ -203,10 +221,28 @@ class DeviceSampler:
             raise ValueError("no user has more than one training interaction")
         self.ptr, self.items, self.reviews = data.to_device(self.device)
         self.index = 0
+        if self.K > 0:
+            self.alias_prob = self.alias_idx = self.item_log_q = None
+            if q is not None:
+                prob, idx = alias_table(q)
+                with np.errstate(divide="ignore"):                        # (an item of weight 0 is never drawn: its -inf is not read)
+                    lq = np.concatenate([[0.0], np.log(self.K * q)]).astype(np.float32)
+                self.alias_prob = torch.from_numpy(prob).to(self.device)
+                self.alias_idx = torch.from_numpy(idx).to(self.device)
+                self.item_log_q = torch.from_numpy(lq).to(self.device)
+            self.user_log_keep = (torch.from_numpy(history_log_keep(data, q)).to(self.device) if self.exclude_history else None)
+            self.negatives = self.log_q = None
 
-    def next_batch(self, packed: bool = False, out: torch.Tensor | None = None):
+    def next_batch(self, packed: bool = False, out: torch.Tensor | None = None, neg_out: torch.Tensor | None = None,
+                   log_q_out: torch.Tensor | None = None):
         """``out``: an int64 (6, B, L) device tensor to fill in place - e.g. ``trainer.ids_ring[slot]``, so the batch goes
-        from the sampler kernel straight into the fused step's input slot (``trainer.step_slot(slot)``), no copy."""
+        from the sampler kernel straight into the fused step's input slot (``trainer.step_slot(slot)``), no copy.
+        ``neg_out`` / ``log_q_out`` (``num_negatives > 0``): the (B, L, K) int64 / float32 device tensors the negatives
+        and their log-Q go to (fresh ones otherwise); ``sampler.negatives`` / ``sampler.log_q`` name them afterwards."""
+        if self.K == 0 and (neg_out is not None or log_q_out is not None):
+            raise ValueError("neg_out / log_q_out need a sampler built with num_negatives > 0")
+        self._check_tensors(("neg_out", neg_out, (self.B, self.L, self.K), torch.int64),
+                            ("log_q_out", log_q_out, (self.B, self.L, self.K), torch.float32))       # (before anything is launched)
         user = torch.empty(self.B, device=self.device, dtype=torch.int64)
         if out is None:
             out = torch.empty(6, self.B, self.L, device=self.device, dtype=torch.int64)
@@ -216,10 +252,46 @@ class DeviceSampler:
         check(_lib.lib().srfrd_sample_batch(ptr(self.ptr), ptr(self.items), ptr(self.reviews), self.data.usernum,
                                             self.data.itemnum, self.B, self.L, self.seed & 0xFFFFFFFF,
                                             self.index & 0xFFFFFFFF, ptr(user), ptr(out), st), "srfrd_sample_batch")
+        if self.K > 0:
+            self.negatives, self.log_q = self.token_negatives(user, out[2], index=self.index, out=neg_out, out_log_q=log_q_out)
         self.index += 1
         if packed:
             return user, out
         return (user, out[0], out[1], out[2], out[3], out[4], out[5])
+
+    def _check_tensors(self, *specs):
+        for name, t, shape, dtype in specs:
+            if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != self.ptr.device):
+                raise ValueError(f"{name} must be a contiguous {dtype} {shape} tensor on the sampler's device")
+
+    def token_negatives(self, user: torch.Tensor, pos: torch.Tensor, *, index: int, state: torch.Tensor | None = None,
+                        out: torch.Tensor | None = None, out_log_q: torch.Tensor | None = None):
+        """K negatives per position of a batch that came from anywhere: ``user`` (B,) and ``pos`` (B, L) int64 on the
+        device, drawn from ``(seed, index)`` by one launch on the current stream -> ``(negatives (B, L, K) int64, log_q
+        (B, L, K) float32)``, id 0 and log_q 0 wherever ``pos == 0``.  ``state``: the trainer's uint32 state tensor
+        (``trainer.state``): its step-seed word enters the stream, so a captured graph draws fresh negatives on every
+        replay.  ``out`` / ``out_log_q``: tensors to fill in place (nothing is allocated then)."""
+        if self.K <= 0:
+            raise RuntimeError("this sampler was built with num_negatives=0")
+        if pos.dim() != 2 or tuple(user.shape) != (pos.shape[0],):
+            raise ValueError(f"user must be (B,) and pos (B, L) (got {tuple(user.shape)} and {tuple(pos.shape)})")
+        B, L = pos.shape
+        self._check_tensors(("user", user, (B,), torch.int64), ("pos", pos, (B, L), torch.int64),
+                            ("out", out, (B, L, self.K), torch.int64), ("out_log_q", out_log_q, (B, L, self.K), torch.float32))
+        if state is not None and (state.element_size() != 4 or state.is_floating_point() or state.numel() < 3
+                                  or not state.is_contiguous() or state.device != self.ptr.device):
+            raise ValueError("state must be the trainer's contiguous 32-bit state tensor on the sampler's device")
+        if out is None:
+            out = torch.empty(B, L, self.K, device=self.device, dtype=torch.int64)
+        if out_log_q is None:
+            out_log_q = torch.empty(B, L, self.K, device=self.device, dtype=torch.float32)
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(_lib.lib().srfrd_token_negatives(ptr(self.ptr), ptr(self.items), self.data.usernum, self.data.itemnum, self.max_hist,
+                                               ptr(user), ptr(pos), B, L, self.K, self.seed & 0xFFFFFFFF, int(index) & 0xFFFFFFFF,
+                                               ptr(state), ptr(self.alias_prob), ptr(self.alias_idx), ptr(self.item_log_q),
+                                               ptr(self.user_log_keep), int(self.exclude_history), ptr(out), ptr(out_log_q), st),
+              "srfrd_token_negatives")
+        return out, out_log_q
 
     def close(self):
         pass

@@ -79,7 +79,10 @@ def sample_token_negatives(n_items: int, positive_ids, num: int, counts=None, al
     ``counts[j] ** alpha`` (``counts`` as in ``sample_negatives``); id 0 in every slot of a position without a target.
     Returns ``(negative_ids (B, L, num) int64, log_q (B, L, num) float32)`` with ``log_q = log(num * q_ids)`` (0 in the
     id-0 slots).  Drawn with torch on the device of ``positive_ids`` (``generator``, if given, must live there).  The draws
-    do not avoid the user's history: accidental hits on the position's own target are dropped by the loss."""
+    do not avoid the user's history: accidental hits on the position's own target are dropped by the loss.  For negatives
+    outside the user's history as the reference samples them, reproducible from (seed, batch index) and drawn by one
+    kernel launch without an allocation, use ``DeviceSampler(..., num_negatives=num)`` (``sampler.negatives`` /
+    ``sampler.log_q``, or ``sampler.token_negatives`` for a batch that came from elsewhere)."""
     pos = torch.as_tensor(positive_ids)
     if pos.dim() != 2:
         raise ValueError(f"positive_ids must be (batch, seq_len) (got shape {tuple(pos.shape)})")
@@ -121,6 +124,34 @@ def negative_q(n_items: int, counts, alpha: float = 1.0):
     if not total > 0 or not np.isfinite(total):
         raise ValueError("counts ** alpha has no positive (finite) weight")
     return w / total
+
+
+def history_log_keep(data, q=None):
+    """float32 (usernum + 1,): ``log(1 - sum of q over the DISTINCT training items of user u)``, the log of the mass that
+    rejecting u's history leaves of the sampling distribution ``q`` (fp64 (itemnum,), ``q[i]`` for item id i + 1, as
+    ``negative_q`` returns it); ``q=None`` is the uniform distribution: ``log(1 - distinct / itemnum)``.  Computed in fp64.
+    Subtracted from ``log(K q)`` it gives the log-Q correction of negatives drawn outside the history
+    (``DeviceSampler(num_negatives=K)``).  A user whose history carries all the mass gets ``-inf``: every slot of such a
+    user comes out 0, so the value is never read at a kept slot."""
+    n_users, n_items = data.usernum + 1, data.itemnum
+    owner = np.repeat(np.arange(n_users, dtype=np.int64), data.train_len())
+    its = np.asarray(data.train_items[: owner.size], dtype=np.int64)
+    ok = (its >= 1) & (its <= n_items)
+    pairs = np.unique(owner[ok] * (n_items + 1) + its[ok])            # one entry per (user, distinct item)
+    pu, pi = pairs // (n_items + 1), pairs % (n_items + 1)
+    if q is None:
+        keep = 1.0 - np.bincount(pu, minlength=n_users).astype(np.float64) / n_items
+        full = np.bincount(pu, minlength=n_users) >= n_items
+    else:
+        q = np.asarray(q, dtype=np.float64)
+        if q.shape != (n_items,):
+            raise ValueError(f"q must have shape ({n_items},) (q[i] for item id i + 1), got {q.shape}")
+        keep = 1.0 - np.bincount(pu, weights=q[pi - 1], minlength=n_users)
+        # all the mass: every item of positive weight is in the history (the fp64 sum may miss 1 by a rounding)
+        full = np.bincount(pu, weights=(q[pi - 1] > 0).astype(np.float64), minlength=n_users) >= np.count_nonzero(q > 0)
+    keep = np.where(full, 0.0, np.maximum(keep, 0.0))
+    with np.errstate(divide="ignore"):
+        return np.log(keep).astype(np.float32)
 
 
 def alias_table(q):

@@ -13,6 +13,14 @@ backward includes the key sort and the rank-1 table reduction of the host layer;
 over ``--reps`` after warm-up, CUDA events.  ``*_gather_tbs``: tokens * (1 + K) * 200 bytes over the time of the pass, the
 rate at which table rows are gathered, to set beside the 8.6 TB/s measured for rows gathered from the Infinity Cache.  Each
 configuration runs in a fresh child process with its own time limit.
+
+    python tools/tneg_latency.py --sampler [--reps 10] [--out profiles/tneg_sampler_latency.json]
+
+times what feeds that loss instead: DeviceSampler.token_negatives (srfrd_token_negatives, one launch into preallocated
+outputs) at the C2 shape (B = 512, L = 50, 50k items; 4096 synthetic users with 5..200 training items each) for K = 16, 64
+and 256, uniform and by popularity (alias table, counts ** 0.75), with and without history exclusion; beside each,
+srfrd_amd.sample_token_negatives (torch.randint / torch.multinomial, no exclusion) on the same positions in the same process.
+``store_gbs``: the bytes of the two outputs (12 per slot) over the kernel's time.
 """
 from __future__ import annotations
 
@@ -110,6 +118,40 @@ def child(name: str, reps: int, only: str | None = None) -> list:
     return results
 
 
+def sampler_child(reps: int) -> list:
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    import srfrd_amd
+    I, L, B, U = 50_000, 50, 512, 4096
+    rng = np.random.RandomState(0)
+    lens = rng.randint(5, 201, U)
+    users = np.repeat(np.arange(1, U + 1), lens)
+    data = srfrd_amd.partition(users, np.concatenate([rng.randint(1, I + 1, users.size - 1), [I]]), rng.rand(users.size) < 0.3)
+    counts = np.bincount(data.train_items, minlength=I + 1).astype(np.float64)
+    results = []
+    for K in (16, 64, 256):
+        for dist in ("uniform", "alias"):
+            kw = dict(neg_counts=counts, neg_alpha=0.75) if dist == "alias" else {}
+            out = {"config": f"C2_K{K}", "distribution": dist, "I": I, "L": L, "B": B, "K": K, "reps": reps,
+                   "max_hist": int(data.train_len().max()), "out_bytes": B * L * K * 12}
+            runs = {}
+            for exclude in (True, False):
+                s = srfrd_amd.DeviceSampler(data, B, L, seed=1, num_negatives=K, exclude_history=exclude, **kw)
+                user, _, _, pos, *_ = s.next_batch()
+                neg, lq = torch.empty_like(s.negatives), torch.empty_like(s.log_q)
+                runs["kernel_exclude" if exclude else "kernel_no_exclude"] = (
+                    lambda s=s, user=user, pos=pos, neg=neg, lq=lq: s.token_negatives(user, pos, index=1, out=neg, out_log_q=lq))
+            cnt = counts if dist == "alias" else None
+            runs["torch_no_exclude"] = lambda: srfrd_amd.sample_token_negatives(I, pos, K, counts=cnt, alpha=0.75)
+            _time(runs, out, reps)
+            out["tokens"] = int((pos != 0).sum())
+            out["store_gbs"] = round(out["out_bytes"] / (out["kernel_exclude_ms"] * 1e-3) / 1e9, 1)
+            out["torch_over_kernel"] = round(out["torch_no_exclude_ms"] / out["kernel_exclude_ms"], 2)
+            results.append(out)
+    return results
+
+
 def _time(runs, out, reps):
     import torch
     for label, fn in runs.items():
@@ -137,13 +179,16 @@ def main():
     ap.add_argument("--timeout", type=int, default=240)
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
+    ap.add_argument("--sampler", action="store_true", help="time the per-position negative sampler instead of the loss")
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(child(a.child, a.reps, a.objective)))
+        print(json.dumps(sampler_child(a.reps) if a.sampler else child(a.child, a.reps, a.objective)))
         return
     results = []
-    for name in a.configs.split(","):
+    for name in (["sampler"] if a.sampler else a.configs.split(",")):
         cmd = [sys.executable, os.path.abspath(__file__), "--child", name, "--reps", str(a.reps)]
+        if a.sampler:
+            cmd.append("--sampler")
         if a.objective:
             cmd += ["--objective", a.objective]
         try:
