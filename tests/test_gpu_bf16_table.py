@@ -10,6 +10,9 @@ from oracle import srfrd_oracle as O
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
+# (tests/test_bf16_family_cover.py reads these: which kernel families the two tests below run on the shadow)
+SHAPES = [("SASRec", 50), ("SRFRN", 50), ("SRFU_B", 20)]
+FUSED_KIND = "SASRec"
 
 
 def _cfg(kind, L=50, I=400, dropout=0.0, bf16=True):
@@ -20,7 +23,7 @@ def _cfg(kind, L=50, I=400, dropout=0.0, bf16=True):
     return O.Cfg(kind, I, L, 50, n_labels=3, dropout=dropout, table_bf16=bf16)
 
 
-@pytest.mark.parametrize("kind,L", [("SASRec", 50), ("SRFRN", 50), ("SRFU_B", 20)])
+@pytest.mark.parametrize("kind,L", SHAPES)
 def test_bf16_table_forward_grads_and_topk_match_the_bf16_oracle(kind, L):
     import srfrd_amd
     from tests.gpu_util import build_model, cuda, maxerr, random_sd
@@ -60,7 +63,7 @@ def test_bf16_table_fused_training_keeps_the_shadow_current(graph):
     import srfrd_amd
     from tests.gpu_util import build_model, cuda, random_sd
     from tests.helpers import assert_post_adam, oracle_step_with_grads
-    cfg = _cfg("SASRec", dropout=0.5)
+    cfg = _cfg(FUSED_KIND, dropout=0.5)
     sd = random_sd(cfg, 9)
     model = build_model(cfg, {k: v.clone() for k, v in sd.items()}).train().use_bf16_table()
     B, base = 12, 77

@@ -101,7 +101,9 @@ def test_long_fused_step_with_dropout_matches_oracle(kind, L):
     """seq_len > 100 training: the forward (first generation up to 112, the row-owner kernel in its training mode above:
     dropout at the four sites, checkpoints written from the transposed score layout, target logits, loss sums) feeding the
     row-chunked backward - two fused Adam steps with dropout 0.5 against the oracle's steps with the same masks; lengths that
-    are not multiples of 4 or 16 and the largest one the kernels take (207: 13 row tiles, five chunks) included."""
+    are not multiples of 4 or 16 and the largest one the forward takes (207: 13 row tiles) included.  (From 205 on the
+    row-chunked backward's LDS no longer fits and the plan answers the global-scratch build; 203 - 13 row tiles, five chunks -
+    runs in tests/test_gpu_bf16_families.py.)"""
     import srfrd_amd
     from tests.gpu_util import build_model, cuda, random_sd
     from tests.helpers import assert_post_adam, oracle_step_with_grads
