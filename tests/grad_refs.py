@@ -1,0 +1,371 @@
+"""The encoder gradients' reference and metric (no GPU): an fp64 oracle and a bound relative to each row's own size.
+
+The suite's older gradient checks are ``max|g - g_oracle32| < 1e-4``: one absolute number for every tensor, against the fp32
+oracle.  The loss is a mean over all target positions, so at the batches those tests use most gradient elements are themselves
+below 1e-4; tests/test_grad_refs.py records which wrong gradients that bar accepts.  Here
+
+  reference  ``fp64_grads``: ``O.grads_of`` on the weights cast to double (the oracle takes its dtype from the weights; dropout
+             keep masks stay the fp32 values ``float32(1 / (1 - p))``, promoted - the operation the kernels perform);
+  metric     ``row_errors``: per row r of a tensor viewed as (shape[0], -1) (a 1-D tensor is one row), over the rows whose
+             fp64 gradient is not exactly zero,   e_r = ||g_r - g64_r||_2 / (||g64_r||_2 + 1e-3 max_r ||g64_r||_2);
+             the floor keeps rows a thousand times smaller than the largest on an absolute footing.  Worst row returned;
+  zero rows  a row whose fp64 gradient is exactly zero (an item no sequence touches, padding row 0, a position that is pad
+             in every sequence) must be exactly zero on the device: ``zero_row_leaks`` counts the elements that are not;
+  K bias     the K slice of every ``in_proj_bias`` has true gradient 0 (tests/helpers.py, drop_kbias): left out of e_r, held
+             to |g| <= R max|g64| over the Q and V slices instead;
+  bound      ``R = bound(e32) = max(64 e32, 2e-5)``, e32 the fp32 ORACLE's row_errors against the fp64 oracle for the same
+             tensor and case, computed on the CPU.  64 is a judgement: the kernels sum the same 50 to 64-term products and
+             attention sums of at most 208 terms in other orders, use the hardware exp / rcp / rsqrt and (non-deterministic
+             mode) sum item rows by float atomics - a few ulp per operation each: tens of times the oracle's own rounding,
+             not hundreds.  ``64 e32 <= 1e-4`` is a condition on the INPUTS of a case (``assert_admissible``, asserted on
+             the CPU and again where the GPU tests compute their bounds), so every bound is at least 100 times tighter than
+             the old bar, relative to the row; the jobs that have no such input are listed in OVER_CAP and clamped there.
+
+Every batch below also keeps every feed-forward ReLU input 2 * RELU_MARGIN away from zero on the fp64 oracle
+(test_gpu_bf16_families.relu_margin): no outlier allowance anywhere.
+
+The cases: test_gpu_bf16_families.CASES (every encoder kernel family the plan can choose; tests/test_bf16_family_cover.py) with
+the fp32 table, plus ``EXTRA``: the <50,32,8,0> first-generation pair (seq_len 20), and at the default geometry (seq_len 50, no
+switch: the ragged pair and the one-launch train kernel) a 17-sequence batch on the tile boundaries and a duplicate-heavy one.
+Kernel names do not carry the table flag, so the names of CASES hold for the fp32 table as they stand.
+"""
+import functools
+from collections import namedtuple
+
+import torch
+
+from oracle import srfrd_oracle as O
+from tests import test_gpu_bf16_families as F
+from tests.test_gpu_bf16_families import RELU_MARGIN, Case, relu_margin
+
+FLOOR = 1e-3
+FACTOR = 64.0
+R_MIN = 2e-5
+CAP = 1e-4
+OLD_BAR = 1e-4            # the suite's absolute bar on max|g - g_oracle32|
+BETA1, BETA2 = 0.9, 0.98
+BASE = 77                 # FusedTrainer(seed=BASE): the first step's dropout seed is O.step_seed(BASE, 1)
+I = F.I
+SD_SEED = 7               # random_sd(cfg, 7), as the bf16 family tests
+L2_EMB = 1e-3
+SEARCH_HEADROOM = 0.8     # seeds are chosen with 64 e32 <= 0.8e-4 (see SEEDS); the tests assert the condition itself, <= 1e-4
+
+_RAG = "srfrd::encoder_{d}_ragged_kernel<{a}>"
+
+
+def _ragged(cid, kind, d_item, d_fake, K, B):
+    f = lambda t: _RAG.format(d="fwd", a=f"{K},{t},{d_item}")
+    b = _RAG.format(d="bwd", a=f"{K},{d_item}")
+    return Case(cid, kind, d_item, d_fake, 1, 50, B, None, None, None, eval_fwd=f(0), last_fwd=f(0), autograd=(f(0), b),
+                fused=(f(1), b))
+
+
+_G32 = "<50,32,8,0,-1,0,0>"
+# ids: "s" seq_len 20; "t*" the tile-boundary batch (TILE_PADS), "u*" the duplicate-heavy batch, both at the default geometry
+EXTRA = [
+    Case("s", "SASRec", 50, 0, 1, 20, 6, None, None, None, **F._same(F._F + _G32, F._B + _G32)),
+    _ragged("t0", "SASRec", 50, 0, 0, 17), _ragged("t1", "SRFR", 45, 5, 1, 17), _ragged("t2", "SRFRN", 45, 5, 2, 17),
+    _ragged("t3", "SRFU_B", 50, 0, -1, 17),
+    _ragged("u0", "SASRec", 50, 0, 0, 12), _ragged("u2", "SRFRN", 45, 5, 2, 12),
+]
+ALL_CASES = list(F.CASES) + EXTRA
+BY_ID = {c.id: c for c in ALL_CASES}
+TRAIN_KERNEL_IDS = ("t0", "t1", "t2", "t3")          # run with train_launch on and off
+L2_ID = "t0"                                         # the one fused case that also runs with l2_emb = L2_EMB
+# leading pad counts of the tile-boundary batch: the boundaries tests/fuzz_ragged.py names, with both neighbours
+TILE_PADS = (0, 1, 3, 4, 5, 15, 16, 17, 19, 20, 21, 35, 36, 37, 48, 49, 50)
+
+# e32 is the fp32 oracle's rounding, and a matrix product sums in the order its CPU's kernels choose: between the two kinds of
+# machine the suite runs on, the worst-tensor e32 of one batch differs by -20 % .. +13 % (5th .. 95th percentile of 2300
+# batches) and by a factor of two at the extremes (1.30e-6 and 1.9e-6 for one tensor of one batch).  So a seed is chosen on
+# both (tools/grad_fp64_report.py --scan on each, then --pick; pick_seed below):
+# (case id, mode) -> batch seed: from the bf16 file's own seed on (6 / 50 for EXTRA), the first of 48 - of 200 where those hold
+# none - at which on BOTH machines relu_margin >= 2 * RELU_MARGIN and 64 e32 <= SEARCH_HEADROOM * CAP for every tensor.
+SEEDS = {
+    ("a", "autograd"): 9, ("a", "fused"): 50, ("b", "autograd"): 6, ("b", "fused"): 62, ("c", "autograd"): 198,
+    ("c", "fused"): 110,
+    ("d", "autograd"): 7, ("d", "fused"): 50, ("e", "autograd"): 6, ("e", "fused"): 51, ("f", "autograd"): 16,
+    ("f", "fused"): 93,
+    ("g", "autograd"): 16, ("g", "fused"): 50, ("h", "autograd"): 9, ("h", "fused"): 78, ("i", "autograd"): 16, ("i", "fused"): 50,
+    ("j", "autograd"): 131, ("j", "fused"): 56, ("k", "autograd"): 11, ("k", "fused"): 90, ("l", "autograd"): 46,
+    ("l", "fused"): 71,
+    ("m", "autograd"): 24, ("m", "fused"): 69, ("n", "autograd"): 131, ("n", "fused"): 56, ("o", "autograd"): 130,
+    ("o", "fused"): 70,
+    ("p", "autograd"): 6, ("p", "fused"): 62, ("q", "autograd"): 9, ("q", "fused"): 50, ("s", "autograd"): 6, ("s", "fused"): 51,
+    ("t0", "autograd"): 10, ("t0", "fused"): 50, ("t1", "autograd"): 97, ("t1", "fused"): 165, ("t2", "autograd"): 92,
+    ("t2", "fused"): 83, ("t3", "autograd"): 65, ("t3", "fused"): 128, ("u0", "autograd"): 12, ("u0", "fused"): 50,
+    ("u2", "autograd"): 11, ("u2", "fused"): 100,
+}
+# Weights: random_sd(cfg, SD_SEED) as in the bf16 family tests, but for b, k and p (SRFRN): the next weight seed, under which
+# their batches are found among the first.
+SD_SEEDS = {"b": 8, "k": 8, "p": 8}
+# Jobs without such a seed.  Of the scanned batches with the ReLU margin they take the one whose e32 is smallest on the worse
+# machine: f 2.2e-6 / 1.8e-6, l 3.3e-6 / 2.7e-6, m 2.8e-6 / 2.2e-6 (autograd / fused; SRFU_B and SRFR at seq_len 64 .. 128: no
+# input comes near the 1.5625e-6 the condition allows - these kinds add one large shared vector to every position, which the V
+# and out_proj rows cancel, and the worst of 150 rows is an extreme value that grows with the length); and the autograd batches
+# of c 1.27e-6, j = n 1.40e-6, o 1.47e-6, t1 1.44e-6, t3 1.41e-6: under the condition on both machines, without the headroom
+# that would promise it on a third.  For these jobs alone the condition is not asserted and `bound` is clamped at CAP -
+# tighter than 64 e32 where it acts, never wider.  They keep their place: f is the only case of the <50,64,8,0> pair, o of the
+# two-head srfrd_long:: pair.
+OVER_CAP = frozenset([(c, m) for c in "flm" for m in ("autograd", "fused")]
+                     + [(c, "autograd") for c in ("c", "j", "n", "o", "t1", "t3")])
+
+
+def case_ids(cases=None):
+    return [f"{c.id}-{c.kind}-L{c.L}" + (f"-{c.switch}" if c.switch else "") + (f"-h{c.heads}" if c.heads > 1 else "")
+            for c in (cases or ALL_CASES)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# reference and metric
+# ---------------------------------------------------------------------------------------------------------------------------
+def fp64_grads(cfg, sd, batch, train=False, seed=0, l2_emb=0.0):
+    """{name: fp64 gradient} of the oracle on the weights cast to double"""
+    return O.grads_of(cfg, {k: v.detach().double() for k, v in sd.items()}, batch, train=train, seed=seed, b0=0, l2_emb=l2_emb)[1]
+
+
+def fp32_grads(cfg, sd, batch, train=False, seed=0, l2_emb=0.0):
+    """the fp32 oracle's gradients, on one thread: e32 is this run's rounding, and the order of a threaded matrix product's
+    sums follows the thread count (seen: 1.50e-6 on 8 threads, 1.61e-6 on 64, for one tensor of one case)"""
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        return O.grads_of(cfg, sd, batch, train=train, seed=seed, b0=0, l2_emb=l2_emb)[1]
+    finally:
+        torch.set_num_threads(n)
+
+
+def _as_rows(t):
+    t = t.detach().cpu().double()
+    return t.reshape(t.shape[0], -1) if t.dim() >= 2 else t.reshape(1, -1)
+
+
+def row_errors(g, g64):
+    """worst e_r over the rows whose fp64 gradient is not exactly zero (0.0 where there is none)"""
+    a, b = _as_rows(g), _as_rows(g64)
+    assert a.shape == b.shape
+    live = (b != 0).any(dim=1)
+    if not bool(live.any()):
+        return 0.0
+    nb = b.norm(dim=1)
+    e = (a - b).norm(dim=1) / (nb + FLOOR * nb.max())
+    return float(e[live].max())
+
+
+def zero_row_leaks(g, g64):
+    """number of non-zero elements of `g` in the rows whose fp64 gradient is exactly zero"""
+    a, b = _as_rows(g), _as_rows(g64)
+    dead = ~(b != 0).any(dim=1)
+    return int((a[dead] != 0).sum())
+
+
+def bound(e32, clamp=False):
+    """max(64 e32, 2e-5); clamp (the OVER_CAP jobs only): never past CAP"""
+    r = max(FACTOR * e32, R_MIN)
+    return min(r, CAP) if clamp else r
+
+
+def is_kbias(name):
+    return name.endswith("in_proj_bias")
+
+
+def without_k(t, D):
+    """the Q and V slices of an in_proj_bias (its K slice's true gradient is 0)"""
+    return torch.cat([t[:D], t[2 * D:]])
+
+
+def tensor_figures(name, g, g64, g32, D, kbias=True, clamp=False, r=None):
+    """One tensor of one run against its reference -> dict: e32, bound, err (the device's row_errors), zero_leaks, old (the
+    former metric: max|g - g32|), and for an in_proj_bias kbias / kbias_limit.  r: the bound, where it is not bound(e32) of
+    these very tensors (the second moment)."""
+    g = g.detach().cpu().double()
+    out = {"old": float((g - g32.double()).abs().max())}
+    kbias = kbias and is_kbias(name)        # (under l2_emb the K slice has a gradient of its own: an ordinary part of the row)
+    if kbias:
+        k = g[D:2 * D]
+        g, g64, g32 = without_k(g, D), without_k(g64, D), without_k(g32, D)
+    out["e32"] = row_errors(g32, g64)
+    out["bound"] = bound(out["e32"], clamp) if r is None else r
+    out["err"] = row_errors(g, g64)
+    out["zero_leaks"] = zero_row_leaks(g, g64)
+    if kbias:
+        out["kbias"], out["kbias_limit"] = float(k.abs().max()), out["bound"] * float(g64.abs().max())
+    return out
+
+
+def failures(fig):
+    """what one tensor_figures() result misses, as text ([] = it holds)"""
+    bad = []
+    if not fig["err"] <= fig["bound"]:
+        bad.append(f"row error {fig['err']:.3e} > {fig['bound']:.3e}")
+    if fig["zero_leaks"]:
+        bad.append(f"{fig['zero_leaks']} non-zero elements in rows whose true gradient is exactly zero")
+    if "kbias" in fig and not fig["kbias"] <= fig["kbias_limit"]:
+        bad.append(f"K bias {fig['kbias']:.3e} > {fig['kbias_limit']:.3e}")
+    return bad
+
+
+def compare(grads, ref, squares=False):
+    """every tensor of `grads` ({name: device gradient}) against a Ref -> {name: tensor_figures}.  squares: `grads` holds
+    g ** 2 (Adam's second moment / (1 - beta2)): compared with g64 ** 2 under twice the gradient's bound; its K-bias slice,
+    as sqrt(v) = |g|, against twice the gradient's K-bias limit."""
+    assert set(grads) == set(ref.g64)
+    out = {}
+    for k in ref.g64:
+        kb = ref.l2 == 0.0
+        if not squares:
+            out[k] = tensor_figures(k, grads[k], ref.g64[k], ref.g32[k], ref.cfg.D, kbias=kb, clamp=ref.clamp)
+            continue
+        r = 2.0 * bound(ref.e32[k], ref.clamp)
+        fig = tensor_figures(k, grads[k], ref.g64[k] ** 2, ref.g32[k].double() ** 2, ref.cfg.D, kbias=kb, r=r)
+        fig["e32"] = ref.e32[k]
+        if "kbias" in fig:
+            fig["kbias"], fig["kbias_limit"] = fig["kbias"] ** 0.5, r * float(without_k(ref.g64[k], ref.cfg.D).abs().max())
+        out[k] = fig
+    return out
+
+
+def assert_holds(figs, what):
+    bad = {k: failures(f) for k, f in figs.items() if failures(f)}
+    worst = max(figs, key=lambda k: figs[k]["err"] / figs[k]["bound"])
+    print(f"{what}: worst {worst} {figs[worst]['err']:.2e} of {figs[worst]['bound']:.2e}"
+          f" (old metric {max(f['old'] for f in figs.values()):.2e})")
+    assert not bad, (what, bad)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# batches
+# ---------------------------------------------------------------------------------------------------------------------------
+def _reviews(g, seq, pos, neg):
+    rsq = torch.where(seq != 0, torch.randint(1, 3, seq.shape, generator=g), torch.zeros_like(seq))
+    prs = torch.where(pos != 0, torch.randint(1, 3, seq.shape, generator=g), torch.zeros_like(pos))
+    return seq, rsq, pos, prs, neg, (neg != 0).long()
+
+
+def tile_batch(seed, L=50):
+    """17 sequences, sequence i with TILE_PADS[i] leading pads (the last is all pad); an interior pad in sequence 3; rows 5
+    and 11 keep target ids on their padded positions (the head's range starts in front of the blocks')"""
+    g = torch.Generator().manual_seed(seed)
+    B = len(TILE_PADS)
+    seq, pos, neg = (torch.randint(1, I + 1, (B, L), generator=g) for _ in range(3))
+    for b, t0 in enumerate(TILE_PADS):
+        seq[b, :t0] = 0
+        if b not in (5, 11):
+            pos[b, :t0] = 0
+            neg[b, :t0] = 0
+    seq[3, 27] = 0
+    return _reviews(g, seq, pos, neg)
+
+
+def dup_batch(seed, B=12, L=50):
+    """a quarter of the rows draw inputs, positives and negatives from items 1..8: one id occurs dozens of times, as input,
+    positive and negative at once; leading pads on the other rows as in any batch"""
+    g = torch.Generator().manual_seed(seed)
+    seq, pos, neg = (torch.randint(1, I + 1, (B, L), generator=g) for _ in range(3))
+    for b in range(B):
+        if b % 4 == 0:
+            for x in (seq, pos, neg):
+                x[b] = torch.randint(1, 9, (L,), generator=g)
+        else:
+            t0 = int(torch.randint(0, L - 1, (1,), generator=g))
+            for x in (seq, pos, neg):
+                x[b, :t0] = 0
+    return _reviews(g, seq, pos, neg)
+
+
+def batch_of(c, seed):
+    import srfrd_amd
+    if c.id.startswith("t"):
+        return tile_batch(seed)
+    if c.id.startswith("u"):
+        return dup_batch(seed, c.B)
+    return tuple(srfrd_amd.synthetic_batch(I, c.L, c.B, seed=seed, device="cpu")[1:])
+
+
+def first_seed(c, mode):
+    return {"autograd": c.seed, "fused": c.fused_seed}[mode] or {"autograd": 6, "fused": 50}[mode]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# per-case references, computed once per process
+# ---------------------------------------------------------------------------------------------------------------------------
+Ref = namedtuple("Ref", "cfg sd batch train seed l2 g64 g32 e32 margin clamp")
+
+
+def cfg_of(c, mode):
+    return F.cfg_of(c, bf16=False, dropout=0.5 if mode == "fused" else 0.0)
+
+
+@functools.lru_cache(maxsize=None)
+def weights(cid):
+    from tests.gpu_util import random_sd
+    return random_sd(cfg_of(BY_ID[cid], "autograd"), SD_SEEDS.get(cid, SD_SEED))
+
+
+def build_ref(c, mode, seed, l2=0.0):
+    """mode "autograd": a training-mode forward with dropout 0; "fused": the first FusedTrainer step, dropout 0.5"""
+    cfg, sd, batch = cfg_of(c, mode), weights(c.id), batch_of(c, seed)
+    train = mode == "fused"
+    dseed = O.step_seed(BASE, 1) if train else 0
+    g64 = fp64_grads(cfg, sd, batch, train=train, seed=dseed, l2_emb=l2)
+    g32 = fp32_grads(cfg, sd, batch, train=train, seed=dseed, l2_emb=l2)
+    e32 = {k: tensor_figures(k, g32[k], g64[k], g32[k], cfg.D, kbias=l2 == 0.0)["e32"] for k in g64}
+    margin = relu_margin(cfg, {k: v.double() for k, v in sd.items()}, batch, train=train, seed=dseed)
+    return Ref(cfg, sd, batch, train, dseed, l2, g64, g32, e32, margin, (c.id, mode) in OVER_CAP)
+
+
+def under_cap(ref):
+    return FACTOR * max(ref.e32.values()) <= CAP
+
+
+def assert_admissible(ref, what):
+    """the condition on a case's inputs, on the oracle alone, on whichever CPU computes the bounds: every ReLU input
+    2 * RELU_MARGIN from zero, and 64 e32 <= CAP for every tensor (but for the OVER_CAP jobs, whose bounds are clamped there)"""
+    worst = max(ref.e32, key=ref.e32.get)
+    print(f"{what}: worst e32 {ref.e32[worst]:.2e} ({worst}), relu margin {ref.margin:.2e}")
+    assert ref.margin >= 2 * RELU_MARGIN, what
+    assert ref.clamp or under_cap(ref), (what, worst, ref.e32[worst])
+
+
+@functools.lru_cache(maxsize=None)
+def reference(cid, mode, l2=0.0):
+    """the Ref of one case and mode at its SEEDS entry, shared by every test of the process; treat as read-only"""
+    return build_ref(BY_ID[cid], mode, SEEDS[cid, mode], l2)
+
+
+def scan_seeds(job):
+    """(case id, mode, count) -> [[seed, worst e32, relu margin], ...] from first_seed on, on THIS machine's CPU"""
+    cid, mode, count = job
+    c = BY_ID[cid]
+    out = []
+    for seed in range(first_seed(c, mode), first_seed(c, mode) + count):
+        ref = build_ref(c, mode, seed)
+        out.append([seed, max(ref.e32.values()), ref.margin])
+    return out
+
+
+def pick_seed(scans):
+    """scans: scan_seeds' rows of one case and mode, one list per kind of machine the suite runs on.  -> (seed, found): the
+    first seed whose ReLU margin holds and whose 64 e32 stays under SEARCH_HEADROOM * CAP on all of them; where there is none,
+    the seed with the margin whose e32 is smallest on its worst machine, and False (an OVER_CAP job)"""
+    ok = [rows for rows in zip(*scans) if all(m >= 2 * RELU_MARGIN for _, _, m in rows)]
+    assert all(len({r[0] for r in rows}) == 1 for rows in ok)
+    for rows in ok:
+        if all(FACTOR * e <= SEARCH_HEADROOM * CAP for _, e, _ in rows):
+            return rows[0][0], True
+    return min(ok, key=lambda rows: max(e for _, e, _ in rows))[0][0], False
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# reading the device's gradients
+# ---------------------------------------------------------------------------------------------------------------------------
+def fused_gradients(trainer, model):
+    """after ONE FusedTrainer step from zero moments: ({name: g}, {name: g ** 2}) in fp64, from exp_avg / (1 - beta1) and
+    exp_avg_sq / (1 - beta2) of the optimizer state"""
+    assert trainer.steps_done == 1 and trainer.betas == (BETA1, BETA2)
+    state = trainer.state_dict()["state"]
+    g, g2 = {}, {}
+    for i, (k, _) in enumerate(model.named_parameters()):
+        g[k] = state[i]["exp_avg"].detach().cpu().double() / (1.0 - BETA1)
+        g2[k] = state[i]["exp_avg_sq"].detach().cpu().double() / (1.0 - BETA2)
+    return g, g2

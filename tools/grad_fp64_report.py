@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Measured agreement of every encoder gradient with the fp64 oracle (GPU box) -> profiles/grad_fp64_errors.json.
+
+    python tools/grad_fp64_report.py [--out profiles/grad_fp64_errors.json]
+    python tools/grad_fp64_report.py --scan OUT.json  # CPU only, once per kind of machine the suite runs on, then
+    python tools/grad_fp64_report.py --pick A.json B.json      # ... the batch-seed table of tests/grad_refs.py
+
+Runs what tests/test_gpu_grad_fp64.py runs (its run_autograd / run_fused) and records per case, mode and tensor (one
+array per line, in the order of `tensors`): e32 (the fp32 oracle's row error against the fp64 oracle), the bound, the
+device's row error, and the former metric max|g - g_oracle32|.  Exit code 1 if a tensor misses its bound.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _setenv(changed):
+    def setenv(name, value):
+        changed.setdefault(name, os.environ.get(name))
+        os.environ[name] = value
+    return setenv
+
+
+def _num(x):
+    return float(f"{x:.2g}")
+
+
+def _record(figs, names, shared):
+    """one run -> arrays in the order of `names`; e32 and bound only where no earlier run of the case has the same reference"""
+    out = {} if shared else {"e32": [_num(figs[k]["e32"]) for k in names], "bound": [_num(figs[k]["bound"]) for k in names]}
+    if shared:
+        out["e32_and_bound_as"] = shared
+    out["err"] = [_num(figs[k]["err"]) for k in names]
+    out["old"] = [_num(figs[k]["old"]) for k in names]
+    kb = [f["kbias"] / f["kbias_limit"] for f in figs.values() if "kbias" in f]
+    if kb:
+        out["kbias_of_limit"] = _num(max(kb))
+    out["zero_leaks"] = sum(f["zero_leaks"] for f in figs.values())
+    return out
+
+
+def _dump(report, f):
+    """json with one array per line"""
+    f.write("{\n")
+    f.write(f' "metric": {json.dumps(report["metric"])},\n "tensors": {{\n')
+    f.write(",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in sorted(report["tensors"].items())))
+    f.write("\n },\n \"cases\": {\n")
+    cases = []
+    for cid, modes in report["cases"].items():
+        runs = ",\n".join(f"   {json.dumps(m)}: " + (json.dumps(r) if not isinstance(r, dict) else
+                          "{\n" + ",\n".join(f"    {json.dumps(k)}: {json.dumps(v)}" for k, v in r.items()) + "}")
+                          for m, r in modes.items())
+        cases.append(f"  {json.dumps(cid)}: {{\n{runs}\n  }}")
+    f.write(",\n".join(cases))
+    f.write("\n }\n}\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grad_fp64_errors.json"))
+    ap.add_argument("--scan", metavar="OUT", help="CPU only: worst e32 and ReLU margin of every job's candidate seeds, here")
+    ap.add_argument("--count", type=int, default=48)
+    ap.add_argument("--jobs", nargs="*", metavar="CASE/MODE", help="--scan: these only")
+    ap.add_argument("--workers", type=int, default=8)
+    ap.add_argument("--pick", nargs="+", metavar="SCAN", help="grad_refs.SEEDS from one --scan file per kind of machine")
+    a = ap.parse_args()
+    from tests import grad_refs as G
+    if a.scan:
+        import multiprocessing as mp
+        jobs = [(c.id, m, a.count) for c in G.ALL_CASES for m in ("autograd", "fused") if not a.jobs or f"{c.id}/{m}" in a.jobs]
+        with mp.get_context("spawn").Pool(a.workers) as pool:
+            rows = pool.map(G.scan_seeds, jobs, chunksize=1)
+        with open(a.scan, "w") as f:
+            json.dump({f"{cid}/{m}": r for (cid, m, _), r in zip(jobs, rows)}, f)
+        return 0
+    if a.pick:
+        scans = [json.load(open(p)) for p in a.pick]
+        for key in scans[0]:
+            seed, found = G.pick_seed([s[key] for s in scans])
+            worst = max(next(r[1] for r in s[key] if r[0] == seed) for s in scans)
+            print(f"{key}: {seed}   worst-machine e32 {worst:.3e}" + ("" if found else "   <-- no seed with headroom: OVER_CAP"))
+        return 0
+    from tests import test_gpu_grad_fp64 as T
+    runs = []
+    for c in G.ALL_CASES:
+        runs.append((c, "autograd", lambda c, env: (T.run_autograd(c, env), None)))
+        for det in (True, False):
+            name = "fused-" + ("deterministic" if det else "atomics")
+            runs.append((c, name, lambda c, env, det=det: T.run_fused(c, det, env)))
+            if c.id in G.TRAIN_KERNEL_IDS:
+                runs.append((c, name + "-two-launches", lambda c, env, det=det: T.run_fused(c, det, env, train_launch=False)))
+            if c.id == G.L2_ID:
+                runs.append((c, name + "-l2_emb", lambda c, env, det=det: T.run_fused(c, det, env, l2=G.L2_EMB)))
+    report, missed, tensors, first = {}, 0, {}, {}
+    for c, mode, fn in runs:
+        changed = {}
+        try:
+            figs, figs2 = fn(c, _setenv(changed))
+        finally:
+            for name, old in changed.items():
+                os.environ.pop(name, None) if old is None else os.environ.__setitem__(name, old)
+        names = tensors.setdefault(c.kind, sorted(figs))
+        ref = "autograd" if mode == "autograd" else "fused-l2_emb" if mode.endswith("l2_emb") else "fused"
+        shared = first.get((c.id, ref))
+        first.setdefault((c.id, ref), mode)
+        entry = report.setdefault(G.case_ids([c])[0], {"kind": c.kind})
+        entry[mode] = _record(figs, names, shared)
+        if figs2 is not None:       # (the same gradient squared, under twice the bound: the worst tensor only)
+            w = max(figs2, key=lambda k: figs2[k]["err"] / figs2[k]["bound"])
+            entry[mode]["second_moment_worst"] = [w, _num(figs2[w]["err"]), _num(figs2[w]["bound"])]
+        both = list(figs.values()) + list((figs2 or {}).values())
+        bad = sum(bool(G.failures(f)) for f in both)
+        missed += bad
+        worst = max(f["err"] / f["bound"] for f in both)
+        print(f"{c.id:3s} {mode:34s} worst err / bound {worst:.3f}" + (f"   <-- {bad} tensors miss" if bad else ""), flush=True)
+    with open(a.out, "w") as f:
+        _dump({"metric": "tests/grad_refs.py: row_errors, bound(e32) = max(64 e32, 2e-5), clamped at 1e-4 for the OVER_CAP jobs; "
+                         "arrays follow `tensors` of the case's kind; old = max|g - g_oracle32|; second_moment_worst = "
+                         "[tensor, row error of g^2, twice the bound]; kbias_of_limit is absent under l2_emb, where the K "
+                         "slice is an ordinary part of its row",
+               "tensors": tensors, "cases": report}, f)
+    print(f"{missed} tensors miss their bound; wrote {a.out}")
+    return 1 if missed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
