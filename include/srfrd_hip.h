@@ -563,6 +563,27 @@ int srfrd_table_reduce_rank1(const int64_t* sorted_keys, const int64_t* order, c
                              float* workspace, int64_t ws_floats, void* stream);
 
 /*
+ * srfrd_table_reduce_rank1 over a list that also holds FULL rows: the one table-gradient reduction of a train step whose
+ * encoder backward leaves full contribution rows (table_contrib's input plane) and whose loss head leaves rank-1 rows
+ * (srfrd_tneg_bwd).  Neither reduce adds to grad_table, so running both would need a dense add over the whole table.
+ * The unsorted list has n entries: entry e < n_rows is rows[e, :d_item] (rows (n_rows, d_item) fp32), entry e >= n_rows the
+ * rank-1 row contrib_coef[r] * hidden[r / rows_per_token, :d_item] with r = e - n_rows (so contrib_coef holds n - n_rows
+ * floats and hidden (n - n_rows) / rows_per_token rows of d_out; both are only read).  sorted_keys / order: a STABLE
+ * ascending sort of the concatenated keys.  Per run of equal keys the entries are summed in sorted order into
+ * grad_table[key]: a full row enters as fmaf(1, row, acc), a rank-1 row as fmaf(coef, hidden, acc).  Keys <= 0 are skipped,
+ * rows without contributions are not touched.  Segments, partials and merge are srfrd_table_reduce_rank1's (one kernel,
+ * the row source a template parameter): bitwise reproducible, and with n_rows == 0 the bits of srfrd_table_reduce_rank1.
+ * SRFRD_E_ARG before any launch: sorted_keys, order, grad_table or workspace NULL; rows NULL with n_rows > 0; contrib_coef
+ * or hidden NULL with n > n_rows; n <= 0 or n > INT_MAX; n_rows < 0 or > n; rows_per_token < 1; d_item < 1 or >
+ * SRFRD_MAX_D; d_out < d_item; ws_floats below srfrd_table_reduce_mixed_workspace_floats(n, d_item) [host] = 2 ceil(n /
+ * SRFRD_TNEG_SPLIT_ROWS) d_item rounded up to 64 (0 for arguments the call refuses).
+ */
+int64_t srfrd_table_reduce_mixed_workspace_floats(int64_t n, int d_item);
+int srfrd_table_reduce_mixed(const int64_t* sorted_keys, const int64_t* order, int64_t n, const float* rows, int64_t n_rows,
+                             const float* contrib_coef, const float* hidden, int d_out, int rows_per_token, int d_item,
+                             float* grad_table, float* workspace, int64_t ws_floats, void* stream);
+
+/*
  * Shared negatives of one sampled-softmax train step, drawn on the device (FusedTrainer(loss="sampled_softmax") captures it
  * into the step graph).  Slot j < K: h1 = fmix32(base ^ j), h2 = fmix32(base ^ (j | 2^31)) with base = fmix32(state[2] +
  * SITE_NEG * 0x9E3779B9) (srfrd_rng.h; state[2] is the step seed word srfrd_step_begin / srfrd_adam_pack_step advance), then

@@ -96,6 +96,8 @@ SIGNATURES = {
     "srfrd_tneg_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _d, _i, _i, _i, _P, _P, _P, _P, _i64, _P]),
     "srfrd_tneg_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _d, _i, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
     "srfrd_table_reduce_rank1": (_i, [_P, _P, _P, _P, _i, _i, _i64, _i, _P, _P, _i64, _P]),
+    "srfrd_table_reduce_mixed_workspace_floats": (_i64, [_i64, _i]),
+    "srfrd_table_reduce_mixed": (_i, [_P, _P, _i64, _P, _i64, _P, _P, _i, _i, _i, _P, _P, _i64, _P]),
 }
 
 _lib = None

@@ -21,7 +21,7 @@
 //   backward  tneg_bwd_kernel     the logits again (same code, same bits); g_tk per slot; dH += g_tk E[n_tk] in the lanes
 //                                 that hold the row, the four groups added in group order -> d_hidden (the whole row, zeros
 //                                 past d_item and at ignored positions); g_tk and its key to the contribution list
-//   table     rank1_segment_kernel / rank1_merge_kernel   (srfrd_table_reduce_rank1) below
+//   table     rank1_segment_kernel / rank1_merge_kernel   (srfrd_table_reduce_rank1, srfrd_table_reduce_mixed) below
 // No float atomics anywhere: two identical calls are bitwise identical.
 
 #include <climits>
@@ -302,7 +302,12 @@ __device__ __forceinline__ void rank1_put(float* __restrict__ dst, int di, int l
   if (lane < di) dst[lane] = acc;
 }
 
+// kMixed (srfrd_table_reduce_mixed): list entries o < n_rows are full rows, rows[o, :di], entering as fmaf(1, row, acc);
+// entry o >= n_rows is the rank-1 row r = o - n_rows.  A lane carries its entry's source as one int for the readlane:
+// the token of a rank-1 row, or ~o of a full row.
+template <bool kMixed>
 __global__ void __launch_bounds__(256) rank1_segment_kernel(const int64_t* __restrict__ keys, const int64_t* __restrict__ order,
+                                                            const float* __restrict__ rows, int64_t n_rows,
                                                             const float* __restrict__ coef, const float* __restrict__ hidden,
                                                             int d_out, int rpt, int64_t n, int di, float* __restrict__ grad_table,
                                                             float* __restrict__ part) {
@@ -321,7 +326,17 @@ __global__ void __launch_bounds__(256) rank1_segment_kernel(const int64_t* __res
     int64_t k = 0;
     int tok = 0;
     float c = 0.f;
-    if (i < s1) {
+    if constexpr (kMixed) {
+      // (a lane past the segment takes the source of the segment's last entry: a valid row, not used)
+      const int64_t o = order[i < s1 ? i : s1 - 1];
+      float co = 1.f;
+      if (o < n_rows) tok = ~(int)o;
+      else {
+        co = coef[o - n_rows];
+        tok = (int)((o - n_rows) / rpt);
+      }
+      if (i < s1) { k = keys[i]; c = co; }
+    } else if (i < s1) {
       k = keys[i];
       const int64_t o = order[i];
       c = coef[o];
@@ -333,7 +348,8 @@ __global__ void __launch_bounds__(256) rank1_segment_kernel(const int64_t* __res
 #pragma unroll
       for (int q = 0; q < 8; ++q) {                           // lanes past the segment hold token 0: a valid row, not used
         const int tq = __builtin_amdgcn_readlane(tok, j0 + q);
-        hv[q] = lane < di ? hidden[(int64_t)tq * d_out + lane] : 0.f;
+        const float* src = kMixed && tq < 0 ? rows + (int64_t)~tq * di : hidden + (int64_t)tq * d_out;
+        hv[q] = lane < di ? src[lane] : 0.f;
       }
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
@@ -469,8 +485,34 @@ extern "C" int srfrd_table_reduce_rank1(const int64_t* sorted_keys, const int64_
   if (ws_floats < rank1_part_floats(n, d_item)) return SRFRD_E_ARG;
   const hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)(((n + kSeg - 1) / kSeg + 3) / 4);
-  hipLaunchKernelGGL(rank1_segment_kernel, dim3(grid), dim3(256), 0, st, sorted_keys, order, contrib_coef, hidden, d_out,
-                     rows_per_token, n, d_item, grad_table, workspace);
+  hipLaunchKernelGGL(rank1_segment_kernel<false>, dim3(grid), dim3(256), 0, st, sorted_keys, order, (const float*)nullptr,
+                     (int64_t)0, contrib_coef, hidden, d_out, rows_per_token, n, d_item, grad_table, workspace);
+  hipLaunchKernelGGL(rank1_merge_kernel, dim3(grid), dim3(256), 0, st, sorted_keys, n, d_item, (const float*)workspace, grad_table);
+  return (int)hipGetLastError();
+}
+
+static bool mixed_args_ok(int64_t n, int64_t n_rows, int rows_per_token, int d_item, int d_out) {
+  return n > 0 && n <= INT_MAX && n_rows >= 0 && n_rows <= n && rows_per_token >= 1 && d_item >= 1 && d_item <= SRFRD_MAX_D &&
+         d_out >= d_item;
+}
+
+extern "C" int64_t srfrd_table_reduce_mixed_workspace_floats(int64_t n, int d_item) {
+  if (!mixed_args_ok(n, 0, 1, d_item, d_item)) return 0;
+  return rank1_part_floats(n, d_item);
+}
+
+extern "C" int srfrd_table_reduce_mixed(const int64_t* sorted_keys, const int64_t* order, int64_t n, const float* rows,
+                                        int64_t n_rows, const float* contrib_coef, const float* hidden, int d_out,
+                                        int rows_per_token, int d_item, float* grad_table, float* workspace, int64_t ws_floats,
+                                        void* stream) {
+  if (!sorted_keys || !order || !grad_table || !workspace || !mixed_args_ok(n, n_rows, rows_per_token, d_item, d_out))
+    return SRFRD_E_ARG;
+  if ((n_rows > 0 && !rows) || (n > n_rows && (!contrib_coef || !hidden))) return SRFRD_E_ARG;
+  if (ws_floats < rank1_part_floats(n, d_item)) return SRFRD_E_ARG;
+  const hipStream_t st = (hipStream_t)stream;
+  const unsigned grid = (unsigned)(((n + kSeg - 1) / kSeg + 3) / 4);
+  hipLaunchKernelGGL(rank1_segment_kernel<true>, dim3(grid), dim3(256), 0, st, sorted_keys, order, rows, n_rows, contrib_coef,
+                     hidden, d_out, rows_per_token, n, d_item, grad_table, workspace);
   hipLaunchKernelGGL(rank1_merge_kernel, dim3(grid), dim3(256), 0, st, sorted_keys, n, d_item, (const float*)workspace, grad_table);
   return (int)hipGetLastError();
 }

@@ -9,7 +9,8 @@ the lse / shape arguments sit the head's own arguments (none, or negatives, log_
 Between d_hidden and the workspace sits the table gradient in one of three forms: a dense (n_items + 1, d_item) write with
 an accumulate flag (XENT); K + T contribution rows and their item keys, summed per item by srfrd_table_reduce (SXENT); or
 T (1 + K) coefficients and keys, summed per item as coef * hidden[t] by srfrd_table_reduce_rank1 (TNEG).  Both reduces run
-over a stable sort of the keys, so every item's rows are added in list order: bitwise reproducible.
+over a stable sort of the keys, so every item's rows are added in list order: bitwise reproducible.  ``table_mixed`` is the
+reduce of a list that holds both full rows and rank-1 rows (srfrd_table_reduce_mixed): FusedTrainer's token-negatives step.
 
 ``launch_fwd`` / ``launch_bwd`` are what the ``srfrd::{xent,sxent,tneg}_{fwd,bwd}`` library ops (ops.py), the modules'
 autograd function (modules.py) and FusedTrainer's cross-entropy step (trainer.py) all call.  Every buffer they would
@@ -57,6 +58,42 @@ def table_rank1(lay, hidden, K, rows, keys, ws, d_table):
     check(_lib.lib().srfrd_table_reduce_rank1(ptr(skeys), ptr(order), ptr(rows), ptr(hidden), lay.d_out, 1 + K, skeys.numel(),
                                               lay.d_item, ptr(d_table), ptr(ws), ws.numel(), _stream()),
           "srfrd_table_reduce_rank1")
+    return d_table
+
+
+def mixed_workspace(n, d_item):
+    """floats of workspace srfrd_table_reduce_mixed needs for a list of n entries (0: it refuses them)"""
+    return int(_lib.lib().srfrd_table_reduce_mixed_workspace_floats(int(n), int(d_item)))
+
+
+def table_mixed(lay, hidden, K, full_rows, coef, keys, ws, d_table, sorted_pair=None):
+    """one table gradient from two kinds of rows (a train step: the encoder backward's full rows, then the TNEG head's
+    rank-1 list): ``keys`` is [the keys of ``full_rows`` (n_rows, d_item) | the keys of ``coef``], stable-sorted here
+    (``sorted_pair``: the (sorted keys, order) of a stable sort the caller has made already); per item the full rows are
+    summed first, in row order, then the rank-1 rows coef * hidden[t] in list order.  The sizes the kernel indexes by are
+    checked here: it reads hidden[(e - n_rows) // (1 + K)] for every list entry e >= n_rows."""
+    n_rows = 0 if full_rows is None else full_rows.shape[0]
+    n_coef = 0 if coef is None else coef.numel()
+    n = keys.numel()
+    if n != n_rows + n_coef:
+        raise ValueError(f"{n} keys for {n_rows} full rows and {n_coef} rank-1 rows")
+    if full_rows is not None and (full_rows.dim() != 2 or full_rows.shape[1] != lay.d_item or not full_rows.is_contiguous()):
+        raise ValueError(f"full_rows must be a contiguous (n_rows, {lay.d_item}) tensor")
+    if n_coef and (hidden.shape[-1] != lay.d_out or not hidden.is_contiguous() or
+                   n_coef > (hidden.numel() // lay.d_out) * (1 + K)):
+        raise ValueError(f"{n_coef} rank-1 rows need ceil({n_coef} / {1 + K}) hidden rows of {lay.d_out}")
+    if ws.numel() < mixed_workspace(n, lay.d_item) or mixed_workspace(n, lay.d_item) <= 0:
+        raise ValueError(f"the workspace holds {ws.numel()} floats; a list of {n} entries needs "
+                         f"{mixed_workspace(n, lay.d_item)} (0: refused)")
+    if sorted_pair is None:
+        skeys, order, d_table = _sorted_keys(lay, keys, d_table)
+    else:
+        skeys, order = sorted_pair
+        if skeys.numel() != n or order.numel() != n or skeys.dtype != torch.int64 or order.dtype != torch.int64:
+            raise ValueError(f"sorted_pair must be two int64 tensors of {n} elements")
+    check(_lib.lib().srfrd_table_reduce_mixed(ptr(skeys), ptr(order), n, ptr(full_rows), n_rows, ptr(coef),
+                                              ptr(hidden) if n_coef else None, lay.d_out, 1 + K, lay.d_item, ptr(d_table),
+                                              ptr(ws), ws.numel(), _stream()), "srfrd_table_reduce_mixed")
     return d_table
 
 

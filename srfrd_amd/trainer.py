@@ -33,7 +33,8 @@ from ._lib import check, ptr
 from .exchange import GradExchange, exchange_active, shard_bounds  # noqa: F401  (shard_bounds re-exported)
 from .sampler import alias_table, negative_q
 
-LOSSES = ("bce", "sampled_softmax", "softmax")
+LOSSES = ("bce", "sampled_softmax", "softmax", "token_softmax", "gbce")
+TOKEN_LOSSES = {"token_softmax": "softmax", "gbce": "gbce"}      # -> the objective of srfrd_tneg_fwd / _bwd
 
 
 def flat_allreduce(flat: torch.Tensor, group=None):
@@ -43,21 +44,34 @@ def flat_allreduce(flat: torch.Tensor, group=None):
     return flat
 
 
-def _loss_config(model, loss, num_negatives, neg_counts, neg_alpha, process_group):
+def _loss_config(model, loss, num_negatives, neg_counts, neg_alpha, process_group, gbce_beta=1.0, tokens=0):
     """The refusals of FusedTrainer's loss arguments, made before anything is allocated; -> q (fp64 numpy (n_items,)) of the
-    popularity sampler, or None"""
+    popularity sampler, or None.  ``tokens``: B L of the step."""
     if loss not in LOSSES:
         raise ValueError(f"loss must be one of {LOSSES} (got {loss!r})")
     if loss != "sampled_softmax" and neg_counts is not None:
-        raise ValueError("neg_counts belongs to loss='sampled_softmax'")
+        raise ValueError("neg_counts belongs to loss='sampled_softmax'" + (
+            f": under loss={loss!r} the negatives are batch data and their sampler owns the distribution"
+            if loss in TOKEN_LOSSES else ""))
     if loss == "bce":
         return None
     q = None
-    if loss == "sampled_softmax":
+    if loss == "sampled_softmax" or loss in TOKEN_LOSSES:
         if int(num_negatives) < 1:
             raise ValueError(f"num_negatives must be at least 1 (got {num_negatives})")
         if neg_counts is not None:
             q = negative_q(model.layout.n_items, neg_counts, neg_alpha)
+    if loss in TOKEN_LOSSES:
+        beta = float(gbce_beta)
+        if not (beta >= 0.0) or beta == float("inf"):
+            raise ValueError(f"gbce_beta must be finite and >= 0 (got {gbce_beta})")
+        if loss == "gbce" and model._kind == "SRFRN":
+            raise ValueError("objective='gbce' is not built for SRFRN: its logits include the fake slice, which BCE "
+                             "(unlike the softmax) is not invariant to")
+        # the step's one key list holds T input rows and T (1 + K) rank-1 rows, indexed with 32-bit ints by the reduction
+        if int(tokens) * (2 + int(num_negatives)) >= 2 ** 31:
+            raise ValueError(f"num_negatives K = {num_negatives}: B L (2 + K) = {int(tokens) * (2 + int(num_negatives))} "
+                             f"must stay below 2^31")
     if model.layout.D > _lib.MAX_D:
         raise ValueError(f"loss={loss!r}: the cross-entropy kernels cover hidden width <= {_lib.MAX_D} (got {model.layout.D})")
     if model.bf16_table:
@@ -74,7 +88,7 @@ class FusedTrainer:
                  eps: float = 1e-8, l2_emb: float = 0.0, seed: int = 42, process_group=None, use_graph: bool = True,
                  slots: int = 1, exchange: str = "sharded", deterministic: bool = False, shadow_gather: bool = False,
                  loss: str = "bce", num_negatives: int = 1024, neg_counts=None, neg_alpha: float = 1.0,
-                 logq_correction: bool = True, remove_accidental_hits: bool = True):
+                 logq_correction: bool = True, remove_accidental_hits: bool = True, gbce_beta: float = 1.0):
         """``shadow_gather`` (sharded exchange over a bf16 item-table shadow, ``model.use_bf16_table()``; SURVEY 8e's alternative
         for BASELINE configs[4]): the fp32 master of an item row and its Adam moments live on the OWNER rank only; after the
         sharded Adam step the all-gather carries the bf16 SHADOW of the table (2 bytes per element: 90 MB instead of 180 MB at
@@ -92,8 +106,15 @@ class FusedTrainer:
         "softmax": the full catalog, as ``model.full_catalog_loss``.  The negative-id planes of a batch are not read under
         a cross-entropy loss.  ``negatives`` / ``log_q`` show what the last step drew.  The cross-entropy steps run on one
         rank with the fp32 item table; the sampled step's table gradient is always reduced in a fixed order (bitwise
-        reproducible, whatever ``deterministic`` says)."""
-        q = _loss_config(model, loss, num_negatives, neg_counts, neg_alpha, process_group)
+        reproducible, whatever ``deterministic`` says).
+        "token_softmax" / "gbce": ``num_negatives`` = K negatives PER POSITION, the two objectives of
+        ``model.token_negatives_loss``, ``gbce_beta`` from ``srfrd_amd.gbce_beta``.  The negatives are
+        batch data: ``step(..., negative_ids (B, L, K), nrs, log_q=None)``, or a producer fills ``neg_ring[s]`` /
+        ``log_q_ring[s]`` beside ``ids_ring[s]`` (``DeviceSampler(num_negatives=K).next_batch(packed=True, out=..., neg_out=...,
+        log_q_out=...)``) and calls ``step_slot(s)``.  ``logq_correction=False``, and "gbce" always, pass no log-Q to the head.
+        Single rank, fp32 table, always bitwise reproducible."""
+        q = _loss_config(model, loss, num_negatives, neg_counts, neg_alpha, process_group, gbce_beta,
+                         int(batch_size) * int(seq_len or model.layout.max_len))
         self.model = model
         model._ensure_flat()
         self.lay = model.layout
@@ -160,8 +181,9 @@ class FusedTrainer:
         self.deterministic = bool(deterministic)
         self.loss_kind = loss
         self.sampled = loss == "sampled_softmax"
-        # (the sampled step keeps the encoder's contribution rows in its own merged buffer, below)
-        self.contrib = torch.zeros(3, B, L, lay.d_item, **f32) if self.deterministic and not self.sampled else None
+        self.token = loss in TOKEN_LOSSES
+        # (the sampled and the token-negatives steps keep the encoder's contribution rows in buffers of their own, below)
+        self.contrib = torch.zeros(3, B, L, lay.d_item, **f32) if self.deterministic and not (self.sampled or self.token) else None
         self.keys = torch.zeros(3, B, L, device=dev, dtype=torch.int64) if self.deterministic else None
         self.n_slabs = _lib.lib().srfrd_bwd_grid(C.byref(lay), B, L)
         self.slabs = torch.empty(self.n_slabs, lay.n_dense, **f32)
@@ -196,7 +218,7 @@ class FusedTrainer:
         self._train_mode = fused
         self.train_launch = True
         if loss != "bce":
-            self._init_ce(q, num_negatives, logq_correction, remove_accidental_hits)
+            self._init_ce(q, num_negatives, logq_correction, remove_accidental_hits, gbce_beta)
         self.packed = model.pack_weights()
         check(_lib.lib().srfrd_step_begin(ptr(self.state), self.lr, self.betas[0], self.betas[1],
                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "srfrd_step_begin")
@@ -208,8 +230,8 @@ class FusedTrainer:
         self.err = torch.zeros(1, device=dev, dtype=torch.int32)   # srfrd_check_ids word of step() / step_packed() inputs
         self._fresh = False      # packed weights known to match the parameters (see refresh())
 
-    def _init_ce(self, q, num_negatives, logq_correction, remove_hits):
-        """buffers of the cross-entropy step"""
+    def _init_ce(self, q, num_negatives, logq_correction, remove_hits, gbce_beta=1.0):
+        """buffers of the cross-entropy step (DESIGN sections 14 and 18)"""
         lay, B, L, dev = self.lay, self.B, self.L, self.flat.device
         f32 = dict(device=dev, dtype=torch.float32)
         T = B * L
@@ -236,23 +258,51 @@ class FusedTrainer:
             # the input plane carries anything here), rows [3T, 3T + K + T) the loss head's; keys of rows [2T, 4T + K)
             self.contrib_ce = torch.zeros(4 * T + K, lay.d_item, **f32)
             self.keys_ce = torch.zeros(2 * T + K, device=dev, dtype=torch.int64)
+        elif self.token:
+            K = self.K = int(num_negatives)
+            self.objective = _lib.TNEG_OBJECTIVES[TOKEN_LOSSES[self.loss_kind]]
+            self.gbce_beta = float(gbce_beta)
+            self.logq_correction = bool(logq_correction)
+            # negatives and their log-Q are batch data: one plane per input slot, beside ids_ring
+            self.neg_ring = torch.zeros(self.slots, B, L, K, device=dev, dtype=torch.int64)
+            self.log_q_ring = torch.zeros(self.slots, B, L, K, **f32)
+            self._last_slot = 0
+            # the encoder's contribution planes (pos, neg, input; only the input plane carries anything here), the head's
+            # rank-1 coefficients, and ONE key list: [clamped input ids (T) | the head's keys (T (1 + K))]
+            self.contrib_tok = torch.zeros(3, B, L, lay.d_item, **f32)
+            self.coef_tok = torch.zeros(T * (1 + K), **f32)
+            self.keys_tok = torch.zeros(T + T * (1 + K), device=dev, dtype=torch.int64)
+            # ... and where its stable sort lands.  The sort is never captured ("The sort stays outside
+            # the graph"): above 2^20 keys rocprim's radix sort zeroes its state with memset nodes, section 14's graph pitfall
+            self.skeys_tok = torch.zeros_like(self.keys_tok)
+            self.order_tok = torch.zeros_like(self.keys_tok)
         elif self.deterministic:
             self.keys_in = torch.zeros(T, device=dev, dtype=torch.int64)
             self.de_ce = torch.zeros(lay.n_items + 1, lay.d_item, **f32)
-        head = loss_heads.SXENT if self.sampled else loss_heads.XENT
-        n_ws = head.workspace(_lib.lib(), lay, B, L, self.K if self.sampled else 0)
+        head = loss_heads.SXENT if self.sampled else loss_heads.TNEG if self.token else loss_heads.XENT
+        n_ws = head.workspace(_lib.lib(), lay, B, L, self.K if self.sampled or self.token else 0)
+        if self.token:
+            # the mixed reduction's list is T (2 + K) long: more than srfrd_tneg_workspace_floats covers
+            n_mix = loss_heads.mixed_workspace(T * (2 + self.K), lay.d_item)
+            n_ws = max(n_ws, n_mix) if n_ws > 1 and n_mix > 0 else 0      # (TNEG.workspace answers 1 for a refusal)
         if n_ws <= 0:
             raise ValueError(f"loss={self.loss_kind!r}: the cross-entropy kernels refuse this model / shape")
         self.ce_ws = torch.zeros(n_ws, **f32)
 
     @property
     def negatives(self):
-        """(K,) int64: the shared negatives the last sampled-softmax step drew (None under another loss); read-only view"""
+        """(K,) int64: the shared negatives the last sampled-softmax step drew; "token_softmax" / "gbce": (B, L, K), the
+        negative plane the last step read (None under another loss); a copy"""
+        if self.token:
+            return self.neg_ring[self._last_slot].detach().clone()
         return self._negatives.detach().clone() if self.sampled else None
 
     @property
     def log_q(self):
-        """(K,) float32: log(K q) of those negatives, whether or not the loss subtracts it (None under another loss)"""
+        """(K,) float32: log(K q) of those negatives, whether or not the loss subtracts it; "token_softmax" / "gbce": (B, L,
+        K), the log-Q plane of the last step's slot (None under another loss); a copy"""
+        if self.token:
+            return self.log_q_ring[self._last_slot].detach().clone()
         return self._log_q.detach().clone() if self.sampled else None
 
     # ---- pieces -------------------------------------------------------------------------------
@@ -329,7 +379,24 @@ class FusedTrainer:
                                     ptr(self.loss_part) if fuse_stats else None, self.B, ptr(self.stats) if fuse_stats else None,
                                     ptr(self.loss) if self.mode == "single" else None, st), "srfrd_reduce_dense")
 
-    def _enqueue_ce_compute(self, slot: int = 0):
+    def _sort_token_keys(self):
+        """the token-negatives step's one stable key sort, into its persistent buffers; eager on the current stream, between the
+        step's two graphs"""
+        torch.sort(self.keys_tok, stable=True, out=(self.skeys_tok, self.order_tok))
+
+    def _enqueue_token_table(self):
+        """the token-negatives step's table gradient from the sorted key list: per item its input positions' full rows
+        (contrib_tok's input plane), then its rank-1 rows coef * hidden[t] (the backward read `hidden`, it did not write it)"""
+        T = self.B * self.L
+        loss_heads.table_mixed(self.lay, self.hidden, self.K, self.contrib_tok[2].view(T, self.lay.d_item), self.coef_tok,
+                               self.keys_tok, self.ce_ws, self.grad, sorted_pair=(self.skeys_tok, self.order_tok))
+
+    def _enqueue_ce_dense(self):
+        L_, lay = _lib.lib(), self.lay
+        check(L_.srfrd_reduce_dense(ptr(self.slabs), self.n_slabs, lay.n_dense, self._dense_ptr(self.grad), None, self.B, None, None,
+                                    self._stream()), "srfrd_reduce_dense")
+
+    def _enqueue_ce_compute(self, slot: int = 0, front_only: bool = False):
         """the cross-entropy step's compute (single rank): [shared negatives] -> encoder forward (checkpoints,
         hidden) -> loss head forward, {sum, count} into stats[1..2] -> loss head backward with d token loss = 1 -> encoder
         backward from d_hidden -> table gradient -> dense slab reduction.  stats[0] stays 0, so the Adam tail's 1 / stats[2]
@@ -352,7 +419,14 @@ class FusedTrainer:
                                          ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), None, ptr(self.scratch),
                                          self.n_scratch, ptr(self.sched), self.sched_mode, st), "srfrd_encoder_fwd_sched")
         # the loss head (loss_heads.py) on the step's own buffers; the fp32 item table is the flat vector's head
-        if self.sampled:
+        if self.token:
+            #  the head leaves T (1 + K) coefficients and, behind the T input keys of the one key list, their
+            # keys, unreduced: the one sort and the one mixed reduction below
+            log_q = self.log_q_ring[slot] if self.logq_correction and self.loss_kind == "token_softmax" else None
+            head, args = loss_heads.TNEG, (self.neg_ring[slot], log_q, self.objective, self.gbce_beta, self.remove_hits)
+            grad_to = dict(rows=self.coef_tok, keys=self.keys_tok[T:], finish=False)
+            contrib = ptr(self.contrib_tok)
+        elif self.sampled:
             # its contribution rows and keys land behind the encoder's in the merged buffers, unreduced: the one sort below
             head, args = loss_heads.SXENT, (self._negatives, self._log_q if self.logq_correction else None, self.remove_hits)
             grad_to = dict(rows=self.contrib_ce[3 * T:], keys=self.keys_ce[T:], finish=False)
@@ -374,7 +448,15 @@ class FusedTrainer:
                                          ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), ptr(self.d_hidden), None, None, 0,
                                          ptr(self.grad), contrib, ptr(self.slabs), ptr(self.scratch), self.n_scratch, ptr(self.sched),
                                          self.sched_mode, st), "srfrd_encoder_bwd_sched")
-        if self.sampled:
+        if self.token:
+            # one stable sort of [input ids (T) | the head's keys (T (1 + K))], then one reduction of both kinds of rows;
+            # front_only: the graph step's first graph ends with the key list (the sort runs eagerly behind it)
+            torch.clamp(ids[0].reshape(-1), 0, lay.n_items, out=self.keys_tok[:T])
+            if front_only:
+                return
+            self._sort_token_keys()
+            self._enqueue_token_table()
+        elif self.sampled:
             # one stable sort of [input ids (T) | the head's keys (K + T)]; the rows they key are contrib_ce[2T:]
             torch.clamp(ids[0].reshape(-1), 0, lay.n_items, out=self.keys_ce[:T])
             skeys, order = torch.sort(self.keys_ce, stable=True)
@@ -386,8 +468,7 @@ class FusedTrainer:
             check(L_.srfrd_table_reduce(ptr(skeys), ptr(order), C.c_void_p(self.contrib.data_ptr() + 4 * 2 * T * di),
                                         skeys.numel(), di, ptr(self.grad), st), "srfrd_table_reduce")
             self.grad[:lay.n_table].add_(self.de_ce.view(-1))
-        check(L_.srfrd_reduce_dense(ptr(self.slabs), self.n_slabs, lay.n_dense, self._dense_ptr(self.grad), None, B, None, None, st),
-              "srfrd_reduce_dense")
+        self._enqueue_ce_dense()
 
     def _enqueue_compute(self, slot: int = 0):
         """forward and backward as their two launches (the data-parallel step, per-launch timing)"""
@@ -540,6 +621,12 @@ class FusedTrainer:
                 restore()
         if self.graph_form == "one" and self.mode != "single":
             pass
+        elif self.mode == "single" and self.token:
+            # two graphs around the eager key sort: per slot everything up to the key list, then (slot-independent) the table
+            # reduction, the slab reduction and the Adam tail
+            self.graph_form = "split"
+            self._graph_a = [graph_of(lambda k=k: self._enqueue_ce_compute(k, front_only=True)) for k in range(self.slots)]
+            self._graph_b = graph_of(lambda: (self._enqueue_token_table(), self._enqueue_ce_dense(), self._enqueue_update()))
         elif self.mode == "single":
             self._graph_a = [graph_of(lambda k=k: (self._enqueue_step_compute(k), self._enqueue_update())) for k in range(self.slots)]
         elif self.mode == "allreduce":
@@ -583,13 +670,15 @@ class FusedTrainer:
         keep = [self.flat, self.m, self.v, self.state, self.grad, self.stats] + ([self.shadow_pad] if self.shadow_gather else [])
         snap = [t.clone() for t in keep]
         if self._graph_one is not None:      # (collectives inside: every rank replays the same number of times)
-            seq = [self._graph_one[0]]
+            seq = [self._graph_one[0].replay]
         else:
-            seq = [g[0] if isinstance(g, list) else g for g in (self._graph_f, self._graph_a, self._graph_u, self._graph_b)
+            seq = [(g[0] if isinstance(g, list) else g).replay for g in (self._graph_f, self._graph_a, self._graph_u, self._graph_b)
                    if g is not None]
+            if self.token:                   # (the eager key sort between the step's two graphs)
+                seq.insert(1, self._sort_token_keys)
         for _ in range(int(replays)):
-            for g in seq:
-                g.replay()
+            for replay in seq:
+                replay()
         torch.cuda.synchronize()
         for dst, src in zip(keep, snap):
             dst.copy_(src)
@@ -641,6 +730,9 @@ class FusedTrainer:
 
     def _loss_signature(self):
         """the loss configuration a resumed run must share (state_dict()["srfrd"]["loss"]; absent: "bce")"""
+        if self.token:
+            return {"kind": self.loss_kind, "num_negatives": self.K, "gbce_beta": self.gbce_beta,
+                    "logq_correction": self.logq_correction, "remove_accidental_hits": self.remove_hits}
         if not self.sampled:
             return {"kind": self.loss_kind}
         return {"kind": self.loss_kind, "num_negatives": self.K, "popularity": self.alias_prob is not None,
@@ -710,14 +802,33 @@ class FusedTrainer:
                 if bits & b))
 
     def step_packed(self, batch6: torch.Tensor) -> torch.Tensor:
-        """One train step on a packed int64 (6, B, L) tensor [seq, rsq, pos, prs, neg, nrs]; returns the device loss."""
+        """One train step on a packed int64 (6, B, L) tensor [seq, rsq, pos, prs, neg, nrs]; returns the device loss.
+        ("token_softmax" / "gbce": the negatives are ``neg_ring[0]`` / ``log_q_ring[0]`` as the caller left them.)"""
         self.ids.copy_(batch6, non_blocking=True)
         self._check_slot(0)
         return self._run()
 
-    def step(self, user_ids, input_ids, fake_ids, positive_ids, positive_fake_ids, negative_ids, negative_fake_ids):
+    def step(self, user_ids, input_ids, fake_ids, positive_ids, positive_fake_ids, negative_ids, negative_fake_ids, log_q=None):
         """Same argument order as the reference model call at trainer.py:30 (``user_ids`` is unused there too).  Under a
-        cross-entropy loss ``negative_ids`` / ``negative_fake_ids`` are not read and may be None."""
+        cross-entropy loss ``negative_ids`` / ``negative_fake_ids`` are not read and may be None.  Under "token_softmax" /
+        "gbce" ``negative_ids`` is the (B, L, K) negative plane and ``log_q`` its (B, L, K) float32 log-Q (None: zeros); they
+        are copied into slot 0 of ``neg_ring`` / ``log_q_ring``, and an id outside [0, n_items] is recorded for ``check()``."""
+        if self.token:
+            shape = (self.B, self.L, self.K)
+            if negative_ids is None or tuple(negative_ids.shape) != shape:
+                raise ValueError(f"loss={self.loss_kind!r}: negative_ids must be a {shape} integer tensor")
+            if log_q is not None and (tuple(log_q.shape) != shape or log_q.dtype != torch.float32):
+                raise ValueError(f"log_q must be a float32 tensor of shape {shape} or None")
+            self.neg_ring[0].copy_(negative_ids, non_blocking=True)
+            if log_q is None:
+                self.log_q_ring[0].zero_()
+            else:
+                self.log_q_ring[0].copy_(log_q, non_blocking=True)
+            neg = self.neg_ring[0]
+            self.err.bitwise_or_(((neg < 0) | (neg > self.lay.n_items)).any().to(torch.int32))      # (no synchronisation)
+            negative_ids = negative_fake_ids = None
+        elif log_q is not None:
+            raise ValueError("log_q belongs to loss='token_softmax'")
         for k, t in enumerate((input_ids, fake_ids, positive_ids, positive_fake_ids, negative_ids, negative_fake_ids)):
             if t is None and k >= 4 and self.loss_kind != "bce":
                 self.ids[k].zero_()
@@ -736,6 +847,8 @@ class FusedTrainer:
         return self._run(slot)
 
     def _run(self, slot: int = 0):
+        if self.token:
+            self._last_slot = slot
         if not self._fresh:
             self.refresh()
         g = self.use_graph
@@ -751,6 +864,9 @@ class FusedTrainer:
             self._graph_one[slot].replay()
         elif self.mode == "single":
             self._graph_a[slot].replay()
+            if self.token:                         # the key sort is not captured: eager, between the step's two graphs
+                self._sort_token_keys()
+                self._graph_b.replay()
         elif self.mode == "allreduce":             # split form: graphs around the host-launched collectives
             self._graph_a[slot].replay()
             self.ex.all_reduce(self.grad)

@@ -6,7 +6,13 @@ loop on the same loss (model(...) -> loss -> backward -> srfrd_amd.Adam).
 Workload C2: SASRec, 50k items, B = 512, L = 50, hidden 50, dropout 0.2 (bench.py's model), one synthetic batch resident
 in the trainer's input ring.  Losses: "bce" (the reference's masked BCE), "sampled_softmax" with K = 256, 1024 and 8192
 shared negatives (uniform, log-Q corrected, accidental hits removed), "softmax" (the full catalog).  The module-level loop
-draws its negatives with srfrd_amd.sample_negatives, the trainer draws them in the graph.
+draws its negatives with srfrd_amd.sample_negatives, the trainer draws them in the graph.  "token_softmax" / "gbce" with
+K = 16, 64 and 256 negatives per position: both sides draw batch and negatives with
+DeviceSampler(num_negatives=K) over a synthetic interaction set of the C2 shape, inside the timed step - the fused side
+straight into the trainer's rings (``step_slot``), the module side into ``model(...)`` -> ``token_negatives_loss``.
+
+    python tools/ce_train_latency.py --configs token_softmax_K16,...,gbce_K256 --out profiles/token_train_latency.json
+    rocprofv3 --kernel-trace --stats -- python tools/ce_train_latency.py --child token_softmax_K64 --fused-only
 
 Per configuration and path: ``*_step_ms`` = median over ``--reps`` single steps, each bracketed by CUDA events and waited
 for (what one step costs from launch to finish); ``*_pipelined_ms`` = CUDA events around ``--reps`` back-to-back steps,
@@ -25,6 +31,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONFIGS = {"bce": dict(loss="bce", K=0), "sampled_K256": dict(loss="sampled_softmax", K=256),
            "sampled_K1024": dict(loss="sampled_softmax", K=1024), "sampled_K8192": dict(loss="sampled_softmax", K=8192),
            "softmax": dict(loss="softmax", K=0)}
+CONFIGS.update({f"{loss}_K{K}": dict(loss=loss, K=K) for loss in ("token_softmax", "gbce") for K in (16, 64, 256)})
+TOKEN = ("token_softmax", "gbce")
 I, L, B, D = 50_000, 50, 512, 50
 
 
@@ -59,7 +67,70 @@ def _model():
     return m.cuda().train()
 
 
-def child(name: str, reps: int, warmup: int) -> dict:
+def _interactions(n_users=20_000, seed=7):
+    """a synthetic interaction set over the C2 catalog: histories of 3..60 uniform items"""
+    import numpy as np
+    import srfrd_amd
+    rng = np.random.RandomState(seed)
+    lens = rng.randint(3, 61, n_users)
+    users = np.repeat(np.arange(1, n_users + 1), lens)
+    items = rng.randint(1, I + 1, users.size)
+    items[0] = I                                    # itemnum is the largest id seen
+    return srfrd_amd.partition(users, items, rng.rand(users.size) < 0.3)
+
+
+def child_token(name: str, reps: int, warmup: int, fused_only: bool = False) -> dict:
+    """the token-negatives losses: the sampler's two launches are part of both timed steps"""
+    sys.path.insert(0, ROOT)
+    import torch
+    import srfrd_amd
+    loss, K = CONFIGS[name]["loss"], CONFIGS[name]["K"]
+    objective = "softmax" if loss == "token_softmax" else "gbce"
+    beta = srfrd_amd.gbce_beta(I, K, 0.75) if loss == "gbce" else 1.0
+    data = _interactions()
+    out = {"config": name, "loss": loss, "K": K, "n_items": I, "B": B, "L": L, "reps": reps}
+
+    tr = srfrd_amd.FusedTrainer(_model(), B, L, loss=loss, num_negatives=K, gbce_beta=beta)
+    sampler = srfrd_amd.DeviceSampler(data, B, L, seed=3, num_negatives=K, model=tr)
+
+    def fused():
+        sampler.next_batch(packed=True, out=tr.ids_ring[0], neg_out=tr.neg_ring[0], log_q_out=tr.log_q_ring[0])
+        tr.step_slot(0)
+
+    for _ in range(warmup):
+        fused()
+    torch.cuda.synchronize()
+    out["tokens"] = int((tr.ids_ring[0][2] != 0).sum())
+    out["fused_graph_step_ms"], out["fused_graph_pipelined_ms"] = _time(fused, reps)
+    out["fused_loss_last"] = round(float(tr.loss), 5)
+    del tr
+    if fused_only:
+        return out
+
+    m = _model()
+    opt = srfrd_amd.Adam(m.parameters(), lr=1e-3, betas=(0.9, 0.98))
+    sampler = srfrd_amd.DeviceSampler(data, B, L, seed=3, num_negatives=K, model=m)
+
+    def module():
+        opt.zero_grad()
+        _, seq, rsq, pos, _, _, _ = sampler.next_batch()
+        h, _, _ = m(None, seq, rsq)
+        lq = sampler.log_q if objective == "softmax" else None
+        lo = m.token_negatives_loss(h, pos, sampler.negatives, objective, lq, beta)
+        lo.backward()
+        opt.step()
+
+    for _ in range(warmup):
+        module()
+    torch.cuda.synchronize()
+    out["module_step_ms"], out["module_pipelined_ms"] = _time(module, reps)
+    out["speedup_step"] = round(out["module_step_ms"] / out["fused_graph_step_ms"], 2)
+    return out
+
+
+def child(name: str, reps: int, warmup: int, fused_only: bool = False) -> dict:
+    if CONFIGS[name]["loss"] in TOKEN:
+        return child_token(name, reps, warmup, fused_only)
     sys.path.insert(0, ROOT)
     import torch
     import srfrd_amd
@@ -117,11 +188,12 @@ def main():
     ap.add_argument("--timeout", type=int, default=240)
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
+    ap.add_argument("--fused-only", action="store_true", help="with --child, a token-negatives config: the graph step alone (a profiler run)")
     a = ap.parse_args()
     if a.reps < 10:
         ap.error("--reps: at least 10")
     if a.child:
-        print(json.dumps(child(a.child, a.reps, a.warmup)))
+        print(json.dumps(child(a.child, a.reps, a.warmup, a.fused_only)))
         return
     results = []
     for name in a.configs.split(","):
