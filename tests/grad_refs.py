@@ -28,13 +28,18 @@ The cases: test_gpu_bf16_families.CASES (every encoder kernel family the plan ca
 the fp32 table, plus ``EXTRA``: the <50,32,8,0> first-generation pair (seq_len 20), and at the default geometry (seq_len 50, no
 switch: the ragged pair and the one-launch train kernel) a 17-sequence batch on the tile boundaries and a duplicate-heavy one.
 Kernel names do not carry the table flag, so the names of CASES hold for the fp32 table as they stand.
+
+A third mode, "head" (the section of that name below), holds the first step of the four catalog losses to the same metric and
+bound rule: reference ``head_grads``, jobs ``HEAD_JOBS``, seeds ``HEAD_SEEDS``.
 """
 import functools
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from oracle import srfrd_oracle as O
+from tests import loss_refs as LR
 from tests import test_gpu_bf16_families as F
 from tests.test_gpu_bf16_families import RELU_MARGIN, Case, relu_margin
 
@@ -283,6 +288,8 @@ def batch_of(c, seed):
 
 
 def first_seed(c, mode):
+    if mode.startswith("head/"):
+        mode = "fused"
     return {"autograd": c.seed, "fused": c.fused_seed}[mode] or {"autograd": 6, "fused": 50}[mode]
 
 
@@ -293,13 +300,13 @@ Ref = namedtuple("Ref", "cfg sd batch train seed l2 g64 g32 e32 margin clamp")
 
 
 def cfg_of(c, mode):
-    return F.cfg_of(c, bf16=False, dropout=0.5 if mode == "fused" else 0.0)
+    return F.cfg_of(c, bf16=False, dropout=0.0 if mode == "autograd" else 0.5)
 
 
 @functools.lru_cache(maxsize=None)
-def weights(cid):
+def weights(cid, sd_seed=None):
     from tests.gpu_util import random_sd
-    return random_sd(cfg_of(BY_ID[cid], "autograd"), SD_SEEDS.get(cid, SD_SEED))
+    return random_sd(cfg_of(BY_ID[cid], "autograd"), sd_seed or SD_SEEDS.get(cid, SD_SEED))
 
 
 def build_ref(c, mode, seed, l2=0.0):
@@ -339,7 +346,7 @@ def scan_seeds(job):
     c = BY_ID[cid]
     out = []
     for seed in range(first_seed(c, mode), first_seed(c, mode) + count):
-        ref = build_ref(c, mode, seed)
+        ref = build_head_ref(head_job(cid, mode[5:]), seed).ref if mode.startswith("head/") else build_ref(c, mode, seed)
         out.append([seed, max(ref.e32.values()), ref.margin])
     return out
 
@@ -354,6 +361,242 @@ def pick_seed(scans):
         if all(FACTOR * e <= SEARCH_HEADROOM * CAP for _, e, _ in rows):
             return rows[0][0], True
     return min(ok, key=lambda rows: max(e for _, e, _ in rows))[0][0], False
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# mode "head": the first FusedTrainer(loss=...) step of the four catalog losses
+# ---------------------------------------------------------------------------------------------------------------------------
+# The step runs srfrd_encoder_fwd_sched with the plan bits CKPT | DROPOUT and srfrd_encoder_bwd_sched with DROPOUT alone: the
+# NON-training instantiations with dropout masks on, the gradient entering through d_hidden - a combination neither mode above
+# reaches ("autograd": those instantiations, dropout 0, gradient through the logits; "fused": the training instantiations).
+# Around it the loss head, its table rows merged with the encoder's input rows (srfrd_table_reduce over contrib_ce,
+# srfrd_table_reduce_mixed over the rank-1 rows, the de_ce add under deterministic=True) and the Adam tail's 1 / stats[2]:
+# stepped weights show none of these scales.  Same cases, weights, dropout, metric and bound rule as "fused".
+HEAD_LOSSES = ("softmax", "sampled_softmax", "token_softmax", "gbce")
+TOKEN_LOSSES = ("token_softmax", "gbce")
+OBJECTIVE = {"token_softmax": "softmax", "gbce": "gbce"}
+GBCE_BETA = 0.6
+K_TOKEN, K_TOKEN_WIDE = 5, 65      # 65 (the duplicate-heavy batches): one more than a wave, many rank-1 rows per item
+K_SAMPLED, NEG_ALPHA = 96, 0.75    # neg_counts = arange(n + 1) ** 0.5, as test_gpu_ce_trainer.test_one_step_against_fp64_oracle
+DEFAULT_IDS = ("t0", "t1", "t2", "t3", "u0", "u2")           # the default geometry: ragged pair
+# Every other case under ONE loss, so that every backward family runs once from d_hidden with masks on: the losses in rotation
+# inside each family (gbce skipped on SRFRN, which the trainer refuses), so that each loss meets a first-generation, a
+# slot-placed, a row-chunked and a srfrd_long:: backward.  Only i and o have a srfrd_long:: backward: they run two losses each.
+ROTATION = {
+    "b": ("softmax",), "c": ("sampled_softmax",), "d": ("token_softmax",), "e": ("gbce",), "f": ("softmax",),     # first generation
+    "q": ("sampled_softmax",), "s": ("token_softmax",),
+    "a": ("gbce",), "g": ("softmax",), "h": ("sampled_softmax",), "p": ("token_softmax",),                        # slot-placed
+    "j": ("gbce",), "k": ("softmax",), "l": ("sampled_softmax",), "m": ("token_softmax",), "n": ("gbce",),        # row-chunked
+    "i": ("softmax", "token_softmax"), "o": ("sampled_softmax", "gbce"),                                          # srfrd_long::
+}
+HEAD_L2 = ("token_softmax", "softmax")     # the two losses L2_ID also runs with l2_emb = L2_EMB (a term NOT divided by the count)
+
+# cid: remove_accidental_hits on for half the jobs; with_lq: whether step() is handed the log-Q plane (None: zeros; "gbce" never
+# passes it to its head, "token_softmax" subtracts it).  l2: l2_emb.
+HeadJob = namedtuple("HeadJob", "cid loss K remove with_lq l2")
+
+
+def _head_jobs():
+    pairs = [(cid, loss) for cid in DEFAULT_IDS for loss in HEAD_LOSSES]
+    pairs += [(c.id, loss) for c in ALL_CASES if c.id in ROTATION for loss in ROTATION[c.id]]
+    pairs = [(cid, loss) for cid, loss in pairs if not (loss == "gbce" and BY_ID[cid].kind == "SRFRN")]
+    jobs, n_tok = [], {loss: 0 for loss in TOKEN_LOSSES}
+    for cid, loss in pairs:
+        K, remove, with_lq = 0, True, True
+        if loss == "sampled_softmax":
+            K = K_SAMPLED
+        elif loss in TOKEN_LOSSES:
+            i = n_tok[loss]
+            n_tok[loss] += 1
+            K = K_TOKEN_WIDE if cid.startswith("u") else K_TOKEN
+            remove, with_lq = i % 2 == 0, i % 3 != 2
+        jobs.append(HeadJob(cid, loss, K, remove, with_lq, 0.0))
+    by = {(j.cid, j.loss): j for j in jobs}
+    return jobs + [by[L2_ID, loss]._replace(l2=L2_EMB) for loss in HEAD_L2]
+
+
+HEAD_JOBS = _head_jobs()
+
+
+def head_job(cid, loss, l2=0.0):
+    return next(j for j in HEAD_JOBS if (j.cid, j.loss, j.l2) == (cid, loss, l2))
+
+
+def head_id(j):
+    return f"{j.cid}-{j.loss}" + ("-l2" if j.l2 else "")
+
+
+# (forward, backward) as srfrd_encoder_plan prints them on the built library for the head step's two launches
+# (test_gpu_bf16_families._plan_bits()["head"]), the backward's read-modify-write flag dropped: the non-training instantiations.
+HEAD_NAMES = {
+    "a": ("srfrd::encoder_fwd_kernel<50,64,8,50,0,0,50>", "srfrd::encoder_bwd_slots_kernel<50,50,0,50>"),
+    "b": ("srfrd::encoder_fwd_kernel<50,64,8,50,2,0,45>", "srfrd::encoder_bwd_kernel<50,64,8,50,2,0,45>"),
+    "c": ("srfrd::encoder_fwd_kernel<0,0,0,0,-1,0,0>", "srfrd::encoder_bwd_kernel<0,0,0,0,-1,0,0>"),
+    "d": ("srfrd::encoder_fwd_kernel<0,0,0,0,-1,0,0>", "srfrd::encoder_bwd_kernel<0,0,0,0,-1,0,0>"),
+    "e": ("srfrd::encoder_fwd_kernel<0,0,0,0,-1,0,0>", "srfrd::encoder_bwd_kernel<0,0,0,0,-1,0,0>"),
+    "f": ("srfrd::encoder_fwd_kernel<50,64,8,0,-1,0,0>", "srfrd::encoder_bwd_kernel<50,64,8,0,-1,0,0>"),
+    "g": ("srfrd::encoder_fwd_kernel<50,112,8,100,0,0,50>", "srfrd::encoder_bwd_slots_kernel<50,100,0,50>"),
+    "h": ("srfrd::encoder_fwd_kernel<0,0,0,0,-1,0,0>", "srfrd::encoder_bwd_slots_kernel<50,100,2,45>"),
+    "i": ("srfrd::encoder_fwd_kernel<50,112,8,100,0,0,50>", "srfrd_long::encoder_bwd_kernel<0,0,0,0,-1,0,0>"),
+    "j": ("srfrd::encoder_fwd_rows_kernel<50,0,50,1>", "srfrd::encoder_bwd_chunks_kernel<50,0,50>"),
+    "k": ("srfrd::encoder_fwd_rows_kernel<50,2,45,1>", "srfrd::encoder_bwd_chunks_kernel<50,2,45>"),
+    "l": ("srfrd::encoder_fwd_rows_kernel<50,-1,50,1>", "srfrd::encoder_bwd_chunks_kernel<50,-1,50>"),
+    "m": ("srfrd::encoder_fwd_rows_kernel<50,1,45,1>", "srfrd::encoder_bwd_chunks_kernel<50,1,45>"),
+    "n": ("srfrd_long::encoder_fwd_kernel<0,0,0,0,-1,0,0>", "srfrd::encoder_bwd_chunks_kernel<50,0,50>"),
+    "o": ("srfrd_long::encoder_fwd_kernel<0,0,0,0,-1,0,0>", "srfrd_long::encoder_bwd_kernel<0,0,0,0,-1,0,0>"),
+    "p": ("srfrd::encoder_fwd_rows_kernel<50,2,45,1>", "srfrd::encoder_bwd_slots_kernel<50,50,2,45>"),
+    "q": ("srfrd::encoder_fwd_kernel<50,64,8,50,0,0,50>", "srfrd::encoder_bwd_kernel<50,64,8,50,0,0,50>"),
+    "s": ("srfrd::encoder_fwd_kernel<50,32,8,0,-1,0,0>", "srfrd::encoder_bwd_kernel<50,32,8,0,-1,0,0>"),
+    "t0": ("srfrd::encoder_fwd_ragged_kernel<0,0,50>", "srfrd::encoder_bwd_ragged_kernel<0,50>"),
+    "t1": ("srfrd::encoder_fwd_ragged_kernel<1,0,45>", "srfrd::encoder_bwd_ragged_kernel<1,45>"),
+    "t2": ("srfrd::encoder_fwd_ragged_kernel<2,0,45>", "srfrd::encoder_bwd_ragged_kernel<2,45>"),
+    "t3": ("srfrd::encoder_fwd_ragged_kernel<-1,0,50>", "srfrd::encoder_bwd_ragged_kernel<-1,50>"),
+    "u0": ("srfrd::encoder_fwd_ragged_kernel<0,0,50>", "srfrd::encoder_bwd_ragged_kernel<0,50>"),
+    "u2": ("srfrd::encoder_fwd_ragged_kernel<2,0,45>", "srfrd::encoder_bwd_ragged_kernel<2,45>"),
+}
+
+# (case id, loss) -> batch seed, chosen as SEEDS is (tools/grad_fp64_report.py --scan --jobs head on each kind of machine, then
+# --pick): from the fused step's first seed on, the first of 200 - of 600 where those hold none - at which on BOTH machines
+# relu_margin >= 2 * RELU_MARGIN and 64 e32 <= SEARCH_HEADROOM * CAP for every tensor.  The l2_emb jobs run at the seed of
+# their case and loss.
+HEAD_SEEDS = {
+    ("t0", "softmax"): 50, ("t0", "sampled_softmax"): 50, ("t0", "token_softmax"): 50, ("t0", "gbce"): 50,
+    ("t1", "softmax"): 192, ("t1", "sampled_softmax"): 93, ("t1", "token_softmax"): 381, ("t1", "gbce"): 50,
+    ("t2", "softmax"): 78, ("t2", "sampled_softmax"): 270, ("t2", "token_softmax"): 309, ("t3", "softmax"): 514,
+    ("t3", "sampled_softmax"): 230, ("t3", "token_softmax"): 512, ("t3", "gbce"): 90, ("u0", "softmax"): 50,
+    ("u0", "sampled_softmax"): 50, ("u0", "token_softmax"): 50, ("u0", "gbce"): 88, ("u2", "softmax"): 191,
+    ("u2", "sampled_softmax"): 551, ("u2", "token_softmax"): 177, ("a", "gbce"): 50, ("b", "softmax"): 124,
+    ("c", "sampled_softmax"): 229, ("d", "token_softmax"): 50, ("e", "gbce"): 52, ("f", "softmax"): 220, ("g", "softmax"): 54,
+    ("h", "sampled_softmax"): 134, ("i", "softmax"): 54, ("i", "token_softmax"): 52, ("j", "gbce"): 56, ("k", "softmax"): 122,
+    ("l", "sampled_softmax"): 112, ("m", "token_softmax"): 83, ("n", "gbce"): 56, ("o", "sampled_softmax"): 70,
+    ("o", "gbce"): 72, ("p", "token_softmax"): 392, ("q", "sampled_softmax"): 50, ("s", "token_softmax"): 50,
+}
+# Weights: as "fused", but for t2 under token_softmax the next weight seed (as SD_SEEDS does for b / k / p): under SD_SEED its
+# first 200 batches hold no seed with headroom on both machines (best 1.66e-6).  The same was tried for the other SRFRN jobs
+# without a seed (t2, u2, b, k under softmax, u2 under token_softmax, h under sampled_softmax) and for t1 / t3 under softmax: no
+# batch of 200 either.
+HEAD_SD_SEEDS = {("t2", "token_softmax"): 8}
+# Head jobs without such a seed: entries (case id, "head/" + loss) of OVER_CAP, bound clamped at CAP, at the scanned batch
+# with the ReLU margin whose e32 is smallest on the worse machine.  The full-catalog softmax on every kind but SASRec (t1 1.36e-6,
+# t2 1.99e-6, t3 1.52e-6, u2 1.76e-6, b 1.52e-6, k 2.69e-6, f 2.42e-6: three hundred logits per position through the shared
+# vector these kinds add); the long SRFU_B / SRFR cases that are over the cap in every mode (f above, l 2.17e-6, m 1.84e-6);
+# the duplicate-heavy SRFRN batch at K = 65 (u2 token_softmax 3.24e-6); and h sampled_softmax 1.34e-6, t3 token_softmax
+# 1.28e-6: under the condition on both machines, without the headroom.
+HEAD_OVER_CAP = frozenset([(cid, "head/softmax") for cid in ("t1", "t2", "t3", "u2", "b", "f", "k")]
+                          + [("l", "head/sampled_softmax"), ("m", "head/token_softmax"), ("u2", "head/token_softmax"),
+                             ("h", "head/sampled_softmax"), ("t3", "head/token_softmax")])
+OVER_CAP = OVER_CAP | HEAD_OVER_CAP
+
+
+def token_negatives(c, pos, K, seed):
+    """(negatives (B, L, K) int64, log_q (B, L, K) float32) on the host from the job's seed: zero at dead positions; at live
+    ones a fifth of the slots unused (0), a seventh accidental hits (the position's own target), every ninth live position -
+    the first among them - with all K slots unused; on the duplicate-heavy batch the rows that draw their ids from items 1..8
+    draw their negatives there too.  log_q: standard normal at live positions."""
+    g = torch.Generator().manual_seed(1000 * seed + K)
+    B, L = pos.shape
+    neg = torch.randint(1, I + 1, (B, L, K), generator=g)
+    if c.id.startswith("u"):
+        neg[0::4] = torch.randint(1, 9, neg[0::4].shape, generator=g)
+    neg[torch.rand(B, L, K, generator=g) < 0.2] = 0
+    hit = torch.rand(B, L, K, generator=g) < 1.0 / 7.0
+    neg = torch.where(hit, pos.unsqueeze(-1).expand_as(neg), neg)
+    live = pos != 0
+    flat = neg.view(-1, K)
+    flat[live.view(-1).nonzero().view(-1)[0::9]] = 0
+    neg = neg * live.unsqueeze(-1)
+    log_q = torch.randn(B, L, K, generator=g) * live.unsqueeze(-1)
+    return neg.contiguous(), log_q.contiguous()
+
+
+def sampled_counts():
+    return torch.arange(I + 1.0) ** 0.5
+
+
+@functools.lru_cache(maxsize=None)
+def sampled_negatives(seed_word, K=K_SAMPLED):
+    """what FusedTrainer(loss="sampled_softmax", num_negatives=K, neg_counts=sampled_counts(), neg_alpha=NEG_ALPHA) draws on
+    the device under the step seed word `seed_word`: (ids (K,) int64, log(K q) (K,) float32), by the numpy restatement"""
+    from srfrd_amd.sampler import alias_table, negative_q
+    q = negative_q(I, sampled_counts(), NEG_ALPHA)
+    prob, alias = alias_table(q)
+    ids = LR.ref_negatives(seed_word, I, K, prob, alias)
+    log_q = np.concatenate([[0.0], np.log(K * q)]).astype(np.float32)[ids]
+    return torch.from_numpy(ids), torch.from_numpy(log_q)
+
+
+def head_grads(cfg, sd, batch, loss, neg=None, log_q=None, beta=1.0, remove=True, seed=0, l2_emb=0.0, double=True, parts=False):
+    """The first catalog-loss step's gradient on the oracle: O.forward in training mode under the step seed, the materialised
+    loss (tests/loss_refs.py) on its hidden state, mean over the positions whose target is not 0; padding rows zeroed and the
+    l2_emb term added exactly as O.grads_of does.  -> (loss, {name: gradient}) in fp64 (double) or fp32; parts: also the
+    item table's gradient through the loss head alone (the rest of that tensor came through the encoder's input rows)."""
+    dt = torch.float64 if double else torch.float32
+    leaves = {k: v.detach().to(dt).clone().requires_grad_(True) for k, v in sd.items()}
+    seq, rsq, pos = batch[:3]
+    h, _, _ = O.forward(cfg, leaves, seq, rsq, train=True, seed=seed, b0=0)
+    item = O.key_item(cfg)
+    table = leaves[item].detach().clone().requires_grad_(True)          # the head's view of the item table: its own leaf
+    E = O.item_table(cfg, {item: table})
+    lq = None if log_q is None else log_q.to(dt)
+    if loss == "softmax":
+        ce = LR.xent_mean_loss(h, E, pos)
+    elif loss == "sampled_softmax":
+        ce = LR.sxent_mean_loss(h, E, pos, neg, lq, remove)
+    else:
+        ce = LR.tneg_mean_loss(h, E, pos, neg, lq if loss == "token_softmax" else None, OBJECTIVE[loss], beta, remove)
+    ce.backward()
+    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
+    head_part = table.grad.clone()
+    head_part[0].zero_()
+    grads[item] = grads[item] + table.grad
+    grads[item][0].zero_()                                              # nn.Embedding(padding_idx=0), as O.grads_of
+    if cfg.kind in ("SRFR", "SRFRN"):
+        grads[O.key_side(cfg)][0].zero_()
+    total = ce.detach()
+    if l2_emb != 0.0:
+        for k, v in leaves.items():
+            nrm = torch.norm(v.detach())
+            total = total + l2_emb * nrm
+            if float(nrm) > 0.0:
+                grads[k] = grads[k] + l2_emb * v.detach() / nrm
+    return (total, grads, head_part) if parts else (total, grads)
+
+
+def _one_thread(fn):
+    n = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        return fn()
+    finally:
+        torch.set_num_threads(n)
+
+
+HeadRef = namedtuple("HeadRef", "ref job neg log_q loss64")     # ref: a Ref; neg / log_q: what the step reads (None: "softmax")
+
+
+def build_head_ref(job, seed):
+    c = BY_ID[job.cid]
+    cfg, batch = cfg_of(c, "head"), batch_of(c, seed)
+    sd = weights(c.id, HEAD_SD_SEEDS.get((job.cid, job.loss)))
+    dseed = O.step_seed(BASE, 1)
+    neg = log_q = None
+    if job.loss == "sampled_softmax":
+        neg, log_q = sampled_negatives(dseed, job.K)
+    elif job.loss in TOKEN_LOSSES:                      # (without job.with_lq the trainer is handed None and reads zeros)
+        neg, log_q = token_negatives(c, batch[2], job.K, seed)
+        log_q = log_q if job.with_lq else None
+    kw = dict(neg=neg, log_q=log_q, beta=GBCE_BETA, remove=job.remove, seed=dseed, l2_emb=job.l2)
+    loss64, g64 = head_grads(cfg, sd, batch, job.loss, double=True, **kw)
+    g32 = _one_thread(lambda: head_grads(cfg, sd, batch, job.loss, double=False, **kw)[1])
+    e32 = {k: tensor_figures(k, g32[k], g64[k], g32[k], cfg.D, kbias=job.l2 == 0.0)["e32"] for k in g64}
+    margin = relu_margin(cfg, {k: v.double() for k, v in sd.items()}, batch, train=True, seed=dseed)
+    clamp = (job.cid, "head/" + job.loss) in OVER_CAP
+    return HeadRef(Ref(cfg, sd, batch, True, dseed, job.l2, g64, g32, e32, margin, clamp), job, neg, log_q, float(loss64))
+
+
+@functools.lru_cache(maxsize=None)
+def head_reference(job):
+    """the HeadRef of one job at its HEAD_SEEDS entry, shared by every test of the process; treat as read-only"""
+    return build_head_ref(job, HEAD_SEEDS[job.cid, job.loss])
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,10 @@
 """What the loss-head tests share (tests/test_gpu_xent.py, test_gpu_sxent.py, test_gpu_tneg.py, test_gpu_loss_widths.py,
-test_gpu_loss_extreme.py): the fp64 references over materialised logits, the inf-norm error measure, and a Python restatement
-of the two run-time kernel choices of the heads (with_ks in srfrd_xent_common.h, with_shape in srfrd_tneg.hip).  Plain torch:
-everything here runs on the CPU as well, except head_model."""
+test_gpu_loss_extreme.py, test_gpu_ce_trainer.py, test_gpu_token_trainer.py, grad_refs.py): the fp64 references over
+materialised logits, the differentiable mean losses the train-step oracles apply to a hidden state, the inf-norm error measure,
+the numpy restatement of the shared-negative sampler, and a Python restatement of the two run-time kernel choices of the heads
+(with_ks in srfrd_xent_common.h, with_shape in srfrd_tneg.hip).  Plain torch and numpy: everything here runs on the CPU as
+well, except head_model."""
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -233,6 +236,68 @@ def tneg_ref(h, E, y, neg, log_q=None, remove=True, reduction="mean", objective=
     if with_abs:
         return loss, gh, ge, ah, float(ae.max())
     return loss, gh, ge
+
+
+def tneg_mean_loss(hidden, E, pos, neg, log_q, objective, beta, remove=True):
+    """the materialised loss in the dtype of its inputs (mean reduction), differentiable"""
+    d, K = E.shape[1], neg.shape[-1]
+    tok = pos.reshape(-1) != 0
+    H, t, N = hidden[..., :d].reshape(-1, d)[tok], pos.reshape(-1)[tok], neg.reshape(-1, K)[tok]
+    sp = (H * E[t]).sum(1)
+    sn = torch.einsum("td,tkd->tk", H, E[N])
+    mask = N == 0
+    if remove:
+        mask = mask | (N == t.unsqueeze(1))
+    if objective == "softmax":
+        if log_q is not None:
+            sn = sn - log_q.reshape(-1, K)[tok].to(sn.dtype)
+        sn = sn.masked_fill(mask, -float("inf"))
+        return (torch.logsumexp(torch.cat([sp.unsqueeze(1), sn], 1), 1) - sp).mean()
+    sp_ = torch.nn.functional.softplus
+    return (beta * sp_(-sp) + sp_(sn).masked_fill(mask, 0.0).sum(1)).mean()
+
+
+def sxent_mean_loss(h, E, pos, neg, log_q, remove=True):
+    """the materialised sampled softmax over the K shared negatives, mean over the targets, differentiable"""
+    _, sp, sn = sxent_logits_ref(h, E, pos, neg, log_q, remove)
+    return (torch.logsumexp(torch.cat([sp.unsqueeze(1), sn], 1), 1) - sp).mean()
+
+
+def xent_mean_loss(h, E, pos):
+    """the materialised full-catalog softmax (items 1 .. n), mean over the targets, differentiable"""
+    d = E.shape[1]
+    y = pos.reshape(-1)
+    hs = h[..., :d].reshape(-1, d)[y != 0]
+    return F.cross_entropy(hs @ E[1:].T, y[y != 0] - 1)
+
+
+# ------------------------------------------------------------------------------------------------ the shared-negative sampler
+M32 = 0xFFFFFFFF
+SITE_NEG = 0x4E470001           # srfrd_rng.h
+
+
+def fmix32(h):
+    h = np.asarray(h, dtype=np.uint64) & M32
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85EBCA6B)) & M32
+    h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0xC2B2AE35)) & M32
+    h ^= h >> np.uint64(16)
+    return h
+
+
+def ref_negatives(seed_word, n_items, K, prob=None, alias=None):
+    """ids (K,) int64 that srfrd_shared_negatives draws for the step seed word `seed_word` (state[2]): numpy, integer for
+    integer"""
+    base = fmix32((int(seed_word) + SITE_NEG * 0x9E3779B9) & M32)
+    j = np.arange(K, dtype=np.uint64)
+    h1 = fmix32(base ^ j)
+    b = (h1 * np.uint64(n_items)) >> np.uint64(32)
+    if prob is not None:
+        h2 = fmix32(base ^ (j | np.uint64(0x80000000)))
+        u = (h2 >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
+        b = np.where(u < prob[b.astype(np.int64)], b, alias[b.astype(np.int64)].astype(np.uint64))
+    return b.astype(np.int64) + 1
 
 
 def tneg_token_loss(h, E, y, neg, log_q, remove, objective, beta):

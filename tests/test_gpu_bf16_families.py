@@ -99,8 +99,10 @@ def _plan_bits():
     from srfrd_amd import _lib as P
     tgt = P.PLAN_POS | P.PLAN_NEG
     # launch mode -> (srfrd_encoder_fwd's mode bits, srfrd_encoder_bwd's) as the two launchers derive them from their arguments
+    # ("head": the catalog-loss step, FusedTrainer._enqueue_ce_compute - no targets, the backward driven by d_hidden)
     return {"eval": (tgt, None), "last": (0, None), "autograd": (tgt | P.PLAN_CKPT, tgt),
-            "fused": (tgt | P.PLAN_CKPT | P.PLAN_LOSS | P.PLAN_DROPOUT, tgt | P.PLAN_FUSED_BCE | P.PLAN_DROPOUT)}
+            "fused": (tgt | P.PLAN_CKPT | P.PLAN_LOSS | P.PLAN_DROPOUT, tgt | P.PLAN_FUSED_BCE | P.PLAN_DROPOUT),
+            "head": (P.PLAN_CKPT | P.PLAN_DROPOUT, P.PLAN_DROPOUT)}
 
 
 def strip_rmw(name):
@@ -121,7 +123,7 @@ def case_scratch(layout, B, L, launch):
     """floats of scratch the callers pass: the module path sizes it per direction, FusedTrainer once for both"""
     from srfrd_amd import _lib
     nf, nb = _lib.scratch_floats(layout, B, L)
-    return (max(nf, nb),) * 2 if launch == "fused" else (nf, nb)
+    return (max(nf, nb),) * 2 if launch in ("fused", "head") else (nf, nb)
 
 
 def cfg_of(c, bf16=True, dropout=0.0):

@@ -1,9 +1,10 @@
 """-m gpu: FusedTrainer(loss="sampled_softmax" | "softmax") and the device-side shared-negative sampler.
 
-The sampler (srfrd_shared_negatives) is restated below in numpy, integer for integer: its ids must agree bit for bit, its
-log-Q output with log(K q) in fp64.  The trainer's step is held against the module-level loop on the same negatives and
-dropout masks (model(...) -> model.sampled_softmax_loss -> backward -> srfrd_amd.Adam), against the fp64 oracle with a
-materialised softmax, and against itself: graph replay = eager, and a resumed run = the uninterrupted one, bit for bit."""
+The sampler (srfrd_shared_negatives) is restated in numpy, integer for integer (tests/loss_refs.py, ref_negatives): its ids
+must agree bit for bit, its log-Q output with log(K q) in fp64.  The trainer's step is held against the module-level loop on
+the same negatives and dropout masks (model(...) -> model.sampled_softmax_loss -> backward -> srfrd_amd.Adam), against the fp64
+oracle with a materialised softmax, and against itself: graph replay = eager, and a resumed run = the uninterrupted one, bit
+for bit."""
 import ctypes as C
 import math
 
@@ -13,36 +14,10 @@ import torch
 
 from oracle import srfrd_oracle as O
 from tests.helpers import assert_post_adam
-from tests.test_gpu_sxent import KINDS, _kind_cfg, _logits_ref
+from tests.loss_refs import M32, ref_negatives, sxent_mean_loss, xent_mean_loss
+from tests.test_gpu_sxent import KINDS, _kind_cfg
 
 pytestmark = pytest.mark.gpu
-
-M32 = 0xFFFFFFFF
-SITE_NEG = 0x4E470001           # srfrd_rng.h
-
-
-# ------------------------------------------------------------------------------------------------ numpy restatement
-def _fmix32(h):
-    h = np.asarray(h, dtype=np.uint64) & M32
-    h ^= h >> np.uint64(16)
-    h = (h * np.uint64(0x85EBCA6B)) & M32
-    h ^= h >> np.uint64(13)
-    h = (h * np.uint64(0xC2B2AE35)) & M32
-    h ^= h >> np.uint64(16)
-    return h
-
-
-def ref_negatives(seed_word, n_items, K, prob=None, alias=None):
-    """ids (K,) int64 that srfrd_shared_negatives draws for the step seed word `seed_word` (state[2])"""
-    base = _fmix32((int(seed_word) + SITE_NEG * 0x9E3779B9) & M32)
-    j = np.arange(K, dtype=np.uint64)
-    h1 = _fmix32(base ^ j)
-    b = (h1 * np.uint64(n_items)) >> np.uint64(32)
-    if prob is not None:
-        h2 = _fmix32(base ^ (j | np.uint64(0x80000000)))
-        u = (h2 >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24)
-        b = np.where(u < prob[b.astype(np.int64)], b, alias[b.astype(np.int64)].astype(np.uint64))
-    return b.astype(np.int64) + 1
 
 
 def _state(seed_word, dev="cuda"):
@@ -174,14 +149,7 @@ def _oracle_step(cfg, sd, batch, loss, neg=None, log_q=None, l2=0.0):
     seq, rsq, pos = (t.cpu() for t in batch[:3])
     h, _, _ = O.forward(cfg, leaves, seq, rsq)
     E = O.item_table(cfg, leaves)
-    if loss == "sampled_softmax":
-        tok, sp, sn = _logits_ref(h, E, pos, neg, log_q, True)
-        ce = (torch.logsumexp(torch.cat([sp.unsqueeze(1), sn], 1), 1) - sp).mean()
-    else:
-        d = E.shape[1]
-        y = pos.reshape(-1)
-        hs = h[..., :d].reshape(-1, d)[y != 0]
-        ce = torch.nn.functional.cross_entropy(hs @ E[1:].T, y[y != 0] - 1)
+    ce = sxent_mean_loss(h, E, pos, neg, log_q, True) if loss == "sampled_softmax" else xent_mean_loss(h, E, pos)
     ce.backward()
     grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)).clone() for k, v in leaves.items()}
     grads[O.key_item(cfg)][0].zero_()                           # padding_idx rows, as O.grads_of

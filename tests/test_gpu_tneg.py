@@ -14,6 +14,7 @@ from tests.helpers import KINDS as GOLDEN_KINDS
 from tests.helpers import assert_post_adam, golden_cfg, load_golden, sub
 from tests.loss_refs import make_inputs
 from tests.loss_refs import rel as _rel
+from tests.loss_refs import tneg_mean_loss as _torch_loss
 from tests.loss_refs import tneg_ref as _ref
 
 pytestmark = pytest.mark.gpu
@@ -257,25 +258,6 @@ def _kind_cfg(kind, L, dropout=0.0):
     if kind in ("SRFR", "SRFRN"):
         return O.Cfg(kind, I, L, 45, d_fake=5, dropout=dropout)
     return O.Cfg(kind, I, L, 50, n_labels=3, dropout=dropout)
-
-
-def _torch_loss(hidden, E, pos, neg, log_q, objective, beta, remove=True):
-    """the materialised loss in the dtype of its inputs (mean reduction), differentiable"""
-    d, K = E.shape[1], neg.shape[-1]
-    tok = pos.reshape(-1) != 0
-    H, t, N = hidden[..., :d].reshape(-1, d)[tok], pos.reshape(-1)[tok], neg.reshape(-1, K)[tok]
-    sp = (H * E[t]).sum(1)
-    sn = torch.einsum("td,tkd->tk", H, E[N])
-    mask = N == 0
-    if remove:
-        mask = mask | (N == t.unsqueeze(1))
-    if objective == "softmax":
-        if log_q is not None:
-            sn = sn - log_q.reshape(-1, K)[tok].to(sn.dtype)
-        sn = sn.masked_fill(mask, -float("inf"))
-        return (torch.logsumexp(torch.cat([sp.unsqueeze(1), sn], 1), 1) - sp).mean()
-    sp_ = torch.nn.functional.softplus
-    return (beta * sp_(-sp) + sp_(sn).masked_fill(mask, 0.0).sum(1)).mean()
 
 
 @pytest.mark.parametrize("L", [20, 50])

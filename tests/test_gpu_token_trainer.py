@@ -11,8 +11,8 @@ import torch
 from oracle import srfrd_oracle as O
 from tests import token_trainer_refs as R
 from tests.helpers import assert_post_adam
+from tests.loss_refs import tneg_mean_loss as _torch_loss
 from tests.test_gpu_sxent import KINDS, _kind_cfg
-from tests.test_gpu_tneg import _torch_loss
 
 pytestmark = pytest.mark.gpu
 M32 = 0xFFFFFFFF

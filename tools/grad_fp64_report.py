@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Measured agreement of every encoder gradient with the fp64 oracle (GPU box) -> profiles/grad_fp64_errors.json.
 
-    python tools/grad_fp64_report.py [--out profiles/grad_fp64_errors.json]
+    python tools/grad_fp64_report.py [--out profiles/grad_fp64_errors.json] [--modes encoder | head]
     python tools/grad_fp64_report.py --scan OUT.json  # CPU only, once per kind of machine the suite runs on, then
     python tools/grad_fp64_report.py --pick A.json B.json      # ... the batch-seed table of tests/grad_refs.py
 
-Runs what tests/test_gpu_grad_fp64.py runs (its run_autograd / run_fused) and records per case, mode and tensor (one
-array per line, in the order of `tensors`): e32 (the fp32 oracle's row error against the fp64 oracle), the bound, the
-device's row error, and the former metric max|g - g_oracle32|.  Exit code 1 if a tensor misses its bound.
+Runs what tests/test_gpu_grad_fp64.py runs (its run_autograd / run_fused) and what tests/test_gpu_head_grad_fp64.py runs (its
+run_head: the first step of the four catalog losses, modes "head-LOSS...") and records per case, mode and tensor (one array
+per line, in the order of `tensors`): e32 (the fp32 oracle's row error against the fp64 oracle), the bound, the
+device's row error, and the former metric max|g - g_oracle32|.  --modes: only that half, the other half's entries of an
+existing --out file kept.  Exit code 1 if a tensor misses its bound.
 """
 import argparse
 import json
@@ -23,6 +25,11 @@ def _setenv(changed):
         changed.setdefault(name, os.environ.get(name))
         os.environ[name] = value
     return setenv
+
+
+def _one_thread():
+    import torch
+    torch.set_num_threads(1)
 
 
 def _num(x):
@@ -62,17 +69,21 @@ def _dump(report, f):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grad_fp64_errors.json"))
+    ap.add_argument("--modes", choices=["all", "encoder", "head"], default="all")
     ap.add_argument("--scan", metavar="OUT", help="CPU only: worst e32 and ReLU margin of every job's candidate seeds, here")
     ap.add_argument("--count", type=int, default=48)
-    ap.add_argument("--jobs", nargs="*", metavar="CASE/MODE", help="--scan: these only")
+    ap.add_argument("--jobs", nargs="*", metavar="CASE/MODE", help="--scan: these only (head: every head/LOSS job)")
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--pick", nargs="+", metavar="SCAN", help="grad_refs.SEEDS from one --scan file per kind of machine")
     a = ap.parse_args()
     from tests import grad_refs as G
     if a.scan:
         import multiprocessing as mp
-        jobs = [(c.id, m, a.count) for c in G.ALL_CASES for m in ("autograd", "fused") if not a.jobs or f"{c.id}/{m}" in a.jobs]
-        with mp.get_context("spawn").Pool(a.workers) as pool:
+        jobs = [(c.id, m, a.count) for c in G.ALL_CASES for m in ("autograd", "fused")]
+        jobs += [(j.cid, "head/" + j.loss, a.count) for j in G.HEAD_JOBS if not j.l2]
+        jobs = [j for j in jobs if not a.jobs or f"{j[0]}/{j[1]}" in a.jobs or (a.jobs == ["head"] and j[1].startswith("head/"))]
+        # (one thread per worker: e32 is a one-thread figure anyway, and workers x threads would oversubscribe the machine)
+        with mp.get_context("spawn").Pool(a.workers, initializer=_one_thread) as pool:
             rows = pool.map(G.scan_seeds, jobs, chunksize=1)
         with open(a.scan, "w") as f:
             json.dump({f"{cid}/{m}": r for (cid, m, _), r in zip(jobs, rows)}, f)
@@ -85,18 +96,28 @@ def main():
             print(f"{key}: {seed}   worst-machine e32 {worst:.3e}" + ("" if found else "   <-- no seed with headroom: OVER_CAP"))
         return 0
     from tests import test_gpu_grad_fp64 as T
-    runs = []
-    for c in G.ALL_CASES:
-        runs.append((c, "autograd", lambda c, env: (T.run_autograd(c, env), None)))
+    from tests import test_gpu_head_grad_fp64 as H
+    runs = []           # (case, mode, the first mode that shares its reference, run)
+    for c in G.ALL_CASES if a.modes != "head" else []:
+        runs.append((c, "autograd", "autograd", lambda c, env: (T.run_autograd(c, env), None)))
         for det in (True, False):
             name = "fused-" + ("deterministic" if det else "atomics")
-            runs.append((c, name, lambda c, env, det=det: T.run_fused(c, det, env)))
+            runs.append((c, name, "fused", lambda c, env, det=det: T.run_fused(c, det, env)))
             if c.id in G.TRAIN_KERNEL_IDS:
-                runs.append((c, name + "-two-launches", lambda c, env, det=det: T.run_fused(c, det, env, train_launch=False)))
+                runs.append((c, name + "-two-launches", "fused",
+                             lambda c, env, det=det: T.run_fused(c, det, env, train_launch=False)))
             if c.id == G.L2_ID:
-                runs.append((c, name + "-l2_emb", lambda c, env, det=det: T.run_fused(c, det, env, l2=G.L2_EMB)))
+                runs.append((c, name + "-l2_emb", "fused-l2_emb", lambda c, env, det=det: T.run_fused(c, det, env, l2=G.L2_EMB)))
+    for (j, det), rid in zip(H.RUNS, H.RUN_IDS) if a.modes != "encoder" else []:
+        name = "head-" + rid.split("-", 1)[1].replace("-l2", "-l2_emb")
+        runs.append((G.BY_ID[j.cid], name, "head-" + G.head_id(j), lambda c, env, j=j, det=det: H.run_head(j, det, env)))
     report, missed, tensors, first = {}, 0, {}, {}
-    for c, mode, fn in runs:
+    if a.modes != "all" and os.path.exists(a.out):
+        kept = json.load(open(a.out))
+        tensors = kept["tensors"]
+        report = {cid: {m: r for m, r in modes.items() if m == "kind" or m.startswith("head-") != (a.modes == "head")}
+                  for cid, modes in kept["cases"].items()}
+    for c, mode, ref, fn in runs:
         changed = {}
         try:
             figs, figs2 = fn(c, _setenv(changed))
@@ -104,7 +125,6 @@ def main():
             for name, old in changed.items():
                 os.environ.pop(name, None) if old is None else os.environ.__setitem__(name, old)
         names = tensors.setdefault(c.kind, sorted(figs))
-        ref = "autograd" if mode == "autograd" else "fused-l2_emb" if mode.endswith("l2_emb") else "fused"
         shared = first.get((c.id, ref))
         first.setdefault((c.id, ref), mode)
         entry = report.setdefault(G.case_ids([c])[0], {"kind": c.kind})
@@ -121,7 +141,8 @@ def main():
         _dump({"metric": "tests/grad_refs.py: row_errors, bound(e32) = max(64 e32, 2e-5), clamped at 1e-4 for the OVER_CAP jobs; "
                          "arrays follow `tensors` of the case's kind; old = max|g - g_oracle32|; second_moment_worst = "
                          "[tensor, row error of g^2, twice the bound]; kbias_of_limit is absent under l2_emb, where the K "
-                         "slice is an ordinary part of its row",
+                         "slice is an ordinary part of its row; modes head-LOSS...: the first FusedTrainer(loss=LOSS) step against "
+                         "grad_refs.head_grads (tests/test_gpu_head_grad_fp64.py)",
                "tensors": tensors, "cases": report}, f)
     print(f"{missed} tensors miss their bound; wrote {a.out}")
     return 1 if missed else 0
