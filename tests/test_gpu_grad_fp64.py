@@ -14,6 +14,8 @@ Before each launch the planned kernel names are asserted as the bf16 file does (
 geometry the plan must offer the one-launch train kernel; the tile-boundary batch also runs as two launches.  One fused case
 runs with l2_emb = 1e-3: that term is not divided by the target count, so it pins the relative scale of the two parts.
 
+The step's loss is held to the fp64 loss of the same reference (tests/fwd_refs.py: relative error <= max(16 e32, 1e-6)).
+
 Per tensor: row_errors <= bound(e32), rows whose fp64 gradient is exactly zero exactly zero, the K slice of in_proj_bias under
 its own rule; exp_avg_sq / (1 - beta2) against g64^2 under twice the bound.  profiles/grad_fp64_errors.json holds the measured
 figures (tools/grad_fp64_report.py calls run_autograd / run_fused below).
@@ -21,6 +23,7 @@ figures (tools/grad_fp64_report.py calls run_autograd / run_fused below).
 import pytest
 import torch
 
+from tests import fwd_refs as R
 from tests import grad_refs as G
 from tests import test_gpu_bf16_families as F
 
@@ -68,6 +71,9 @@ def run_fused(c, det, setenv, train_launch=True, l2=0.0):
             "srfrd::encoder_train_ragged_kernel<"), "the plan offers no train kernel here"
     loss = tr.step(None, *cuda(*ref.batch))
     assert bool(torch.isfinite(loss).all())
+    # the step's loss (the fused BCE head's partial sums, the 1 / count scale, the l2_emb term) against the fp64 loss of the
+    # same reference: tests/fwd_refs.py, |loss - loss64| / loss64 <= max(16 e32, 1e-6)
+    R.assert_loss_holds(loss.detach().cpu(), R.fused_step_reference(c.id), f"case {c.id} fused det={det} l2={l2}", l2)
     g, g2 = G.fused_gradients(tr, model)
     return G.compare(g, ref), G.compare(g2, ref, squares=True)
 
