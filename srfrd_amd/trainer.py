@@ -20,6 +20,7 @@ mean-over-all-targets loss of trainer.py:36-38 (not an average of per-rank means
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -35,6 +36,30 @@ from .sampler import alias_table, negative_q
 
 LOSSES = ("bce", "sampled_softmax", "softmax", "token_softmax", "gbce")
 TOKEN_LOSSES = {"token_softmax": "softmax", "gbce": "gbce"}      # -> the objective of srfrd_tneg_fwd / _bwd
+
+
+def step_program(mode: str, token: bool = False):
+    """THE order of a train step under exchange ``mode`` ("single" | "allreduce" | "sharded"; ``token``: a loss with K negatives
+    per position): FusedTrainer's eager step, graph capture, replay and spin_up all walk this list of stages (kind, per_slot,
+    calls) - FusedTrainer methods called in order, with the input slot where per_slot.  "graph": they only enqueue stream work,
+    so the stage is captured (per slot where per_slot: the kernels' id pointers are baked in).  "eager" / "collective": a host
+    action between two graphs - the token step's key sort, which is never captured / the exchange."""
+    G, E, X = "graph", "eager", "collective"
+    if mode == "single" and token:
+        return [(G, True, ("_enqueue_ce_compute",)), (E, False, ("_sort_token_keys",)),
+                (G, False, ("_enqueue_token_table", "_enqueue_ce_dense", "_enqueue_update"))]
+    if mode == "single":
+        return [(G, True, ("_enqueue_compute_update",))]
+    if mode == "allreduce":
+        return [(G, True, ("_enqueue_compute",)), (X, False, ("_all_reduce_grad",)), (G, False, ("_enqueue_update",))]
+    # sharded: the 16-byte statistics all-reduce is in flight under the backward; `_scatter_grad` waits for it
+    return [(G, True, ("_enqueue_fwd",)), (X, False, ("_start_stats_reduce",)), (G, True, ("_enqueue_bwd",)),
+            (X, False, ("_scatter_grad",)), (G, False, ("_enqueue_shard_update",)), (X, False, ("_gather_params",)),
+            (G, False, ("_enqueue_shard_finish",))]
+
+
+# RCCL collectives are stream work: the whole data-parallel step, collectives included, as one graph per slot
+ONE_GRAPH = [("graph", True, ("_enqueue_step",))]
 
 
 def flat_allreduce(flat: torch.Tensor, group=None):
@@ -223,7 +248,9 @@ class FusedTrainer:
         check(_lib.lib().srfrd_step_begin(ptr(self.state), self.lr, self.betas[0], self.betas[1],
                                           C.c_void_p(torch.cuda.current_stream().cuda_stream)), "srfrd_step_begin")
         self.use_graph = bool(use_graph)
-        self._graph_a = self._graph_b = self._graph_f = self._graph_u = self._graph_one = None
+        self._program = step_program(self.mode, self.token)
+        self._graphs = None              # (stages, their graphs) once captured: `captured`
+        self._stats_handle = None        # sharded form: the statistics all-reduce in flight between two eager stages
         self.graph_form = None           # "one" | "split" once captured (data parallel: one graph with the collectives inside, or graphs around them)
         self.graph_capture_error = None
         self.steps_done = 0
@@ -279,7 +306,23 @@ class FusedTrainer:
         elif self.deterministic:
             self.keys_in = torch.zeros(T, device=dev, dtype=torch.int64)
             self.de_ce = torch.zeros(lay.n_items + 1, lay.d_item, **f32)
-        head = loss_heads.SXENT if self.sampled else loss_heads.TNEG if self.token else loss_heads.XENT
+        # What the step's compute asks of the loss: its head, where the head's backward leaves the table gradient, the encoder
+        # backward's contribution buffer, the key list whose first T entries are the clamped input ids and the rows it keys
+        # (ce_rows None: the token step's program sorts and reduces its list; ce_keys None: nothing to reduce)
+        if self.token:       #  T (1 + K) coefficients and, behind the T input keys, their keys, unreduced
+            head, self.ce_grad_to = loss_heads.TNEG, dict(rows=self.coef_tok, keys=self.keys_tok[T:], finish=False)
+            self.ce_contrib, self.ce_keys, self.ce_rows = self.contrib_tok, self.keys_tok, None
+        elif self.sampled:   # its rows and keys land behind the encoder's in the merged buffers, unreduced: one sort for both
+            head, self.ce_grad_to = loss_heads.SXENT, dict(rows=self.contrib_ce[3 * T:], keys=self.keys_ce[T:], finish=False)
+            self.ce_contrib, self.ce_keys, self.ce_rows = self.contrib_ce, self.keys_ce, self.contrib_ce[2 * T:]
+        else:
+            # xent_bwd writes a dense table gradient; the deterministic encoder table reduction STORES its rows (the input
+            # plane of `contrib`), so there the head's part waits in de_ce and is added afterwards
+            det = self.contrib is not None
+            head, self.ce_grad_to = loss_heads.XENT, dict(d_table=self.de_ce if det else self.grad, accumulate=not det)
+            self.ce_contrib = self.contrib
+            self.ce_keys, self.ce_rows = (self.keys_in, self.contrib[2]) if det else (None, None)
+        self.ce_head = head
         n_ws = head.workspace(_lib.lib(), lay, B, L, self.K if self.sampled or self.token else 0)
         if self.token:
             # the mixed reduction's list is T (2 + K) long: more than srfrd_tneg_workspace_floats covers
@@ -312,53 +355,66 @@ class FusedTrainer:
     def _dense_ptr(self, base):
         return C.c_void_p(base.data_ptr() + 4 * self.n_tab)
 
-    def _ids_of(self, slot):
-        ids = self.ids_ring[slot]
-        fk = ids[1] if self.lay.kind != 0 else None
-        pfk, nfk = (ids[3], ids[5]) if self.lay.kind == 2 else (None, None)
+    def _enc_args(self, slot, targets: bool):
+        """the arguments every encoder entry point begins with: layout and tables, the slot's id planes (``targets``: the
+        positive / negative planes and their logits too; else NULL - checkpoints and hidden states only), shape, dropout
+        rate and seed word, this rank's first global sequence, then the forward's outputs and checkpoints"""
+        ids, kind = self.ids_ring[slot], self.lay.kind
+        fk = ids[1] if kind != 0 else None
+        pos, neg, pl, nl = (ids[2], ids[4], self.pl, self.nl) if targets else (None, None, None, None)
+        pfk, nfk = (ids[3], ids[5]) if targets and kind == 2 else (None, None)
         p = self.model.dropout_rate if self.model.training else 0.0
-        return ids, fk, pfk, nfk, p, C.c_void_p(self.state.data_ptr() + 8), self.rank * self.B
+        lay_t, tab = self.model._table_args()
+        return (C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk), ptr(pos), ptr(pfk),
+                ptr(neg), ptr(nfk), self.B, self.L, p, 0, C.c_void_p(self.state.data_ptr() + 8), self.rank * self.B,
+                ptr(self.hidden), ptr(pl), ptr(nl), ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux))
+
+    def _bwd_args(self, d_hidden, contrib):
+        """what a backward adds to `_enc_args`: the hidden-state gradient it starts from (None: the BCE gradient of the
+        target logits, fused), the gradient vector, the item-table contribution rows (None: float atomics into the gradient),
+        the dense slabs and the scratch"""
+        return (ptr(d_hidden), None, None, int(d_hidden is None), ptr(self.grad), ptr(contrib), ptr(self.slabs),
+                ptr(self.scratch), self.n_scratch)
+
+    def _sched_args(self):
+        return ptr(self.sched), self.sched_mode, self._stream()
+
+    def _launch_fwd(self, slot, targets: bool):
+        check(_lib.lib().srfrd_encoder_fwd_sched(*self._enc_args(slot, targets), ptr(self.loss_part) if targets else None,
+                                                 ptr(self.scratch), self.n_scratch, *self._sched_args()), "srfrd_encoder_fwd_sched")
+
+    def _launch_bwd(self, slot, d_hidden=None, contrib=None):
+        check(_lib.lib().srfrd_encoder_bwd_sched(*self._enc_args(slot, d_hidden is None), *self._bwd_args(d_hidden, contrib),
+                                                 *self._sched_args()), "srfrd_encoder_bwd_sched")
+
+    def _launch_train(self, slot):
+        """forward and BCE backward of every sequence as one launch"""
+        check(_lib.lib().srfrd_encoder_train_sched(*self._enc_args(slot, True), ptr(self.loss_part), *self._bwd_args(None, self.contrib),
+                                                   *self._sched_args()), "srfrd_encoder_train_sched")
+
+    def _enqueue_prologue(self, slot):
+        """ahead of the forward: the norms of the parameters it uses (l2_emb), the batch's sequence -> workgroup schedule"""
+        L_, st = _lib.lib(), self._stream()
+        if self.l2 != 0.0:
+            check(L_.srfrd_l2_norms(ptr(self.flat), ptr(self.seg_off), ptr(self.seg_len), self.seg_off.numel(), self.n_tab,
+                                    self.l2, ptr(self.l2_partial), ptr(self.l2buf), ptr(self.l2_dense), st), "srfrd_l2_norms")
+        if self.sched_mode:
+            check(L_.srfrd_seq_order(ptr(self.ids_ring[slot][0]), self.B, self.L, self.pair_stride, ptr(self.sched), st),
+                  "srfrd_seq_order")
 
     def _enqueue_l2_apply(self, grad_ptr, param, i0, i1):
         """grad[i0:i1] += count * l2_emb * p / ||p|| (the Adam step that follows divides by the count)"""
         check(_lib.lib().srfrd_l2_apply(grad_ptr, ptr(param), i0, min(i1, self.n_flat), self.n_tab, ptr(self.l2buf),
                                         ptr(self.l2_dense), ptr(self.stats), self._stream()), "srfrd_l2_apply")
 
-    def _enqueue_fwd(self, slot: int = 0, train: bool = False):
-        """the forward (train: the forward and the backward, one srfrd_encoder_train_sched launch)"""
-        L_, lay, st = _lib.lib(), self.lay, self._stream()
-        if self.l2 != 0.0:               # norms of the parameters this step's forward uses
-            check(L_.srfrd_l2_norms(ptr(self.flat), ptr(self.seg_off), ptr(self.seg_len), self.seg_off.numel(), self.n_tab,
-                                    self.l2, ptr(self.l2_partial), ptr(self.l2buf), ptr(self.l2_dense), st), "srfrd_l2_norms")
-        ids, fk, pfk, nfk, p, seed_dev, seq0 = self._ids_of(slot)
-        lay_t, tab = self.model._table_args()
-        if self.sched_mode:
-            check(L_.srfrd_seq_order(ptr(ids[0]), self.B, self.L, self.pair_stride, ptr(self.sched), st), "srfrd_seq_order")
-        if train:
-            check(L_.srfrd_encoder_train_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk),
-                                               ptr(ids[2]), ptr(pfk), ptr(ids[4]), ptr(nfk), self.B, self.L, p, 0, seed_dev, seq0,
-                                               ptr(self.hidden), ptr(self.pl), ptr(self.nl), ptr(self.save_x), ptr(self.save_h1),
-                                               ptr(self.save_aux), ptr(self.loss_part), None, None, None, 1, ptr(self.grad),
-                                               ptr(self.contrib), ptr(self.slabs), ptr(self.scratch), self.n_scratch, ptr(self.sched),
-                                               self.sched_mode, st), "srfrd_encoder_train_sched")
-            self._enqueue_grad_tail(slot)
-            return
-        check(L_.srfrd_encoder_fwd_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk), ptr(ids[2]),
-                                         ptr(pfk), ptr(ids[4]), ptr(nfk), self.B, self.L, p, 0, seed_dev, seq0, ptr(self.hidden),
-                                         ptr(self.pl), ptr(self.nl), ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), ptr(self.loss_part),
-                                         ptr(self.scratch), self.n_scratch, ptr(self.sched), self.sched_mode, st), "srfrd_encoder_fwd_sched")
+    def _enqueue_fwd(self, slot: int = 0):
+        self._enqueue_prologue(slot)
+        self._launch_fwd(slot, True)
         if self.mode == "sharded":       # the statistics are forward outputs: reduce them now, exchange them under the backward
-            check(L_.srfrd_loss_stats(ptr(self.loss_part), self.B, ptr(self.stats), None, st), "srfrd_loss_stats")
+            check(_lib.lib().srfrd_loss_stats(ptr(self.loss_part), self.B, ptr(self.stats), None, self._stream()), "srfrd_loss_stats")
 
     def _enqueue_bwd(self, slot: int = 0):
-        L_, lay, st = _lib.lib(), self.lay, self._stream()
-        ids, fk, pfk, nfk, p, seed_dev, seq0 = self._ids_of(slot)
-        lay_t, tab = self.model._table_args()
-        check(L_.srfrd_encoder_bwd_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk), ptr(ids[2]),
-                                         ptr(pfk), ptr(ids[4]), ptr(nfk), self.B, self.L, p, 0, seed_dev, seq0, ptr(self.hidden),
-                                         ptr(self.pl), ptr(self.nl), ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), None, None, None, 1,
-                                         ptr(self.grad), ptr(self.contrib), ptr(self.slabs), ptr(self.scratch), self.n_scratch,
-                                         ptr(self.sched), self.sched_mode, st), "srfrd_encoder_bwd_sched")
+        self._launch_bwd(slot, None, self.contrib)
         self._enqueue_grad_tail(slot)
 
     def _enqueue_grad_tail(self, slot: int = 0):
@@ -396,79 +452,49 @@ class FusedTrainer:
         check(L_.srfrd_reduce_dense(ptr(self.slabs), self.n_slabs, lay.n_dense, self._dense_ptr(self.grad), None, self.B, None, None,
                                     self._stream()), "srfrd_reduce_dense")
 
-    def _enqueue_ce_compute(self, slot: int = 0, front_only: bool = False):
+    def _enqueue_ce_compute(self, slot: int = 0):
         """the cross-entropy step's compute (single rank): [shared negatives] -> encoder forward (checkpoints,
         hidden) -> loss head forward, {sum, count} into stats[1..2] -> loss head backward with d token loss = 1 -> encoder
         backward from d_hidden -> table gradient -> dense slab reduction.  stats[0] stays 0, so the Adam tail's 1 / stats[2]
-        and srfrd_loss_finalize give the gradient of the mean and the mean."""
-        L_, lay, st = _lib.lib(), self.lay, self._stream()
-        B, L, T, di = self.B, self.L, self.B * self.L, lay.d_item
-        if self.l2 != 0.0:
-            check(L_.srfrd_l2_norms(ptr(self.flat), ptr(self.seg_off), ptr(self.seg_len), self.seg_off.numel(), self.n_tab,
-                                    self.l2, ptr(self.l2_partial), ptr(self.l2buf), ptr(self.l2_dense), st), "srfrd_l2_norms")
-        ids, fk, pfk, nfk, p, seed_dev, seq0 = self._ids_of(slot)
-        lay_t, tab = self.model._table_args()
-        if self.sched_mode:
-            check(L_.srfrd_seq_order(ptr(ids[0]), B, L, self.pair_stride, ptr(self.sched), st), "srfrd_seq_order")
+        and srfrd_loss_finalize give the gradient of the mean and the mean.  The token-negatives step's ends with its key list:
+        the sort, the table gradient and the slab reduction are the step program's next stages."""
+        lay = self.lay
+        self._enqueue_prologue(slot)
         if self.sampled:
-            check(L_.srfrd_shared_negatives(ptr(self.state), lay.n_items, self.K, ptr(self.alias_prob), ptr(self.alias_idx),
-                                            ptr(self.item_log_q), ptr(self._negatives), ptr(self._log_q), st),
+            check(_lib.lib().srfrd_shared_negatives(ptr(self.state), lay.n_items, self.K, ptr(self.alias_prob), ptr(self.alias_idx),
+                                                    ptr(self.item_log_q), ptr(self._negatives), ptr(self._log_q), self._stream()),
                   "srfrd_shared_negatives")
-        check(L_.srfrd_encoder_fwd_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk),
-                                         None, None, None, None, B, L, p, 0, seed_dev, seq0, ptr(self.hidden), None, None,
-                                         ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), None, ptr(self.scratch),
-                                         self.n_scratch, ptr(self.sched), self.sched_mode, st), "srfrd_encoder_fwd_sched")
+        self._launch_fwd(slot, False)
         # the loss head (loss_heads.py) on the step's own buffers; the fp32 item table is the flat vector's head
         if self.token:
-            # (DESIGN section 18) the head leaves T (1 + K) coefficients and, behind the T input keys of the one key list, their
-            # keys, unreduced: the one sort and the one mixed reduction below
             log_q = self.log_q_ring[slot] if self.logq_correction and self.loss_kind == "token_softmax" else None
-            head, args = loss_heads.TNEG, (self.neg_ring[slot], log_q, self.objective, self.gbce_beta, self.remove_hits)
-            grad_to = dict(rows=self.coef_tok, keys=self.keys_tok[T:], finish=False)
-            contrib = ptr(self.contrib_tok)
-        elif self.sampled:
-            # its contribution rows and keys land behind the encoder's in the merged buffers, unreduced: the one sort below
-            head, args = loss_heads.SXENT, (self._negatives, self._log_q if self.logq_correction else None, self.remove_hits)
-            grad_to = dict(rows=self.contrib_ce[3 * T:], keys=self.keys_ce[T:], finish=False)
-            contrib = ptr(self.contrib_ce)
+            args = (self.neg_ring[slot], log_q, self.objective, self.gbce_beta, self.remove_hits)
         else:
-            # xent_bwd writes a dense table gradient; the deterministic encoder table reduction below STORES its rows, so
-            # there the head's part waits in de_ce and is added afterwards
-            det = self.contrib is not None
-            head, args = loss_heads.XENT, ()
-            grad_to = dict(d_table=self.de_ce if det else self.grad, accumulate=not det)
-            contrib = ptr(self.contrib)
-        table, tgt = ptr(self.flat), ids[2]
-        loss_heads.launch_fwd(head, lay, table, self.hidden, tgt, args, ws=self.ce_ws,
+            args = (self._negatives, self._log_q if self.logq_correction else None, self.remove_hits) if self.sampled else ()
+        table, tgt = ptr(self.flat), self.ids_ring[slot][2]
+        loss_heads.launch_fwd(self.ce_head, lay, table, self.hidden, tgt, args, ws=self.ce_ws,
                               out=(self.token_loss, self.lse, self.stats[1:]))       # {sum, count} -> stats[1], stats[2]
-        loss_heads.launch_bwd(head, lay, table, self.hidden, tgt, args, self.lse, self.d_token, ws=self.ce_ws,
-                              d_hidden=self.d_hidden, **grad_to)
-        check(L_.srfrd_encoder_bwd_sched(C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk),
-                                         None, None, None, None, B, L, p, 0, seed_dev, seq0, ptr(self.hidden), None, None,
-                                         ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux), ptr(self.d_hidden), None, None, 0,
-                                         ptr(self.grad), contrib, ptr(self.slabs), ptr(self.scratch), self.n_scratch, ptr(self.sched),
-                                         self.sched_mode, st), "srfrd_encoder_bwd_sched")
+        loss_heads.launch_bwd(self.ce_head, lay, table, self.hidden, tgt, args, self.lse, self.d_token, ws=self.ce_ws,
+                              d_hidden=self.d_hidden, **self.ce_grad_to)
+        self._launch_bwd(slot, self.d_hidden, self.ce_contrib)
+        if self.ce_keys is not None:
+            self._enqueue_table_tail(slot, self.ce_keys, self.ce_rows)
         if self.token:
-            # one stable sort of [input ids (T) | the head's keys (T (1 + K))], then one reduction of both kinds of rows;
-            # front_only: the graph step's first graph ends with the key list (the sort runs eagerly behind it)
-            torch.clamp(ids[0].reshape(-1), 0, lay.n_items, out=self.keys_tok[:T])
-            if front_only:
-                return
-            self._sort_token_keys()
-            self._enqueue_token_table()
-        elif self.sampled:
-            # one stable sort of [input ids (T) | the head's keys (K + T)]; the rows they key are contrib_ce[2T:]
-            torch.clamp(ids[0].reshape(-1), 0, lay.n_items, out=self.keys_ce[:T])
-            skeys, order = torch.sort(self.keys_ce, stable=True)
-            check(L_.srfrd_table_reduce(ptr(skeys), ptr(order), C.c_void_p(self.contrib_ce.data_ptr() + 4 * 2 * T * di),
-                                        skeys.numel(), di, ptr(self.grad), st), "srfrd_table_reduce")
-        elif self.contrib is not None:
-            torch.clamp(ids[0].reshape(-1), 0, lay.n_items, out=self.keys_in)
-            skeys, order = torch.sort(self.keys_in, stable=True)
-            check(L_.srfrd_table_reduce(ptr(skeys), ptr(order), C.c_void_p(self.contrib.data_ptr() + 4 * 2 * T * di),
-                                        skeys.numel(), di, ptr(self.grad), st), "srfrd_table_reduce")
+            return
+        if self.ce_rows is not None and not self.sampled:
             self.grad[:lay.n_table].add_(self.de_ce.view(-1))
         self._enqueue_ce_dense()
+
+    def _enqueue_table_tail(self, slot, keys, rows):
+        """the clamped input ids into the head of the key list ``keys``; then (``rows`` given: the contribution rows the list
+        keys, in list order) one stable sort and one ordered sum per item into the table gradient"""
+        lay = self.lay
+        torch.clamp(self.ids_ring[slot][0].reshape(-1), 0, lay.n_items, out=keys[:self.B * self.L])
+        if rows is None:
+            return
+        skeys, order = torch.sort(keys, stable=True)
+        check(_lib.lib().srfrd_table_reduce(ptr(skeys), ptr(order), ptr(rows), skeys.numel(), lay.d_item, ptr(self.grad),
+                                            self._stream()), "srfrd_table_reduce")
 
     def _enqueue_compute(self, slot: int = 0):
         """forward and backward as their two launches (the data-parallel step, per-launch timing)"""
@@ -482,9 +508,16 @@ class FusedTrainer:
             self._enqueue_ce_compute(slot)
         elif self.mode == "single" and self.train_launch and _lib.encoder_plan_train(
                 self.lay, self.B, self.L, self._train_mode, _lib.env_switches())[0]:
-            self._enqueue_fwd(slot, train=True)
+            self._enqueue_prologue(slot)
+            self._launch_train(slot)
+            self._enqueue_grad_tail(slot)
         else:
             self._enqueue_compute(slot)
+
+    def _enqueue_compute_update(self, slot: int = 0):
+        """the single-rank step, whole: one graph per slot"""
+        self._enqueue_step_compute(slot)
+        self._enqueue_update()
 
     def _enqueue_update(self):
         """single rank / all-reduce form: Adam over the whole flat vector + re-pack + optimizer-state advance, one launch"""
@@ -548,108 +581,112 @@ class FusedTrainer:
         if self.l2 != 0.0:
             self.loss.add_(self.l2buf[1:2])
 
-    def _enqueue_dp_step(self, slot: int = 0):
-        """the whole data-parallel step on the current stream, collectives included (eager, or under capture with RCCL)"""
-        if self.mode == "allreduce":
-            self._enqueue_compute(slot)
-            self.ex.all_reduce(self.grad)
-            self._enqueue_update()
-        else:
-            self._enqueue_fwd(slot)
-            h = self.ex.all_reduce_stats(self.stats)               # 16 bytes, in flight under the backward
-            self._enqueue_bwd(slot)
-            self.ex.reduce_scatter(self.grad, self.recv)
-            if h is not None:
-                h.wait()
-            self._enqueue_shard_update()
-            self._gather_params()
-            self._enqueue_shard_finish()
+    # ---- the eager stages of the data-parallel programs ---------------------------------------
+    def _all_reduce_grad(self):
+        self.ex.all_reduce(self.grad)
 
-    def _capture(self):
-        # warm-up on a side stream (sets the LDS attributes, loads code objects), then capture
+    def _start_stats_reduce(self):
+        self._stats_handle = self.ex.all_reduce_stats(self.stats)      # 16 bytes, in flight under the backward
+
+    def _scatter_grad(self):
+        self.ex.reduce_scatter(self.grad, self.recv)
+        h, self._stats_handle = self._stats_handle, None
+        if h is not None:
+            h.wait()
+
+    # ---- the walks over the step program ------------------------------------------------------
+    def _walk(self, stages, graphs, slot, local=False):
+        """``stages`` in order: a stage with graphs is replayed, any other has its methods called; ``local``: without the
+        collectives"""
+        for (kind, per_slot, calls), gs in zip(stages, graphs):
+            if gs is not None:
+                gs[slot if per_slot else 0].replay()
+            elif not (local and kind == "collective"):
+                for name in calls:
+                    getattr(self, name)(*((slot,) if per_slot else ()))
+
+    def _enqueue_step(self, slot: int = 0, local: bool = False):
+        """the whole step on the current stream: the eager step, and (data parallel over RCCL, whose collectives are stream
+        work) the body of the one-graph form"""
+        self._walk(self._program, [None] * len(self._program), slot, local)
+
+    def _replay(self, slot: int = 0, local: bool = False):
+        """the captured step: its graphs replayed, the eager stages between them called"""
+        self._walk(*self._graphs, slot, local)
+
+    @property
+    def captured(self) -> bool:
+        return self._graphs is not None
+
+    @contextlib.contextmanager
+    def _snapshot(self):
+        """everything a step changes - parameters, moments, optimizer state words, gradient, statistics - put back on exit
+        (and by the ``restore`` it yields), with what the model derives from the parameters"""
         torch.cuda.synchronize()
         keep = [self.flat, self.m, self.v, self.state, self.grad, self.stats] + ([self.shadow_pad] if self.shadow_gather else [])
         snap = [t.clone() for t in keep]
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            if self.mode != "single" and self.ex.native:
-                # RCCL: one whole step EAGERLY, collectives included, before anything is captured - every collective type the
-                # graph will hold has then run once on this communicator (lazy channel / buffer set-up cannot be captured)
-                self._enqueue_dp_step()
-            else:
-                self._enqueue_step_compute()
-                if self.mode == "sharded":
-                    self._enqueue_shard_update()
-                    self._enqueue_shard_finish()
-                else:
-                    self._enqueue_update()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
 
         def restore():
+            torch.cuda.synchronize()
             for dst, src in zip(keep, snap):
                 dst.copy_(src)
-            self.model.pack_weights()         # the warm-up step re-packed the stepped weights: restore that too
+            self.model.pack_weights()         # the steps re-packed the stepped weights: restore that too
             if not self.shadow_gather:        # ... and re-derived the bf16 shadow of the stepped table (if one is in use;
                 self.model.refresh_bf16_table()   # shadow_gather: the shadow itself is part of the snapshot)
+            torch.cuda.synchronize()
 
-        restore()
-        # thread_local capture mode: a collective backend's watchdog thread may touch the HIP runtime while we capture
+        try:
+            yield restore
+        finally:
+            restore()
 
-        def graph_of(fn):
+    def _graphs_of(self, stages):
+        """one graph per graph stage and slot (the kernels' id pointers are baked in; a slot-independent stage: one graph),
+        None per eager stage"""
+        def graph_of(stage, slot):
             g = torch.cuda.CUDAGraph()
+            # thread_local capture mode: a collective backend's watchdog thread may touch the HIP runtime while we capture
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                fn()
+                self._walk([stage], [None], slot)
             return g
 
-        # one graph per input slot (the kernels' id pointers are baked in)
-        self.graph_form = "one" if self.mode == "single" else "split"
-        if self.mode != "single" and self.ex.native and os.environ.get("SRFRD_DP_SPLIT_GRAPHS", "") != "1":
-            # RCCL collectives are stream work: the WHOLE data-parallel step - compute, collectives, sharded Adam, re-pack -
-            # goes into ONE graph per slot, so a step is one host launch and nothing on the host sits between the kernels and
-            # the collectives.  (ProcessGroupNCCL forks its internal stream off the capturing one and joins it back: the
-            # statistics all-reduce stays concurrent with the backward inside the graph.)  If this torch / RCCL pair refuses
-            # the capture, the step falls back to the split form below; `graph_form` says which one runs.
-            try:
-                self._graph_one = [graph_of(lambda k=k: self._enqueue_dp_step(k)) for k in range(self.slots)]
-                self.graph_form = "one"
-            except Exception as e:                      # noqa: BLE001 - any capture failure selects the split form
-                self._graph_one = None
-                self.graph_capture_error = repr(e)
-                torch.cuda.synchronize()
-                restore()
-        if self.graph_form == "one" and self.mode != "single":
-            pass
-        elif self.mode == "single" and self.token:
-            # two graphs around the eager key sort: per slot everything up to the key list, then (slot-independent) the table
-            # reduction, the slab reduction and the Adam tail
-            self.graph_form = "split"
-            self._graph_a = [graph_of(lambda k=k: self._enqueue_ce_compute(k, front_only=True)) for k in range(self.slots)]
-            self._graph_b = graph_of(lambda: (self._enqueue_token_table(), self._enqueue_ce_dense(), self._enqueue_update()))
-        elif self.mode == "single":
-            self._graph_a = [graph_of(lambda k=k: (self._enqueue_step_compute(k), self._enqueue_update())) for k in range(self.slots)]
-        elif self.mode == "allreduce":
-            self._graph_a = [graph_of(lambda k=k: self._enqueue_compute(k)) for k in range(self.slots)]
-            self._graph_b = graph_of(self._enqueue_update)
-        else:
-            self._graph_f = [graph_of(lambda k=k: self._enqueue_fwd(k)) for k in range(self.slots)]
-            self._graph_a = [graph_of(lambda k=k: self._enqueue_bwd(k)) for k in range(self.slots)]
-            self._graph_u = graph_of(self._enqueue_shard_update)
-            self._graph_b = graph_of(self._enqueue_shard_finish)
-        # The first replay of a graph also uploads it to the device (tens of microseconds, once per graph - and there is one
-        # graph per input slot): replay each once here, inside the snapshot, so that no step pays for it.  (Compute graphs
-        # only: no collective is involved, every rank does the same.)
-        if self._graph_one is None:
-            for gs in (self._graph_f, self._graph_a, [self._graph_u], [self._graph_b]):
-                for g in (gs or []):
-                    if g is not None:
-                        g.replay()
-        else:
-            for g in self._graph_one:       # (holds collectives: every rank replays the same graphs in the same order)
-                g.replay()
-        torch.cuda.synchronize()
-        restore()
+        return [[graph_of(st, k) for k in range(self.slots if st[1] else 1)] if st[0] == "graph" else None for st in stages]
+
+    def _capture(self):
+        # warm-up on a side stream (sets the LDS attributes, loads code objects), then capture
+        rccl = self.mode != "single" and self.ex.native
+        with self._snapshot():
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                # RCCL: one whole step EAGERLY, collectives included, before anything is captured - every collective type the
+                # graph will hold has then run once on this communicator (lazy channel / buffer set-up cannot be captured)
+                self._enqueue_step(0, local=not rccl)
+            torch.cuda.current_stream().wait_stream(s)
+        with self._snapshot() as restore:
+            stages = graphs = None
+            if rccl and os.environ.get("SRFRD_DP_SPLIT_GRAPHS", "") != "1":
+                # RCCL collectives are stream work: the WHOLE data-parallel step - compute, collectives, sharded Adam, re-pack -
+                # goes into ONE graph per slot, so a step is one host launch and nothing on the host sits between the kernels and
+                # the collectives.  (ProcessGroupNCCL forks its internal stream off the capturing one and joins it back: the
+                # statistics all-reduce stays concurrent with the backward inside the graph.)  If this torch / RCCL pair refuses
+                # the capture, the step falls back to the split form below; `graph_form` says which one runs.
+                try:
+                    stages, graphs = ONE_GRAPH, self._graphs_of(ONE_GRAPH)
+                except Exception as e:                      # noqa: BLE001 - any capture failure selects the split form
+                    stages = None
+                    self.graph_capture_error = repr(e)
+                    restore()
+            if stages is None:
+                stages, graphs = self._program, self._graphs_of(self._program)
+            self._graphs = (stages, graphs)
+            self.graph_form = "one" if len(stages) == 1 else "split"      # (one graph per step, or graphs around eager stages)
+            # The first replay of a graph also uploads it to the device (tens of microseconds, once per graph - and there is one
+            # graph per input slot): replay each once here, inside the snapshot, so that no step pays for it.  (Split form: the
+            # graphs only, no collective is involved; one-graph form: every rank replays the same graphs in the same order.)
+            for gs in graphs:
+                for g in gs or ():
+                    g.replay()
 
     # ---- public -------------------------------------------------------------------------------
     def spin_up(self, replays: int = 200):
@@ -664,28 +701,11 @@ class FusedTrainer:
             return
         if not self._fresh:
             self.refresh()
-        if self._graph_a is None and self._graph_one is None:
+        if not self.captured:
             self._capture()
-        torch.cuda.synchronize()
-        keep = [self.flat, self.m, self.v, self.state, self.grad, self.stats] + ([self.shadow_pad] if self.shadow_gather else [])
-        snap = [t.clone() for t in keep]
-        if self._graph_one is not None:      # (collectives inside: every rank replays the same number of times)
-            seq = [self._graph_one[0].replay]
-        else:
-            seq = [(g[0] if isinstance(g, list) else g).replay for g in (self._graph_f, self._graph_a, self._graph_u, self._graph_b)
-                   if g is not None]
-            if self.token:                   # (the eager key sort between the step's two graphs)
-                seq.insert(1, self._sort_token_keys)
-        for _ in range(int(replays)):
-            for replay in seq:
-                replay()
-        torch.cuda.synchronize()
-        for dst, src in zip(keep, snap):
-            dst.copy_(src)
-        self.model.pack_weights()
-        if not self.shadow_gather:
-            self.model.refresh_bf16_table()
-        torch.cuda.synchronize()
+        with self._snapshot():
+            for _ in range(int(replays)):
+                self._replay(0, local=True)
 
     def refresh(self):
         """Re-derive everything the step keeps derived from the parameters (the MFMA-fragment-ordered weight copy).  Call
@@ -780,7 +800,7 @@ class FusedTrainer:
         # step size, bias correction and dropout seed of the NEXT step (t = steps_done + 1), as after an uninterrupted run.
         # (The captured graphs bake lr / betas in as launch arguments: they are re-captured.)
         check(_lib.lib().srfrd_step_begin(ptr(self.state), self.lr, self.betas[0], self.betas[1], self._stream()), "srfrd_step_begin")
-        self._graph_a = self._graph_b = self._graph_f = self._graph_u = self._graph_one = None
+        self._graphs = None
         self._fresh = False
 
     def _check_slot(self, slot: int = 0):
@@ -851,35 +871,11 @@ class FusedTrainer:
             self._last_slot = slot
         if not self._fresh:
             self.refresh()
-        g = self.use_graph
-        if g and self._graph_a is None and self._graph_one is None:
-            self._capture()
-        if not g:
-            if self.mode == "single":
-                self._enqueue_step_compute(slot)
-                self._enqueue_update()
-            else:
-                self._enqueue_dp_step(slot)
-        elif self._graph_one is not None:          # data parallel, collectives captured: ONE host launch per step
-            self._graph_one[slot].replay()
-        elif self.mode == "single":
-            self._graph_a[slot].replay()
-            if self.token:                         # the key sort is not captured: eager, between the step's two graphs
-                self._sort_token_keys()
-                self._graph_b.replay()
-        elif self.mode == "allreduce":             # split form: graphs around the host-launched collectives
-            self._graph_a[slot].replay()
-            self.ex.all_reduce(self.grad)
-            self._graph_b.replay()
+        if not self.use_graph:
+            self._enqueue_step(slot)
         else:
-            self._graph_f[slot].replay()
-            h = self.ex.all_reduce_stats(self.stats)               # 16 bytes, in flight under the backward
-            self._graph_a[slot].replay()
-            self.ex.reduce_scatter(self.grad, self.recv)
-            if h is not None:
-                h.wait()
-            self._graph_u.replay()
-            self._gather_params()
-            self._graph_b.replay()
+            if not self.captured:
+                self._capture()
+            self._replay(slot)
         self.steps_done += 1
         return self.loss

@@ -244,6 +244,38 @@ def test_graph_equals_eager_and_resume_is_bitwise(loss, det):
         other.load_state_dict(opt_sd)
 
 
+@pytest.mark.parametrize("loss, kw", [("sampled_softmax", dict(num_negatives=64)), ("softmax", dict(deterministic=True))])
+def test_spin_up_leaves_the_training_trajectory_untouched(loss, kw):
+    """FusedTrainer.spin_up() under the catalog losses: 7 replays of a filled slot inside the snapshot, then three steps -
+    losses, parameters, both moments and (sampled: the state word the device sampler draws from is restored) the negatives
+    of every step bit for bit those of a run without it.  400 items, L 50 (the ragged pair), B 16, dropout 0.5."""
+    import srfrd_amd
+    from tests.gpu_util import build_model, random_sd
+    cfg = O.Cfg("SRFRN", 400, 50, 45, d_fake=5, dropout=0.5)
+    sd = random_sd(cfg, 21)
+    B = 16
+    batches = [_batch(cfg, B, 80 + i) for i in range(3)]
+    outs = []
+    for spin in (False, True):
+        tr = srfrd_amd.FusedTrainer(build_model(cfg, sd).train(), B, 50, loss=loss, seed=77, **kw)
+        if spin:
+            tr.ids_ring[0].copy_(torch.stack(batches[2]))
+            tr.spin_up(7)
+            assert tr.captured and tr.graph_form == "one" and tr.steps_done == 0
+        losses, drawn = [], []
+        for b in batches:
+            losses.append(float(tr.step(None, *b)))
+            drawn.append(tr.negatives)
+        assert all(math.isfinite(x) for x in losses)
+        torch.cuda.synchronize()
+        outs.append((losses, drawn, (tr.flat.detach().clone(), tr.m.detach().clone(), tr.v.detach().clone())))
+    assert outs[0][0] == outs[1][0]
+    assert all(torch.equal(x, y) for x, y in zip(outs[0][2], outs[1][2]))
+    if loss == "sampled_softmax":
+        assert all(torch.equal(x, y) for x, y in zip(outs[0][1], outs[1][1]))
+        assert not torch.equal(outs[0][1][0], outs[0][1][1])           # (every step draws its own)
+
+
 @pytest.mark.parametrize("loss", ["sampled_softmax", "softmax"])
 def test_batch_without_targets_behaves_as_bce(loss):
     import srfrd_amd

@@ -48,7 +48,7 @@ def test_fused_trainer_graph_steps_match_reference(name):
         assert abs(float(loss.cpu()) - float(g[f"loss{step}"])) < TOL, step
         if step == 0:
             msd1 = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    assert tr.graph_form == "one" and tr._graph_a is not None, tr.graph_capture_error
+    assert tr.graph_form == "one" and tr.captured, tr.graph_capture_error
     msd3 = {k: v.detach().cpu() for k, v in model.state_dict().items()}
     if L == 20:
         for k in w1:

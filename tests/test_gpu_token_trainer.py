@@ -236,6 +236,33 @@ def test_graph_equals_eager_resume_and_foreign_states(loss):
 
 
 @pytest.mark.parametrize("loss", ["token_softmax", "gbce"])
+def test_spin_up_leaves_the_training_trajectory_untouched(loss):
+    """FusedTrainer.spin_up() on the step of two graphs around the eager key sort: 7 replays of a filled slot (ids, negatives
+    and log-Q) inside the snapshot, then three steps - losses, parameters and both moments bit for bit those of a run without
+    it.  400 items, L 50 (the ragged pair), B 16, K 3, dropout 0.5."""
+    from tests.gpu_util import random_sd
+    cfg = O.Cfg("SRFU_B", 400, 50, 50, n_labels=3, dropout=0.5)
+    sd = random_sd(cfg, 21)
+    B, K = 16, 3
+    batches = [_batch(cfg, B, 80 + i) for i in range(3)]
+    negs = [_negatives(cfg, b[2], K, 50 + i) for i, b in enumerate(batches)]
+    outs = []
+    for spin in (False, True):
+        tr = _trainer(cfg, sd, B, loss, K, gbce_beta=0.7, seed=77)
+        if spin:
+            tr.ids_ring[0].copy_(torch.stack(batches[2]))
+            tr.neg_ring[0].copy_(negs[2][0])
+            tr.log_q_ring[0].copy_(negs[2][1])
+            tr.spin_up(7)
+            assert tr.captured and tr.graph_form == "split" and tr.steps_done == 0
+        losses = [float(_step(tr, b, *n)) for b, n in zip(batches, negs)]
+        assert all(math.isfinite(x) for x in losses)
+        outs.append((losses, _bits(tr)))
+    assert outs[0][0] == outs[1][0]
+    assert _same(outs[0][1], outs[1][1])
+
+
+@pytest.mark.parametrize("loss", ["token_softmax", "gbce"])
 def test_batch_without_targets_behaves_as_bce(loss):
     from tests.gpu_util import random_sd
     cfg = _kind_cfg("SASRec", 20)

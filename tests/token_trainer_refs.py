@@ -178,4 +178,4 @@ def step_keys(input_ids, targets, negatives, n_items, remove_hits):
 
 # (B, L, K, n_items) of every FusedTrainer(loss="token_softmax" | "gbce") that tests/test_gpu_token_trainer.py builds
 TRAINER_SHAPES = [(16, 20, 1, 300), (16, 20, 5, 300), (16, 20, 65, 300), (16, 50, 1, 300), (16, 50, 5, 300), (16, 50, 65, 300),
-                  (8, 20, 24, 300), (8, 20, 1, 300), (8, 20, 7, 300), (16, 20, 65, 8), (512, 50, 64, 50_000)]
+                  (8, 20, 24, 300), (8, 20, 1, 300), (8, 20, 7, 300), (16, 20, 65, 8), (512, 50, 64, 50_000), (16, 50, 3, 400)]

@@ -125,7 +125,6 @@ def run():
 def run_c4(I=200_000, L=100, which="bwd_slots"):
     """seq_len 100 fused training step (BASELINE configs[3] geometry): the slot-placed backward, phase by phase
     (--c5: seq_len 200, the row-chunked backward)"""
-    import ctypes as C
     import json
     import torch
     os.environ["SRFRD_LIB_PATH"] = OUT
@@ -144,15 +143,10 @@ def run_c4(I=200_000, L=100, which="bwd_slots"):
     tr.refresh()
     tr.ids.copy_(srfrd_amd.synthetic_batch(I, L, B, seed=1, device="cuda", packed=True)[1])
     tr._enqueue_fwd()
-    ids, fk, pfk, nfk, p, seed_dev, seq0 = tr._ids_of(0)
-    lay_t, tab = m._table_args()
 
-    def bwd(dbg):
-        check(_lib.lib().srfrd_encoder_bwd(C.byref(lay_t), tab, tr._dense_ptr(tr.flat), ptr(tr.packed), ptr(ids[0]), ptr(fk), ptr(ids[2]),
-                                           ptr(pfk), ptr(ids[4]), ptr(nfk), B, L, p, 0, seed_dev, seq0, ptr(tr.hidden), ptr(tr.pl),
-                                           ptr(tr.nl), ptr(tr.save_x), ptr(tr.save_h1), ptr(tr.save_aux), None, None, None, 1,
-                                           ptr(tr.grad), None, ptr(tr.slabs), ptr(tr.scratch), tr.n_scratch,
-                                           ptr(dbg.view(torch.float32)), 0, tr._stream()), "srfrd_encoder_bwd")
+    def bwd(dbg):      # the trainer's own backward arguments, the stamp buffer in the schedule's place
+        check(_lib.lib().srfrd_encoder_bwd(*tr._enc_args(0, True), *tr._bwd_args(None, None), ptr(dbg.view(torch.float32)), 0,
+                                           tr._stream()), "srfrd_encoder_bwd")
     dbg = torch.zeros(1024, 128, device="cuda", dtype=torch.int64)
     dbg2 = torch.zeros(1024, 128, device="cuda", dtype=torch.int64)
     bwd(dbg)
