@@ -301,7 +301,7 @@ int srfrd_loss_stats(const float* loss_part, int B, float* stats, float* loss_ou
  * (double precision, as torch.optim.Adam computes them on the host), next dropout seed.
  *  state: uint32[32] {t, base_seed, step_seed, -, float step_size, float bc2_sqrt, ticket root, -, 16 ticket shards, -...}
  *         (words 6 and 8..23 are the hand-off counters of srfrd_adam_pack_step, zero between launches; callers that
- *         never use that entry point may pass 8 words)
+ *         never use that entry point may pass 8 words; words 3 and 7 are written by srfrd_step_begin_sched only, below)
  */
 int srfrd_step_begin(uint32_t* state, double lr, double beta1, double beta2, void* stream);
 
@@ -330,6 +330,82 @@ int srfrd_adam_step(float* param, float* grad, float* m, float* v, int64_t n, in
 int srfrd_adam_pack_step(const srfrd_layout* lay, float* param, float* grad, float* m, float* v, int64_t n,
                          int64_t n_table_pad, int64_t n_zero, double lr, double beta1, double beta2, double eps,
                          uint32_t* state, const float* stats, float* packed, uint16_t* table_bf16, void* stream);
+
+/*
+ * Learning-rate schedule, decoupled weight decay and gradient-norm clipping for the two Adam entry points above (DESIGN
+ * section 19).  The schedule lives on the device, beside the step counter: a captured graph holds `opts` as a constant
+ * and only t varies from replay to replay.
+ *
+ * THE formula (srfrd_amd.lr_at is its host mirror): for the 1-based step t, lr_t = lr * f(t), in double precision, with
+ * w = warmup_steps, T = total_steps, r = final_ratio:
+ *   t <= w :  f = t / w
+ *   else   :  u = min(1, (t - w) / max(1, T - w)), and
+ *             SRFRD_SCHED_CONSTANT  f = 1
+ *             SRFRD_SCHED_LINEAR    f = 1 - (1 - r) u
+ *             SRFRD_SCHED_COSINE    f = r + (1 - r) (1 + cos(pi u)) / 2
+ * so f(w) = 1, f(T) = r, and f stays at r past T (T is not read under SRFRD_SCHED_CONSTANT).
+ */
+enum { SRFRD_SCHED_CONSTANT = 0, SRFRD_SCHED_LINEAR = 1, SRFRD_SCHED_COSINE = 2 };
+
+typedef struct srfrd_optim_opts {
+  double lr, beta1, beta2;         /* base rate, Adam betas */
+  double weight_decay;             /* decoupled (AdamW): p *= 1 - lr_t * weight_decay ahead of the Adam update; >= 0 */
+  double final_ratio;              /* r, in [0, 1] */
+  int64_t warmup_steps;            /* w >= 0 */
+  int64_t total_steps;             /* T >= w under a decaying schedule */
+  int32_t schedule;                /* SRFRD_SCHED_* */
+  int32_t reserved;                /* 0 */
+} srfrd_optim_opts;
+
+/* srfrd_step_begin under a schedule: t += 1, next dropout seed, and with lr_t of the NEW t
+ *   state[4] = float(lr_t / (1 - b1^t)), state[5] = float(sqrt(1 - b2^t))       (srfrd_step_begin's words, lr_t for lr)
+ *   state[3] = float(lr_t), state[7] = float(1 - lr_t * weight_decay)           (the factor torch.optim.AdamW multiplies by)
+ * Every other word stays untouched.  With SRFRD_SCHED_CONSTANT, no warmup and no decay words 0, 2, 4 and 5 are bitwise
+ * srfrd_step_begin's.  SRFRD_E_ARG before any launch: state or opts NULL, a negative or NaN weight_decay, a negative
+ * warmup_steps, a decaying schedule with total_steps < warmup_steps, an unknown schedule, final_ratio outside [0, 1]. */
+int srfrd_step_begin_sched(uint32_t* state, const srfrd_optim_opts* opts, void* stream);
+
+/* Workgroups, and fp64 partial sums, of srfrd_grad_norm at most: `partial` holds this many doubles. */
+#define SRFRD_GRAD_NORM_PARTIALS 1024
+/* Floats of one workgroup's share of the vector at least (shares grow, in steps of four floats, once n exceeds
+ * SRFRD_GRAD_NORM_PARTIALS of them). */
+#define SRFRD_GRAD_NORM_SHARE 4096
+
+/*
+ * Global L2 norm of the flat gradient and torch.nn.utils.clip_grad_norm_'s coefficient, deterministic:
+ *   out[0] = sqrt(sum_i grad[i]^2) * gscale      gscale = 1 / stats[2] (the count the Adam step divides by), 1 if stats == NULL
+ *   out[1] = min(1, max_norm / (out[0] + 1e-6))  max_norm = +inf only measures (coefficient 1); a NaN norm gives a NaN
+ *                                                coefficient, as torch's clamp does
+ * Squares and sums are fp64 (the square of a float is exact in a double).  Workgroup g of ceil(n4 / share4) sums the
+ * contiguous floats [4 g share4, 4 (g + 1) share4), n4 = n / 4, share4 = max(SRFRD_GRAD_NORM_SHARE / 4, ceil(n4 /
+ * SRFRD_GRAD_NORM_PARTIALS)): the split depends on n alone, never on the device.  A second one-wave kernel behind the
+ * same entry point adds the partials - lane l its sixteen in index order, then the 64 lane sums in lane order, then the
+ * n % 4 tail elements in index order - so two calls on the same data give the same bits.
+ * grad is 16-byte aligned; partial: SRFRD_GRAD_NORM_PARTIALS doubles of workspace; out: 2 floats.
+ * SRFRD_E_ARG before any launch: grad, partial or out NULL, grad misaligned, n <= 0, max_norm <= 0 or NaN.
+ */
+int srfrd_grad_norm(const float* grad, int64_t n, const float* stats, double max_norm, double* partial, float* out,
+                    void* stream);
+
+/*
+ * srfrd_adam_step with clipping and decoupled weight decay: per element
+ *   gs = gscale * coef (one float multiply; coef = clip[1], srfrd_grad_norm's out - 1 if clip == NULL);  g = grad[i] * gs;
+ *   m, v as srfrd_adam_step;  p = p * state[7] - step_size * m / (sqrt(v) / bc2_sqrt + eps)
+ * `state` comes from srfrd_step_begin_sched (words 4, 5, 7).  With clip == NULL and state[7] == 1 the result is bitwise
+ * srfrd_adam_step's.  Argument checks as srfrd_adam_step.
+ */
+int srfrd_adamw_step(float* param, float* grad, float* m, float* v, int64_t n, int64_t i0, int64_t i1,
+                     int64_t n_zero, double beta1, double beta2, double eps,
+                     const uint32_t* state, const float* stats, const float* clip, uint16_t* table_bf16, int64_t n_table,
+                     void* stream);
+
+/* srfrd_adam_pack_step with srfrd_adamw_step's arithmetic; the last block to finish makes srfrd_step_begin_sched's advance
+ * under `opts` (which also carries lr and the betas).  Argument checks: srfrd_adam_pack_step's and
+ * srfrd_step_begin_sched's, all before any launch. */
+int srfrd_adamw_pack_step(const srfrd_layout* lay, float* param, float* grad, float* m, float* v, int64_t n,
+                          int64_t n_table_pad, int64_t n_zero, const srfrd_optim_opts* opts, double eps,
+                          uint32_t* state, const float* stats, const float* clip, float* packed, uint16_t* table_bf16,
+                          void* stream);
 
 /* bf16 shadow of an fp32 vector (round to nearest even; fp32 denormals are rounded, not flushed; NaN stays NaN):
  * out[i] = bf16(src[i]), i < n.  Builds / refreshes the item-table

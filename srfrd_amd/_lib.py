@@ -32,9 +32,21 @@ class Layout(C.Structure):
                    ("n_dense", C.c_int64), ("n_table", C.c_int64)])
 
 
+class OptimOpts(C.Structure):
+    """srfrd_optim_opts: base rate and betas, decoupled weight decay, and the learning-rate schedule of include/srfrd_hip.h"""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("weight_decay", C.c_double),
+                ("final_ratio", C.c_double), ("warmup_steps", C.c_int64), ("total_steps", C.c_int64), ("schedule", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+SCHEDULES = {"constant": 0, "linear": 1, "cosine": 2}      # SRFRD_SCHED_*
+GRAD_NORM_PARTIALS = 1024                                  # SRFRD_GRAD_NORM_PARTIALS: doubles of srfrd_grad_norm's workspace
+GRAD_NORM_SHARE = 4096                                     # SRFRD_GRAD_NORM_SHARE
+
 _P = C.c_void_p
 _i, _i64, _u32, _d = C.c_int, C.c_int64, C.c_uint32, C.c_double
 _LP = C.POINTER(Layout)
+_OP = C.POINTER(OptimOpts)
 
 # name -> (restype, argtypes); must list every symbol include/srfrd_hip.h declares (tests/test_abi.py checks it)
 SIGNATURES = {
@@ -68,6 +80,10 @@ SIGNATURES = {
     "srfrd_step_begin": (_i, [_P, _d, _d, _d, _P]),
     "srfrd_adam_step": (_i, [_P, _P, _P, _P, _i64, _i64, _i64, _i64, _d, _d, _d, _P, _P, _P, _i64, _P]),
     "srfrd_adam_pack_step": (_i, [_LP, _P, _P, _P, _P, _i64, _i64, _i64, _d, _d, _d, _d, _P, _P, _P, _P, _P]),
+    "srfrd_step_begin_sched": (_i, [_P, _OP, _P]),
+    "srfrd_grad_norm": (_i, [_P, _i64, _P, _d, _P, _P, _P]),
+    "srfrd_adamw_step": (_i, [_P, _P, _P, _P, _i64, _i64, _i64, _i64, _d, _d, _d, _P, _P, _P, _P, _i64, _P]),
+    "srfrd_adamw_pack_step": (_i, [_LP, _P, _P, _P, _P, _i64, _i64, _i64, _OP, _d, _P, _P, _P, _P, _P, _P]),
     "srfrd_table_to_bf16": (_i, [_P, _i64, _P, _P]),
     "srfrd_loss_finalize": (_i, [_P, _P, _P]),
     "srfrd_l2_norms": (_i, [_P, _P, _P, _i, _i64, _d, _P, _P, _P, _P]),

@@ -891,6 +891,32 @@ __device__ __forceinline__ void step_advance(uint32_t* state, double lr, double 
   ((float*)state)[5] = (float)sqrt(bc2);
 }
 
+// lr_t = lr f(t) of include/srfrd_hip.h (the one statement of the formula), 1-based t, in double
+__device__ __forceinline__ double sched_lr(const srfrd_optim_opts& o, uint32_t t) {
+  const double w = (double)o.warmup_steps, td = (double)t;
+  if (td <= w) return o.lr * (td / w);
+  if (o.schedule == SRFRD_SCHED_CONSTANT) return o.lr;
+  const double span = (double)(o.total_steps - o.warmup_steps);
+  const double u = fmin(1.0, (td - w) / fmax(1.0, span)), r = o.final_ratio;
+  if (o.schedule == SRFRD_SCHED_LINEAR) return o.lr * (1.0 - (1.0 - r) * u);
+  return o.lr * (r + (1.0 - r) * (0.5 * (1.0 + cos(3.14159265358979323846 * u))));
+}
+
+// step_advance under a schedule (one thread): the same words with lr_t of the new t for lr, and the two words only this
+// advance writes - state[3] = lr_t, state[7] = 1 - lr_t * weight_decay (the factor of torch.optim.AdamW's decay)
+__device__ __forceinline__ void step_advance_sched(uint32_t* state, const srfrd_optim_opts& o) {
+  const uint32_t t = state[0] + 1u;
+  state[0] = t;
+  state[2] = step_seed(state[1], t);
+  const double lr_t = sched_lr(o, t);
+  const double bc1 = 1.0 - pow(o.beta1, (double)t);
+  const double bc2 = 1.0 - pow(o.beta2, (double)t);
+  ((float*)state)[3] = (float)lr_t;
+  ((float*)state)[4] = (float)(lr_t / bc1);
+  ((float*)state)[5] = (float)sqrt(bc2);
+  ((float*)state)[7] = (float)(1.0 - lr_t * o.weight_decay);
+}
+
 __device__ __forceinline__ float softplus_f(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
 __device__ __forceinline__ float sigmoid_f(float z) { return 1.0f / (1.0f + expf(-z)); }
 

@@ -106,11 +106,27 @@ __global__ void step_begin_kernel(uint32_t* state, double lr, double b1, double 
   if (threadIdx.x == 0 && blockIdx.x == 0) step_advance(state, lr, b1, b2);
 }
 
+__global__ void step_begin_sched_kernel(uint32_t* state, srfrd_optim_opts opts) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) step_advance_sched(state, opts);
+}
+
+// a * b rounded on its own: the contraction pragma keeps the compiler from fusing it into a later addition.  (The decayed
+// parameter p * decay fused into the update would be fma(p, decay, -(step_size * q)): with decay == 1 not the bits of the
+// plain kernel's fma(-step_size, q, p).  Unfused, the W form at decay == 1 runs the plain form's arithmetic.)
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// W: the AdamW form - the parameter is first multiplied by `decay` (state[7] = 1 - lr_t * weight_decay), torch.optim.AdamW's
+// p.mul_(1 - lr * wd) ahead of the addcdiv_.  W = false compiles to what it was before the template existed.
+template <bool W>
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float b1, float b2, float eps,
-                                         float step_size, float bc2s) {
+                                         float step_size, float bc2s, float decay) {
   m = m * b1 + (1.0f - b1) * g;           // exp_avg.lerp_(grad, 1 - beta1) == exp_avg*b1 + (1-b1)*g up to rounding
   v = v * b2 + ((1.0f - b2) * g) * g;     // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
   const float denom = sqrtf(v) / bc2s + eps;
+  if constexpr (W) p = mul_rounded(p, decay);
   p = p - step_size * (m / denom);
 }
 
@@ -135,13 +151,30 @@ __global__ void __launch_bounds__(256) table_to_bf16_kernel(const float* __restr
   for (int64_t i = (nvec << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = f32_to_bf16(src[i]);
 }
 
+// What a W = true instantiation of the Adam kernels takes behind the W = false parameters (a parameter pack: the W = false
+// kernels keep the parameter list, and with it the instructions, they had before the template existed)
+template <class A, class... R>
+__device__ __forceinline__ A first_arg(A a, R...) { return a; }
+template <class A, class B>
+__device__ __forceinline__ const B& second_arg(const A&, const B& b) { return b; }
+
+// srfrd_adam_step (W = false, no Extra) and srfrd_adamw_step (W = true, Extra = const float* clip: the gradient scale carries
+// the clip coefficient, the parameter is decayed): the loops written once
+template <bool W, class... Extra>
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ m,
                                                   float* __restrict__ v, int64_t i0, int64_t i1, int64_t n_zero, float b1,
                                                   float b2, float eps, const uint32_t* __restrict__ state,
-                                                  const float* __restrict__ stats, uint16_t* __restrict__ shadow, int64_t n_shadow) {
+                                                  const float* __restrict__ stats, uint16_t* __restrict__ shadow, int64_t n_shadow,
+                                                  Extra... extra) {
   const float step_size = ((const float*)state)[4];
   const float bc2s = ((const float*)state)[5];
-  const float gscale = stats ? 1.0f / stats[2] : 1.0f;
+  float gscale = stats ? 1.0f / stats[2] : 1.0f;
+  float decay = 1.0f;
+  if constexpr (W) {
+    const float* __restrict__ clip = first_arg(extra...);
+    gscale = gscale * (clip ? clip[1] : 1.0f);       // gs = gscale * coef: one float multiply
+    decay = ((const float*)state)[7];
+  }
   // i0 is a multiple of 4 (host guarantees), so float4 lanes are aligned
   const int64_t nvec = (i1 - i0) >> 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -151,10 +184,10 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ param, fl
     float4 g4 = *reinterpret_cast<const float4*>(grad + i);
     float4 m4 = *reinterpret_cast<float4*>(m + i);
     float4 v4 = *reinterpret_cast<float4*>(v + i);
-    adam_one(p4.x, g4.x * gscale, m4.x, v4.x, b1, b2, eps, step_size, bc2s);
-    adam_one(p4.y, g4.y * gscale, m4.y, v4.y, b1, b2, eps, step_size, bc2s);
-    adam_one(p4.z, g4.z * gscale, m4.z, v4.z, b1, b2, eps, step_size, bc2s);
-    adam_one(p4.w, g4.w * gscale, m4.w, v4.w, b1, b2, eps, step_size, bc2s);
+    adam_one<W>(p4.x, g4.x * gscale, m4.x, v4.x, b1, b2, eps, step_size, bc2s, decay);
+    adam_one<W>(p4.y, g4.y * gscale, m4.y, v4.y, b1, b2, eps, step_size, bc2s, decay);
+    adam_one<W>(p4.z, g4.z * gscale, m4.z, v4.z, b1, b2, eps, step_size, bc2s, decay);
+    adam_one<W>(p4.w, g4.w * gscale, m4.w, v4.w, b1, b2, eps, step_size, bc2s, decay);
     *reinterpret_cast<float4*>(param + i) = p4;
     *reinterpret_cast<float4*>(m + i) = m4;
     *reinterpret_cast<float4*>(v + i) = v4;
@@ -166,7 +199,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ param, fl
   const int64_t tail0 = i0 + (nvec << 2);
   for (int64_t i = tail0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < i1; i += stride) {
     float p = param[i], mm = m[i], vv = v[i];
-    adam_one(p, grad[i] * gscale, mm, vv, b1, b2, eps, step_size, bc2s);
+    adam_one<W>(p, grad[i] * gscale, mm, vv, b1, b2, eps, step_size, bc2s, decay);
     param[i] = p; m[i] = mm; v[i] = vv;
     if (i < n_zero) grad[i] = 0.f;
     if (shadow != nullptr && i < n_shadow) shadow[i] = f32_to_bf16(p);
@@ -206,15 +239,24 @@ __device__ __forceinline__ void pack_scatter(const Dims& d, int64_t j, float val
 
 // Adam over the whole flat vector + re-pack of the stepped encoder weights + (last block to finish) the optimizer-state
 // advance for the next step: one launch where the train step used to end with two.
+// (W = true, Extra = const float* clip, srfrd_optim_opts opts: srfrd_adamw_pack_step - clip coefficient, decay, and the advance
+// under the schedule in `opts`.)
+template <bool W, class... Extra>
 __global__ void __launch_bounds__(512) adam_pack_kernel(float* __restrict__ param, float* __restrict__ grad, float* __restrict__ m,
                                                        float* __restrict__ v, int64_t n, int64_t n_tab, int64_t n_zero, float b1,
                                                        float b2, float eps, uint32_t* __restrict__ state,
                                                        const float* __restrict__ stats, Dims dims, float* __restrict__ packed,
                                                        double lr, double b1d, double b2d, uint16_t* __restrict__ shadow,
-                                                       int64_t n_shadow) {
+                                                       int64_t n_shadow, Extra... extra) {
   const float step_size = ((const float*)state)[4];
   const float bc2s = ((const float*)state)[5];
-  const float gscale = stats ? 1.0f / stats[2] : 1.0f;
+  float gscale = stats ? 1.0f / stats[2] : 1.0f;
+  float decay = 1.0f;
+  if constexpr (W) {
+    const float* __restrict__ clip = first_arg(extra...);
+    gscale = gscale * (clip ? clip[1] : 1.0f);
+    decay = ((const float*)state)[7];
+  }
   const int64_t nvec = n >> 2;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t w_lo = n_tab + dims.blk0;          // first dense index that can be an encoder weight
@@ -224,10 +266,10 @@ __global__ void __launch_bounds__(512) adam_pack_kernel(float* __restrict__ para
     float4 g4 = *reinterpret_cast<const float4*>(grad + i);
     float4 m4 = *reinterpret_cast<float4*>(m + i);
     float4 v4 = *reinterpret_cast<float4*>(v + i);
-    adam_one(p4.x, g4.x * gscale, m4.x, v4.x, b1, b2, eps, step_size, bc2s);
-    adam_one(p4.y, g4.y * gscale, m4.y, v4.y, b1, b2, eps, step_size, bc2s);
-    adam_one(p4.z, g4.z * gscale, m4.z, v4.z, b1, b2, eps, step_size, bc2s);
-    adam_one(p4.w, g4.w * gscale, m4.w, v4.w, b1, b2, eps, step_size, bc2s);
+    adam_one<W>(p4.x, g4.x * gscale, m4.x, v4.x, b1, b2, eps, step_size, bc2s, decay);
+    adam_one<W>(p4.y, g4.y * gscale, m4.y, v4.y, b1, b2, eps, step_size, bc2s, decay);
+    adam_one<W>(p4.z, g4.z * gscale, m4.z, v4.z, b1, b2, eps, step_size, bc2s, decay);
+    adam_one<W>(p4.w, g4.w * gscale, m4.w, v4.w, b1, b2, eps, step_size, bc2s, decay);
     *reinterpret_cast<float4*>(param + i) = p4;
     *reinterpret_cast<float4*>(m + i) = m4;
     *reinterpret_cast<float4*>(v + i) = v4;
@@ -243,7 +285,7 @@ __global__ void __launch_bounds__(512) adam_pack_kernel(float* __restrict__ para
   }
   for (int64_t i = (nvec << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {     // scalar tail
     float p = param[i], mm = m[i], vv = v[i];
-    adam_one(p, grad[i] * gscale, mm, vv, b1, b2, eps, step_size, bc2s);
+    adam_one<W>(p, grad[i] * gscale, mm, vv, b1, b2, eps, step_size, bc2s, decay);
     param[i] = p; m[i] = mm; v[i] = vv;
     if (i < n_zero) grad[i] = 0.f;
     if (shadow != nullptr && i < n_shadow) shadow[i] = f32_to_bf16(p);
@@ -262,7 +304,8 @@ __global__ void __launch_bounds__(512) adam_pack_kernel(float* __restrict__ para
       state[8 + shard] = 0;
       if (atomicAdd(&state[6], 1u) == n_shards - 1u) {
         state[6] = 0;
-        step_advance(state, lr, b1d, b2d);
+        if constexpr (W) step_advance_sched(state, second_arg(extra...));      // (lr, b1d, b2d: inside its opts too)
+        else step_advance(state, lr, b1d, b2d);
       }
     }
   }
@@ -342,6 +385,69 @@ __global__ void __launch_bounds__(256) l2_apply_kernel(float* __restrict__ grad,
   }
 }
 
+// ---- global L2 norm of the flat gradient + clip_grad_norm_'s coefficient (srfrd_grad_norm).
+// Two kernels behind the one entry point, as srfrd_l2_norms, not one kernel with a last-block ticket: the ticket form would
+// publish the partials to another block, so every block would pay an agent-scope release (a write-back of its XCD's dirty L2
+// lines, right behind a backward that left the whole gradient dirty) and the last one an acquire; the kernel boundary gives
+// the same visibility for one dependent launch (~1.5 us inside the graph) and leaves nothing to get wrong.
+// Pass A: workgroup g sums the squares of float4s [g share4, (g + 1) share4) in fp64 - the square of a float is exact in a
+// double, so only the additions round, at 2^-53.  Four independent accumulators per thread (four 16-byte loads in flight), a
+// fixed in-block tree.
+__device__ __forceinline__ double sq4(const float4& a) {
+  const double x = a.x, y = a.y, z = a.z, w = a.w;
+  return (x * x + y * y) + (z * z + w * w);
+}
+
+__global__ void __launch_bounds__(256) grad_norm_partial_kernel(const float* __restrict__ grad, int64_t n4, int64_t share4,
+                                                               double* __restrict__ partial) {
+  __shared__ double red[4];
+  const float4* __restrict__ g4 = reinterpret_cast<const float4*>(grad);
+  const int64_t lo = (int64_t)blockIdx.x * share4;
+  const int64_t hi = lo + share4 < n4 ? lo + share4 : n4;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  int64_t q = lo + threadIdx.x;
+  for (; q + 768 < hi; q += 1024) {
+    const float4 a = g4[q], b = g4[q + 256], c = g4[q + 512], d = g4[q + 768];
+    s0 += sq4(a); s1 += sq4(b); s2 += sq4(c); s3 += sq4(d);
+  }
+  for (; q < hi; q += 256) s0 += sq4(g4[q]);
+  double s = (s0 + s1) + (s2 + s3);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// Pass B (one wave): lane l adds partials [16 l, 16 l + 16) in index order, lane 0 the 64 lane sums in lane order and the
+// n % 4 tail elements in index order; then the norm and the coefficient.
+__global__ void __launch_bounds__(64) grad_norm_finish_kernel(const double* __restrict__ partial, int n_part,
+                                                             const float* __restrict__ grad, int64_t n,
+                                                             const float* __restrict__ stats, double max_norm,
+                                                             float* __restrict__ out) {
+  __shared__ double lane_sum[64];
+  constexpr int kPer = SRFRD_GRAD_NORM_PARTIALS / 64;
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    const int g = (int)threadIdx.x * kPer + k;
+    if (g < n_part) s += partial[g];
+  }
+  lane_sum[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double total = 0.0;
+  for (int l = 0; l < 64; ++l) total += lane_sum[l];
+  for (int64_t i = n & ~3ll; i < n; ++i) { const double x = grad[i]; total += x * x; }
+  const double norm = stats ? sqrt(total) / (double)stats[2] : sqrt(total);
+  const float nf = (float)norm;
+  // clip_grad_norm_: max_norm / (norm + 1e-6) clamped to at most 1.  Written with comparisons, not fmin: a NaN norm must
+  // give a NaN coefficient (fmin would answer 1).
+  const double c = max_norm / ((double)nf + 1e-6);
+  out[0] = nf;
+  out[1] = c < 1.0 ? (float)c : (c >= 1.0 ? 1.0f : __builtin_nanf(""));
+}
+
 __global__ void loss_finalize_kernel(const float* stats, float* loss_out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) loss_out[0] = stats[0] / stats[2] + stats[1] / stats[2];
 }
@@ -380,6 +486,35 @@ extern "C" int srfrd_step_begin(uint32_t* state, double lr, double beta1, double
   return (int)hipGetLastError();
 }
 
+// every refusal of a schedule / decay description (negated comparisons: a NaN fails them too)
+static bool optim_opts_ok(const srfrd_optim_opts* o) {
+  if (!o) return false;
+  if (!(o->weight_decay >= 0.0) || !(o->final_ratio >= 0.0 && o->final_ratio <= 1.0) || o->warmup_steps < 0) return false;
+  if (o->schedule != SRFRD_SCHED_CONSTANT && o->schedule != SRFRD_SCHED_LINEAR && o->schedule != SRFRD_SCHED_COSINE) return false;
+  if (o->schedule != SRFRD_SCHED_CONSTANT && o->total_steps < o->warmup_steps) return false;
+  return true;
+}
+
+extern "C" int srfrd_step_begin_sched(uint32_t* state, const srfrd_optim_opts* opts, void* stream) {
+  if (!state || !optim_opts_ok(opts)) return SRFRD_E_ARG;
+  hipLaunchKernelGGL(step_begin_sched_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, *opts);
+  return (int)hipGetLastError();
+}
+
+extern "C" int srfrd_grad_norm(const float* grad, int64_t n, const float* stats, double max_norm, double* partial, float* out,
+                               void* stream) {
+  if (!grad || !partial || !out || n <= 0 || ((uintptr_t)grad & 15) || !(max_norm > 0.0)) return SRFRD_E_ARG;
+  const int64_t n4 = n >> 2;
+  int64_t share4 = (n4 + SRFRD_GRAD_NORM_PARTIALS - 1) / SRFRD_GRAD_NORM_PARTIALS;
+  if (share4 < SRFRD_GRAD_NORM_SHARE / 4) share4 = SRFRD_GRAD_NORM_SHARE / 4;
+  const int n_part = (int)((n4 + share4 - 1) / share4);          // <= SRFRD_GRAD_NORM_PARTIALS; 0 for n < 4
+  if (n_part > 0)
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(n_part), dim3(256), 0, (hipStream_t)stream, grad, n4, share4, partial);
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, n_part, grad, n, stats, max_norm,
+                     out);
+  return (int)hipGetLastError();
+}
+
 extern "C" int srfrd_table_to_bf16(const float* src, int64_t n, uint16_t* out, void* stream) {
   if (!src || !out || n <= 0) return SRFRD_E_ARG;
   int64_t grid = ((n >> 2) + 1 + 255) / 256;
@@ -388,23 +523,46 @@ extern "C" int srfrd_table_to_bf16(const float* src, int64_t n, uint16_t* out, v
   return (int)hipGetLastError();
 }
 
-extern "C" int srfrd_adam_step(float* param, float* grad, float* m, float* v, int64_t n, int64_t i0, int64_t i1,
-                               int64_t n_zero, double beta1, double beta2, double eps, const uint32_t* state,
-                               const float* stats, uint16_t* table_bf16, int64_t n_table, void* stream) {
+// srfrd_adam_step / srfrd_adamw_step: the same checks, grid and arguments; W adds the clip pointer
+template <bool W>
+static int adam_step_launch(float* param, float* grad, float* m, float* v, int64_t n, int64_t i0, int64_t i1, int64_t n_zero,
+                            double beta1, double beta2, double eps, const uint32_t* state, const float* stats, const float* clip,
+                            uint16_t* table_bf16, int64_t n_table, void* stream) {
   if (!param || !grad || !m || !v || !state || n <= 0 || i0 < 0 || i1 > n || i0 > i1) return SRFRD_E_ARG;
   if (i0 == i1) return 0;                 // an empty slice launches nothing, wherever it sits (shard_bounds' last ranks)
   if (i0 & 3) return SRFRD_E_ARG;
   const int64_t nvec = ((i1 - i0) >> 2) + 1;
   int64_t grid = (nvec + 255) / 256;
   if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(adam_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, i0, i1, n_zero,
-                     (float)beta1, (float)beta2, (float)eps, state, stats, table_bf16, table_bf16 ? n_table : 0);
+  if constexpr (W)
+    hipLaunchKernelGGL((adam_kernel<true, const float*>), dim3((int)grid), dim3(256), 0, (hipStream_t)stream, param, grad, m, v,
+                       i0, i1, n_zero, (float)beta1, (float)beta2, (float)eps, state, stats, table_bf16,
+                       table_bf16 ? n_table : 0, clip);
+  else
+    hipLaunchKernelGGL(adam_kernel<false>, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, param, grad, m, v, i0, i1, n_zero,
+                       (float)beta1, (float)beta2, (float)eps, state, stats, table_bf16, table_bf16 ? n_table : 0);
   return (int)hipGetLastError();
 }
 
-extern "C" int srfrd_adam_pack_step(const srfrd_layout* lay, float* param, float* grad, float* m, float* v, int64_t n,
-                                    int64_t n_table_pad, int64_t n_zero, double lr, double beta1, double beta2, double eps,
-                                    uint32_t* state, const float* stats, float* packed, uint16_t* table_bf16, void* stream) {
+extern "C" int srfrd_adam_step(float* param, float* grad, float* m, float* v, int64_t n, int64_t i0, int64_t i1,
+                               int64_t n_zero, double beta1, double beta2, double eps, const uint32_t* state,
+                               const float* stats, uint16_t* table_bf16, int64_t n_table, void* stream) {
+  return adam_step_launch<false>(param, grad, m, v, n, i0, i1, n_zero, beta1, beta2, eps, state, stats, nullptr, table_bf16,
+                                 n_table, stream);
+}
+
+extern "C" int srfrd_adamw_step(float* param, float* grad, float* m, float* v, int64_t n, int64_t i0, int64_t i1,
+                                int64_t n_zero, double beta1, double beta2, double eps, const uint32_t* state,
+                                const float* stats, const float* clip, uint16_t* table_bf16, int64_t n_table, void* stream) {
+  return adam_step_launch<true>(param, grad, m, v, n, i0, i1, n_zero, beta1, beta2, eps, state, stats, clip, table_bf16, n_table,
+                                stream);
+}
+
+// srfrd_adam_pack_step / srfrd_adamw_pack_step: the same checks, layout description and grid
+template <bool W>
+static int adam_pack_launch(const srfrd_layout* lay, float* param, float* grad, float* m, float* v, int64_t n,
+                            int64_t n_table_pad, int64_t n_zero, const srfrd_optim_opts& o, double eps, uint32_t* state,
+                            const float* stats, const float* clip, float* packed, uint16_t* table_bf16, void* stream) {
   if (!lay || !param || !grad || !m || !v || !state || !packed || n <= 0 || n_table_pad < 0 || (n_table_pad & 3) ||
       n_table_pad + lay->n_dense > n)
     return SRFRD_E_ARG;
@@ -422,10 +580,33 @@ extern "C" int srfrd_adam_pack_step(const srfrd_layout* lay, float* param, float
   // 22.2 / 19.3 / 21.1 / 22.0 / 26.3 / 25.8 us; 1 M-item table 1.440 -> 1.431 ms per step)
   int64_t grid = ((n >> 2) + 1 + 511) / 512;
   if (grid > 768) grid = 768;
-  hipLaunchKernelGGL(adam_pack_kernel, dim3((int)grid), dim3(512), 0, (hipStream_t)stream, param, grad, m, v, n, n_table_pad,
-                     n_zero, (float)beta1, (float)beta2, (float)eps, state, stats, d, packed, lr, beta1, beta2, table_bf16,
-                     table_bf16 ? lay->n_table : 0);
+  if constexpr (W)
+    hipLaunchKernelGGL((adam_pack_kernel<true, const float*, srfrd_optim_opts>), dim3((int)grid), dim3(512), 0,
+                       (hipStream_t)stream, param, grad, m, v, n, n_table_pad, n_zero, (float)o.beta1, (float)o.beta2, (float)eps,
+                       state, stats, d, packed, o.lr, o.beta1, o.beta2, table_bf16, table_bf16 ? lay->n_table : 0, clip, o);
+  else
+    hipLaunchKernelGGL(adam_pack_kernel<false>, dim3((int)grid), dim3(512), 0, (hipStream_t)stream, param, grad, m, v, n, n_table_pad,
+                       n_zero, (float)o.beta1, (float)o.beta2, (float)eps, state, stats, d, packed, o.lr, o.beta1, o.beta2,
+                       table_bf16, table_bf16 ? lay->n_table : 0);
   return (int)hipGetLastError();
+}
+
+extern "C" int srfrd_adam_pack_step(const srfrd_layout* lay, float* param, float* grad, float* m, float* v, int64_t n,
+                                    int64_t n_table_pad, int64_t n_zero, double lr, double beta1, double beta2, double eps,
+                                    uint32_t* state, const float* stats, float* packed, uint16_t* table_bf16, void* stream) {
+  srfrd_optim_opts o = {};
+  o.lr = lr; o.beta1 = beta1; o.beta2 = beta2;
+  return adam_pack_launch<false>(lay, param, grad, m, v, n, n_table_pad, n_zero, o, eps, state, stats, nullptr, packed, table_bf16,
+                                 stream);
+}
+
+extern "C" int srfrd_adamw_pack_step(const srfrd_layout* lay, float* param, float* grad, float* m, float* v, int64_t n,
+                                     int64_t n_table_pad, int64_t n_zero, const srfrd_optim_opts* opts, double eps,
+                                     uint32_t* state, const float* stats, const float* clip, float* packed,
+                                     uint16_t* table_bf16, void* stream) {
+  if (!optim_opts_ok(opts)) return SRFRD_E_ARG;
+  return adam_pack_launch<true>(lay, param, grad, m, v, n, n_table_pad, n_zero, *opts, eps, state, stats, clip, packed, table_bf16,
+                                stream);
 }
 
 extern "C" int srfrd_l2_norms(const float* param, const int64_t* seg_off, const int64_t* seg_len, int n_seg, int64_t n_table_pad,

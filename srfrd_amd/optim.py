@@ -15,7 +15,11 @@ comes out bit-unchanged: a parameter and its two moments per held tensor and ste
 step when the table is frozen (0.6 GB of traffic at 1 M x 50).  Like torch, every parameter keeps its own step count (the
 bias corrections follow it); parameters whose counts differ are stepped by one launch per count.  ``state_dict()`` /
 ``load_state_dict()`` use torch.optim.Adam's own format, so a run can move between the two optimizers (and
-``FusedTrainer``)."""
+``FusedTrainer``).
+
+`srfrd_amd.AdamW` is the same optimizer with torch.optim.AdamW's decoupled weight decay: it steps through ``srfrd_adamw_step``
+behind ``srfrd_step_begin_sched`` at the group's current ``lr`` (a constant schedule: torch's LR schedulers keep working, they
+rewrite ``lr`` between steps)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -128,7 +132,6 @@ class Adam(torch.optim.Optimizer):
             self._resolve()             # (first step, or the model re-flattened its parameters)
             self._p0, self._pl = ps[0].data_ptr(), ps[-1].data_ptr()
         g = self.param_groups[0]
-        lr, (b1, b2), eps = g["lr"], g["betas"], g["eps"]
         groups = {}                     # step count -> the listed parameters with a gradient that have taken that many steps
         for i, (p, off, k) in enumerate(self._spans):
             if p.grad is not None:
@@ -151,9 +154,7 @@ class Adam(torch.optim.Optimizer):
             if count != self._steps:
                 self._dev_state[0] = count
             # t += 1 and the bias corrections in double precision on the device, then the step over the whole vector
-            check(L_.srfrd_step_begin(ptr(self._dev_state), lr, b1, b2, st), "srfrd_step_begin")
-            check(L_.srfrd_adam_step(ptr(self._flat), gptr, ptr(self._m), ptr(self._v), n, 0, n, 0, b1, b2, eps,
-                                     ptr(self._dev_state), None, None, 0, st), "srfrd_adam_step")
+            self._launch(L_, gptr, n, g, st)
             self._steps = count + 1
             for lo, hi, p, m, v in held:
                 self._flat[lo:hi].copy_(p); self._m[lo:hi].copy_(m); self._v[lo:hi].copy_(v)
@@ -162,6 +163,20 @@ class Adam(torch.optim.Optimizer):
                 self._counts[i] += 1
         del keep
         return loss
+
+    def _launch(self, L_, gptr, n, g, st):
+        lr, (b1, b2), eps = g["lr"], g["betas"], g["eps"]
+        check(L_.srfrd_step_begin(ptr(self._dev_state), lr, b1, b2, st), "srfrd_step_begin")
+        check(L_.srfrd_adam_step(ptr(self._flat), gptr, ptr(self._m), ptr(self._v), n, 0, n, 0, b1, b2, eps,
+                                 ptr(self._dev_state), None, None, 0, st), "srfrd_adam_step")
+
+    def _decay_of(self, g):
+        """what state_dict()'s param group says about the decay"""
+        return {}
+
+    def _check_loaded_group(self, group):
+        if any(group.get(k) for k in ("weight_decay", "amsgrad", "maximize")):
+            raise ValueError("srfrd_amd.Adam implements plain Adam (no weight decay / amsgrad / maximize)")
 
     # ---- torch.optim.Adam's state format ---------------------------------------------------------------------------------
     def state_dict(self):
@@ -179,12 +194,12 @@ class Adam(torch.optim.Optimizer):
         group = {"lr": g["lr"], "betas": g["betas"], "eps": g["eps"], "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
                  "params": list(range(len(ps)))}
+        group.update(self._decay_of(g))
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
         group = sd["param_groups"][0]
-        if any(group.get(k) for k in ("weight_decay", "amsgrad", "maximize")):
-            raise ValueError("srfrd_amd.Adam implements plain Adam (no weight decay / amsgrad / maximize)")
+        self._check_loaded_group(group)
         g = self.param_groups[0]
         g["lr"], g["betas"], g["eps"] = float(group["lr"]), (float(group["betas"][0]), float(group["betas"][1])), float(group["eps"])
         # Kept until the next _resolve() scatters it into the moments: the parameters become views of the flat vector only
@@ -192,3 +207,39 @@ class Adam(torch.optim.Optimizer):
         self._loaded = {int(i): {"step": s["step"], "exp_avg": s["exp_avg"].detach().clone(), "exp_avg_sq": s["exp_avg_sq"].detach().clone()}
                         for i, s in sd["state"].items()}
         self._spans = None
+
+
+class AdamW(Adam):
+    """``srfrd_amd.Adam`` with torch.optim.AdamW's decoupled weight decay: ``p *= 1 - lr * weight_decay`` ahead of the Adam
+    update, over the whole flat vector as one group (``srfrd_adamw_step``)."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 amsgrad: bool = False):
+        if amsgrad:
+            raise ValueError("srfrd_amd.AdamW: no amsgrad")
+        if not (float(weight_decay) >= 0.0) or float(weight_decay) == float("inf"):
+            raise ValueError(f"weight_decay must be finite and >= 0 (got {weight_decay})")
+        super().__init__(params, lr, betas, eps)
+        self.param_groups[0]["weight_decay"] = float(weight_decay)
+
+    def _launch(self, L_, gptr, n, g, st):
+        # a constant schedule at the group's CURRENT rate: state[4] = lr / bc1, state[7] = 1 - lr * weight_decay
+        opts = _lib.OptimOpts(float(g["lr"]), g["betas"][0], g["betas"][1], float(g["weight_decay"]), 0.0, 0, 0,
+                              _lib.SCHEDULES["constant"], 0)
+        check(L_.srfrd_step_begin_sched(ptr(self._dev_state), C.byref(opts), st), "srfrd_step_begin_sched")
+        check(L_.srfrd_adamw_step(ptr(self._flat), gptr, ptr(self._m), ptr(self._v), n, 0, n, 0, g["betas"][0], g["betas"][1],
+                                  g["eps"], ptr(self._dev_state), None, None, None, 0, st), "srfrd_adamw_step")
+
+    def _decay_of(self, g):
+        return {"weight_decay": g["weight_decay"], "decoupled_weight_decay": True}
+
+    def _check_loaded_group(self, group):
+        if any(group.get(k) for k in ("amsgrad", "maximize")):
+            raise ValueError("srfrd_amd.AdamW: no amsgrad / maximize")
+        if group.get("weight_decay") and group.get("decoupled_weight_decay") is False:
+            raise ValueError("srfrd_amd.AdamW implements decoupled weight decay only: this state was saved under the coupled, "
+                             "L2-style weight_decay of torch.optim.Adam")
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        self.param_groups[0]["weight_decay"] = float(sd["param_groups"][0].get("weight_decay") or 0.0)

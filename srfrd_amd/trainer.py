@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import math
 import os
 
 import torch
@@ -106,6 +107,71 @@ def _loss_config(model, loss, num_negatives, neg_counts, neg_alpha, process_grou
     return q
 
 
+LR_SCHEDULES = tuple(_lib.SCHEDULES)
+
+
+def lr_at(step: int, lr: float, schedule: str = "constant", warmup_steps: int = 0, total_steps: int | None = None,
+          final_lr_ratio: float = 0.0) -> float:
+    """The learning rate of the 1-based ``step``: the host mirror, in Python doubles, of the one formula the device evaluates
+    (include/srfrd_hip.h, srfrd_step_begin_sched): linear warmup ``step / warmup_steps``, then ``u = min(1, (step - warmup) /
+    max(1, total - warmup))`` and "constant": 1, "linear": ``1 - (1 - r) u``, "cosine": ``r + (1 - r) (1 + cos(pi u)) / 2``,
+    ``r = final_lr_ratio`` - which the factor keeps past ``total_steps``."""
+    if schedule not in _lib.SCHEDULES:
+        raise ValueError(f"lr_schedule must be one of {LR_SCHEDULES} (got {schedule!r})")
+    if int(step) < 1:
+        raise ValueError(f"step counts from 1 (got {step})")
+    t, w = float(int(step)), float(int(warmup_steps))
+    if t <= w:
+        return float(lr) * (t / w)
+    if schedule == "constant":
+        return float(lr)
+    if total_steps is None:
+        raise ValueError(f"lr_schedule={schedule!r} decays towards total_steps: give it")
+    u = min(1.0, (t - w) / max(1.0, float(int(total_steps) - int(warmup_steps))))
+    r = float(final_lr_ratio)
+    if schedule == "linear":
+        return float(lr) * (1.0 - (1.0 - r) * u)
+    return float(lr) * (r + (1.0 - r) * (0.5 * (1.0 + math.cos(math.pi * u))))
+
+
+def _optim_config(lr, betas, weight_decay=0.0, max_grad_norm=None, lr_schedule="constant", warmup_steps=0, total_steps=None,
+                  final_lr_ratio=0.0, process_group=None):
+    """The refusals of FusedTrainer's optimizer options, made on the host before anything is allocated; -> (opts, max_norm):
+    ``opts`` the ``_lib.OptimOpts`` of the scheduled entry points, or None where every option is neutral (no decay, no
+    clipping, a constant rate without warmup) and the step is the plain Adam step, launch for launch; ``max_norm`` a float or
+    None."""
+    if lr_schedule not in _lib.SCHEDULES:
+        raise ValueError(f"lr_schedule must be one of {LR_SCHEDULES} (got {lr_schedule!r})")
+    wd = float(weight_decay)
+    if not (wd >= 0.0) or wd == float("inf"):
+        raise ValueError(f"weight_decay must be finite and >= 0 (got {weight_decay})")
+    max_norm = None if max_grad_norm is None else float(max_grad_norm)
+    if max_norm is not None and not (max_norm > 0.0):
+        raise ValueError(f"max_grad_norm must be > 0, or None for no clipping (got {max_grad_norm})")
+    w = int(warmup_steps)
+    if w < 0 or w != warmup_steps:
+        raise ValueError(f"warmup_steps must be a whole number >= 0 (got {warmup_steps})")
+    r = float(final_lr_ratio)
+    if not (0.0 <= r <= 1.0):
+        raise ValueError(f"final_lr_ratio must lie in [0, 1] (got {final_lr_ratio})")
+    decays = lr_schedule != "constant"
+    if decays:
+        if total_steps is None:
+            raise ValueError(f"lr_schedule={lr_schedule!r} decays towards total_steps: give it")
+        if int(total_steps) != total_steps or int(total_steps) < w:
+            raise ValueError(f"total_steps must be a whole number >= warmup_steps = {w} (got {total_steps})")
+    if wd == 0.0 and max_norm is None and not decays and w == 0:
+        return None, None
+    if exchange_active(process_group):
+        raise ValueError("weight_decay / max_grad_norm / lr_schedule / warmup_steps train on a single rank: the sharded step "
+                         "advances the optimizer state inside srfrd_pack_weights and owns a slice of the gradient only, so it "
+                         "needs a variant of its own and a collective for the norm (DESIGN section 19); the all-reduce form "
+                         "waits for the same work")
+    opts = _lib.OptimOpts(float(lr), float(betas[0]), float(betas[1]), wd, r, w, int(total_steps) if decays else 0,
+                          _lib.SCHEDULES[lr_schedule], 0)
+    return opts, max_norm
+
+
 class FusedTrainer:
     """Owns optimizer state and step buffers for one model on one GPU (one rank of a DP job)."""
 
@@ -113,7 +179,9 @@ class FusedTrainer:
                  eps: float = 1e-8, l2_emb: float = 0.0, seed: int = 42, process_group=None, use_graph: bool = True,
                  slots: int = 1, exchange: str = "sharded", deterministic: bool = False, shadow_gather: bool = False,
                  loss: str = "bce", num_negatives: int = 1024, neg_counts=None, neg_alpha: float = 1.0,
-                 logq_correction: bool = True, remove_accidental_hits: bool = True, gbce_beta: float = 1.0):
+                 logq_correction: bool = True, remove_accidental_hits: bool = True, gbce_beta: float = 1.0,
+                 weight_decay: float = 0.0, max_grad_norm: float | None = None, lr_schedule: str = "constant",
+                 warmup_steps: int = 0, total_steps: int | None = None, final_lr_ratio: float = 0.0):
         """``shadow_gather`` (sharded exchange over a bf16 item-table shadow, ``model.use_bf16_table()``; SURVEY 8e's alternative
         for BASELINE configs[4]): the fp32 master of an item row and its Adam moments live on the OWNER rank only; after the
         sharded Adam step the all-gather carries the bf16 SHADOW of the table (2 bytes per element: 90 MB instead of 180 MB at
@@ -137,7 +205,15 @@ class FusedTrainer:
         batch data: ``step(..., negative_ids (B, L, K), nrs, log_q=None)``, or a producer fills ``neg_ring[s]`` /
         ``log_q_ring[s]`` beside ``ids_ring[s]`` (``DeviceSampler(num_negatives=K).next_batch(packed=True, out=..., neg_out=...,
         log_q_out=...)``) and calls ``step_slot(s)``.  ``logq_correction=False``, and "gbce" always, pass no log-Q to the head.
-        Single rank, fp32 table, always bitwise reproducible."""
+        Single rank, fp32 table, always bitwise reproducible.
+        ``weight_decay`` (decoupled, torch.optim.AdamW's: the whole flat vector is one group), ``max_grad_norm``
+        (``torch.nn.utils.clip_grad_norm_`` over the whole gradient, ``l2_emb`` term included; ``float("inf")`` only measures),
+        ``lr_schedule`` ("constant" | "linear" | "cosine") with ``warmup_steps``, ``total_steps`` and ``final_lr_ratio``
+        (``srfrd_amd.lr_at`` is the formula): all three live on the device, inside the captured step -
+        ``grad_norm`` and ``next_lr`` show them.  Single rank.  With every one at its default the step issues exactly the
+        launches of plain Adam."""
+        self.opts, self.max_norm = _optim_config(lr, betas, weight_decay, max_grad_norm, lr_schedule, warmup_steps, total_steps,
+                                                 final_lr_ratio, process_group)
         q = _loss_config(model, loss, num_negatives, neg_counts, neg_alpha, process_group, gbce_beta,
                          int(batch_size) * int(seq_len or model.layout.max_len))
         self.model = model
@@ -203,6 +279,9 @@ class FusedTrainer:
             self.l2_dense = torch.zeros(self.n_flat - self.n_tab, **f32)
         self.state = torch.zeros(32, device=dev, dtype=torch.int32)
         self.state[1] = int(seed) & 0x7FFFFFFF
+        if self.max_norm is not None:        # srfrd_grad_norm's workspace and its {norm, coefficient}
+            self.norm_partial = torch.zeros(_lib.GRAD_NORM_PARTIALS, device=dev, dtype=torch.float64)
+            self.clip = torch.zeros(2, **f32)
         self.deterministic = bool(deterministic)
         self.loss_kind = loss
         self.sampled = loss == "sampled_softmax"
@@ -245,8 +324,7 @@ class FusedTrainer:
         if loss != "bce":
             self._init_ce(q, num_negatives, logq_correction, remove_accidental_hits, gbce_beta)
         self.packed = model.pack_weights()
-        check(_lib.lib().srfrd_step_begin(ptr(self.state), self.lr, self.betas[0], self.betas[1],
-                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)), "srfrd_step_begin")
+        self._step_begin()
         self.use_graph = bool(use_graph)
         self._program = step_program(self.mode, self.token)
         self._graphs = None              # (stages, their graphs) once captured: `captured`
@@ -348,9 +426,28 @@ class FusedTrainer:
             return self.log_q_ring[self._last_slot].detach().clone()
         return self._log_q.detach().clone() if self.sampled else None
 
+    @property
+    def grad_norm(self):
+        """device scalar (a view): the last step's global L2 norm of the mean-loss gradient, the ``l2_emb`` term included,
+        before clipping (None without ``max_grad_norm``; ``float("inf")`` measures without clipping)"""
+        return self.clip[0] if self.max_norm is not None else None
+
+    @property
+    def next_lr(self):
+        """device scalar (a view): the learning rate the next step will use (None where no option is set: ``lr`` then)"""
+        return self.state[3:4].view(torch.float32)[0] if self.opts is not None else None
+
     # ---- pieces -------------------------------------------------------------------------------
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def _step_begin(self):
+        """state words of the step t = state[0] + 1: plain, or (an option set) under the schedule"""
+        if self.opts is None:
+            check(_lib.lib().srfrd_step_begin(ptr(self.state), self.lr, self.betas[0], self.betas[1], self._stream()),
+                  "srfrd_step_begin")
+        else:
+            check(_lib.lib().srfrd_step_begin_sched(ptr(self.state), C.byref(self.opts), self._stream()), "srfrd_step_begin_sched")
 
     def _dense_ptr(self, base):
         return C.c_void_p(base.data_ptr() + 4 * self.n_tab)
@@ -520,14 +617,26 @@ class FusedTrainer:
         self._enqueue_update()
 
     def _enqueue_update(self):
-        """single rank / all-reduce form: Adam over the whole flat vector + re-pack + optimizer-state advance, one launch"""
+        """single rank / all-reduce form: Adam over the whole flat vector + re-pack + optimizer-state advance, one launch
+        (an optimizer option set: [the gradient norm, then] the AdamW form of that launch)"""
         L_, st = _lib.lib(), self._stream()
         if self.l2 != 0.0:
             self._enqueue_l2_apply(ptr(self.grad), self.flat, 0, self.n_flat)
-        check(L_.srfrd_adam_pack_step(C.byref(self.lay), ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v),
-                                      self.n_flat, self.n_tab, self.n_tab, self.lr, self.betas[0], self.betas[1], self.eps,
-                                      ptr(self.state), ptr(self.stats), ptr(self.packed), ptr(self.model._table16), st),
-              "srfrd_adam_pack_step")
+        if self.opts is None:
+            check(L_.srfrd_adam_pack_step(C.byref(self.lay), ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v),
+                                          self.n_flat, self.n_tab, self.n_tab, self.lr, self.betas[0], self.betas[1], self.eps,
+                                          ptr(self.state), ptr(self.stats), ptr(self.packed), ptr(self.model._table16), st),
+                  "srfrd_adam_pack_step")
+        else:
+            # the options (DESIGN section 19): the gradient's global norm and clip coefficient, measured behind the l2_emb term,
+            # then Adam with the coefficient in its gradient scale, the decay factor of state[7], and the scheduled advance
+            if self.max_norm is not None:
+                check(L_.srfrd_grad_norm(ptr(self.grad), self.n_flat, ptr(self.stats), self.max_norm, ptr(self.norm_partial),
+                                         ptr(self.clip), st), "srfrd_grad_norm")
+            check(L_.srfrd_adamw_pack_step(C.byref(self.lay), ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v),
+                                           self.n_flat, self.n_tab, self.n_tab, C.byref(self.opts), self.eps, ptr(self.state),
+                                           ptr(self.stats), ptr(self.clip) if self.max_norm is not None else None,
+                                           ptr(self.packed), ptr(self.model._table16), st), "srfrd_adamw_pack_step")
         if self.mode != "single" or self.loss_kind != "bce":      # (single-rank BCE: the slab reduction wrote the loss)
             check(L_.srfrd_loss_finalize(ptr(self.stats), ptr(self.loss), st), "srfrd_loss_finalize")
         if self.l2 != 0.0:
@@ -624,6 +733,8 @@ class FusedTrainer:
         (and by the ``restore`` it yields), with what the model derives from the parameters"""
         torch.cuda.synchronize()
         keep = [self.flat, self.m, self.v, self.state, self.grad, self.stats] + ([self.shadow_pad] if self.shadow_gather else [])
+        if self.max_norm is not None:
+            keep.append(self.clip)           # (`grad_norm` keeps showing the last real step)
         snap = [t.clone() for t in keep]
 
         def restore():
@@ -740,10 +851,16 @@ class FusedTrainer:
             o, n = off[id(p)], p.numel()
             state[i] = {"step": torch.tensor(float(self.steps_done)),
                         "exp_avg": m[o:o + n].view(p.shape).clone(), "exp_avg_sq": v[o:o + n].view(p.shape).clone()}
-        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "decoupled_weight_decay": False,
-                 "params": list(range(len(params)))}
+        wd = self.opts.weight_decay if self.opts is not None else 0.0
+        group = {"lr": self.lr, "betas": self.betas, "eps": self.eps, "weight_decay": wd if wd else 0, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": bool(wd), "params": list(range(len(params)))}
         extra = {"seed": int(self.state[1].item()), "steps_done": int(self.steps_done)}
+        if self.opts is not None:        # (`lr` above stays the BASE rate: the schedule maps it to the step's)
+            o = self.opts
+            extra["schedule"] = {"kind": LR_SCHEDULES[o.schedule], "warmup_steps": int(o.warmup_steps),
+                                 "total_steps": int(o.total_steps) if o.schedule else None, "final_lr_ratio": float(o.final_ratio)}
+            extra["max_grad_norm"] = self.max_norm
         if self.loss_kind != "bce":
             extra["loss"] = self._loss_signature()
         return {"state": state, "param_groups": [group], "srfrd": extra}
@@ -759,13 +876,21 @@ class FusedTrainer:
                 "logq_correction": self.logq_correction, "remove_accidental_hits": self.remove_hits}
 
     def load_state_dict(self, sd):
-        """Inverse of state_dict(); also takes the state_dict of a torch.optim.Adam that stepped the same model's
-        parameters (the module-level path), so a run can move between the two.  Hyper-parameters come from the dict."""
+        """Inverse of state_dict(); also takes the state_dict of a torch.optim.Adam / AdamW (or srfrd_amd.Adam / AdamW) that
+        stepped the same model's parameters (the module-level path), so a run can move between the two.  Hyper-parameters come
+        from the dict: ``lr`` is the BASE rate, ``weight_decay`` is taken with ``decoupled_weight_decay`` only (the coupled,
+        L2-style decay of torch.optim.Adam is refused), and ``"srfrd"`` carries the schedule and ``max_grad_norm``; where it
+        carries neither (a torch optimizer's state) this trainer keeps its own.  The state of a torch LR scheduler is NOT
+        translated: give the trainer the schedule's closed form instead.  The state words are recomputed for t = steps_done + 1
+        under the schedule, so a resumed run is bitwise the uninterrupted one."""
         params = list(self.model.parameters())
         off = {id(p): o for p, o in self.model._slots}
         group = sd["param_groups"][0]
-        if any(group.get(k) for k in ("weight_decay", "amsgrad", "maximize")):
-            raise ValueError("FusedTrainer implements plain Adam (no weight decay / amsgrad / maximize)")
+        if any(group.get(k) for k in ("amsgrad", "maximize")):
+            raise ValueError("FusedTrainer implements Adam / AdamW (no amsgrad / maximize)")
+        if group.get("weight_decay") and not group.get("decoupled_weight_decay"):
+            raise ValueError("FusedTrainer implements decoupled weight decay (AdamW) only: the coupled, L2-style weight_decay of "
+                             "torch.optim.Adam is refused")
         if list(group["params"]) != list(range(len(params))):
             raise ValueError("optimizer state does not cover this model's parameters in order")
         steps = {int(float(st["step"])) for st in sd["state"].values()}
@@ -776,8 +901,21 @@ class FusedTrainer:
             mine = self._loss_signature() if self.loss_kind != "bce" else {"kind": "bce"}
             if saved != mine:
                 raise ValueError(f"optimizer state was saved under loss {saved}; this trainer trains {mine}")
-        self.lr, self.betas, self.eps = float(group["lr"]), (float(group["betas"][0]), float(group["betas"][1])), float(group["eps"])
+        lr, betas, eps = float(group["lr"]), (float(group["betas"][0]), float(group["betas"][1])), float(group["eps"])
+        # the options: the saved ones, else (a torch optimizer's state) this trainer's own; validated before anything changes
+        extra = sd.get("srfrd") or {}
+        mine = self.opts
+        sch = extra.get("schedule") or ({"kind": LR_SCHEDULES[mine.schedule], "warmup_steps": int(mine.warmup_steps),
+                                         "total_steps": int(mine.total_steps), "final_lr_ratio": float(mine.final_ratio)}
+                                        if mine is not None else {"kind": "constant"})
+        max_norm = extra["max_grad_norm"] if "schedule" in extra or "max_grad_norm" in extra else self.max_norm
+        opts, max_norm = _optim_config(lr, betas, float(group.get("weight_decay") or 0.0), max_norm, sch["kind"],
+                                       sch.get("warmup_steps", 0), sch.get("total_steps"), sch.get("final_lr_ratio", 0.0), self.group)
         dev = self.flat.device
+        if max_norm is not None and self.max_norm is None:
+            self.norm_partial = torch.zeros(_lib.GRAD_NORM_PARTIALS, device=dev, dtype=torch.float64)
+            self.clip = torch.zeros(2, device=dev, dtype=torch.float32)
+        self.lr, self.betas, self.eps, self.opts, self.max_norm = lr, betas, eps, opts, max_norm
         m = torch.zeros(self.ex.n_pad if self.mode == "sharded" else self.n_flat, device=dev, dtype=torch.float32)
         v = torch.zeros_like(m)
         for i, p in enumerate(params):
@@ -792,14 +930,13 @@ class FusedTrainer:
         else:
             self.m.copy_(m); self.v.copy_(v)
         self.steps_done = steps.pop() if steps else 0
-        extra = sd.get("srfrd") or {}
         seed = int(extra.get("seed", int(self.state[1].item()))) & 0x7FFFFFFF
         self.state.zero_()                                 # (ticket words of the fused tail included)
         self.state[0] = self.steps_done
         self.state[1] = seed
         # step size, bias correction and dropout seed of the NEXT step (t = steps_done + 1), as after an uninterrupted run.
         # (The captured graphs bake lr / betas in as launch arguments: they are re-captured.)
-        check(_lib.lib().srfrd_step_begin(ptr(self.state), self.lr, self.betas[0], self.betas[1], self._stream()), "srfrd_step_begin")
+        self._step_begin()
         self._graphs = None
         self._fresh = False
 
