@@ -79,7 +79,8 @@ typedef struct srfrd_layout {
 } srfrd_layout;
 
 /* [host] fills `lay`; replaces the per-class constructors' shape logic (reference SRFR_model.py:54-90, 155-190,
- * 431-466, 573-615). */
+ * 431-466, 573-615).  n_blocks outside 1 .. SRFRD_MAX_BLOCKS -> SRFRD_E_ARG: the backward kernels prefetch the checkpoints of
+ * block n_blocks - 1 before their loop, so a model without blocks is refused here, not run. */
 int srfrd_layout_init(srfrd_layout* lay, int kind, int n_items, int max_len, int d_item, int d_fake,
                       int n_labels, int n_blocks, int n_heads);
 

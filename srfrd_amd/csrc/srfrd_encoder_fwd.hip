@@ -361,7 +361,7 @@ extern "C" int srfrd_encoder_fwd_last(const srfrd_layout* lay, const void* item_
 
 extern "C" int srfrd_layout_init(srfrd_layout* lay, int kind, int n_items, int max_len, int d_item, int d_fake,
                                  int n_labels, int n_blocks, int n_heads) {
-  if (!lay || kind < 0 || kind > SRFRD_SRFU_R || n_items < 1 || max_len < 1 || d_item < 1 || n_blocks < 0 ||
+  if (!lay || kind < 0 || kind > SRFRD_SRFU_R || n_items < 1 || max_len < 1 || d_item < 1 || n_blocks < 1 ||
       n_blocks > SRFRD_MAX_BLOCKS || n_heads < 1)
     return SRFRD_E_ARG;
   const bool has_fake = kind == SRFRD_SRFR || kind == SRFRD_SRFRN;

@@ -176,6 +176,8 @@ class _SRFRDBase(nn.Module):
         self.forward_layers = nn.ModuleList()
 
     def _finish(self, item_number, max_len, d_item, d_fake, n_labels, num_blocks, num_heads, dropout_rate):
+        if not 1 <= int(num_blocks) <= _lib.MAX_BLOCKS:      # (here, not at the first make_layout: the kernels take no depth 0)
+            raise ValueError(f"num_blocks must be 1 .. {_lib.MAX_BLOCKS}, got {num_blocks}")
         self._cfg = dict(kind=self._kind, n_items=item_number, max_len=max_len, d_item=d_item, d_fake=d_fake,
                          n_labels=n_labels, n_blocks=num_blocks, n_heads=num_heads)
         self.dropout_rate = float(dropout_rate)

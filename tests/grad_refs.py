@@ -73,9 +73,33 @@ EXTRA = [
     _ragged("t3", "SRFU_B", 50, 0, -1, 17),
     _ragged("u0", "SASRec", 50, 0, 0, 12), _ragged("u2", "SRFRN", 45, 5, 2, 12),
 ]
-ALL_CASES = list(F.CASES) + EXTRA
+DEPTH2_CASES = list(F.CASES) + EXTRA                 # num_blocks = 2: the list the catalog-loss "head" mode stays on
+
+# Depths 1, 3 and 8 (every case above has two blocks, so each of its blocks is the first or the last: a checkpoint offset, a
+# packed-weight index, a LayerNorm-cache slot or a dropout site that is right for i = 0 and i = n - 1 and wrong in between
+# passes all of them; so does a prefetch that is wrong only where one block is both).  Twins of the cases above - same kind,
+# width, heads, switch, batch size and kernel names, id "<twin's id>.<depth>" - with the fp32 table:
+#   1, 3  one case per family key the plan produces at that depth (tests/test_depth_cover.py): both sides of every kind-variant
+#         backward (a | p, b | q, g | h, j | k, t0 | t2), SRFR (c), the two-head generic pair (d).  k at seq_len 200: with three
+#         blocks the row-chunked backward's LDS no longer fits at 203 and the plan answers srfrd_long:: there;
+#   8     the LayerNorm caches are at their largest ((4 * 8 + 2) * 64 floats, twice in a backward) and move the plan: the
+#         first-generation backward no longer fits at LP = 64 (41 280 floats of 40 960), so the two-head pair (d) runs the generic
+#         forward with the srfrd_long:: backward; the default geometry (t0, t2: ragged pair, one-launch train kernel), the
+#         slot-placed backward at seq_len 100 (g) and the row-owner / row-chunked pair at seq_len 113 (l) keep their names.
+_TWINS_1_3 = ("a", "b", "c", "d", "f", "g", "h", "i", "j", "k", "n", "p", "q", "s", "t0", "t2")
+_DEPTH8 = {"t0": {}, "t2": {}, "g": {}, "l": {}, "d": F._same(F._F + F._GEN, F._BL + F._GEN)}
+_DEPTH_L = {("k", 3): 200}
+
+
+def _twin(cid, n, **names):
+    base = next(c for c in DEPTH2_CASES if c.id == cid)
+    return base._replace(id=f"{cid}.{n}", blocks=n, L=_DEPTH_L.get((cid, n), base.L), **names)
+
+
+DEPTH = [_twin(cid, n) for n in (1, 3) for cid in _TWINS_1_3] + [_twin(cid, 8, **names) for cid, names in _DEPTH8.items()]
+ALL_CASES = DEPTH2_CASES + DEPTH
 BY_ID = {c.id: c for c in ALL_CASES}
-TRAIN_KERNEL_IDS = ("t0", "t1", "t2", "t3")          # run with train_launch on and off
+TRAIN_KERNEL_IDS = ("t0", "t1", "t2", "t3", "t0.1", "t0.3", "t0.8")          # run with train_launch on and off
 L2_ID = "t0"                                         # the one fused case that also runs with l2_emb = L2_EMB
 # leading pad counts of the tile-boundary batch: the boundaries tests/fuzz_ragged.py names, with both neighbours
 TILE_PADS = (0, 1, 3, 4, 5, 15, 16, 17, 19, 20, 21, 35, 36, 37, 48, 49, 50)
@@ -101,9 +125,31 @@ SEEDS = {
     ("t2", "fused"): 83, ("t3", "autograd"): 65, ("t3", "fused"): 128, ("u0", "autograd"): 12, ("u0", "fused"): 50,
     ("u2", "autograd"): 11, ("u2", "fused"): 100,
 }
+# DEPTH, by the same rule over 200 batches a job, from three scans: both kinds of machine, and the first kind once more with the
+# BLAS library held to its AVX2 code path (MKL_CBWR=AVX2; its default is AVX-512).  The third scan moved six picks and no job
+# in or out of OVER_CAP; one batch differed by 42 % between the kinds (k.3 autograd at batch 35: 1.13e-6 and 1.60e-6).
+SEEDS.update({
+    ("a.1", "autograd"): 8, ("a.1", "fused"): 50, ("b.1", "autograd"): 7, ("b.1", "fused"): 54, ("c.1", "autograd"): 104,
+    ("c.1", "fused"): 194, ("d.1", "autograd"): 8, ("d.1", "fused"): 50, ("f.1", "autograd"): 153, ("f.1", "fused"): 202,
+    ("g.1", "autograd"): 9, ("g.1", "fused"): 50, ("h.1", "autograd"): 13, ("h.1", "fused"): 67, ("i.1", "autograd"): 9,
+    ("i.1", "fused"): 50, ("j.1", "autograd"): 11, ("j.1", "fused"): 57, ("k.1", "autograd"): 29, ("k.1", "fused"): 84,
+    ("n.1", "autograd"): 11, ("n.1", "fused"): 57, ("p.1", "autograd"): 7, ("p.1", "fused"): 54, ("q.1", "autograd"): 8,
+    ("q.1", "fused"): 50, ("s.1", "autograd"): 6, ("s.1", "fused"): 50, ("t0.1", "autograd"): 6, ("t0.1", "fused"): 50,
+    ("t2.1", "autograd"): 13, ("t2.1", "fused"): 51,
+    ("a.3", "autograd"): 9, ("a.3", "fused"): 54, ("b.3", "autograd"): 26, ("b.3", "fused"): 168, ("c.3", "autograd"): 185,
+    ("c.3", "fused"): 55, ("d.3", "autograd"): 11, ("d.3", "fused"): 55, ("f.3", "autograd"): 201, ("f.3", "fused"): 85,
+    ("g.3", "autograd"): 107, ("g.3", "fused"): 67, ("h.3", "autograd"): 37, ("h.3", "fused"): 143, ("i.3", "autograd"): 107,
+    ("i.3", "fused"): 67, ("j.3", "autograd"): 208, ("j.3", "fused"): 124, ("k.3", "autograd"): 88, ("k.3", "fused"): 157,
+    ("n.3", "autograd"): 208, ("n.3", "fused"): 124, ("p.3", "autograd"): 26, ("p.3", "fused"): 168, ("q.3", "autograd"): 9,
+    ("q.3", "fused"): 54, ("s.3", "autograd"): 12, ("s.3", "fused"): 55, ("t0.3", "autograd"): 11, ("t0.3", "fused"): 51,
+    ("t2.3", "autograd"): 21, ("t2.3", "fused"): 79,
+    ("t0.8", "autograd"): 104, ("t0.8", "fused"): 224, ("t2.8", "autograd"): 45, ("t2.8", "fused"): 69, ("g.8", "autograd"): 107,
+    ("g.8", "fused"): 72, ("l.8", "autograd"): 106, ("l.8", "fused"): 55, ("d.8", "autograd"): 63, ("d.8", "fused"): 58,
+})
 # Weights: random_sd(cfg, SD_SEED) as in the bf16 family tests, but for b, k and p (SRFRN): the next weight seed, under which
-# their batches are found among the first.
-SD_SEEDS = {"b": 8, "k": 8, "p": 8}
+# their batches are found among the first.  At depth 3 the same for h, k and t2 (under SD_SEED: no batch of 200 with headroom for
+# h.3 in either mode, k.3 in either mode, t2.3 fused; under 8 all but the fused jobs of h.3 and k.3 have one).
+SD_SEEDS = {"b": 8, "k": 8, "p": 8, "h.3": 8, "k.3": 8, "t2.3": 8}
 # Jobs without such a seed.  Of the scanned batches with the ReLU margin they take the one whose e32 is smallest on the worse
 # machine: f 2.2e-6 / 1.8e-6, l 3.3e-6 / 2.7e-6, m 2.8e-6 / 2.2e-6 (autograd / fused; SRFU_B and SRFR at seq_len 64 .. 128: no
 # input comes near the 1.5625e-6 the condition allows - these kinds add one large shared vector to every position, which the V
@@ -114,11 +160,22 @@ SD_SEEDS = {"b": 8, "k": 8, "p": 8}
 # two-head srfrd_long:: pair.
 OVER_CAP = frozenset([(c, m) for c in "flm" for m in ("autograd", "fused")]
                      + [(c, "autograd") for c in ("c", "j", "n", "o", "t1", "t3")])
+# DEPTH.  e32 grows with the depth (worst tensor of the chosen batches, worse code path: 5.8e-7 .. 1.2e-6 at depth 1 outside
+# this set, 1.0e-6 .. 1.25e-6 at depth 3, 2.3e-6 .. 6.9e-6 at depth 8), so at depth 8 the condition has no input: EVERY depth-8
+# job is clamped at CAP, 14 .. 43 times its e32 where an admissible job has 64.  At depths 1 and 3, of 200 batches: SRFR and
+# SRFU_B as at depth 2 (c.1 1.42e-6 / 1.27e-6, f.1 1.71e-6 / 1.36e-6, c.3 2.22e-6 / 2.22e-6, f.3 2.70e-6 / 2.24e-6), the fused
+# steps of SRFRN at depth 3 (b.3 = p.3 1.43e-6, h.3 1.34e-6, k.3 1.55e-6) and j.3 = n.3 autograd 1.65e-6 (seq_len 200).
+# MAX_DEPTH_OVER_CAP: they may be a quarter of the depth-1 and depth-3 jobs at most (tests/test_grad_refs.py).
+DEPTH_OVER_CAP = frozenset([(c.id, m) for c in DEPTH if c.blocks == 8 for m in ("autograd", "fused")]
+                           + [(c, m) for c in ("c.1", "f.1", "c.3", "f.3") for m in ("autograd", "fused")]
+                           + [(c, "fused") for c in ("b.3", "p.3", "h.3", "k.3")] + [("j.3", "autograd"), ("n.3", "autograd")])
+MAX_DEPTH_OVER_CAP = 2 * sum(c.blocks != 8 for c in DEPTH) // 4
+OVER_CAP = OVER_CAP | DEPTH_OVER_CAP
 
 
 def case_ids(cases=None):
     return [f"{c.id}-{c.kind}-L{c.L}" + (f"-{c.switch}" if c.switch else "") + (f"-h{c.heads}" if c.heads > 1 else "")
-            for c in (cases or ALL_CASES)]
+            + (f"-b{c.blocks}" if c.blocks != 2 else "") for c in (cases or ALL_CASES)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

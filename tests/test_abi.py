@@ -66,6 +66,33 @@ def test_argument_errors_are_codes_not_crashes():
     assert lib.srfrd_aux_floats(C.byref(lay), 4, 20) == 2 * 4 * (5 * 20 * 50 + 20 * 32)
 
 
+def test_depth_outside_1_to_8_is_refused():
+    """The backward kernels prefetch block n_blocks - 1's checkpoints in front of their loop: with no block that is a read in
+    front of the allocation.  So depth 0 is refused where the layout is made and where a model is constructed - never run."""
+    import srfrd_amd
+    from srfrd_amd import _lib
+    lib = _lib.lib()
+    lay = _lib.Layout()
+    assert _lib.MAX_BLOCKS == 8
+    for nb in (0, -1, 9):
+        assert lib.srfrd_layout_init(C.byref(lay), 0, 100, 20, 50, 0, 0, nb, 1) == -1, nb
+        with pytest.raises(RuntimeError):
+            _lib.make_layout("SASRec", 100, 20, 50, 0, 0, n_blocks=nb)
+    for nb in (1, 8):
+        assert _lib.make_layout("SASRec", 100, 20, 50, 0, 0, n_blocks=nb).n_blocks == nb
+    make = {"SASRec": lambda nb: srfrd_amd.SASRec(100, 20, 50, 0.0, nb, 1, "cpu"),
+            "SRFR": lambda nb: srfrd_amd.SRFR(100, 20, 45, 5, 0.0, nb, 1, "cpu"),
+            "SRFRN": lambda nb: srfrd_amd.SRFRN(100, 20, 45, 5, 0.0, nb, 1, "cpu"),
+            "SRFU_B": lambda nb: srfrd_amd.SRFU_B(100, 20, 50, 3, 0.0, nb, 1, "cpu"),
+            "SRFU_F": lambda nb: srfrd_amd.SRFU_F(100, 20, 50, 3, 0.0, nb, 1, "cpu"),
+            "SRFU_R": lambda nb: srfrd_amd.SRFU_R(100, 20, 50, 3, 0.0, nb, 1, "cpu")}
+    for kind, ctor in make.items():
+        for nb in (0, 9, -1):
+            with pytest.raises(ValueError, match="num_blocks"):         # at construction, not at the first layout
+                ctor(nb)
+        assert ctor(1).layout.n_blocks == 1 and ctor(8).layout.n_blocks == 8, kind
+
+
 def test_torch_library_ops_are_registered():
     """SURVEY 8b: the launchers are dispatcher-visible custom ops (namespace srfrd::), not opaque ctypes calls; each has a
     fake implementation (shape propagation) and the encoder forward a registered backward."""

@@ -67,7 +67,7 @@ def _targets():
 
 
 def _case_layout(c):
-    return _lib.make_layout(c.kind, F.I, c.L, c.d_item, c.d_fake, 3 if c.kind.startswith("SRFU") else 0, 2, c.heads)
+    return _lib.make_layout(c.kind, F.I, c.L, c.d_item, c.d_fake, 3 if c.kind.startswith("SRFU") else 0, c.blocks, c.heads)
 
 
 def _produced():

@@ -34,8 +34,12 @@ MODES = {
 SWITCH_SETS = [None] + list(P.SWITCHES)
 
 
-def _layout(kind, di, df, nl, heads):
-    return _lib.make_layout(kind, 300, 208, di, df, nl, 2, heads)
+SIZE_DEPTHS = (1, 2, 3, 8)   # tests/golden/encoder_plan_sizes.json
+DEPTHS = (1, 2, 3, 4, 8)    # 2: every existing row; 4: the first depth without the row-chunked backward at seq_len 200
+
+
+def _layout(kind, di, df, nl, heads, nb=2):
+    return _lib.make_layout(kind, 300, 208, di, df, nl, nb, heads)
 
 
 def _variant(kind, di, D, heads):
@@ -53,9 +57,10 @@ def _lds_floats(L, D, nb, bwd):
     return max(LP * DS, LP * SLD) + 4 * LP * DS + 64 + 4 * LP + 64 + ln
 
 
-def expected(kind, di, df, heads, B, L, mode, sw, scratch):
-    """(forward name, grid), (backward name, grid) as the launchers chose them before the plan (hidden 50 = d_item + d_fake)"""
-    D, nb, LIM = di + df, 2, 160 * 1024
+def expected(kind, di, df, heads, B, L, mode, sw, scratch, nb):
+    """(forward name, grid), (backward name, grid) as the launchers chose them before the plan (hidden 50 = d_item + d_fake);
+    nb: the depth, which enters through the LayerNorm caches of every LDS size below and through nothing else"""
+    D, LIM = di + df, 160 * 1024
     kv = _variant(kind, di, D, heads)
     on = lambda s: sw == s
     taps = bool(mode & P.PLAN_TAPS)
@@ -131,17 +136,31 @@ def _rows():
         yield kind, di, df, nl, heads, L, mname, sw, B
 
 
-def test_plan_matches_the_dispatch_rules():
+def _mismatches(nb, nb_expected):
+    """rows at which the plan of a depth-`nb` layout differs from expected(..., nb_expected)"""
     bad = []
     for kind, di, df, nl, heads, L, mname, sw, B in _rows():
-        lay = _layout(kind, di, df, nl, heads)
+        lay = _layout(kind, di, df, nl, heads, nb)
         sw_bits = P.SWITCHES[sw] if sw else 0
         for scratch in (max(_lib.scratch_floats(lay, B, L)), 0):
             got = _lib.encoder_plan(lay, B, L, MODES[mname], sw_bits, N_CU, scratch)
-            want = expected(kind, di, df, heads, B, L, MODES[mname], sw, scratch)
+            want = expected(kind, di, df, heads, B, L, MODES[mname], sw, scratch, nb_expected)
             if got != want:
                 bad.append((kind, di, heads, L, mname, sw, B, scratch, got, want))
+    return bad
+
+
+@pytest.mark.parametrize("nb", DEPTHS)
+def test_plan_matches_the_dispatch_rules(nb):
+    bad = _mismatches(nb, nb)
     assert not bad, f"{len(bad)} rows differ, first: {bad[:3]}"
+
+
+@pytest.mark.parametrize("nb,other", [(2, 8), (8, 7), (3, 4), (4, 3)])
+def test_the_dispatch_rules_notice_a_wrong_depth(nb, other):
+    """the table above is not blind to the depth: `expected` handed another one differs from the plan (8 against 7: the
+    first-generation forward's grid and backward; 3 against 4: the row-chunked backward at seq_len 200)"""
+    assert _mismatches(nb, other)
 
 
 def test_forward_is_ragged_iff_backward_is():
@@ -168,11 +187,15 @@ def test_backward_grid_follows_srfrd_bwd_grid(n_cu):
 def test_scratch_and_lds_sizes_are_unchanged():
     """srfrd_scratch_floats / srfrd_lds_bytes are ABI: the values pinned before the plan existed"""
     pinned = json.load(open(os.path.join(GOLDEN, "encoder_plan_sizes.json")))
-    for (kind, di, df, nl, heads), L in itertools.product(LAYOUTS, LENGTHS):
-        lay = _layout(kind, di, df, nl, heads)
+    seen = set()
+    for ((kind, di, df, nl, heads), L), nb in itertools.product(itertools.product(LAYOUTS, LENGTHS), SIZE_DEPTHS):
+        lay = _layout(kind, di, df, nl, heads, nb)
         for B in (6, 600):
             got = list(_lib.scratch_floats(lay, B, L)) + list(_lib.lds_bytes(lay, L))
-            assert got == pinned[f"{kind}/{di}/{heads}/{L}/{B}"], (kind, di, heads, L, B)
+            key = f"{kind}/{di}/{heads}/{L}/{B}" + ("" if nb == 2 else f"/b{nb}")      # depth 2: the keys as they were
+            seen.add(key)
+            assert got == pinned[key], (kind, di, heads, L, B, nb)
+    assert seen == set(pinned)
 
 
 # (layout, L, mode, switch) -> (forward, backward): rows seen in kernel traces (B = 6 unless noted)
@@ -204,6 +227,49 @@ def test_pinned_rows(lay, L, mname, sw, fwd, bwd):
     (f, _), (b, _) = _lib.encoder_plan(layout, 6, L, MODES[mname], P.SWITCHES[sw] if sw else 0, N_CU,
                                        max(_lib.scratch_floats(layout, 6, L)))
     assert (f, b) == (fwd, bwd)
+
+
+# The LayerNorm caches ((4 nb + 2) * 64 floats, twice in a backward) are the only depth-dependent term of every LDS size, and
+# they move three boundaries of the plan.  Rows as the built library answers them:
+# (layout, depth, L, B, mode, switch) -> ((forward, grid), (backward, grid)), srfrd_lds_bytes, srfrd_scratch_floats
+_S = ("SASRec", 50, 0, 0, 1)
+_S2 = ("SASRec", 50, 0, 0, 2)
+_GENF, _GENB = "srfrd::encoder_fwd_kernel<0,0,0,0,-1,0,0>", "srfrd::encoder_bwd_kernel<0,0,0,0,-1,0,0>"
+_F50 = "srfrd::encoder_fwd_kernel<50,64,8,50,0,{},50>"
+DEPTH_PINNED = [
+    # first-generation backward at LP = 64, D = 50: 40 768 floats at depth 7, 41 280 (> 40 960 = 160 KB) at depth 8
+    (_S2, 7, 50, 6, "fused_p", None, ((_GENF, 6), (_GENB, 6)), (81408, 163072), (0, 0)),
+    (_S2, 8, 50, 6, "fused_p", None, ((_GENF, 6), ("srfrd_long::encoder_bwd_kernel<0,0,0,0,-1,0,0>", 6)), (82432, 0), (0, 248448)),
+    (_S, 7, 50, 600, "fused_p", "SRFRD_NO_SLOTS50", ((_F50.format(1), 512), ("srfrd::encoder_bwd_kernel<50,64,8,50,0,1,50>", 512)),
+     (81408, 163072), (0, 0)),
+    # ... where the working set is over the limit the slot-placed backward is the long-sequence answer at seq_len 50 too, and
+    # SRFRD_NO_SLOTS50 (a switch of the LDS-resident selection) no longer reaches the first-generation kernel
+    (_S, 8, 50, 600, "fused_p", "SRFRD_NO_SLOTS50", ((_F50.format(1), 256), ("srfrd::encoder_bwd_slots_kernel<50,50,0,50,true>", 512)),
+     (82432, 0), (0, 21200896)),
+    # row-chunked backward at seq_len 200: 40 688 floats at depth 3, 41 200 at depth 4
+    (_S, 3, 200, 6, "fused_p", None, (("srfrd::encoder_fwd_rows_kernel<50,0,50,1>", 6), ("srfrd::encoder_bwd_chunks_kernel<50,0,50,false>", 6)),
+     (0, 0), (543744, 1088640)),
+    (_S, 4, 200, 6, "fused_p", None, (("srfrd::encoder_fwd_rows_kernel<50,0,50,1>", 6), ("srfrd_long::encoder_bwd_kernel<0,0,0,0,-1,0,0>", 6)),
+     (0, 0), (545280, 1091712)),
+    # first-generation forward at seq_len 50: two workgroups per CU up to depth 7 (81 408 B each), one at depth 8 (82 432 B)
+    (_S, 7, 50, 600, "eval", "SRFRD_NO_RAGGED", ((_F50.format(0), 512), ("srfrd::encoder_bwd_slots_kernel<50,50,0,50,true>", 512)),
+     (81408, 163072), (0, 0)),
+    (_S, 8, 50, 600, "eval", "SRFRD_NO_RAGGED", ((_F50.format(0), 256), ("srfrd::encoder_bwd_slots_kernel<50,50,0,50,true>", 512)),
+     (82432, 0), (0, 21200896)),
+    # the ragged pair follows the same forward grid; its backward keeps 2 x CUs at every depth (one workgroup fits a CU from
+    # depth 3 on; no workgroup of it waits on another)
+    (_S, 7, 50, 600, "eval", None, (("srfrd::encoder_fwd_ragged_kernel<0,0,50>", 512), ("srfrd::encoder_bwd_ragged_kernel<0,50,true>", 512)),
+     (81408, 163072), (0, 0)),
+    (_S, 8, 50, 600, "eval", None, (("srfrd::encoder_fwd_ragged_kernel<0,0,50>", 256), ("srfrd::encoder_bwd_ragged_kernel<0,50,true>", 512)),
+     (82432, 0), (0, 21200896)),
+]
+
+
+@pytest.mark.parametrize("lay,nb,L,B,mname,sw,plan,lds,scratch", DEPTH_PINNED)
+def test_depth_moves_the_family_boundaries(lay, nb, L, B, mname, sw, plan, lds, scratch):
+    layout = _layout(*lay, nb)
+    assert _lib.lds_bytes(layout, L) == lds and _lib.scratch_floats(layout, B, L) == scratch
+    assert _lib.encoder_plan(layout, B, L, MODES[mname], P.SWITCHES[sw] if sw else 0, N_CU, max(scratch)) == plan
 
 
 def test_c2_geometry_and_unsupported_cases():

@@ -49,7 +49,7 @@ def test_case_list_seeds_and_the_over_cap_set():
 @pytest.mark.parametrize("c", R.ALL_CASES, ids=[c.id for c in R.ALL_CASES])
 def test_every_mode_has_the_plans_kernel_name(c):
     """the name each GPU run asserts before it launches, against the host-only plan under the mode bits the launchers derive"""
-    lay = _lib.make_layout(c.kind, G.I, c.L, c.d_item, c.d_fake, 3 if c.kind.startswith("SRFU") else 0, 2, c.heads)
+    lay = _lib.make_layout(c.kind, G.I, c.L, c.d_item, c.d_fake, 3 if c.kind.startswith("SRFU") else 0, c.blocks, c.heads)
     sw = _lib.SWITCHES[c.switch] if c.switch else 0
     scratch = _lib.scratch_floats(lay, c.B, c.L)[0]          # (the module path sizes it per direction)
     for mode in R.MODES:

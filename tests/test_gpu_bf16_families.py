@@ -32,7 +32,8 @@ I = 300
 # on it (observed on the hidden states: 1.4e-6).  Batches are chosen so that no ReLU input is closer to zero than three times that.
 RELU_MARGIN = 1e-5
 
-Case = namedtuple("Case", "id kind d_item d_fake heads L B switch seed fused_seed eval_fwd last_fwd autograd fused")
+Case = namedtuple("Case", "id kind d_item d_fake heads L B switch seed fused_seed eval_fwd last_fwd autograd fused blocks",
+                  defaults=(2,))          # blocks: the depth (tests/grad_refs.py, DEPTH, holds the others)
 
 _F = "srfrd::encoder_fwd_kernel"
 _B = "srfrd::encoder_bwd_kernel"
@@ -128,7 +129,7 @@ def case_scratch(layout, B, L, launch):
 
 def cfg_of(c, bf16=True, dropout=0.0):
     return O.Cfg(c.kind, I, c.L, c.d_item, d_fake=c.d_fake, n_labels=3 if c.kind.startswith("SRFU") else 0, num_heads=c.heads,
-                 dropout=dropout, table_bf16=bf16)
+                 num_blocks=c.blocks, dropout=dropout, table_bf16=bf16)
 
 
 def relu_margin(cfg, sd, batch, train=False, seed=0):

@@ -1,7 +1,8 @@
 """-m gpu, fp32 item table: every encoder forward output against the fp64 oracle, relative to its own row's size
 (tests/fwd_refs.py: reference, metric, bound, modes and seeds; tests/test_fwd_refs.py: their CPU side).
 
-Three launches on every case of grad_refs.ALL_CASES - the gradient suite's list, which reaches every encoder kernel family:
+Three launches on every case of grad_refs.ALL_CASES - the gradient suite's list, which reaches every encoder kernel family at
+two blocks and, through grad_refs.DEPTH, again at depths 1 and 3, with five cases at depth 8:
 
   eval   ``model.eval()``, ``model(...)`` under no_grad: hidden state, positive and negative logits - the evaluation
          instantiations (T = 0, no checkpoint), which no gradient test runs;

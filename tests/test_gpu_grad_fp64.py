@@ -2,7 +2,8 @@
 reference, metric, bound, cases and seeds; tests/test_grad_refs.py: their CPU side).
 
 Two ways to a gradient, both on every case of grad_refs.ALL_CASES - test_gpu_bf16_families.CASES, which reach every encoder
-kernel family, plus the <50,32,8,0> pair and the default geometry's tile-boundary and duplicate-heavy batches:
+kernel family, plus the <50,32,8,0> pair, the default geometry's tile-boundary and duplicate-heavy batches, and grad_refs.DEPTH:
+every family again at depths 1 and 3 and five cases at depth 8 (ids "-b<n>"; every other case has two blocks):
 
   autograd  a training-mode forward (dropout 0) and ``loss.backward()`` through ``model(...)``: ``p.grad``;
   fused     ONE ``FusedTrainer.step`` from fresh moments with dropout 0.5, both scatter modes: the optimizer state then holds

@@ -40,11 +40,25 @@ def test_seed_table_is_complete_and_batches_have_their_shape():
     assert top <= 8 and all(int((x == top).sum()) >= 12 for x in (seq, pos, neg))
 
 
+def test_depth_jobs_over_the_cap_are_the_depth_8_ones_and_a_quarter_of_the_rest_at_most():
+    """at depth 8 the condition 64 e32 <= CAP has no input (every job clamped at CAP - tighter than 64 e32, never wider); at
+    depths 1 and 3 it has, and the jobs listed without one stay an exception"""
+    jobs = {(c.id, m) for c in G.DEPTH for m in ("autograd", "fused")}
+    deep = {(c.id, m) for c in G.DEPTH if c.blocks == 8 for m in ("autograd", "fused")}
+    mine = G.OVER_CAP & jobs
+    assert mine == G.DEPTH_OVER_CAP and deep <= mine and len(deep) == 10
+    assert len(mine - deep) <= G.MAX_DEPTH_OVER_CAP == len(jobs - deep) // 4
+    assert not any(k[0] in {c.id for c in G.DEPTH} for k in G.OVER_CAP - mine)       # (no head job at another depth)
+    for cid, mode in sorted(deep):                  # the clamp acts on every depth-8 job: its bounds are CAP, not 64 e32
+        ref = G.reference(cid, mode)
+        assert ref.clamp and not G.under_cap(ref) and max(G.bound(e, True) for e in ref.e32.values()) == G.CAP, (cid, mode)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # names and families
 # ---------------------------------------------------------------------------------------------------------------------------
 def _lay(c):
-    return _lib.make_layout(c.kind, G.I, c.L, c.d_item, c.d_fake, 3 if c.kind.startswith("SRFU") else 0, 2, c.heads)
+    return _lib.make_layout(c.kind, G.I, c.L, c.d_item, c.d_fake, 3 if c.kind.startswith("SRFU") else 0, c.blocks, c.heads)
 
 
 @pytest.mark.parametrize("c", G.EXTRA, ids=[c.id for c in G.EXTRA])

@@ -69,11 +69,11 @@ def test_head_jobs_cover_what_they_claim():
     default = {(cid, loss) for cid in G.DEFAULT_IDS for loss in G.HEAD_LOSSES if not (loss == "gbce" and srfrn(cid))}
     assert len(default) == 22 and default <= pairs
     assert not any(j.loss == "gbce" and srfrn(j.cid) for j in jobs)
-    assert {j.cid for j in jobs} == {c.id for c in G.ALL_CASES}
+    assert {j.cid for j in jobs} == {c.id for c in G.DEPTH2_CASES}          # (the head mode stays at two blocks)
     assert all(G.HEAD_NAMES[cid][1].startswith("srfrd::encoder_bwd_ragged_kernel<") for cid in G.DEFAULT_IDS)
     met = {(j.loss, _family(G.HEAD_NAMES[j.cid][1])) for j in jobs}
     assert {(loss, fam) for loss in G.HEAD_LOSSES for fam in ("first", "slots", "chunks", "long", "ragged")} <= met
-    assert {G.HEAD_NAMES[j.cid][1] for j in jobs} == {c.autograd[1] for c in G.ALL_CASES}      # every non-training backward
+    assert {G.HEAD_NAMES[j.cid][1] for j in jobs} == {c.autograd[1] for c in G.DEPTH2_CASES}      # every non-training backward
     for loss in G.TOKEN_LOSSES:
         mine = [j for j in jobs if j.loss == loss]
         assert {j.remove for j in mine} == {True, False} and {j.with_lq for j in mine} == {True, False}
@@ -83,10 +83,10 @@ def test_head_jobs_cover_what_they_claim():
     assert {k for k in G.OVER_CAP if k[1].startswith("head/")} <= {(j.cid, "head/" + j.loss) for j in jobs}
 
 
-@pytest.mark.parametrize("c", G.ALL_CASES, ids=[c.id for c in G.ALL_CASES])
+@pytest.mark.parametrize("c", G.DEPTH2_CASES, ids=[c.id for c in G.DEPTH2_CASES])
 def test_head_names_are_the_plans(c):
     """the names each GPU job asserts before its step, against the host-only plan under the head launch's mode bits"""
-    lay = _lib.make_layout(c.kind, G.I, c.L, c.d_item, c.d_fake, 3 if c.kind.startswith("SRFU") else 0, 2, c.heads)
+    lay = _lib.make_layout(c.kind, G.I, c.L, c.d_item, c.d_fake, 3 if c.kind.startswith("SRFU") else 0, c.blocks, c.heads)
     sw = _lib.SWITCHES[c.switch] if c.switch else 0
     assert F._plan_bits()["head"] == (_lib.PLAN_CKPT | _lib.PLAN_DROPOUT, _lib.PLAN_DROPOUT)
     assert F.planned(lay, c.B, c.L, "head", sw, N_CU, *F.case_scratch(lay, c.B, c.L, "head")) == G.HEAD_NAMES[c.id]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measured agreement of every encoder forward output with the fp64 oracle (GPU box) -> profiles/fwd_fp64_errors.json.
 
-    python tools/fwd_fp64_report.py [--out profiles/fwd_fp64_errors.json]
+    python tools/fwd_fp64_report.py [--out profiles/fwd_fp64_errors.json] [--cases depth | ID ...]
     python tools/fwd_fp64_report.py --scan OUT.json   # CPU only, once per kind of machine the suite runs on, then
     python tools/fwd_fp64_report.py --pick A.json B.json       # ... the entries of tests/fwd_refs.FWD_SEEDS / FWD_OVER_CAP
 
@@ -18,7 +18,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tools.grad_fp64_report import _num, _one_thread, _setenv  # noqa: E402
+from tools.grad_fp64_report import _num, _one_thread, _setenv, selected_cases  # noqa: E402
 
 
 def _record(figs, names):
@@ -28,6 +28,8 @@ def _record(figs, names):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fwd_fp64_errors.json"))
+    ap.add_argument("--cases", nargs="+", metavar="ID", help="only these cases of fwd_refs.ALL_CASES (\"depth\": grad_refs.DEPTH), "
+                    "without the wave batch; every other entry of an existing --out file is kept")
     ap.add_argument("--scan", metavar="OUT", help="CPU only: worst e32 of every job's candidate seeds, here")
     ap.add_argument("--count", type=int, default=8)
     ap.add_argument("--workers", type=int, default=8)
@@ -37,7 +39,7 @@ def main():
     from tests import grad_refs as G
     if a.scan:
         import multiprocessing as mp
-        jobs = [(c.id, m, a.count) for c in R.ALL_CASES for m in R.MODES]
+        jobs = [(c.id, m, a.count) for c in selected_cases(G, a.cases) for m in R.MODES]
         with mp.get_context("spawn").Pool(a.workers, initializer=_one_thread) as pool:
             rows = pool.map(R.scan_seeds, jobs, chunksize=1)
         with open(a.scan, "w") as f:
@@ -54,10 +56,12 @@ def main():
         return 0
     from tests import test_gpu_fwd_fp64 as T
     runs = [(G.case_ids([c])[0], mode, lambda env, c=c, fn=fn: fn(c, env))
-            for c in R.ALL_CASES for mode, fn in (("eval", T.run_eval), ("last", T.run_last), ("train", T.run_train))]
-    runs += [("wave-" + "-".join(f"{k}{R.WAVE[k]}" for k in ("kind", "B", "L")), mode, lambda env, mode=mode: T.run_wave(mode, env))
+            for c in selected_cases(G, a.cases) for mode, fn in (("eval", T.run_eval), ("last", T.run_last), ("train", T.run_train))]
+    runs += [] if a.cases else [("wave-" + "-".join(f"{k}{R.WAVE[k]}" for k in ("kind", "B", "L")), mode, lambda env, mode=mode: T.run_wave(mode, env))
              for mode in ("eval", "last")]
     report, missed = {}, 0
+    if a.cases and os.path.exists(a.out):
+        report = {cid: modes for cid, modes in json.load(open(a.out))["cases"].items() if cid not in {r[0] for r in runs}}
     for cid, mode, fn in runs:
         changed = {}
         try:

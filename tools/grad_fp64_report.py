@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Measured agreement of every encoder gradient with the fp64 oracle (GPU box) -> profiles/grad_fp64_errors.json.
 
-    python tools/grad_fp64_report.py [--out profiles/grad_fp64_errors.json] [--modes encoder | head]
+    python tools/grad_fp64_report.py [--out profiles/grad_fp64_errors.json] [--modes encoder | head] [--cases depth | ID ...]
     python tools/grad_fp64_report.py --scan OUT.json  # CPU only, once per kind of machine the suite runs on, then
     python tools/grad_fp64_report.py --pick A.json B.json      # ... the batch-seed table of tests/grad_refs.py
 
@@ -66,10 +66,21 @@ def _dump(report, f):
     f.write("\n }\n}\n")
 
 
+def selected_cases(G, ids):
+    """--cases: the cases of grad_refs.ALL_CASES with these ids ("depth": grad_refs.DEPTH); all of them without the option"""
+    if not ids:
+        return list(G.ALL_CASES)
+    want = {c.id for c in G.DEPTH} if ids == ["depth"] else set(ids)
+    assert want <= set(G.BY_ID), sorted(want - set(G.BY_ID))
+    return [c for c in G.ALL_CASES if c.id in want]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grad_fp64_errors.json"))
     ap.add_argument("--modes", choices=["all", "encoder", "head"], default="all")
+    ap.add_argument("--cases", nargs="+", metavar="ID", help="only these cases of grad_refs.ALL_CASES (\"depth\": grad_refs.DEPTH), "
+                    "encoder modes only; every other entry of an existing --out file is kept")
     ap.add_argument("--scan", metavar="OUT", help="CPU only: worst e32 and ReLU margin of every job's candidate seeds, here")
     ap.add_argument("--count", type=int, default=48)
     ap.add_argument("--jobs", nargs="*", metavar="CASE/MODE", help="--scan: these only (head: every head/LOSS job)")
@@ -98,7 +109,10 @@ def main():
     from tests import test_gpu_grad_fp64 as T
     from tests import test_gpu_head_grad_fp64 as H
     runs = []           # (case, mode, the first mode that shares its reference, run)
-    for c in G.ALL_CASES if a.modes != "head" else []:
+    chosen = selected_cases(G, a.cases)
+    if a.cases:
+        a.modes = "encoder"
+    for c in chosen if a.modes != "head" else []:
         runs.append((c, "autograd", "autograd", lambda c, env: (T.run_autograd(c, env), None)))
         for det in (True, False):
             name = "fused-" + ("deterministic" if det else "atomics")
@@ -115,7 +129,8 @@ def main():
     if a.modes != "all" and os.path.exists(a.out):
         kept = json.load(open(a.out))
         tensors = kept["tensors"]
-        report = {cid: {m: r for m, r in modes.items() if m == "kind" or m.startswith("head-") != (a.modes == "head")}
+        report = {cid: {m: r for m, r in modes.items() if m == "kind" or m.startswith("head-") != (a.modes == "head")
+                        or (a.cases and cid not in G.case_ids(chosen))}
                   for cid, modes in kept["cases"].items()}
     for c, mode, ref, fn in runs:
         changed = {}
@@ -124,10 +139,11 @@ def main():
         finally:
             for name, old in changed.items():
                 os.environ.pop(name, None) if old is None else os.environ.__setitem__(name, old)
-        names = tensors.setdefault(c.kind, sorted(figs))
+        kind = c.kind if c.blocks == 2 else f"{c.kind}-b{c.blocks}"      # (another depth has another tensor list)
+        names = tensors.setdefault(kind, sorted(figs))
         shared = first.get((c.id, ref))
         first.setdefault((c.id, ref), mode)
-        entry = report.setdefault(G.case_ids([c])[0], {"kind": c.kind})
+        entry = report.setdefault(G.case_ids([c])[0], {"kind": kind})
         entry[mode] = _record(figs, names, shared)
         if figs2 is not None:       # (the same gradient squared, under twice the bound: the worst tensor only)
             w = max(figs2, key=lambda k: figs2[k]["err"] / figs2[k]["bound"])
