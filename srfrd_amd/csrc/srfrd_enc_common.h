@@ -59,6 +59,12 @@ struct EncArgs {
 constexpr int kSchedG = 0, kSchedT0 = 16;
 __host__ __device__ __forceinline__ int64_t sched_ints(int B) { return kSchedT0 + (int64_t)B; }
 
+}  // namespace SRFRD_NS
+
+#include "srfrd_enc_bwd_head.h"      // kHeadRows: the per-position arrays that the LDS sizes below count
+
+namespace SRFRD_NS {
+
 // Checkpoint layout: SEQUENCE-major.  Everything the backward reads back for sequence b is contiguous per buffer -
 // save_x: (nb + 1) blocks of [L][D] at b * (nb + 1) * L * D; save_h1: nb blocks at b * nb * L * D; save_aux
 // (srfrd_aux_floats): nb blocks of aux_seq_floats at b * nb * aux_seq_floats, each the planes r, o, q, k, v [L][D] and
@@ -95,7 +101,8 @@ constexpr int kSlotWaves = 8;
 __host__ __device__ constexpr int slots_R(int L) { return (L + 3) & ~3; }
 __host__ __device__ constexpr int64_t slots_lds_floats(int L, int D, int n_blocks) {
   const int LP = (L + 15) & ~15, DS = ((D + 3) & ~3) + 2;
-  return 6ll * slots_R(L) * DS + 11ll * LP + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
+  // six slots; the head's per-position arrays, s_delta and a spare one; s_misc
+  return 6ll * slots_R(L) * DS + (kHeadRows + 2ll) * LP + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
 }
 // Row-chunked backward (srfrd_encoder_bwd_chunks_kernel.inc): seq_len 17..208, three [L][D] intermediates in scratch.
 constexpr int kCkWaves = 8;
@@ -104,13 +111,14 @@ __host__ __device__ constexpr int64_t chunks_lds_floats(int L, int D, int n_bloc
   const int LP = (L + 15) & ~15, DS = ((D + 3) & ~3) + 2, LR = (L + 3) & ~3;
   // K | V, then a pool that is the score chunk + two chunk slots (attention pass) or five chunk slots (projection pass)
   const int64_t pool_att = (int64_t)kCkRows * (LR + 2) + 2ll * kCkRows * DS, pool_prj = 5ll * kCkRows * DS;
-  return 2ll * LR * DS + (pool_att > pool_prj ? pool_att : pool_prj) + 11ll * LP + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
+  return 2ll * LR * DS + (pool_att > pool_prj ? pool_att : pool_prj) + (kHeadRows + 2ll) * LP + 64 + 2ll * ln_cache_floats(n_blocks) + kSlack;
 }
 __host__ __device__ constexpr int64_t chunks_scratch_floats(int L, int D) { return 3ll * (((L + 3) & ~3) * D + 64); }
 // Ragged backward (srfrd_encoder_bwd_ragged_kernel.inc): seq_len 50, hidden 50.
 // Per-sequence working sets (floats) of the ragged pair, without the LayerNorm caches:
 constexpr int kRagFwdWork = 64 * 66 + 4 * 64 * 54 + 4 * 64 + 64;    // scores / x [64][66], four [64][54], 4 per-row arrays, misc
-constexpr int kRagBwdWork = 12 * 54 + 6 * 52 * 54 + 12 * 64 + 64;   // guard (12 rows), six [52][54] slots, 12 per-row arrays, misc
+// guard (12 rows), six [52][54] slots, the head's per-row arrays + s_delta, s_brep, s_dummy, misc
+constexpr int kRagBwdWork = 12 * 54 + 6 * 52 * 54 + (kHeadRows + 3) * 64 + 64;
 __host__ __device__ constexpr int64_t bwd_ragged_lds_floats(int n_blocks) {
   // working set + two LayerNorm caches + slack
   return kRagBwdWork + 2ll * ln_cache_floats(n_blocks) + kSlack;

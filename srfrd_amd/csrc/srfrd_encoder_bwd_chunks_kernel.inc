@@ -85,17 +85,17 @@ __global__ void __launch_bounds__(kCkWaves * 64) encoder_bwd_chunks_kernel(const
   lds_f* regC = regB + CR * SLD;
   const int pool = imax(CR * SLD + 2 * CSZ, 5 * CSZ);
   lds_f* tail = regB + pool;
-  lds_i* s_in = (lds_i*)tail;
-  lds_f* s_keep = tail + LP;
-  lds_i* s_pid = (lds_i*)(tail + 2 * LP);
-  lds_i* s_nid = (lds_i*)(tail + 3 * LP);
-  lds_i* s_fk = (lds_i*)(tail + 4 * LP);
-  lds_i* s_pfk = (lds_i*)(tail + 5 * LP);
-  lds_i* s_nfk = (lds_i*)(tail + 6 * LP);
-  lds_f* s_dpl = tail + 7 * LP;
-  lds_f* s_dnl = tail + 8 * LP;
-  lds_f* s_delta = tail + 9 * LP;
-  lds_f* s_misc = tail + 11 * LP;        // 64
+  lds_i* s_in = (lds_i*)(tail + kRowIn * LP);
+  lds_f* s_keep = tail + kRowKeep * LP;
+  lds_i* s_pid = (lds_i*)(tail + kRowPid * LP);
+  lds_i* s_nid = (lds_i*)(tail + kRowNid * LP);
+  lds_i* s_fk = (lds_i*)(tail + kRowFk * LP);
+  lds_i* s_pfk = (lds_i*)(tail + kRowPfk * LP);
+  lds_i* s_nfk = (lds_i*)(tail + kRowNfk * LP);
+  lds_f* s_dpl = tail + kRowDpl * LP;
+  lds_f* s_dnl = tail + kRowDnl * LP;
+  lds_f* s_delta = tail + kHeadRows * LP;
+  lds_f* s_misc = tail + (kHeadRows + 2) * LP;        // 64
   lds_f* s_ln = s_misc + 64;
   lds_f* s_lng = s_ln + ln_cache_floats(ly.n_blocks);
   __syncthreads();
@@ -181,10 +181,7 @@ __global__ void __launch_bounds__(kCkWaves * 64) encoder_bwd_chunks_kernel(const
       if (in) {
         if (a.fused_bce) {                   // fused masked BCE (trainer.py:36-38): both terms indexed by pos != 0
           const float pl = a.c_pl[rowbase + t], nl = a.c_nl[rowbase + t];
-          if (pid != 0) {
-            dp = sigmoid_f(pl) - 1.0f;
-            dn = sigmoid_f(nl);
-          }
+          bce_dlogits(pid, pl, nl, dp, dn);
         } else {                             // upstream logit gradients (the autograd path)
           if (a.d_pos && a.pos_ids) dp = a.d_pos[rowbase + t];
           if (a.d_neg && a.neg_ids) dn = a.d_neg[rowbase + t];
@@ -265,11 +262,7 @@ __global__ void __launch_bounds__(kCkWaves * 64) encoder_bwd_chunks_kernel(const
           };
           if (a.table16 != nullptr) chunks(std::true_type{});
           else chunks(std::false_type{});
-          if (dout < D)
-            for (int idx = tid; idx < rows * (D - dout); idx += nthr) {
-              const int tt = idx / (D - dout), cc = dout + idx - tt * (D - dout);
-              sG[tt * DS + cc] = 0.f;
-            }
+          head_zero_cols(sG, DS, rows, dout, D, tid, nthr);
           zero_tail_rows(sG, rows);
         }
         __syncthreads();
@@ -306,11 +299,7 @@ __global__ void __launch_bounds__(kCkWaves * 64) encoder_bwd_chunks_kernel(const
           }
         // last LayerNorm backward: dx -> sK, g * xhat -> sO
         ln_bwd_rows<false>(nw, sG, lnin, sK, sO, rows, CR, DS, dout, s_ln + (4 * ly.n_blocks) * 64);
-        if (dout < D)
-          for (int idx = tid; idx < rows * (D - dout); idx += nthr) {
-            const int tt = idx / (D - dout), cc = dout + idx - tt * (D - dout);
-            sK[tt * DS + cc] = 0.f;
-          }
+        head_zero_cols(sK, DS, rows, dout, D, tid, nthr);
         zero_tail_rows(sK, rows);
         __syncthreads();
         gemm_tiles<0>(nw, 1, (dout + 15) >> 4, kr, OnesRow{}, Mat{sG, DS},

@@ -38,7 +38,7 @@ __global__ void __launch_bounds__(NW_ > 0 ? NW_ * 64 : 512) encoder_bwd_kernel(c
   constexpr int CIT = D_ > 0 ? (LP_ * (CV2 ? D_ / 2 : D_) + NW_ * 64 - 1) / (NW_ * 64) : 4;
   constexpr int PIT = D_ > 0 ? (LP_ * LP_ / 2 + NW_ * 64 - 1) / (NW_ * 64) : 4;      // the [L][LP] probability block, in pairs
   const int szA = LP * DS, szS = imax(LP * SLD, szA);
-  const int tailsz = 10 * LP + 64 + 2 * ln_cache_floats(ly.n_blocks);
+  const int tailsz = (kHeadRows + 1) * LP + 64 + 2 * ln_cache_floats(ly.n_blocks);
 #ifdef SRFRD_BUF_GLOBAL
   // long-sequence build: buffers are taken from LDS while they fit (in priority order), then from the workgroup's
   // slice of the global scratch; pointers are generic, the hardware routes each flat access by aperture
@@ -64,16 +64,16 @@ __global__ void __launch_bounds__(NW_ > 0 ? NW_ * 64 : 512) encoder_bwd_kernel(c
   bX = carve(szA); bQN = carve(szA); bQ = carve(szA); bK = carve(szA);
   bV = carve(szA); bO = carve(szA); bG = carve(szA); bT = carve(szA + kSlack);
   S1 = carve(szS); S2 = carve(szS + kSlack);
-  lds_i* s_in = (lds_i*)tail;
-  lds_f* s_keep = tail + LP;
-  lds_i* s_pid = (lds_i*)(tail + 2 * LP);
-  lds_i* s_nid = (lds_i*)(tail + 3 * LP);
-  lds_i* s_fk = (lds_i*)(tail + 4 * LP);
-  lds_i* s_pfk = (lds_i*)(tail + 5 * LP);
-  lds_i* s_nfk = (lds_i*)(tail + 6 * LP);
-  lds_f* s_dpl = tail + 7 * LP;
-  lds_f* s_dnl = tail + 8 * LP;
-  lds_f* s_misc = tail + 10 * LP;        // 64
+  lds_i* s_in = (lds_i*)(tail + kRowIn * LP);
+  lds_f* s_keep = tail + kRowKeep * LP;
+  lds_i* s_pid = (lds_i*)(tail + kRowPid * LP);
+  lds_i* s_nid = (lds_i*)(tail + kRowNid * LP);
+  lds_i* s_fk = (lds_i*)(tail + kRowFk * LP);
+  lds_i* s_pfk = (lds_i*)(tail + kRowPfk * LP);
+  lds_i* s_nfk = (lds_i*)(tail + kRowNfk * LP);
+  lds_f* s_dpl = tail + kRowDpl * LP;
+  lds_f* s_dnl = tail + kRowDnl * LP;
+  lds_f* s_misc = tail + (kHeadRows + 1) * LP;        // 64
   lds_f* s_ln = s_misc + 64;             // LayerNorm parameter cache
   lds_f* s_lng = s_ln + ln_cache_floats(ly.n_blocks);   // LayerNorm parameter-gradient accumulators (same indexing)
   __syncthreads();
@@ -165,10 +165,7 @@ __global__ void __launch_bounds__(NW_ > 0 ? NW_ * 64 : 512) encoder_bwd_kernel(c
       if (in) {
         if (fused) {
           const float pl = a.c_pl[rowbase + t], nl = a.c_nl[rowbase + t];     // (not behind `pid != 0`: same round trip)
-          if (pid != 0) {
-            dp = sigmoid_f(pl) - 1.0f;
-            dn = sigmoid_f(nl);
-          }
+          bce_dlogits(pid, pl, nl, dp, dn);
         } else {
           if (a.d_pos) dp = a.d_pos[rowbase + t];
           if (a.d_neg) dn = a.d_neg[rowbase + t];

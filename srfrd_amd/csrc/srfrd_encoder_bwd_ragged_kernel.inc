@@ -45,7 +45,7 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
   constexpr int L = 50, D = 50, LP = 64, DK = 52, DS = 54, NT = 4, MT = 4;
   constexpr int R = 52, SZ = R * DS, SLD = R + 2, SH = kRagSH;
   static_assert(SH == LP - R && R * SLD <= SZ + 2 * R, "slot geometry");
-  static_assert(kRagBwdWork == SH * DS + 6 * SZ + 13 * LP, "working set");
+  static_assert(kRagBwdWork == SH * DS + 6 * SZ + (kHeadRows + 4) * LP, "working set");
   constexpr bool CV2 = true;
   constexpr int CIT = (R * (D / 2) + nthr - 1) / nthr;
   constexpr int PIT = (R * (R / 2) + nthr - 1) / nthr;
@@ -53,19 +53,19 @@ __device__ __forceinline__ void rag_bwd_seq(const EncArgs& a, const RagBwdLds& m
 #pragma unroll
   for (int s = 0; s < 6; ++s) slot[s] = m.base + SH * DS + s * SZ;
   lds_f* tail = m.base + SH * DS + 6 * SZ;
-  lds_i* s_in = (lds_i*)tail;            // per-position arrays (position coordinates)
-  lds_f* s_keep = tail + LP;
-  lds_i* s_pid = (lds_i*)(tail + 2 * LP);
-  lds_i* s_nid = (lds_i*)(tail + 3 * LP);
-  lds_i* s_fk = (lds_i*)(tail + 4 * LP);
-  lds_i* s_pfk = (lds_i*)(tail + 5 * LP);
-  lds_i* s_nfk = (lds_i*)(tail + 6 * LP);
-  lds_f* s_dpl = tail + 7 * LP;
-  lds_f* s_dnl = tail + 8 * LP;
-  lds_f* s_delta = tail + 9 * LP;
-  lds_f* s_brep = tail + 10 * LP;        // t0 P_i,rep of the block being walked
-  lds_f* s_dummy = tail + 11 * LP;       // 64 scratch words: where branch-free epilogues store what must not land anywhere
-  lds_f* s_misc = tail + 12 * LP;        // 64
+  lds_i* s_in = (lds_i*)(tail + kRowIn * LP);   // per-position arrays (position coordinates)
+  lds_f* s_keep = tail + kRowKeep * LP;
+  lds_i* s_pid = (lds_i*)(tail + kRowPid * LP);
+  lds_i* s_nid = (lds_i*)(tail + kRowNid * LP);
+  lds_i* s_fk = (lds_i*)(tail + kRowFk * LP);
+  lds_i* s_pfk = (lds_i*)(tail + kRowPfk * LP);
+  lds_i* s_nfk = (lds_i*)(tail + kRowNfk * LP);
+  lds_f* s_dpl = tail + kRowDpl * LP;
+  lds_f* s_dnl = tail + kRowDnl * LP;
+  lds_f* s_delta = tail + kHeadRows * LP;
+  lds_f* s_brep = tail + (kHeadRows + 1) * LP;        // t0 P_i,rep of the block being walked
+  lds_f* s_dummy = tail + (kHeadRows + 2) * LP;       // 64 scratch words: where branch-free epilogues store what must not land anywhere
+  lds_f* s_misc = tail + (kHeadRows + 3) * LP;        // 64
   lds_f* s_ln = m.s_ln;
   lds_f* s_lng = m.s_lng;
   const float* P = a.dense;
@@ -695,7 +695,7 @@ template <int K_, int DI_>
 __device__ __forceinline__ void rag_seam_handoff(const RagBwdLds& m, const RagSeam& hs, int W, int tid) {
   constexpr int nthr = 512, L = 50, D = 50, LP = 64, DS = 54, R = 52, SZ = R * DS, SH = kRagSH;
   constexpr int dout = (K_ == SRFRD_SRFR) ? DI_ : D;
-  constexpr int oX = SH * DS, oG = oX + kRagSeamG * SZ, oT = oX + 6 * SZ, nT = 9 * LP;
+  constexpr int oX = SH * DS, oG = oX + kRagSeamG * SZ, oT = oX + 6 * SZ, nT = kHeadRows * LP;
   lds_f* base = m.base;
   const int krp = hs.t0 >= 1 ? hs.t0 - 1 : 0;
   const int r0 = ((krp + SH) >> 4) << 4;
@@ -719,15 +719,15 @@ __device__ __forceinline__ void rag_seam_handoff(const RagBwdLds& m, const RagSe
   if (tid < LP) {
     lds_f* tail = base + oT;
     lds_i* ti = (lds_i*)tail;
-    ti[tid] = hs.id;
-    tail[LP + tid] = hs.id != 0 ? 1.f : 0.f;
-    ti[2 * LP + tid] = hs.pid;
-    ti[3 * LP + tid] = hs.nid;
-    ti[4 * LP + tid] = hs.fk;
-    ti[5 * LP + tid] = hs.pfk;
-    ti[6 * LP + tid] = hs.nfk;
-    tail[7 * LP + tid] = hs.dp;
-    tail[8 * LP + tid] = hs.dn;
+    ti[kRowIn * LP + tid] = hs.id;
+    tail[kRowKeep * LP + tid] = hs.id != 0 ? 1.f : 0.f;
+    ti[kRowPid * LP + tid] = hs.pid;
+    ti[kRowNid * LP + tid] = hs.nid;
+    ti[kRowFk * LP + tid] = hs.fk;
+    ti[kRowPfk * LP + tid] = hs.pfk;
+    ti[kRowNfk * LP + tid] = hs.nfk;
+    tail[kRowDpl * LP + tid] = hs.dp;
+    tail[kRowDnl * LP + tid] = hs.dn;
   }
 }
 

@@ -59,17 +59,17 @@ __global__ void __launch_bounds__(kSlotWaves * 64, (L_ <= 52 ? 4 : 2)) encoder_b
 #pragma unroll
   for (int s = 0; s < 6; ++s) slot[s] = base + s * SZ;
   lds_f* tail = base + 6 * SZ;
-  lds_i* s_in = (lds_i*)tail;
-  lds_f* s_keep = tail + LP;
-  lds_i* s_pid = (lds_i*)(tail + 2 * LP);
-  lds_i* s_nid = (lds_i*)(tail + 3 * LP);
-  lds_i* s_fk = (lds_i*)(tail + 4 * LP);
-  lds_i* s_pfk = (lds_i*)(tail + 5 * LP);
-  lds_i* s_nfk = (lds_i*)(tail + 6 * LP);
-  lds_f* s_dpl = tail + 7 * LP;
-  lds_f* s_dnl = tail + 8 * LP;
-  lds_f* s_delta = tail + 9 * LP;        // do_i . o_i of the block being walked
-  lds_f* s_misc = tail + 11 * LP;        // 64
+  lds_i* s_in = (lds_i*)(tail + kRowIn * LP);
+  lds_f* s_keep = tail + kRowKeep * LP;
+  lds_i* s_pid = (lds_i*)(tail + kRowPid * LP);
+  lds_i* s_nid = (lds_i*)(tail + kRowNid * LP);
+  lds_i* s_fk = (lds_i*)(tail + kRowFk * LP);
+  lds_i* s_pfk = (lds_i*)(tail + kRowPfk * LP);
+  lds_i* s_nfk = (lds_i*)(tail + kRowNfk * LP);
+  lds_f* s_dpl = tail + kRowDpl * LP;
+  lds_f* s_dnl = tail + kRowDnl * LP;
+  lds_f* s_delta = tail + kHeadRows * LP;        // do_i . o_i of the block being walked
+  lds_f* s_misc = tail + (kHeadRows + 2) * LP;        // 64
   lds_f* s_ln = s_misc + 64;             // LayerNorm parameter cache
   lds_f* s_lng = s_ln + ln_cache_floats(ly.n_blocks);   // LayerNorm parameter-gradient accumulators (same indexing)
   __syncthreads();
@@ -147,10 +147,7 @@ __global__ void __launch_bounds__(kSlotWaves * 64, (L_ <= 52 ? 4 : 2)) encoder_b
       if (in) {
         if (a.fused_bce) {                   // fused masked BCE (trainer.py:36-38): both terms indexed by pos != 0
           const float pl = a.c_pl[rowbase + t], nl = a.c_nl[rowbase + t];
-          if (pid != 0) {
-            dp = sigmoid_f(pl) - 1.0f;
-            dn = sigmoid_f(nl);
-          }
+          bce_dlogits(pid, pl, nl, dp, dn);
         } else {                             // upstream logit gradients (the autograd path)
           if (a.d_pos && a.pos_ids) dp = a.d_pos[rowbase + t];
           if (a.d_neg && a.neg_ids) dn = a.d_neg[rowbase + t];
@@ -233,11 +230,7 @@ __global__ void __launch_bounds__(kSlotWaves * 64, (L_ <= 52 ? 4 : 2)) encoder_b
       };
       if (a.table16 != nullptr) chunks(std::true_type{});
       else chunks(std::false_type{});
-      if (dout < D)
-        for (int idx = tid; idx < L * (D - dout); idx += nthr) {
-          const int tt = idx / (D - dout), cc = dout + idx - tt * (D - dout);
-          sG[tt * DS + cc] = 0.f;
-        }
+      head_zero_cols(sG, DS, L, dout, D, tid, nthr);
     }
     __syncthreads();
     // Pass 2: item-table scatter (float atomics, no return): at most two contiguous row segments per wave-instruction
@@ -268,11 +261,7 @@ __global__ void __launch_bounds__(kSlotWaves * 64, (L_ <= 52 ? 4 : 2)) encoder_b
       }, [&](int p) { return ly.off_side + dfk + p; });
     // ---- last LayerNorm backward: dx -> sK, g * xhat -> sO; dgamma / dbeta as ones-row GEMMs
     ln_bwd_rows<false>(nw, sG, lnin, sK, sO, L, R, DS, dout, s_ln + (4 * ly.n_blocks) * 64);
-    if (dout < D)
-      for (int idx = tid; idx < L * (D - dout); idx += nthr) {
-        const int tt = idx / (D - dout), cc = dout + idx - tt * (D - dout);
-        sK[tt * DS + cc] = 0.f;
-      }
+    head_zero_cols(sK, DS, L, dout, D, tid, nthr);
     zero_pad_rows(sK);
     __syncthreads();
     gemm_tiles<0>(nw, 1, (dout + 15) >> 4, R, OnesRow{}, Mat{sG, DS},

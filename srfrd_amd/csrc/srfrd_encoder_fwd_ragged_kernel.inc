@@ -122,14 +122,8 @@ __device__ __forceinline__ int rag_take(const EncArgs& a, lds_i* scr, int iter, 
 // that every lane of the head pass executes)
 __device__ __forceinline__ float softplus_fast(float z) { return fmaxf(z, 0.f) + __logf(1.0f + __expf(-fabsf(z))); }
 
-// The fused masked BCE's logit gradients (trainer.py:36-38: both terms indexed by pos != 0) and what they send back into the
-// head: one definition for the backward's head and the train kernel's forward head (SEAM_), so that both contract the same way.
-__device__ __forceinline__ void bce_dlogits(int pid, float pl, float nl, float& dp, float& dn) {
-  if (pid != 0) {
-    dp = sigmoid_f(pl) - 1.0f;
-    dn = sigmoid_f(nl);
-  }
-}
+// What the fused masked BCE's logit gradients (bce_dlogits: srfrd_enc_bwd_head.h) send back into the head: one definition for
+// the backward's head and the train kernel's forward head (SEAM_), so that both contract the same way.
 // d hidden[t][c] of a column with target rows: the upstream gradient (0 under the fused BCE) plus dp * (positive row) +
 // dn * (negative row)
 __device__ __forceinline__ float head_dh(float up, float dp, float pv, float dn, float nv) {

@@ -2,7 +2,9 @@
 
 Each forward source builds its own ``ItemTable{a.table, a.table16}`` gather and each backward source carries its own copy of
 the two-instantiation target gather (2-byte loads, the ``item ? shadow : side`` select of SRFRN's fake channel, per-kernel chunk
-and tail arithmetic); the ``srfrd_long::`` builds compile the same sources a second time.  tests/test_gpu_bf16_table.py meets
+and tail arithmetic); the ``srfrd_long::`` builds compile the same sources a second time.  The backward sources share the
+order of their per-position arrays, ``bce_dlogits`` and the zero fill (``srfrd_enc_bwd_head.h``), not the gather: written as one
+function it changed every kernel's instruction schedule.  tests/test_gpu_bf16_table.py meets
 the ragged pair and the <50,32,8> first-generation pair; the cases below meet the rest: every shape and switch already runs in
 fp32 (test_gpu_long.py, test_gpu_train.py, test_gpu_heads.py, test_encoder_plan.py) - the only new input is table_bf16 = 1.
 
