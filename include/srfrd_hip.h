@@ -239,6 +239,21 @@ int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* item_table, c
                               float* grad_table, float* table_contrib, float* grad_slabs,
                               float* scratch, int64_t scratch_floats,
                               const int32_t* sched, int sched_mode, void* stream);
+/* [device] srfrd_encoder_train_sched for the fused BCE step WITHOUT srfrd_seq_order in front of it and without its workspace:
+ * pair_stride > 0 asks for the length order of sched_mode 1 with that stride, and every workgroup finds the batch's first
+ * non-pad positions from input_ids itself, as its first instructions (B <= 1024; larger batches: no schedule, as there);
+ * pair_stride 0: no schedule; < 0, or input_ids not 16-byte aligned: SRFRD_E_ARG.  The same sequence -> workgroup assignment as srfrd_seq_order +
+ * srfrd_encoder_train_sched, so the same results bit for bit.  Takes no scratch (the kernel has not read it since the
+ * forward -> backward hand-off stays on chip) and no upstream gradients: fused_bce as there. */
+int srfrd_encoder_train_ranked(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
+                               const int64_t* input_ids, const int64_t* fake_ids,
+                               const int64_t* pos_ids, const int64_t* pos_fake,
+                               const int64_t* neg_ids, const int64_t* neg_fake,
+                               int B, int L, double dropout_p, uint32_t seed, const uint32_t* seed_dev, int64_t seq_index0,
+                               float* hidden, float* pos_logits, float* neg_logits,
+                               float* save_x, float* save_h1, float* save_aux, float* loss_part,
+                               int fused_bce, float* grad_table, float* table_contrib, float* grad_slabs,
+                               int pair_stride, void* stream);
 
 /* Inference forward for ranking: the encoder state of the LAST position only, hidden_last (B, d_out) - what the reference's
  * predict() takes from log2feats (SRFR_model.py:668-681: `log_feats[:, -1, :]`).  Same arithmetic as srfrd_encoder_fwd in

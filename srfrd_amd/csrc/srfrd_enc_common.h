@@ -44,9 +44,11 @@ struct EncArgs {
   const int* sched;    // int32 workspace, layout below (kSched*)
   int sched_mode;      // 0 none, 1 length order (workgroup x takes the sequence of rank perm(x): see rag_take)
   int ragged_off;      // diagnostic: the ragged kernels compute every row (t0 = 0), as the full kernels do
-  // (was the ragged train kernel's forward -> backward buffer for d hidden; that hand-off stays in LDS now and no kernel reads
-  // this.  The field keeps the argument block's size, and with it every kernel's implicit-argument offsets, as they were.)
-  float* head_dh;
+  // ragged train kernel, srfrd_encoder_train_ranked: > 0 = length order with this pair stride and NO workspace - every workgroup
+  // finds the batch's first-item positions itself (rag_rank_batch); 0: `sched` decides.  (The two words stand where a pointer
+  // no kernel read any more stood: the argument block keeps its size, every kernel its implicit-argument offsets.)
+  int rank_G;
+  int rank_pad_;
 };
 
 // Schedule workspace (int32), filled by srfrd_seq_order for ONE batch:

@@ -109,13 +109,107 @@ __device__ __forceinline__ int rag_select(const RagT0& t0v, int B, int want, lds
 // One workgroup's next sequence (wave-uniform; -1: none left).  Length order: the first G workgroups (one per CU, in dispatch
 // order) take the G longest sequences, the next G the shortest ascending - the workgroup that joins the longest sequence's CU
 // brings the shortest one - everything else in descending order.
+__device__ __forceinline__ int rag_want(int x, int G, int B) { return x < G ? x : (x < 2 * G ? B - 1 - (x - G) : x - G); }
 __device__ __forceinline__ int rag_take(const EncArgs& a, lds_i* scr, int iter, int tid, const RagT0& t0v) {
   const int x = (int)blockIdx.x + iter * (int)gridDim.x;
   if (x >= a.B) return -1;
   if (!rag_ordered(a)) return x;
-  const int G = a.sched[kSchedG];
-  const int want = x < G ? x : (x < 2 * G ? a.B - 1 - (x - G) : x - G);
-  return rag_select(t0v, a.B, want, scr, tid);
+  return rag_select(t0v, a.B, rag_want(x, a.sched[kSchedG], a.B), scr, tid);
+}
+
+// The batch's first-item positions WITHOUT srfrd_seq_order's launch (srfrd_encoder_train_ranked): every workgroup reads the
+// whole id plane itself - B * 50 ids, flat, 16 bytes (two ids) per lane: thread t takes the pairs t, t + 512, ... (coalesced: a
+// wave reads 128 consecutive ids; 8-byte loads run at 0.6 of this rate) - and all it keeps of an id is whether it is zero.  A
+// round costs a wave two compares and four lane writes: the ballots of its 25 rounds collect in four registers (lane j: round
+// j) and go to LDS in one store each, where they form two bitmaps in pair order - bit q of the first: id 2 q is not zero, of
+// the second: id 2 q + 1.  A sequence's 50 ids are the pairs 25 b .. 25 b + 24; thread b takes those 25 bits from either bitmap
+// and counts the zeros in front.  All loads of the first 512 sequences are requested before anything waits; zero_fill() - the
+// caller's LDS fill, which must cover bm - runs in their shadow.  bm: kRagRankWords LDS words, left zeroed again.  Ends WITHOUT
+// a barrier: the caller's next one orders the last stores.  Same values as srfrd_seq_order writes (50 for a sequence of pads; a
+// zero behind the first item is no pad), so rag_select picks the same sequences.  B <= 512 * kRagChunks; ids 16-byte aligned.
+constexpr int kRagRankHalf = kRagChunks * 512 * 25 / 32 + 2;      // words of one bitmap (+ 2: a window is read as two words)
+constexpr int kRagRankWords = 2 * kRagRankHalf;
+// v_writelane_b32 (value, lane, old): clang has the read builtin only; the intrinsic by its own name
+extern "C" __device__ int srfrd_writelane(int, int, int) __asm("llvm.amdgcn.writelane.i32");
+typedef long long RagIdPair __attribute__((ext_vector_type(2)));
+template <class ZF>
+__device__ __forceinline__ RagT0 rag_rank_batch(const int64_t* __restrict__ ids, int B, lds_i* bm, int tid, const ZF& zero_fill) {
+  constexpr int L = 50, NJ = L / 2;              // 512 sequences are NJ rounds of 512 id pairs
+  static_assert(NJ <= 64 && kRagRankWords <= 4 * 512, "one lane per round; four words per thread to clear");
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n2 = B * NJ;                         // id pairs of the plane
+  const RagIdPair* __restrict__ pairs = reinterpret_cast<const RagIdPair*>(ids);
+  RagIdPair v[NJ];
+  auto request = [&](int c) {
+    if ((c + 1) * NJ * 512 <= n2) {              // (uniform) 512 whole sequences: nothing to clamp
+      const unsigned off = (unsigned)tid << 4;
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        v[j] = *reinterpret_cast<const RagIdPair*>(reinterpret_cast<const char*>(pairs + (c * NJ + j) * 512) + off);
+    } else {
+      // (a round's first pair and the pairs left from there are scalars, the lane's share a 32-bit byte offset.  Clamped: every
+      // address is one of the plane's; what a lane behind the batch reads lands in bits behind the last sequence's, which
+      // nobody looks at)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const int first = min((c * NJ + j) * 512, n2 - 1);
+        const unsigned off = (unsigned)min(tid, n2 - 1 - first) << 4;
+        v[j] = *reinterpret_cast<const RagIdPair*>(reinterpret_cast<const char*>(pairs + first) + off);
+      }
+      asm volatile("");                          // (keeps the two forms apart: merged, every load waits for a selected 64-bit address)
+    }
+  };
+  auto collect = [&](int c) {
+    int e_lo = 0, e_hi = 0, o_lo = 0, o_hi = 0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const unsigned long long me = __ballot(v[j].x != 0), mo = __ballot(v[j].y != 0);
+      e_lo = srfrd_writelane((int)(unsigned)me, j, e_lo);
+      e_hi = srfrd_writelane((int)(unsigned)(me >> 32), j, e_hi);
+      o_lo = srfrd_writelane((int)(unsigned)mo, j, o_lo);
+      o_hi = srfrd_writelane((int)(unsigned)(mo >> 32), j, o_hi);
+    }
+    if (lane < NJ) {                             // pairs ((c NJ + lane) 8 + wave) 64 ..: that 64-bit word of either bitmap
+      const int w = (((c * NJ + lane) << 3) + wave) << 1;
+      bm[w] = e_lo;
+      bm[w + 1] = e_hi;
+      bm[kRagRankHalf + w] = o_lo;
+      bm[kRagRankHalf + w + 1] = o_hi;
+    }
+  };
+  request(0);
+  __builtin_amdgcn_sched_barrier(0);
+  zero_fill();
+  __syncthreads();
+  collect(0);
+#pragma unroll 1
+  for (int c = 1; c < kRagChunks; ++c)
+    if (c * 512 < B) {                           // (uniform)
+      request(c);
+      collect(c);
+    }
+  __syncthreads();
+  RagT0 t;
+#pragma unroll
+  for (int c = 0; c < kRagChunks; ++c) {
+    const int b = c * 512 + tid;
+    int t0 = L;
+    if (b < B) {                                 // bits 25 b .. 25 b + 24 of either bitmap
+      const int w = (b * NJ) >> 5, sh = (b * NJ) & 31;
+      const unsigned long long we = ((unsigned long long)(unsigned)bm[w + 1] << 32) | (unsigned)bm[w];
+      const unsigned long long wo = ((unsigned long long)(unsigned)bm[kRagRankHalf + w + 1] << 32) | (unsigned)bm[kRagRankHalf + w];
+      const unsigned xe = (unsigned)(we >> sh) & ((1u << NJ) - 1u), xo = (unsigned)(wo >> sh) & ((1u << NJ) - 1u);
+      const int pe = xe ? 2 * __builtin_ctz(xe) : L, po = xo ? 2 * __builtin_ctz(xo) + 1 : L;
+      t0 = min(pe, po);
+    }
+    t.v[c] = t0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i * 512 + tid < kRagRankWords) bm[i * 512 + tid] = 0;
+  return t;
 }
 
 // softplus on the hardware exp / log (1e-7 absolute: the loss is compared at 1e-4; log1pf / expf expand to ~200 instructions

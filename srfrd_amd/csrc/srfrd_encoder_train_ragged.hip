@@ -28,12 +28,22 @@ __global__ void __launch_bounds__(512, 4) encoder_train_ragged_kernel(const EncA
   constexpr int W = kRagFwdWork > kRagBwdWork ? kRagFwdWork : kRagBwdWork;
   int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const RagT0 t0v = rag_load_t0(a, tid);
   lds_f* base = (lds_f*)smem;
-  {
+  auto zero_fill = [&]() {
     const int total = (int)train_ragged_lds_floats(ly.n_blocks);
     for (int i = tid; i < total; i += nthr) base[i] = 0.f;
+  };
+  // length order: from the schedule workspace, or (srfrd_encoder_train_ranked) from the id plane itself - no launch in front
+  const bool ranked = a.rank_G > 0 && a.B <= 512 * kRagChunks;
+  RagT0 t0v;
+  if (ranked) {
+    t0v = rag_rank_batch(a.in_ids, a.B, (lds_i*)base, tid, zero_fill);
+  } else {
+    t0v = rag_load_t0(a, tid);
+    zero_fill();
   }
+  // pair stride of the length order; 0: workgroup x takes sequence x
+  const int G = __builtin_amdgcn_readfirstlane(ranked ? a.rank_G : (rag_ordered(a) ? a.sched[kSchedG] : 0));
   RagFwdLds fm;
   fm.bXS = base;
   fm.bQN = base + LP * SLD;
@@ -63,7 +73,9 @@ __global__ void __launch_bounds__(512, 4) encoder_train_ragged_kernel(const EncA
       for (int i = tid; i < W; i += nthr) base[i] = 0.f;
       __syncthreads();
     }
-    const int b = __builtin_amdgcn_readfirstlane(rag_take(a, (lds_i*)fm.bXS, iter, tid, t0v));
+    const int x = (int)blockIdx.x + iter * (int)gridDim.x;      // rag_take, with the lengths and the stride found above
+    const int take = x >= a.B ? -1 : (G > 0 ? rag_select(t0v, a.B, rag_want(x, G, a.B), (lds_i*)fm.bXS, tid) : x);
+    const int b = __builtin_amdgcn_readfirstlane(take);
     if (b < 0) break;
     const RagSeam hs = rag_fwd_seq<K_, 1, DI_, true>(a, fm, b, tid, wave, seed);
     // (rag_fwd_seq ended with a workgroup barrier: its checkpoint stores are visible to every wave of the workgroup, and
@@ -93,20 +105,19 @@ extern "C" int64_t srfrd_train_scratch_floats(const srfrd_layout* lay, int B, in
   return (int64_t)B * L * (lay->d_out + (lay->kind == SRFRD_SRFRN ? 2 : 0));
 }
 
-extern "C" int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
-                                         const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids,
-                                         const int64_t* pos_fake, const int64_t* neg_ids, const int64_t* neg_fake, int B, int L,
-                                         double dropout_p, uint32_t seed, const uint32_t* seed_dev, int64_t seq_index0,
-                                         float* hidden, float* pos_logits, float* neg_logits, float* save_x, float* save_h1,
-                                         float* save_aux, float* loss_part, const float* d_hidden, const float* d_pos,
-                                         const float* d_neg, int fused_bce, float* grad_table, float* table_contrib,
-                                         float* grad_slabs, float* scratch, int64_t scratch_floats, const int32_t* sched,
-                                         int sched_mode, void* stream) {
-  if (sched_mode < 0 || sched_mode > 1 || (sched_mode != 0 && !sched)) return SRFRD_E_ARG;
+// both entry points: `sched` / `sched_mode` as srfrd_encoder_train_sched takes them, or rank_G > 0 and no workspace
+static int train_launch(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
+                        const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids, const int64_t* pos_fake,
+                        const int64_t* neg_ids, const int64_t* neg_fake, int B, int L, double dropout_p, uint32_t seed,
+                        const uint32_t* seed_dev, int64_t seq_index0, float* hidden, float* pos_logits, float* neg_logits,
+                        float* save_x, float* save_h1, float* save_aux, float* loss_part, const float* d_hidden, int fused_bce,
+                        float* grad_table, float* table_contrib, float* grad_slabs, float* scratch, int64_t scratch_floats,
+                        bool demand_scratch, const int32_t* sched, int sched_mode, int rank_G, void* stream) {
   const int sw = read_switches();
   EncArgs a = {};
   a.sched = sched_mode != 0 ? sched : nullptr;
   a.sched_mode = a.sched ? sched_mode : 0;
+  a.rank_G = rank_G;
   a.ragged_off = (sw & SRFRD_SW_RAGGED_FULL_ROWS) != 0;
   const int rc = fill_args(a, lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L,
                            dropout_p, seed, seed_dev, seq_index0);
@@ -121,11 +132,42 @@ extern "C" int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* it
                    (dropout_p > 0.0 ? SRFRD_PLAN_DROPOUT : 0) | (fused_bce && !d_hidden ? SRFRD_PLAN_FUSED_BCE : 0);
   const KernelPlan k = encoder_plan(*lay, B, L, mode, sw, num_cu(), scratch ? scratch_floats : 0).train;
   if (k.rc) return k.rc;
-  if (!scratch || scratch_floats < srfrd_train_scratch_floats(lay, B, L)) return SRFRD_E_ARG;
+  if (demand_scratch && (!scratch || scratch_floats < srfrd_train_scratch_floats(lay, B, L))) return SRFRD_E_ARG;
   a.hidden = hidden; a.pos_logits = pos_logits; a.neg_logits = neg_logits;
   a.save_x = save_x; a.save_h1 = save_h1; a.save_aux = save_aux; a.loss_part = loss_part;
   a.c_hidden = hidden; a.c_pl = pos_logits; a.c_nl = neg_logits; a.c_save_x = save_x; a.c_save_h1 = save_h1; a.c_save_aux = save_aux;
   a.fused_bce = 1;
   a.grad_table = grad_table; a.grad_slabs = grad_slabs; a.contrib = table_contrib;
   return launch_train_ragged(k, a, stream);
+}
+
+extern "C" int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
+                                         const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids,
+                                         const int64_t* pos_fake, const int64_t* neg_ids, const int64_t* neg_fake, int B, int L,
+                                         double dropout_p, uint32_t seed, const uint32_t* seed_dev, int64_t seq_index0,
+                                         float* hidden, float* pos_logits, float* neg_logits, float* save_x, float* save_h1,
+                                         float* save_aux, float* loss_part, const float* d_hidden, const float* d_pos,
+                                         const float* d_neg, int fused_bce, float* grad_table, float* table_contrib,
+                                         float* grad_slabs, float* scratch, int64_t scratch_floats, const int32_t* sched,
+                                         int sched_mode, void* stream) {
+  if (sched_mode < 0 || sched_mode > 1 || (sched_mode != 0 && !sched)) return SRFRD_E_ARG;
+  (void)d_pos; (void)d_neg;
+  return train_launch(lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L, dropout_p,
+                      seed, seed_dev, seq_index0, hidden, pos_logits, neg_logits, save_x, save_h1, save_aux, loss_part, d_hidden,
+                      fused_bce, grad_table, table_contrib, grad_slabs, scratch, scratch_floats, true, sched, sched_mode, 0, stream);
+}
+
+// srfrd_encoder_train_sched without srfrd_seq_order in front of it: pair_stride > 0 asks for the length order of sched_mode 1
+// and every workgroup ranks the batch from input_ids itself (rag_rank_batch); 0: no schedule.  No scratch: nothing reads it.
+extern "C" int srfrd_encoder_train_ranked(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
+                                          const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids,
+                                          const int64_t* pos_fake, const int64_t* neg_ids, const int64_t* neg_fake, int B, int L,
+                                          double dropout_p, uint32_t seed, const uint32_t* seed_dev, int64_t seq_index0,
+                                          float* hidden, float* pos_logits, float* neg_logits, float* save_x, float* save_h1,
+                                          float* save_aux, float* loss_part, int fused_bce, float* grad_table,
+                                          float* table_contrib, float* grad_slabs, int pair_stride, void* stream) {
+  if (pair_stride < 0 || (reinterpret_cast<uintptr_t>(input_ids) & 15) != 0) return SRFRD_E_ARG;      // (the scan reads two ids per lane)
+  return train_launch(lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L, dropout_p,
+                      seed, seed_dev, seq_index0, hidden, pos_logits, neg_logits, save_x, save_h1, save_aux, loss_part, nullptr,
+                      fused_bce, grad_table, table_contrib, grad_slabs, nullptr, 0, false, nullptr, 0, pair_stride, stream);
 }

@@ -4,7 +4,7 @@
 
 as five stream-ordered launches on persistent buffers (encoder_fwd, encoder_bwd, reduce_dense [+ loss], adam_step,
 pack_weights [+ optimizer-state advance for the next step]; single rank at seq_len 50: encoder_fwd and encoder_bwd are ONE
-launch, srfrd_encoder_train_sched), captured into one HIP graph when no collective sits in the middle.  Differences from the reference
+launch, srfrd_encoder_train_ranked), captured into one HIP graph when no collective sits in the middle.  Differences from the reference
 loop, all behaviour-preserving: the loss is never synchronised to the host (``loss`` stays a device scalar), the
 ``l2_emb * ||p||`` terms (trainer.py:39: one Frobenius norm per parameter tensor) cost two small launches and one pass over
 the gradient when l2_emb != 0 and nothing at the reference's 0.0, and dropout masks come from the coordinate hash of csrc/srfrd_rng.h instead of torch's Bernoulli stream.
@@ -317,7 +317,7 @@ class FusedTrainer:
         self.sched_mode = min(1, int(os.environ.get("SRFRD_SCHED", "1"))) if ragged else 0
         self.sched = torch.zeros(int(_lib.lib().srfrd_sched_ints(B)), device=dev, dtype=torch.int32) if self.sched_mode else None
         self.pair_stride = max(1, _lib.lib().srfrd_bwd_grid(C.byref(lay), 1 << 30, L) // 2)      # CUs: workgroups of the first round
-        # single rank: forward + backward as one launch where the plan has a train kernel (srfrd_encoder_train_sched), asked
+        # single rank: forward + backward as one launch where the plan has a train kernel (srfrd_encoder_train_ranked), asked
         # at every enqueue under the environment's switches then; False: always the two launches (A/B comparisons)
         self._train_mode = fused
         self.train_launch = True
@@ -485,17 +485,20 @@ class FusedTrainer:
                                                  *self._sched_args()), "srfrd_encoder_bwd_sched")
 
     def _launch_train(self, slot):
-        """forward and BCE backward of every sequence as one launch"""
-        check(_lib.lib().srfrd_encoder_train_sched(*self._enc_args(slot, True), ptr(self.loss_part), *self._bwd_args(None, self.contrib),
-                                                   *self._sched_args()), "srfrd_encoder_train_sched")
+        """forward and BCE backward of every sequence as one launch; the kernel ranks the batch by length itself (no
+        srfrd_seq_order in front, `sched` untouched): the two launches' sequence -> workgroup order, so their bits"""
+        check(_lib.lib().srfrd_encoder_train_ranked(*self._enc_args(slot, True), ptr(self.loss_part), 1, ptr(self.grad),
+                                                    ptr(self.contrib), ptr(self.slabs), self.pair_stride if self.sched_mode else 0,
+                                                    self._stream()), "srfrd_encoder_train_ranked")
 
-    def _enqueue_prologue(self, slot):
-        """ahead of the forward: the norms of the parameters it uses (l2_emb), the batch's sequence -> workgroup schedule"""
+    def _enqueue_prologue(self, slot, schedule: bool = True):
+        """ahead of the forward: the norms of the parameters it uses (l2_emb), the batch's sequence -> workgroup schedule
+        (``schedule`` False: the launch that follows ranks the batch itself)"""
         L_, st = _lib.lib(), self._stream()
         if self.l2 != 0.0:
             check(L_.srfrd_l2_norms(ptr(self.flat), ptr(self.seg_off), ptr(self.seg_len), self.seg_off.numel(), self.n_tab,
                                     self.l2, ptr(self.l2_partial), ptr(self.l2buf), ptr(self.l2_dense), st), "srfrd_l2_norms")
-        if self.sched_mode:
+        if self.sched_mode and schedule:
             check(L_.srfrd_seq_order(ptr(self.ids_ring[slot][0]), self.B, self.L, self.pair_stride, ptr(self.sched), st),
                   "srfrd_seq_order")
 
@@ -605,7 +608,7 @@ class FusedTrainer:
             self._enqueue_ce_compute(slot)
         elif self.mode == "single" and self.train_launch and _lib.encoder_plan_train(
                 self.lay, self.B, self.L, self._train_mode, _lib.env_switches())[0]:
-            self._enqueue_prologue(slot)
+            self._enqueue_prologue(slot, schedule=False)
             self._launch_train(slot)
             self._enqueue_grad_tail(slot)
         else:
