@@ -443,6 +443,13 @@ int srfrd_l2_apply(float* grad, const float* param, int64_t i0, int64_t i1, int6
 
 int srfrd_loss_finalize(const float* stats, float* loss_out, void* stream);
 
+/* Which build is running: returns the wave mask the HOST code of this library was compiled with (-DSRFRD_SKEW=<mask>, the
+ * schedule-skew diagnostic build of srfrd_dev.h; 0 in the product) and, when out_dev is not NULL, launches one thread that
+ * stores the mask the DEVICE code was compiled with into out_dev[0].  Two builds loaded into one process carry the same
+ * symbol names: a handle whose host and device answers both name its own mask runs its own code objects
+ * (tests/test_gpu_skew_bits.py).  A launch failure reads as a negative return (-(hipError_t)), never as a mask. */
+int srfrd_skew_mask(uint32_t* out_dev, void* stream);
+
 /* get_Labels (reference SRFR_model.py:546-570) and SRFRN.predict's user label (:244); labels int64 (B).
  * kind = SRFRD_SRFU_B / _F / _R, or SRFRD_SRFRN for the predict label. */
 int srfrd_user_labels(int kind, const int64_t* fake_ids, int B, int L, int64_t* labels, void* stream);

@@ -88,6 +88,7 @@ SIGNATURES = {
     "srfrd_adamw_pack_step": (_i, [_LP, _P, _P, _P, _P, _i64, _i64, _i64, _OP, _d, _P, _P, _P, _P, _P, _P]),
     "srfrd_table_to_bf16": (_i, [_P, _i64, _P, _P]),
     "srfrd_loss_finalize": (_i, [_P, _P, _P]),
+    "srfrd_skew_mask": (_i, [_P, _P]),
     "srfrd_l2_norms": (_i, [_P, _P, _P, _i, _i64, _d, _P, _P, _P, _P]),
     "srfrd_l2_apply": (_i, [_P, _P, _i64, _i64, _i64, _P, _P, _P, _P]),
     "srfrd_user_labels": (_i, [_i, _P, _i, _i, _P, _P]),

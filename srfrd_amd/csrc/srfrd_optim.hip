@@ -452,6 +452,17 @@ __global__ void loss_finalize_kernel(const float* stats, float* loss_out) {
   if (threadIdx.x == 0 && blockIdx.x == 0) loss_out[0] = stats[0] / stats[2] + stats[1] / stats[2];
 }
 
+// the wave mask of the schedule-skew diagnostic build (srfrd_dev.h) this translation unit was compiled with; 0: the product
+#ifdef SRFRD_SKEW
+constexpr uint32_t kSkewMask = (uint32_t)(SRFRD_SKEW);
+#else
+constexpr uint32_t kSkewMask = 0u;
+#endif
+
+__global__ void skew_mask_kernel(uint32_t* out) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = kSkewMask;
+}
+
 }  // namespace srfrd
 
 using namespace srfrd;
@@ -630,6 +641,15 @@ extern "C" int srfrd_l2_apply(float* grad, const float* param, int64_t i0, int64
   hipLaunchKernelGGL(l2_apply_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, grad, param, i0, i1, n_table_pad, l2buf,
                      dense_scale, stats);
   return (int)hipGetLastError();
+}
+
+extern "C" int srfrd_skew_mask(uint32_t* out_dev, void* stream) {
+  if (out_dev != nullptr) {
+    hipLaunchKernelGGL(skew_mask_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, out_dev);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return -(int)e;
+  }
+  return (int)kSkewMask;
 }
 
 extern "C" int srfrd_loss_finalize(const float* stats, float* loss_out, void* stream) {

@@ -9,6 +9,10 @@ waves of the mask sleep ~2 us, so the others run far ahead inside the barrier in
 results under every mask; an unsynchronised read-early / write-late pair inside one interval fails the parity tests.
 (The first-generation backward's end-of-block buffer swap was such a pair: it showed up once in some hundred full-suite
 runs; under mask 0x0f0f it fails 43 of the 58 training tests every time.)
+
+__graft_entry__.build() itself links three of these libraries (0x0f0f over every unit; 0x5555 and 0xaaaa over the units without
+an encoder kernel, around the 0x0f0f encoder objects) and tests/test_gpu_skew_bits.py compares them with the product bit for
+bit inside one process, in seconds.  This tool stays the way to put the ENCODER kernels under the other nine masks.
 """
 import os
 import subprocess
