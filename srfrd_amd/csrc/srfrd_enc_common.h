@@ -1,5 +1,5 @@
 // Shared pieces of the fused encoder translation units (forward / backward): launch arguments, the LayerNorm
-// parameter cache, debug taps, host-side argument marshalling.
+// parameter cache, debug taps, the launchers' helpers.
 #pragma once
 #include <cstdlib>
 #include <type_traits>
@@ -266,47 +266,6 @@ __device__ __forceinline__ void tap(const EncArgs& a, int b, int slot, const lds
 // ================================================================================================
 // host side
 // ================================================================================================
-[[maybe_unused]] static int fill_args(EncArgs& a, const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
-                     const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids, const int64_t* pos_fake,
-                     const int64_t* neg_ids, const int64_t* neg_fake, int B, int L, double dropout_p, uint32_t seed,
-                     const uint32_t* seed_dev, int64_t seq_index0) {
-  if (!lay || !item_table || !dense || !packed || !input_ids || B <= 0 || L <= 0) return SRFRD_E_ARG;
-  if (lay->D > SRFRD_MAX_D || lay->n_heads < 1 || lay->D % lay->n_heads != 0 || lay->n_blocks > SRFRD_MAX_BLOCKS) return SRFRD_E_UNSUPPORTED;
-  if (L > lay->max_len) return SRFRD_E_ARG;
-  if (dropout_p < 0.0 || dropout_p >= 1.0) return SRFRD_E_ARG;
-  if (lay->kind == SRFRD_SRFRN && ((pos_ids && !pos_fake) || (neg_ids && !neg_fake))) return SRFRD_E_ARG;
-  Dims& d = a.dm;
-  d.kind = lay->kind; d.d_item = lay->d_item; d.d_fake = lay->d_fake; d.D = lay->D; d.d_out = lay->d_out;
-  d.n_labels = lay->n_labels; d.n_blocks = lay->n_blocks; d.n_items = lay->n_items; d.n_heads = lay->n_heads;
-  d.off_pos = (int)lay->off_pos; d.off_side = (int)lay->off_side;
-  d.blk0 = lay->n_blocks > 0 ? (int)lay->blk[0].ln1_w : 0;
-  d.blk_stride = blk_stride_of(lay->D);
-  for (int i = 0; i < lay->n_blocks; ++i) {        // the kernels recompute block offsets arithmetically: check the table agrees
-    const BlkOff o = blk_off(d.blk0 + i * d.blk_stride, lay->D);
-    const srfrd_block_off& t = lay->blk[i];
-    if (t.ln1_w != o.ln1_w || t.ln1_b != o.ln1_b || t.in_w != o.in_w || t.in_b != o.in_b || t.out_w != o.out_w ||
-        t.out_b != o.out_b || t.ln2_w != o.ln2_w || t.ln2_b != o.ln2_b || t.c1_w != o.c1_w || t.c1_b != o.c1_b ||
-        t.c2_w != o.c2_w || t.c2_b != o.c2_b)
-      return SRFRD_E_ARG;
-  }
-  d.off_lc_w = (int)lay->off_lc_w; d.off_lc_b = (int)lay->off_lc_b; d.off_ll_w = (int)lay->off_ll_w; d.off_ll_b = (int)lay->off_ll_b;
-  d.n_dense = (int)lay->n_dense;
-  a.table = lay->table_bf16 ? nullptr : (const float*)item_table;
-  a.table16 = lay->table_bf16 ? (const uint16_t*)item_table : nullptr;
-  a.dense = dense;
-  a.packed = packed;
-  a.in_ids = input_ids; a.fk_ids = fake_ids; a.pos_ids = pos_ids; a.pos_fk = pos_fake; a.neg_ids = neg_ids; a.neg_fk = neg_fake;
-  a.B = B; a.L = L;
-  a.seed = seed; a.seed_dev = seed_dev;
-  a.drop_on = dropout_p > 0.0;
-  double thr = dropout_p * 4294967296.0;
-  a.drop_thr = thr >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)thr;
-  a.drop_scale = (float)(1.0 / (1.0 - dropout_p));
-  a.seq0 = seq_index0;
-  a.qscale = (float)sqrt(1.0 / (double)(lay->D / lay->n_heads));
-  return 0;
-}
-
 // kind variant -> <K, DI>: f(std::integral_constant<int, v>) for a plan's variant v (kKindVariants[v] are the arguments)
 template <class F>
 static int with_variant(int v, F&& f) {
@@ -316,6 +275,15 @@ static int with_variant(int v, F&& f) {
     case 2: return f(std::integral_constant<int, 2>());
     default: return f(std::integral_constant<int, 3>());
   }
+}
+
+// a plan's kind variant and flag -> template arguments: f(K, DI, flag) as integral constants, usable as <K, DI, flag>
+template <class F>
+static int with_variant_flag(const KernelPlan& k, F&& f) {
+  return with_variant(k.variant, [&](auto v) {
+    constexpr KindVariant kv = kKindVariants[decltype(v)::value];
+    return with_flag(k.flag, [&](auto t) { return f(std::integral_constant<int, kv.K>(), std::integral_constant<int, kv.DI>(), t); });
+  });
 }
 
 // kind variant of a layout: the hidden-50, one-head specialisations cover these kinds and width splits (-1: none)

@@ -54,8 +54,43 @@ struct EncPlan {
   KernelPlan train;        // a training forward and its fused-BCE backward as ONE launch (srfrd_encoder_train_sched), or rc set
 };
 
+// One call of a launching entry point (srfrd_encoder_fwd* / _bwd* / _train_*), its arguments by name: what the entry point
+// does not take stays zero.  Host only, never a kernel argument: enc_run builds the kernels' EncArgs from it.
+struct EncCall {
+  const srfrd_layout* lay;
+  const void* item_table;
+  const float *dense, *packed;
+  const int64_t *input_ids, *fake_ids, *pos_ids, *pos_fake, *neg_ids, *neg_fake;
+  int B, L;
+  double dropout_p;
+  uint32_t seed;
+  const uint32_t* seed_dev;
+  int64_t seq_index0;
+  float *hidden, *pos_logits, *neg_logits, *save_x, *save_h1, *save_aux;   // the forward writes them, the backward reads them
+  float* loss_part;
+  const float *d_hidden, *d_pos, *d_neg;     // upstream gradients (the train pass takes none)
+  int fused_bce;
+  float *grad_table, *table_contrib, *grad_slabs, *scratch;
+  int64_t scratch_floats;
+  float* dbg;
+  int dbg_seq, last_only;
+  const int32_t* sched;
+  int sched_mode, rank_G;    // rank_G: srfrd_encoder_train_ranked's pair stride
+  bool demand_scratch;       // srfrd_encoder_train_sched: srfrd_train_scratch_floats or more, once the plan has a kernel
+  void* stream;
+};
+enum Pass { kForward, kBackward, kTrain };
+// The one path from a call to a launch (srfrd_encoder_fwd.hip): the shared refusals, the pass's own, the plan, the launch.
+// An entry point makes its own check (check_sched, the ranked step's pair stride), names its arguments and calls this.
+int enc_run(const EncCall& c, Pass pass);
+inline bool check_sched(const int32_t* sched, int sched_mode) { return sched_mode == 0 || (sched_mode == 1 && sched); }
+// a layout the fused kernels cover (enc_run and the plan queries answer SRFRD_E_UNSUPPORTED otherwise)
+inline bool layout_supported(const srfrd_layout& lay) {
+  return lay.D <= SRFRD_MAX_D && lay.n_heads >= 1 && lay.D % lay.n_heads == 0 && lay.n_blocks <= SRFRD_MAX_BLOCKS;
+}
+
 // mode: SRFRD_PLAN_* bits, switches: SRFRD_SW_* bits (read_switches), n_cu: CUs of the device, scratch_floats: the caller's
-// scratch (0 when none).  The layout is one fill_args accepted.
+// scratch (0 when none).  The layout is one layout_supported accepts.
 EncPlan encoder_plan(const srfrd_layout& lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats);
 // the instantiation's name as a kernel trace prints it (without spaces), e.g. "srfrd::encoder_fwd_ragged_kernel<0,1,50>"
 void plan_name(const KernelPlan& k, char* buf, int len);

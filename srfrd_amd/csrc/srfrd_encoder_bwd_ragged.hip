@@ -9,10 +9,7 @@
 namespace srfrd {
 
 int launch_bwd_ragged(const KernelPlan& k, const EncArgs& a, void* stream) {
-  return with_variant(k.variant, [&](auto v) {
-    constexpr KindVariant kv = kKindVariants[decltype(v)::value];
-    return with_flag(k.flag, [&](auto rmw) { return launch_enc(encoder_bwd_ragged_kernel<kv.K, kv.DI, decltype(rmw)::value>, k, stream, a); });
-  });
+  return with_variant_flag(k, [&](auto K, auto DI, auto rmw) { return launch_enc(encoder_bwd_ragged_kernel<K, DI, rmw>, k, stream, a); });
 }
 
 }  // namespace srfrd

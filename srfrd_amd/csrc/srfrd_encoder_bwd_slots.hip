@@ -8,13 +8,9 @@
 namespace srfrd {
 
 int launch_bwd_slots(const KernelPlan& k, const EncArgs& a, void* stream) {
-  return with_variant(k.variant, [&](auto v) {
-    constexpr KindVariant kv = kKindVariants[decltype(v)::value];
-    return with_flag(k.flag, [&](auto rmw) {
-      constexpr bool r = decltype(rmw)::value;
-      return k.form == kL50 ? launch_enc(encoder_bwd_slots_kernel<50, 50, kv.K, kv.DI, r>, k, stream, a)
-                            : launch_enc(encoder_bwd_slots_kernel<50, 100, kv.K, kv.DI, r>, k, stream, a);
-    });
+  return with_variant_flag(k, [&](auto K, auto DI, auto rmw) {
+    return k.form == kL50 ? launch_enc(encoder_bwd_slots_kernel<50, 50, K, DI, rmw>, k, stream, a)
+                          : launch_enc(encoder_bwd_slots_kernel<50, 100, K, DI, rmw>, k, stream, a);
   });
 }
 

@@ -49,6 +49,9 @@ __global__ void __launch_bounds__(256) pack_weights_kernel(const srfrd_layout ly
 
 using namespace srfrd;
 
+// floats of the caller's scratch per workgroup of a global-scratch build
+static int64_t scratch_stride(int64_t lds_floats) { return (lds_floats + 2 * kSlack + 63) & ~63ll; }
+
 extern "C" int64_t srfrd_aux_floats(const srfrd_layout* lay, int B, int L) {
   if (!lay || B <= 0 || L <= 0) return SRFRD_E_ARG;
   const Geom g = make_geom(L, lay->D);
@@ -61,8 +64,8 @@ extern "C" int srfrd_scratch_floats(const srfrd_layout* lay, int B, int L, int64
   const int64_t f = fwd_lds_floats(g, lay->n_blocks), bw = bwd_lds_floats(g, lay->n_blocks);
   int gf = num_cu();
   if (gf > B) gf = B;
-  if (fwd_floats) *fwd_floats = f * 4 <= kLdsLimit ? 0 : ((f + 2 * kSlack + 63) & ~63ll) * gf;
-  if (bwd_floats) *bwd_floats = bw * 4 <= kLdsLimit ? 0 : ((bw + 2 * kSlack + 63) & ~63ll) * bwd_grid(*lay, B, L, num_cu());
+  if (fwd_floats) *fwd_floats = f * 4 <= kLdsLimit ? 0 : scratch_stride(f) * gf;
+  if (bwd_floats) *bwd_floats = bw * 4 <= kLdsLimit ? 0 : scratch_stride(bw) * bwd_grid(*lay, B, L, num_cu());
   return 0;
 }
 
@@ -114,7 +117,6 @@ static KernelPlan kernel(Family fam, int form, int variant, bool flag, int grid,
 }
 static KernelPlan unsupported() { return KernelPlan{SRFRD_E_UNSUPPORTED, 0, 0, -1, false, 0, 0, 0, 0}; }
 static bool fits(int64_t floats) { return floats * 4 <= kLdsLimit; }
-static int64_t scratch_stride(int64_t lds_floats) { return (lds_floats + 2 * kSlack + 63) & ~63ll; }
 
 EncPlan encoder_plan(const srfrd_layout& lay, int B, int L, int mode, int sw, int n_cu, int64_t scratch_floats) {
   const Geom g = make_geom(L, lay.D);
@@ -243,10 +245,7 @@ int launch_fwd_first(const KernelPlan& k, const EncArgs& a, void* stream) {
   switch (k.form) {
     case kL50:
       if (k.variant < 0) return launch_enc(encoder_fwd_kernel<50, 64, 8, 50>, k, stream, a);
-      return with_variant(k.variant, [&](auto v) {
-        constexpr KindVariant kv = kKindVariants[decltype(v)::value];
-        return with_flag(k.flag, [&](auto t) { return launch_enc(encoder_fwd_kernel<50, 64, 8, 50, kv.K, decltype(t)::value, kv.DI>, k, stream, a); });
-      });
+      return with_variant_flag(k, [&](auto K, auto DI, auto t) { return launch_enc(encoder_fwd_kernel<50, 64, 8, 50, K, t, DI>, k, stream, a); });
     case kL100:
       return k.flag ? launch_enc(encoder_fwd_kernel<50, 112, 16, 100, SRFRD_SASREC, 1, 50>, k, stream, a)
                     : launch_enc(encoder_fwd_kernel<50, 112, 8, 100, SRFRD_SASREC, 0, 50>, k, stream, a);
@@ -261,11 +260,8 @@ int launch_fwd_first(const KernelPlan& k, const EncArgs& a, void* stream) {
 extern "C" int srfrd_encoder_plan(const srfrd_layout* lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats,
                                   char* fwd_name, char* bwd_name, int name_len, int32_t* grids) {
   if (!lay || B <= 0 || L <= 0 || n_cu <= 0 || scratch_floats < 0 || !grids) return SRFRD_E_ARG;
-  EncPlan p;
-  if (lay->D > SRFRD_MAX_D || lay->n_heads < 1 || lay->D % lay->n_heads != 0 || lay->n_blocks > SRFRD_MAX_BLOCKS)
-    p.fwd = p.bwd = unsupported();             // (what fill_args answers)
-  else
-    p = encoder_plan(*lay, B, L, mode, switches, n_cu, scratch_floats);
+  EncPlan p = {unsupported(), unsupported(), unsupported()};
+  if (layout_supported(*lay)) p = encoder_plan(*lay, B, L, mode, switches, n_cu, scratch_floats);
   if (fwd_name) plan_name(p.fwd, fwd_name, name_len);
   if (bwd_name) plan_name(p.bwd, bwd_name, name_len);
   grids[0] = p.fwd.rc ? p.fwd.rc : p.fwd.grid;
@@ -276,55 +272,112 @@ extern "C" int srfrd_encoder_plan(const srfrd_layout* lay, int B, int L, int mod
 extern "C" int srfrd_encoder_plan_train(const srfrd_layout* lay, int B, int L, int mode, int switches, int n_cu, int64_t scratch_floats,
                                         char* name, int name_len, int32_t* grid) {
   if (!lay || B <= 0 || L <= 0 || n_cu <= 0 || scratch_floats < 0 || !grid) return SRFRD_E_ARG;
-  KernelPlan k = unsupported();
-  if (!(lay->D > SRFRD_MAX_D || lay->n_heads < 1 || lay->D % lay->n_heads != 0 || lay->n_blocks > SRFRD_MAX_BLOCKS))
-    k = encoder_plan(*lay, B, L, mode, switches, n_cu, scratch_floats).train;
+  const KernelPlan k = layout_supported(*lay) ? encoder_plan(*lay, B, L, mode, switches, n_cu, scratch_floats).train : unsupported();
   if (name) plan_name(k, name, name_len);
   *grid = k.rc ? k.rc : k.grid;
   return 0;
 }
 
-static int encoder_fwd_impl(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
-                            const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids,
-                            const int64_t* pos_fake, const int64_t* neg_ids, const int64_t* neg_fake, int B, int L,
-                            double dropout_p, uint32_t seed, const uint32_t* seed_dev, int64_t seq_index0,
-                            float* hidden, float* pos_logits, float* neg_logits, float* save_x, float* save_h1,
-                            float* save_aux, float* loss_part, float* scratch, int64_t scratch_floats, float* dbg, int dbg_seq,
-                            int last_only, const int32_t* sched, int sched_mode, void* stream) {
+// ---- from a call to a launch: every launching entry point of the encoder goes through enc_run ----
+namespace srfrd {
+// the refusals every pass shares, and the kernels' view of the layout, the inputs and the dropout
+static int fill_args(EncArgs& a, const EncCall& c) {
+  const srfrd_layout* lay = c.lay;
+  if (!lay || !c.item_table || !c.dense || !c.packed || !c.input_ids || c.B <= 0 || c.L <= 0) return SRFRD_E_ARG;
+  if (!layout_supported(*lay)) return SRFRD_E_UNSUPPORTED;
+  if (c.L > lay->max_len) return SRFRD_E_ARG;
+  if (c.dropout_p < 0.0 || c.dropout_p >= 1.0) return SRFRD_E_ARG;
+  if (lay->kind == SRFRD_SRFRN && ((c.pos_ids && !c.pos_fake) || (c.neg_ids && !c.neg_fake))) return SRFRD_E_ARG;
+  Dims& d = a.dm;
+  d.kind = lay->kind; d.d_item = lay->d_item; d.d_fake = lay->d_fake; d.D = lay->D; d.d_out = lay->d_out;
+  d.n_labels = lay->n_labels; d.n_blocks = lay->n_blocks; d.n_items = lay->n_items; d.n_heads = lay->n_heads;
+  d.off_pos = (int)lay->off_pos; d.off_side = (int)lay->off_side;
+  d.blk0 = lay->n_blocks > 0 ? (int)lay->blk[0].ln1_w : 0;
+  d.blk_stride = blk_stride_of(lay->D);
+  for (int i = 0; i < lay->n_blocks; ++i) {        // the kernels recompute block offsets arithmetically: check the table agrees
+    const BlkOff o = blk_off(d.blk0 + i * d.blk_stride, lay->D);
+    const srfrd_block_off& t = lay->blk[i];
+    if (t.ln1_w != o.ln1_w || t.ln1_b != o.ln1_b || t.in_w != o.in_w || t.in_b != o.in_b || t.out_w != o.out_w ||
+        t.out_b != o.out_b || t.ln2_w != o.ln2_w || t.ln2_b != o.ln2_b || t.c1_w != o.c1_w || t.c1_b != o.c1_b ||
+        t.c2_w != o.c2_w || t.c2_b != o.c2_b)
+      return SRFRD_E_ARG;
+  }
+  d.off_lc_w = (int)lay->off_lc_w; d.off_lc_b = (int)lay->off_lc_b; d.off_ll_w = (int)lay->off_ll_w; d.off_ll_b = (int)lay->off_ll_b;
+  d.n_dense = (int)lay->n_dense;
+  a.table = lay->table_bf16 ? nullptr : (const float*)c.item_table;
+  a.table16 = lay->table_bf16 ? (const uint16_t*)c.item_table : nullptr;
+  a.dense = c.dense; a.packed = c.packed;
+  a.in_ids = c.input_ids; a.fk_ids = c.fake_ids; a.pos_ids = c.pos_ids; a.pos_fk = c.pos_fake; a.neg_ids = c.neg_ids; a.neg_fk = c.neg_fake;
+  a.B = c.B; a.L = c.L; a.seed = c.seed; a.seed_dev = c.seed_dev;
+  a.drop_on = c.dropout_p > 0.0;
+  double thr = c.dropout_p * 4294967296.0;
+  a.drop_thr = thr >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)thr;
+  a.drop_scale = (float)(1.0 / (1.0 - c.dropout_p));
+  a.seq0 = c.seq_index0;
+  a.qscale = (float)sqrt(1.0 / (double)(lay->D / lay->n_heads));
+  return 0;
+}
+
+// SRFRD_PLAN_* bits of a call: what it carries, as the plan's `mode` wants it
+static int plan_mode(const EncCall& c, Pass pass) {
+  int mode = (c.pos_ids ? SRFRD_PLAN_POS : 0) | (c.neg_ids ? SRFRD_PLAN_NEG : 0) | (c.dropout_p > 0.0 ? SRFRD_PLAN_DROPOUT : 0);
+  if (pass != kBackward) mode |= (c.save_x || pass == kTrain ? SRFRD_PLAN_CKPT : 0) | (c.loss_part ? SRFRD_PLAN_LOSS : 0);
+  if (pass != kForward) mode |= c.fused_bce && !c.d_hidden ? SRFRD_PLAN_FUSED_BCE : 0;
+#ifndef SRFRD_STAMPS
+  if (pass != kTrain && c.dbg) mode |= SRFRD_PLAN_TAPS;            // (diagnostic build: `dbg` receives the phase stamps, not taps)
+#endif
+  return mode;
+}
+
+int enc_run(const EncCall& c, Pass pass) {
+  const bool fwd = pass != kBackward, bwd = pass != kForward;      // the train pass is both
   const int sw = read_switches();
   EncArgs a = {};
-  a.last_only = last_only;
-  a.sched = sched_mode != 0 ? sched : nullptr;
-  a.sched_mode = a.sched ? sched_mode : 0;
-  a.ragged_off = (sw & SRFRD_SW_RAGGED_FULL_ROWS) != 0;
-  int rc = fill_args(a, lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L,
-                     dropout_p, seed, seed_dev, seq_index0);
-  if (rc) return rc;
-  if (!hidden || (pos_ids && !pos_logits) || (neg_ids && !neg_logits)) return SRFRD_E_ARG;
-  if (loss_part && !(pos_ids && neg_ids)) return SRFRD_E_ARG;
-  a.hidden = hidden; a.pos_logits = pos_logits; a.neg_logits = neg_logits;
-  if ((save_x != nullptr) != (save_h1 != nullptr) || (save_x != nullptr) != (save_aux != nullptr)) return SRFRD_E_ARG;
-  a.save_x = save_x; a.save_h1 = save_h1; a.save_aux = save_aux; a.loss_part = loss_part;
-  a.dbg = dbg; a.dbg_seq = dbg_seq;
-  srfrd_debug_shape(lay, L, &a.dbg_slot, nullptr);
-  int mode = (pos_ids ? SRFRD_PLAN_POS : 0) | (neg_ids ? SRFRD_PLAN_NEG : 0) | (save_x ? SRFRD_PLAN_CKPT : 0) |
-             (loss_part ? SRFRD_PLAN_LOSS : 0) | (dropout_p > 0.0 ? SRFRD_PLAN_DROPOUT : 0);
-#ifndef SRFRD_STAMPS
-  if (dbg) mode |= SRFRD_PLAN_TAPS;            // (diagnostic build: `dbg` receives the phase stamps, not taps)
-#endif
-  const KernelPlan k = encoder_plan(*lay, B, L, mode, sw, num_cu(), scratch ? scratch_floats : 0).fwd;
+  a.sched = c.sched_mode != 0 ? c.sched : nullptr;
+  a.sched_mode = a.sched ? c.sched_mode : 0;
+  a.rank_G = c.rank_G; a.ragged_off = (sw & SRFRD_SW_RAGGED_FULL_ROWS) != 0;
+  if (const int rc = fill_args(a, c)) return rc;
+  // outputs and checkpoints
+  if (fwd) {
+    if (!c.hidden || (c.pos_ids && !c.pos_logits) || (c.neg_ids && !c.neg_logits)) return SRFRD_E_ARG;
+    if (c.loss_part && !(c.pos_ids && c.neg_ids)) return SRFRD_E_ARG;
+    if ((c.save_x != nullptr) != (c.save_h1 != nullptr) || (c.save_x != nullptr) != (c.save_aux != nullptr)) return SRFRD_E_ARG;
+  }
+  if (bwd) {
+    if (!c.hidden || !c.save_x || !c.save_h1 || !c.save_aux || !c.grad_table || !c.grad_slabs) return SRFRD_E_ARG;
+    if (c.fused_bce && !(c.pos_ids && c.neg_ids && c.pos_logits && c.neg_logits)) return SRFRD_E_ARG;
+  }
+  const EncPlan p = encoder_plan(*c.lay, c.B, c.L, plan_mode(c, pass), sw, num_cu(), c.scratch ? c.scratch_floats : 0);
+  const KernelPlan& k = pass == kForward ? p.fwd : pass == kBackward ? p.bwd : p.train;
   if (k.rc) return k.rc;
-  if (k.scratch_stride) {
-    a.scratch = scratch;
-    a.scratch_stride = k.scratch_stride;
+  if (c.demand_scratch && (!c.scratch || c.scratch_floats < srfrd_train_scratch_floats(c.lay, c.B, c.L))) return SRFRD_E_ARG;
+  if (fwd) {
+    a.hidden = c.hidden; a.pos_logits = c.pos_logits; a.neg_logits = c.neg_logits; a.last_only = c.last_only;
+    a.save_x = c.save_x; a.save_h1 = c.save_h1; a.save_aux = c.save_aux; a.loss_part = c.loss_part;
   }
+  if (bwd) {                                   // (the train pass: what its forward half has just written)
+    a.c_hidden = c.hidden; a.c_pl = c.pos_logits; a.c_nl = c.neg_logits; a.c_save_x = c.save_x; a.c_save_h1 = c.save_h1; a.c_save_aux = c.save_aux;
+    a.grad_table = c.grad_table; a.grad_slabs = c.grad_slabs; a.contrib = c.table_contrib;
+    a.fused_bce = pass == kTrain ? 1 : c.fused_bce;                // (the plan offers no train kernel without it)
+  }
+  if (pass == kBackward) { a.d_hidden = c.d_hidden; a.d_pos = c.d_pos; a.d_neg = c.d_neg; }
+  if (pass != kTrain) { a.dbg = c.dbg; a.dbg_seq = c.dbg_seq; srfrd_debug_shape(c.lay, c.L, &a.dbg_slot, nullptr); }
+  if (k.scratch_stride) { a.scratch = c.scratch; a.scratch_stride = k.scratch_stride; }
   switch (k.family) {
-    case kFwdRows: return launch_fwd_rows(k, a, stream);
-    case kFwdRagged: return launch_fwd_ragged(k, a, stream);
-    case kFwdLong: return launch_fwd_long(k, &a, stream);
-    default: return launch_fwd_first(k, a, stream);
+    case kFwdFirst: return launch_fwd_first(k, a, c.stream);
+    case kFwdRows: return launch_fwd_rows(k, a, c.stream);
+    case kFwdRagged: return launch_fwd_ragged(k, a, c.stream);
+    case kFwdLong: return launch_fwd_long(k, &a, c.stream);
+    case kBwdFirst: return launch_bwd_first(k, a, c.stream);
+    case kBwdRagged: return launch_bwd_ragged(k, a, c.stream);
+    case kBwdSlots: return launch_bwd_slots(k, a, c.stream);
+    case kBwdChunks: return launch_bwd_chunks(k, a, c.stream);
+    case kBwdLong: return launch_bwd_long(k, &a, c.stream);
+    case kTrainRagged: return launch_train_ragged(k, a, c.stream);
   }
+  return SRFRD_E_UNSUPPORTED;
 }
+}  // namespace srfrd
 
 extern "C" int srfrd_encoder_fwd(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
                                  const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids,
@@ -333,9 +386,13 @@ extern "C" int srfrd_encoder_fwd(const srfrd_layout* lay, const void* item_table
                                  float* hidden, float* pos_logits, float* neg_logits, float* save_x, float* save_h1,
                                  float* save_aux, float* loss_part, float* scratch, int64_t scratch_floats, float* dbg, int dbg_seq,
                                  void* stream) {
-  return encoder_fwd_impl(lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L, dropout_p,
-                          seed, seed_dev, seq_index0, hidden, pos_logits, neg_logits, save_x, save_h1, save_aux, loss_part, scratch,
-                          scratch_floats, dbg, dbg_seq, 0, nullptr, 0, stream);
+  EncCall c = {};
+  c.lay = lay; c.item_table = item_table; c.dense = dense; c.packed = packed; c.input_ids = input_ids; c.fake_ids = fake_ids;
+  c.pos_ids = pos_ids; c.pos_fake = pos_fake; c.neg_ids = neg_ids; c.neg_fake = neg_fake; c.B = B; c.L = L; c.dropout_p = dropout_p;
+  c.seed = seed; c.seed_dev = seed_dev; c.seq_index0 = seq_index0; c.hidden = hidden; c.pos_logits = pos_logits; c.neg_logits = neg_logits;
+  c.save_x = save_x; c.save_h1 = save_h1; c.save_aux = save_aux; c.loss_part = loss_part;
+  c.scratch = scratch; c.scratch_floats = scratch_floats; c.dbg = dbg; c.dbg_seq = dbg_seq; c.stream = stream;
+  return enc_run(c, kForward);
 }
 
 extern "C" int srfrd_encoder_fwd_sched(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
@@ -345,18 +402,23 @@ extern "C" int srfrd_encoder_fwd_sched(const srfrd_layout* lay, const void* item
                                        float* hidden, float* pos_logits, float* neg_logits, float* save_x, float* save_h1,
                                        float* save_aux, float* loss_part, float* scratch, int64_t scratch_floats,
                                        const int32_t* sched, int sched_mode, void* stream) {
-  if (sched_mode < 0 || sched_mode > 1 || (sched_mode != 0 && !sched)) return SRFRD_E_ARG;
-  return encoder_fwd_impl(lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L, dropout_p,
-                          seed, seed_dev, seq_index0, hidden, pos_logits, neg_logits, save_x, save_h1, save_aux, loss_part, scratch,
-                          scratch_floats, nullptr, 0, 0, sched, sched_mode, stream);
+  if (!check_sched(sched, sched_mode)) return SRFRD_E_ARG;
+  EncCall c = {};
+  c.lay = lay; c.item_table = item_table; c.dense = dense; c.packed = packed; c.input_ids = input_ids; c.fake_ids = fake_ids;
+  c.pos_ids = pos_ids; c.pos_fake = pos_fake; c.neg_ids = neg_ids; c.neg_fake = neg_fake; c.B = B; c.L = L; c.dropout_p = dropout_p;
+  c.seed = seed; c.seed_dev = seed_dev; c.seq_index0 = seq_index0; c.hidden = hidden; c.pos_logits = pos_logits; c.neg_logits = neg_logits;
+  c.save_x = save_x; c.save_h1 = save_h1; c.save_aux = save_aux; c.loss_part = loss_part;
+  c.scratch = scratch; c.scratch_floats = scratch_floats; c.sched = sched; c.sched_mode = sched_mode; c.stream = stream;
+  return enc_run(c, kForward);
 }
 
 extern "C" int srfrd_encoder_fwd_last(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
                                       const int64_t* input_ids, const int64_t* fake_ids, int B, int L, float* hidden_last,
                                       float* scratch, int64_t scratch_floats, void* stream) {
-  return encoder_fwd_impl(lay, item_table, dense, packed, input_ids, fake_ids, nullptr, nullptr, nullptr, nullptr, B, L, 0.0, 0,
-                          nullptr, 0, hidden_last, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, scratch, scratch_floats,
-                          nullptr, 0, 1, nullptr, 0, stream);
+  EncCall c = {};
+  c.lay = lay; c.item_table = item_table; c.dense = dense; c.packed = packed; c.input_ids = input_ids; c.fake_ids = fake_ids;
+  c.B = B; c.L = L; c.hidden = hidden_last; c.last_only = 1; c.scratch = scratch; c.scratch_floats = scratch_floats; c.stream = stream;
+  return enc_run(c, kForward);
 }
 
 extern "C" int srfrd_layout_init(srfrd_layout* lay, int kind, int n_items, int max_len, int d_item, int d_fake,

@@ -40,10 +40,7 @@ extern "C" int srfrd_seq_order(const int64_t* input_ids, int B, int L, int pair_
 namespace srfrd {
 
 int launch_fwd_ragged(const KernelPlan& k, const EncArgs& a, void* stream) {
-  return with_variant(k.variant, [&](auto v) {
-    constexpr KindVariant kv = kKindVariants[decltype(v)::value];
-    return with_flag(k.flag, [&](auto train) { return launch_enc(encoder_fwd_ragged_kernel<kv.K, decltype(train)::value, kv.DI>, k, stream, a); });
-  });
+  return with_variant_flag(k, [&](auto K, auto DI, auto train) { return launch_enc(encoder_fwd_ragged_kernel<K, train, DI>, k, stream, a); });
 }
 
 }  // namespace srfrd

@@ -9,10 +9,7 @@
 namespace srfrd {
 
 int launch_fwd_rows(const KernelPlan& k, const EncArgs& a, void* stream) {
-  return with_variant(k.variant, [&](auto v) {
-    constexpr KindVariant kv = kKindVariants[decltype(v)::value];
-    return with_flag(k.flag, [&](auto mode) { return launch_enc(encoder_fwd_rows_kernel<50, kv.K, kv.DI, decltype(mode)::value>, k, stream, a); });
-  });
+  return with_variant_flag(k, [&](auto K, auto DI, auto mode) { return launch_enc(encoder_fwd_rows_kernel<50, K, DI, mode>, k, stream, a); });
 }
 
 }  // namespace srfrd

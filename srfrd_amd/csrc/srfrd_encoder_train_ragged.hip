@@ -87,10 +87,7 @@ __global__ void __launch_bounds__(512, 4) encoder_train_ragged_kernel(const EncA
 }
 
 int launch_train_ragged(const KernelPlan& k, const EncArgs& a, void* stream) {
-  return with_variant(k.variant, [&](auto v) {
-    constexpr KindVariant kv = kKindVariants[decltype(v)::value];
-    return with_flag(k.flag, [&](auto rmw) { return launch_enc(encoder_train_ragged_kernel<kv.K, kv.DI, decltype(rmw)::value>, k, stream, a); });
-  });
+  return with_variant_flag(k, [&](auto K, auto DI, auto rmw) { return launch_enc(encoder_train_ragged_kernel<K, DI, rmw>, k, stream, a); });
 }
 
 }  // namespace srfrd
@@ -105,42 +102,6 @@ extern "C" int64_t srfrd_train_scratch_floats(const srfrd_layout* lay, int B, in
   return (int64_t)B * L * (lay->d_out + (lay->kind == SRFRD_SRFRN ? 2 : 0));
 }
 
-// both entry points: `sched` / `sched_mode` as srfrd_encoder_train_sched takes them, or rank_G > 0 and no workspace
-static int train_launch(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
-                        const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids, const int64_t* pos_fake,
-                        const int64_t* neg_ids, const int64_t* neg_fake, int B, int L, double dropout_p, uint32_t seed,
-                        const uint32_t* seed_dev, int64_t seq_index0, float* hidden, float* pos_logits, float* neg_logits,
-                        float* save_x, float* save_h1, float* save_aux, float* loss_part, const float* d_hidden, int fused_bce,
-                        float* grad_table, float* table_contrib, float* grad_slabs, float* scratch, int64_t scratch_floats,
-                        bool demand_scratch, const int32_t* sched, int sched_mode, int rank_G, void* stream) {
-  const int sw = read_switches();
-  EncArgs a = {};
-  a.sched = sched_mode != 0 ? sched : nullptr;
-  a.sched_mode = a.sched ? sched_mode : 0;
-  a.rank_G = rank_G;
-  a.ragged_off = (sw & SRFRD_SW_RAGGED_FULL_ROWS) != 0;
-  const int rc = fill_args(a, lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L,
-                           dropout_p, seed, seed_dev, seq_index0);
-  if (rc) return rc;
-  // what srfrd_encoder_fwd_sched and srfrd_encoder_bwd_sched each refuse
-  if (!hidden || (pos_ids && !pos_logits) || (neg_ids && !neg_logits)) return SRFRD_E_ARG;
-  if (loss_part && !(pos_ids && neg_ids)) return SRFRD_E_ARG;
-  if ((save_x != nullptr) != (save_h1 != nullptr) || (save_x != nullptr) != (save_aux != nullptr)) return SRFRD_E_ARG;
-  if (!save_x || !grad_table || !grad_slabs) return SRFRD_E_ARG;
-  if (fused_bce && !(pos_ids && neg_ids)) return SRFRD_E_ARG;
-  const int mode = (pos_ids ? SRFRD_PLAN_POS : 0) | (neg_ids ? SRFRD_PLAN_NEG : 0) | SRFRD_PLAN_CKPT | (loss_part ? SRFRD_PLAN_LOSS : 0) |
-                   (dropout_p > 0.0 ? SRFRD_PLAN_DROPOUT : 0) | (fused_bce && !d_hidden ? SRFRD_PLAN_FUSED_BCE : 0);
-  const KernelPlan k = encoder_plan(*lay, B, L, mode, sw, num_cu(), scratch ? scratch_floats : 0).train;
-  if (k.rc) return k.rc;
-  if (demand_scratch && (!scratch || scratch_floats < srfrd_train_scratch_floats(lay, B, L))) return SRFRD_E_ARG;
-  a.hidden = hidden; a.pos_logits = pos_logits; a.neg_logits = neg_logits;
-  a.save_x = save_x; a.save_h1 = save_h1; a.save_aux = save_aux; a.loss_part = loss_part;
-  a.c_hidden = hidden; a.c_pl = pos_logits; a.c_nl = neg_logits; a.c_save_x = save_x; a.c_save_h1 = save_h1; a.c_save_aux = save_aux;
-  a.fused_bce = 1;
-  a.grad_table = grad_table; a.grad_slabs = grad_slabs; a.contrib = table_contrib;
-  return launch_train_ragged(k, a, stream);
-}
-
 extern "C" int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* item_table, const float* dense, const float* packed,
                                          const int64_t* input_ids, const int64_t* fake_ids, const int64_t* pos_ids,
                                          const int64_t* pos_fake, const int64_t* neg_ids, const int64_t* neg_fake, int B, int L,
@@ -150,11 +111,17 @@ extern "C" int srfrd_encoder_train_sched(const srfrd_layout* lay, const void* it
                                          const float* d_neg, int fused_bce, float* grad_table, float* table_contrib,
                                          float* grad_slabs, float* scratch, int64_t scratch_floats, const int32_t* sched,
                                          int sched_mode, void* stream) {
-  if (sched_mode < 0 || sched_mode > 1 || (sched_mode != 0 && !sched)) return SRFRD_E_ARG;
-  (void)d_pos; (void)d_neg;
-  return train_launch(lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L, dropout_p,
-                      seed, seed_dev, seq_index0, hidden, pos_logits, neg_logits, save_x, save_h1, save_aux, loss_part, d_hidden,
-                      fused_bce, grad_table, table_contrib, grad_slabs, scratch, scratch_floats, true, sched, sched_mode, 0, stream);
+  if (!check_sched(sched, sched_mode)) return SRFRD_E_ARG;
+  (void)d_pos; (void)d_neg;                  // (the kernel computes the logit gradients itself; a d_hidden makes the plan refuse)
+  EncCall c = {};
+  c.lay = lay; c.item_table = item_table; c.dense = dense; c.packed = packed; c.input_ids = input_ids; c.fake_ids = fake_ids;
+  c.pos_ids = pos_ids; c.pos_fake = pos_fake; c.neg_ids = neg_ids; c.neg_fake = neg_fake; c.B = B; c.L = L; c.dropout_p = dropout_p;
+  c.seed = seed; c.seed_dev = seed_dev; c.seq_index0 = seq_index0; c.hidden = hidden; c.pos_logits = pos_logits; c.neg_logits = neg_logits;
+  c.save_x = save_x; c.save_h1 = save_h1; c.save_aux = save_aux; c.loss_part = loss_part;
+  c.d_hidden = d_hidden; c.fused_bce = fused_bce; c.grad_table = grad_table; c.table_contrib = table_contrib; c.grad_slabs = grad_slabs;
+  c.scratch = scratch; c.scratch_floats = scratch_floats; c.demand_scratch = true;
+  c.sched = sched; c.sched_mode = sched_mode; c.stream = stream;
+  return enc_run(c, kTrain);
 }
 
 // srfrd_encoder_train_sched without srfrd_seq_order in front of it: pair_stride > 0 asks for the length order of sched_mode 1
@@ -167,7 +134,12 @@ extern "C" int srfrd_encoder_train_ranked(const srfrd_layout* lay, const void* i
                                           float* save_aux, float* loss_part, int fused_bce, float* grad_table,
                                           float* table_contrib, float* grad_slabs, int pair_stride, void* stream) {
   if (pair_stride < 0 || (reinterpret_cast<uintptr_t>(input_ids) & 15) != 0) return SRFRD_E_ARG;      // (the scan reads two ids per lane)
-  return train_launch(lay, item_table, dense, packed, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, B, L, dropout_p,
-                      seed, seed_dev, seq_index0, hidden, pos_logits, neg_logits, save_x, save_h1, save_aux, loss_part, nullptr,
-                      fused_bce, grad_table, table_contrib, grad_slabs, nullptr, 0, false, nullptr, 0, pair_stride, stream);
+  EncCall c = {};
+  c.lay = lay; c.item_table = item_table; c.dense = dense; c.packed = packed; c.input_ids = input_ids; c.fake_ids = fake_ids;
+  c.pos_ids = pos_ids; c.pos_fake = pos_fake; c.neg_ids = neg_ids; c.neg_fake = neg_fake; c.B = B; c.L = L; c.dropout_p = dropout_p;
+  c.seed = seed; c.seed_dev = seed_dev; c.seq_index0 = seq_index0; c.hidden = hidden; c.pos_logits = pos_logits; c.neg_logits = neg_logits;
+  c.save_x = save_x; c.save_h1 = save_h1; c.save_aux = save_aux; c.loss_part = loss_part;
+  c.fused_bce = fused_bce; c.grad_table = grad_table; c.table_contrib = table_contrib; c.grad_slabs = grad_slabs;
+  c.rank_G = pair_stride; c.stream = stream;
+  return enc_run(c, kTrain);
 }
