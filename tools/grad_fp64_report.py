@@ -2,6 +2,7 @@
 """Measured agreement of every encoder gradient with the fp64 oracle (GPU box) -> profiles/grad_fp64_errors.json.
 
     python tools/grad_fp64_report.py [--out profiles/grad_fp64_errors.json] [--modes encoder | head] [--cases depth | ID ...]
+    python tools/grad_fp64_report.py --wave [--cases ID ...]   # tests/test_gpu_wave_fp64.py -> profiles/wave_fp64_errors.json
     python tools/grad_fp64_report.py --scan OUT.json  # CPU only, once per kind of machine the suite runs on, then
     python tools/grad_fp64_report.py --pick A.json B.json      # ... the batch-seed table of tests/grad_refs.py
 
@@ -75,9 +76,75 @@ def selected_cases(G, ids):
     return [c for c in G.ALL_CASES if c.id in want]
 
 
+def wave(out, ids):
+    """--wave: what tests/test_gpu_wave_fp64.py runs (batches of more sequences than workgroups) -> profiles/wave_fp64_errors.json:
+    per case the forward's differing elements (0 expected) and, per run and tensor, the worst row's error"""
+    from tests import grad_refs as G
+    from tests import test_gpu_wave_fp64 as T
+    from tests import wave_refs as W
+    chosen = [c for c in W.CASES if not ids or c.id in ids]
+    report, tensors, missed, differing = {}, {}, 0, 0
+    for c in chosen:
+        runs = [("masks", lambda c, env: T.run_masks(c, env)[0]), ("autograd", T.run_autograd)]
+        for det in (True, False):
+            name = "fused-" + ("deterministic" if det else "atomics")
+            runs.append((name, lambda c, env, det=det: T.run_fused(c, det, env)))
+            if c.id in W.TRAIN_KERNEL_IDS:
+                runs.append((name + "-two-launches", lambda c, env, det=det: T.run_fused(c, det, env, train_launch=False)))
+        kind = c.kind if c.blocks == 2 else f"{c.kind}-b{c.blocks}"
+        entry = report.setdefault(G.case_ids([c])[0], {"kind": kind})
+        first = None
+        for mode, fn in [(m, None) for m in ("eval", "last", "train", "masks-forward")] + runs:
+            changed = {}
+            try:
+                got = T.run_forward_bits(c, mode.split("-")[0], _setenv(changed)) if fn is None else fn(c, _setenv(changed))
+            finally:
+                for name, old in changed.items():
+                    os.environ.pop(name, None) if old is None else os.environ.__setitem__(name, old)
+            if fn is None:
+                entry.setdefault("forward_differing_elements", {})[mode] = sum(got.values())
+                differing += sum(got.values())
+                continue
+            figs, figs2, copies = got if isinstance(got, tuple) else (got, None, None)
+            names = tensors.setdefault(kind, sorted(figs))
+            if first is None:           # (B, the copies, e32_tiled and the bounds are the case's: with its first run)
+                ref = W.reference(c.id, T._n_cu())
+                entry["B"], entry["copies"] = ref.B, ref.k
+                entry["exceptions"] = {n: [_num(ref.e32[n]), _num(ref.bounds[n])] for n in W.exceptions_of(ref)}
+                entry["e32_tiled"] = [_num(ref.e32[k]) for k in names]
+            entry[mode] = _record(figs, names, first)
+            first = first or mode
+            for k in ("e32", "bound", "old", "e32_and_bound_as"):
+                entry[mode].pop(k, None)
+            if figs2 is not None:
+                w = max(figs2, key=lambda k: figs2[k]["err"] / figs2[k]["bound"])
+                entry[mode]["second_moment_worst"] = [w, _num(figs2[w]["err"]), _num(figs2[w]["bound"])]
+                entry[mode]["copies_differing_elements"] = sum(copies.values())
+                differing += sum(copies.values())
+            both = list(figs.values()) + list((figs2 or {}).values())
+            bad = sum(bool(G.failures(f)) for f in both)
+            missed += bad
+            worst = max(f["err"] / f["bound"] for f in both)
+            print(f"{c.id:5s} {mode:34s} worst err / bound {worst:.3f}" + (f"   <-- {bad} tensors miss" if bad else ""), flush=True)
+        print(f"{c.id:5s} forward: differing elements {entry['forward_differing_elements']}; exceptions {entry['exceptions']}",
+              flush=True)
+    with open(out, "w") as f:
+        _dump({"metric": "tests/wave_refs.py: grad_refs.row_errors (worst row) against the BASE batch's fp64 gradient, bound 1e-4, "
+                         "for the tensors of `exceptions` [e32_tiled, bound = min(4 e32_tiled, 1 / (2 B))]; arrays follow "
+                         "`tensors` of the case's kind; masks: one tiled launch at dropout 0.5 against the fp64 sum of the "
+                         "untiled launches; second_moment_worst = [tensor, row error of g^2, twice the bound]; "
+                         "forward_differing_elements / copies_differing_elements: elements of a per-sequence output that "
+                         "differ from the untiled launch / from the first copy (0 expected)",
+               "tensors": tensors, "cases": report}, f)
+    print(f"{missed} tensors miss their bound, {differing} forward elements differ; wrote {out}")
+    return 1 if missed or differing else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "grad_fp64_errors.json"))
+    ap.add_argument("--wave", action="store_true", help="the batches of more sequences than workgroups "
+                    "(tests/test_gpu_wave_fp64.py) -> profiles/wave_fp64_errors.json unless --out says otherwise")
+    ap.add_argument("--out", help="default: profiles/grad_fp64_errors.json (--wave: profiles/wave_fp64_errors.json)")
     ap.add_argument("--modes", choices=["all", "encoder", "head"], default="all")
     ap.add_argument("--cases", nargs="+", metavar="ID", help="only these cases of grad_refs.ALL_CASES (\"depth\": grad_refs.DEPTH), "
                     "encoder modes only; every other entry of an existing --out file is kept")
@@ -87,7 +154,10 @@ def main():
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--pick", nargs="+", metavar="SCAN", help="grad_refs.SEEDS from one --scan file per kind of machine")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "wave_fp64_errors.json" if a.wave else "grad_fp64_errors.json")
     from tests import grad_refs as G
+    if a.wave:
+        return wave(a.out, a.cases)
     if a.scan:
         import multiprocessing as mp
         jobs = [(c.id, m, a.count) for c in G.ALL_CASES for m in ("autograd", "fused")]
