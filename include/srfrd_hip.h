@@ -68,8 +68,23 @@ typedef struct srfrd_layout {
                                    bf16 SHADOW of it (uint16_t, same shape; BASELINE configs[1] / [4] "bf16" table): the
                                    forward / backward / ranking GATHERS read half the bytes; gradients, the fp32 master
                                    and Adam are unchanged (the optimizer launchers rewrite the shadow) */
-  int32_t reserved0;
-  int64_t off_pos;              /* pos_embed / pos_emb                  (max_len, d_item) */
+  int32_t flags;                /* SRFRD_LAYOUT_* bits; srfrd_layout_init writes 0.  A layout with a bit outside the ones defined
+                                   below is refused: the plan queries and every encoder entry point answer
+                                   SRFRD_E_UNSUPPORTED before any launch.  Ranking, the loss heads and the optimizer do not read it.
+                                   SRFRD_LAYOUT_MASK_PAD_KEYS: the LEADING pads of a sequence leave its attention keys (the
+                                   original SASRec's key-padding mask; the reference passes none, SRFR_model.py:112).  With
+                                   t0(b) = the index of the first non-zero id of input_ids[b] (L if there is none):
+                                    - a live query row r >= t0 has P[r, j] = softmax_j(s[r, j]) over t0 <= j <= r; keys j < t0 get an
+                                      exact 0 and take no part in the row maximum;
+                                    - only the leading pads are masked: an id 0 at a position >= t0 stays a key, as without the flag;
+                                    - pad query rows r < t0 produce the zero outputs they produce without the flag (their internal
+                                      values are unspecified but finite); a sequence of pads gives zeros and no NaN;
+                                    - attention-dropout masks keep their (row, col) coordinates; embedding, LayerNorms, FFN, heads,
+                                      logits and the BCE partial sums are unchanged;
+                                    - the backward is the gradient of the above: dk / dv of a leading pad are exact zeros, so the
+                                      key / value biases lose those terms;
+                                    - flag off, or a batch without pads: the results without the flag, bit for bit. */
+  int64_t off_pos;             /* pos_embed / pos_emb                  (max_len, d_item) */
   int64_t off_side;             /* fake_embed / user_label_embed        (side_rows, side_cols) */
   srfrd_block_off blk[SRFRD_MAX_BLOCKS];
   int64_t off_lc_w, off_lc_b;   /* last_conv.{weight,bias}  (d_item,D,1),(d_item)   SRFR only, else -1 */
@@ -77,6 +92,7 @@ typedef struct srfrd_layout {
   int64_t n_dense;              /* elements in the dense vector */
   int64_t n_table;              /* (n_items + 1) * d_item */
 } srfrd_layout;
+#define SRFRD_LAYOUT_MASK_PAD_KEYS 1     /* srfrd_layout::flags: see there */
 
 /* [host] fills `lay`; replaces the per-class constructors' shape logic (reference SRFR_model.py:54-90, 155-190,
  * 431-466, 573-615).  n_blocks outside 1 .. SRFRD_MAX_BLOCKS -> SRFRD_E_ARG: the backward kernels prefetch the checkpoints of

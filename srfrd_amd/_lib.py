@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("SRFRD_LIB_PATH") or os.path.join(_HERE, "lib", "libsr
 
 MAX_BLOCKS = 8
 MAX_D = 64
+LAYOUT_MASK_PAD_KEYS = 1        # SRFRD_LAYOUT_MASK_PAD_KEYS: srfrd_layout.flags, the leading pads leave the attention keys
 EXCL_CAP = 4096                 # SRFRD_EXCL_CAP: most ids one row of an exclusion set may hold
 KINDS = {"SASRec": 0, "SRFR": 1, "SRFRN": 2, "SRFU_B": 3, "SRFU_F": 4, "SRFU_R": 5}
 _ERR = {-1: "SRFRD_E_ARG (bad argument)", -2: "SRFRD_E_UNSUPPORTED (configuration outside the fused kernels: "
@@ -26,7 +27,7 @@ class BlockOff(C.Structure):
 
 class Layout(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("kind", "n_items", "max_len", "d_item", "d_fake", "D", "d_out", "n_labels",
-                                          "n_blocks", "n_heads", "side_rows", "side_cols", "table_bf16", "reserved0")]
+                                          "n_blocks", "n_heads", "side_rows", "side_cols", "table_bf16", "flags")]
                 + [("off_pos", C.c_int64), ("off_side", C.c_int64), ("blk", BlockOff * MAX_BLOCKS),
                    ("off_lc_w", C.c_int64), ("off_lc_b", C.c_int64), ("off_ll_w", C.c_int64), ("off_ll_b", C.c_int64),
                    ("n_dense", C.c_int64), ("n_table", C.c_int64)])

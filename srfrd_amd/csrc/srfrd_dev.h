@@ -158,6 +158,7 @@ __device__ __forceinline__ int clamp_id(int64_t v, int hi) {
 struct Dims {
   int kind, d_item, d_fake, D, d_out, n_labels, n_blocks, n_items, n_heads;
   int off_pos, off_side, blk0, blk_stride, off_lc_w, off_lc_b, off_ll_w, off_ll_b, n_dense;
+  int flags;            // srfrd_layout::flags (SRFRD_LAYOUT_* bits): read by the forward kernels' softmax sites only
 };
 struct BlkOff {
   int ln1_w, ln1_b, in_w, in_b, out_w, out_b, ln2_w, ln2_b, c1_w, c1_b, c2_w, c2_b;
@@ -703,6 +704,30 @@ __device__ __forceinline__ void ln_bwd_rows(int nw, const lds_f* GY, const lds_f
       }
     }
   }
+}
+
+// srfrd_layout::flags & SRFRD_LAYOUT_MASK_PAD_KEYS: the first position of keep[0 .. L) that is no pad (L: none), found by
+// every wave for itself from the pad mask the id load left in LDS - no barrier, no LDS of its own.  Wave-uniform.
+template <class KP>
+__device__ __forceinline__ int first_live(const KP* keep, int L) {
+  const int lane = threadIdx.x & 63;
+  for (int j0 = 0; j0 < L; j0 += 64) {
+    const int j = j0 + lane;
+    const unsigned long long nz = __ballot(j < L && keep[j] != 0.f);
+    if (nz) return j0 + (int)__builtin_ctzll(nz);
+  }
+  return L;
+}
+
+// srfrd_layout::flags & SRFRD_LAYOUT_MASK_PAD_KEYS, in front of softmax_rows: the scores of the leading pads (keys j < t0) of
+// the live query rows r >= t0 become -inf - exact zero probabilities, no part in the row maximum.  A pad query row keeps its
+// keys: finite, and masked to zero behind the FFN.  Rows and keys are dealt as softmax_rows deals them (a quad a row, lane q
+// the keys q, q + kRL, ...), so every lane overwrites what it reads next itself: no barrier in between.
+__device__ __forceinline__ void mask_pad_keys(int nw, lds_f* S, int rows, int sld, int row0, int t0) {
+  const int q = threadIdx.x & (kRL - 1), rpp = (nw << 6) / kRL;
+  for (int r = row0 + threadIdx.x / kRL; r < rows; r += rpp)
+    if (r >= t0)
+      for (int j = q; j < t0; j += kRL) S[r * sld + j] = -INFINITY;
 }
 
 struct OnesRow {        // A operand whose row 0 is all ones (rows 1..15 zero): C row 0 = column sums of B

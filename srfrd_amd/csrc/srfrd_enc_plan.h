@@ -86,7 +86,8 @@ int enc_run(const EncCall& c, Pass pass);
 inline bool check_sched(const int32_t* sched, int sched_mode) { return sched_mode == 0 || (sched_mode == 1 && sched); }
 // a layout the fused kernels cover (enc_run and the plan queries answer SRFRD_E_UNSUPPORTED otherwise)
 inline bool layout_supported(const srfrd_layout& lay) {
-  return lay.D <= SRFRD_MAX_D && lay.n_heads >= 1 && lay.D % lay.n_heads == 0 && lay.n_blocks <= SRFRD_MAX_BLOCKS;
+  return lay.D <= SRFRD_MAX_D && lay.n_heads >= 1 && lay.D % lay.n_heads == 0 && lay.n_blocks <= SRFRD_MAX_BLOCKS &&
+         (lay.flags & ~SRFRD_LAYOUT_MASK_PAD_KEYS) == 0;
 }
 
 // mode: SRFRD_PLAN_* bits, switches: SRFRD_SW_* bits (read_switches), n_cu: CUs of the device, scratch_floats: the caller's

@@ -304,6 +304,7 @@ static int fill_args(EncArgs& a, const EncCall& c) {
   }
   d.off_lc_w = (int)lay->off_lc_w; d.off_lc_b = (int)lay->off_lc_b; d.off_ll_w = (int)lay->off_ll_w; d.off_ll_b = (int)lay->off_ll_b;
   d.n_dense = (int)lay->n_dense;
+  d.flags = lay->flags;
   a.table = lay->table_bf16 ? nullptr : (const float*)c.item_table;
   a.table16 = lay->table_bf16 ? (const uint16_t*)c.item_table : nullptr;
   a.dense = c.dense; a.packed = c.packed;

@@ -193,6 +193,7 @@ __global__ void __launch_bounds__(NW_ > 0 ? NW_ * 64 : 512, NW_ == 8 ? (LP_ <= 6
           __syncthreads();
           {
             const DropSite dsA = drop_site(drop_on, seed, site_attn(i, h), seq, a.drop_thr, a.drop_scale);
+            if (ly.flags & SRFRD_LAYOUT_MASK_PAD_KEYS) mask_pad_keys(nw, bXS, L, SLD, r0, first_live(s_keep, L));
             softmax_rows<true>(nw, bXS, L, SLD, LP, dsA, nullptr, sv_p ? sv_p + (int64_t)h * L * LP : nullptr, r0);
           }
           __syncthreads();
@@ -215,6 +216,9 @@ __global__ void __launch_bounds__(NW_ > 0 ? NW_ * 64 : 512, NW_ == 8 ? (LP_ <= 6
       // causal softmax (+ attention dropout); keys j > r get exact zeros up to LP
       {
         const DropSite dsA = drop_site(drop_on, seed, site_attn(i), seq, a.drop_thr, a.drop_scale);
+        // key-padding mask (srfrd_layout::flags): the leading pads, counted from the pad mask the id load left in LDS, leave
+        // the keys of the live rows.  Without the flag nothing runs here and the softmax is the one it was.
+        if (ly.flags & SRFRD_LAYOUT_MASK_PAD_KEYS) mask_pad_keys(nw, bXS, L, SLD, r0, first_live(s_keep, L));
         softmax_rows<true>(nw, bXS, L, SLD, LP, dsA, nullptr, sv_p, r0);
       }
       __syncthreads();

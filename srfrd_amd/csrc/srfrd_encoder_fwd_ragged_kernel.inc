@@ -710,7 +710,23 @@ __device__ __forceinline__ RagSeam rag_fwd_seq(const EncArgs& a, const RagFwdLds
     __syncthreads();
     {
       const DropSite dsA = drop_site(drop_on, seed, site_attn(i), seq, a.drop_thr, a.drop_scale);
-      rag_softmax(bXS, rq0, r0, v0, kr, t0, SH + L, dsA, sv_p, tid);
+      // Key-padding mask (srfrd_layout::flags): the t0 merged pads are no key - the softmax runs as for a sequence whose first
+      // key is its first valid position (no representative, no multiplicity term), which leaves exact zeros in the
+      // representative's checkpoint column (c_i P_i,rep); column LP - 1 (t0 P_i,rep, which only a row with a representative
+      // writes) gets its zeros here: the ragged backward reads both, and every merged-key term it forms from them vanishes.
+      // (SRFRD_RAGGED_FULL_ROWS walks the pads as rows of their own, t0 = 0: they are counted again here, and the pad QUERY
+      // rows become dead rows - zero probabilities, finite.)  Without the flag the call is the one it was.
+      int v0m = v0, krm = kr, t0m = t0;
+      if (ly.flags & SRFRD_LAYOUT_MASK_PAD_KEYS) {
+        int vt = v0;
+        if (a.ragged_off) {
+          const unsigned long long nz = __ballot(s_in[tid & 63] != 0);
+          vt = __builtin_amdgcn_readfirstlane(nz ? (int)__builtin_ctzll(nz) : SH + L);
+        }
+        if (vt > SH) { v0m = vt; krm = vt; t0m = 0; }
+        if (sv_p != nullptr && t0 >= 1 && tid >= t0 && tid < L) sv_p[tid * LP + LP - 1] = 0.f;
+      }
+      rag_softmax(bXS, rq0, r0, v0m, krm, t0m, SH + L, dsA, sv_p, tid);
     }
     __syncthreads();
     // o = P v  (q is dead: o overlays it); tile m of the queries meets key tiles <= m: the pairs {0,3}, {1,2} cost the same

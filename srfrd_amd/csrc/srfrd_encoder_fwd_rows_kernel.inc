@@ -323,13 +323,17 @@ __global__ void __launch_bounds__(kRowWaves * 64) encoder_fwd_rows_kernel(const 
           }
           // causal softmax of query R = row0 + li over its keys j <= R (registers of this lane and of lanes li + 16 lq')
           const int R = row0 + li;
+          // key-padding mask (srfrd_layout::flags): the leading pads, counted from the pad mask of the id load; a pad query
+          // row keeps its keys (finite, masked to zero behind the FFN)
+          const int kt0 = (ly.flags & SRFRD_LAYOUT_MASK_PAD_KEYS) ? first_live(s_keep, L) : 0;
+          const int klo = R >= kt0 ? kt0 : 0;      // first key of the row
           float m = -INFINITY;
 #pragma unroll
           for (int ct = 0; ct < kRowMaxTiles; ++ct)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int j = (ct << 4) + (lq << 2) + r;
-              const bool on = ct <= t && j <= R;
+              const bool on = ct <= t && j >= klo && j <= R;
               s[ct][r] = on ? s[ct][r] : -INFINITY;
               m = fmaxf(m, s[ct][r]);
             }

@@ -306,7 +306,7 @@ class _SRFRDBase(nn.Module):
         self._ensure_flat()
         self._bf16_auto = bool(auto_refresh)
         if on:
-            lay16 = _lib.Layout.from_buffer_copy(bytes(self.layout))
+            lay16 = _lib.Layout.from_buffer_copy(bytes(self.layout))      # (flags included: use_key_padding_mask)
             lay16.table_bf16 = 1
             self._lay16 = lay16
             self._table16 = torch.empty(self.layout.n_table, device=self._flat.device, dtype=torch.int16)
@@ -325,6 +325,25 @@ class _SRFRDBase(nn.Module):
                 self._table16 = torch.empty(self.layout.n_table, device=self._flat.device, dtype=torch.int16)
             check(_lib.lib().srfrd_table_to_bf16(ptr(self._flat), self.layout.n_table, ptr(self._table16), _stream()),
                   "srfrd_table_to_bf16")
+
+    # ---- key-padding mask (the original SASRec's; no reference counterpart: it passes none, SRFR_model.py:112)
+    def use_key_padding_mask(self, on: bool = True):
+        """Mask every sequence's LEADING pads out of its attention keys (``srfrd_layout.flags``, include/srfrd_hip.h): a live
+        position then attends to the history alone, so its output no longer depends on how much padding precedes it - the
+        same user scores the same at any window that holds the history.  An id 0 behind the first item stays a key.
+        Every path that takes the model's layout follows: forward / backward, predict, topk, target_rank, evaluation and
+        srfrd_amd.Adam; a ``FusedTrainer`` reads the switch when it is built and refuses to step once it has changed.
+        Not part of any ``state_dict``.  Off, or on a batch without pads: the unmasked results, bit for bit."""
+        lay = self.layout
+        bit = _lib.LAYOUT_MASK_PAD_KEYS
+        lay.flags = (lay.flags | bit) if on else (lay.flags & ~bit)
+        if self._lay16 is not None:
+            self._lay16.flags = lay.flags
+        return self
+
+    @property
+    def key_padding_mask(self) -> bool:
+        return bool(self.layout.flags & _lib.LAYOUT_MASK_PAD_KEYS)
 
     def _table_args(self):
         """(layout, item-table pointer) as the gathering launchers take them: fp32 parameter, or the bf16 shadow"""

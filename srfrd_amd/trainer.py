@@ -219,6 +219,7 @@ class FusedTrainer:
         self.model = model
         model._ensure_flat()
         self.lay = model.layout
+        self._key_mask = model.key_padding_mask      # (in the captured launches' arguments: fixed for this trainer's life)
         self.flat = model._flat
         dev = self.flat.device
         self.B, self.L = int(batch_size), int(seq_len or self.lay.max_len)
@@ -1007,6 +1008,9 @@ class FusedTrainer:
         return self._run(slot)
 
     def _run(self, slot: int = 0):
+        if self.model.key_padding_mask != self._key_mask:
+            raise RuntimeError("model.use_key_padding_mask() changed after this FusedTrainer was built (its launches carry the "
+                               "layout's flags as they were): build a new trainer")
         if self.token:
             self._last_slot = slot
         if not self._fresh:
