@@ -5,7 +5,11 @@ There is no CPU fallback: if the library is missing this module raises, and ever
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
+import re
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SRFRD_LIB_PATH") or os.path.join(_HERE, "lib", "libsrfrd_hip.so")
@@ -48,77 +52,108 @@ _P = C.c_void_p
 _i, _i64, _u32, _d = C.c_int, C.c_int64, C.c_uint32, C.c_double
 _LP = C.POINTER(Layout)
 _OP = C.POINTER(OptimOpts)
+_TYPES = {"i": _i, "q": _i64, "u": _u32, "d": _d, "p": _P, "lay": _LP, "opt": _OP, "pq": C.POINTER(_i64), "pi": C.POINTER(C.c_int32)}
 
-# name -> (restype, argtypes); must list every symbol include/srfrd_hip.h declares (tests/test_abi.py checks it)
-SIGNATURES = {
-    "srfrd_layout_init": (_i, [_LP, _i, _i, _i, _i, _i, _i, _i, _i]),
-    "srfrd_lds_bytes": (_i, [_LP, _i, C.POINTER(_i64), C.POINTER(_i64)]),
-    "srfrd_scratch_floats": (_i, [_LP, _i, _i, C.POINTER(_i64), C.POINTER(_i64)]),
-    "srfrd_bwd_grid": (_i, [_LP, _i, _i]),
-    "srfrd_debug_shape": (_i, [_LP, _i, C.POINTER(_i64), C.POINTER(C.c_int32)]),
-    "srfrd_packed_floats": (_i64, [_LP]),
-    "srfrd_pack_weights": (_i, [_LP, _P, _P, _P, _d, _d, _d, _P]),
-    "srfrd_encoder_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
-                               _P, _P, _P, _P, _P, _P, _P, _P, _i64, _P, _i, _P]),
-    "srfrd_encoder_fwd_last": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _P, _P, _i64, _P]),
-    "srfrd_encoder_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
-                               _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _P, _i64, _P, _i, _P]),
-    "srfrd_sched_ints": (_i64, [_i]),
-    "srfrd_seq_order": (_i, [_P, _i, _i, _i, _P, _P]),
-    "srfrd_encoder_plan": (_i, [_LP, _i, _i, _i, _i, _i, _i64, _P, _P, _i, _P]),
-    "srfrd_encoder_fwd_sched": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
-                                     _P, _P, _P, _P, _P, _P, _P, _P, _i64, _P, _i, _P]),
-    "srfrd_encoder_bwd_sched": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
-                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _P, _i64, _P, _i, _P]),
-    "srfrd_encoder_plan_train": (_i, [_LP, _i, _i, _i, _i, _i, _i64, _P, _i, _P]),
-    "srfrd_train_scratch_floats": (_i64, [_LP, _i, _i]),
-    "srfrd_encoder_train_sched": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
-                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _P, _i64, _P, _i, _P]),
-    "srfrd_encoder_train_ranked": (_i, [_LP, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _d, _u32, _P, _i64,
-                                        _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _P, _i, _P]),
-    "srfrd_table_reduce": (_i, [_P, _P, _P, _i64, _i, _P, _P]),
-    "srfrd_aux_floats": (_i64, [_LP, _i, _i]),
-    "srfrd_reduce_dense": (_i, [_P, _i, _i64, _P, _P, _i, _P, _P, _P]),
-    "srfrd_loss_stats": (_i, [_P, _i, _P, _P, _P]),
-    "srfrd_step_begin": (_i, [_P, _d, _d, _d, _P]),
-    "srfrd_adam_step": (_i, [_P, _P, _P, _P, _i64, _i64, _i64, _i64, _d, _d, _d, _P, _P, _P, _i64, _P]),
-    "srfrd_adam_pack_step": (_i, [_LP, _P, _P, _P, _P, _i64, _i64, _i64, _d, _d, _d, _d, _P, _P, _P, _P, _P]),
-    "srfrd_step_begin_sched": (_i, [_P, _OP, _P]),
-    "srfrd_grad_norm": (_i, [_P, _i64, _P, _d, _P, _P, _P]),
-    "srfrd_adamw_step": (_i, [_P, _P, _P, _P, _i64, _i64, _i64, _i64, _d, _d, _d, _P, _P, _P, _P, _i64, _P]),
-    "srfrd_adamw_pack_step": (_i, [_LP, _P, _P, _P, _P, _i64, _i64, _i64, _OP, _d, _P, _P, _P, _P, _P, _P]),
-    "srfrd_table_to_bf16": (_i, [_P, _i64, _P, _P]),
-    "srfrd_loss_finalize": (_i, [_P, _P, _P]),
-    "srfrd_skew_mask": (_i, [_P, _P]),
-    "srfrd_l2_norms": (_i, [_P, _P, _P, _i, _i64, _d, _P, _P, _P, _P]),
-    "srfrd_l2_apply": (_i, [_P, _P, _i64, _i64, _i64, _P, _P, _P, _P]),
-    "srfrd_user_labels": (_i, [_i, _P, _i, _i, _P, _P]),
-    "srfrd_check_ids": (_i, [_P, _P, _P, _P, _P, _P, _i64, _i64, _i64, _P, _P]),
-    "srfrd_predict_logits": (_i, [_LP, _P, _P, _P, _i, _i, _P, _i, _i64, _P, _P, _P]),
-    "srfrd_topk_workspace_bytes": (_i64, [_i, _i, _i64]),
-    "srfrd_logits_topk": (_i, [_LP, _P, _P, _P, _i, _i, _i64, _i64, _i, _P, _i, _P, _P, _P, _P]),
-    "srfrd_topk_merge": (_i, [_P, _P, _i, _i, _i, _P, _P, _P]),
-    "srfrd_excl_workspace_bytes": (_i64, [_i, _i, _i64]),
-    "srfrd_logits_topk_excl": (_i, [_LP, _P, _P, _P, _i, _i, _i64, _i64, _i, _P, _i, _P, _P, _i, _P, _P, _P, _P, _P]),
-    "srfrd_target_rank": (_i, [_LP, _P, _P, _P, _i, _i, _i64, _i64, _i, _P, _P, _P, _P, _i, _i, _P, _P, _P, _P]),
-    "srfrd_rank_plan": (_i, [_LP, _i, _i, _i, _i64, _i64, _i, _i, _i, _i, _P, _i, _P]),
-    "srfrd_eval_rank": (_i, [_P, _i, _i, _P, _P, _P]),
-    "srfrd_sample_batch": (_i, [_P, _P, _P, _i, _i, _i, _i, _u32, _u32, _P, _P, _P]),
-    "srfrd_xent_workspace_floats": (_i64, [_LP, _i, _i]),
-    "srfrd_xent_fwd": (_i, [_LP, _P, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
-    "srfrd_xent_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _P, _P, _i, _P, _i64, _P]),
-    "srfrd_sxent_workspace_floats": (_i64, [_LP, _i, _i, _i]),
-    "srfrd_sxent_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _P, _i64, _P]),
-    "srfrd_sxent_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
-    "srfrd_shared_negatives": (_i, [_P, _i, _i, _P, _P, _P, _P, _P, _P]),
-    "srfrd_token_negatives": (_i, [_P, _P, _i, _i, _i, _P, _P, _i, _i, _i, _u32, _u32, _P, _P, _P, _P, _P, _i, _P, _P, _P]),
-    "srfrd_tneg_workspace_floats": (_i64, [_LP, _i, _i, _i]),
-    "srfrd_tneg_fwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _d, _i, _i, _i, _P, _P, _P, _P, _i64, _P]),
-    "srfrd_tneg_bwd": (_i, [_LP, _P, _P, _P, _P, _P, _i, _i, _d, _i, _P, _P, _i, _i, _P, _P, _P, _P, _i64, _P]),
-    "srfrd_table_reduce_rank1": (_i, [_P, _P, _P, _P, _i, _i, _i64, _i, _P, _P, _i64, _P]),
-    "srfrd_table_reduce_mixed_workspace_floats": (_i64, [_i64, _i]),
-    "srfrd_table_reduce_mixed": (_i, [_P, _P, _i64, _P, _i64, _P, _P, _i, _i, _i, _P, _P, _i64, _P]),
-}
+# what the six encoder entry points that run a whole forward or backward begin with (`encoder_head` builds its values)
+_ENC_HEAD = ("lay:lay item_table dense packed input_ids fake_ids pos_ids pos_fake neg_ids neg_fake B:i L:i dropout_p:d seed:u "
+             "seed_dev seq_index0:q hidden pos_logits neg_logits save_x save_h1 save_aux")
+# THE table of the C ABI: every symbol include/srfrd_hip.h declares, its parameters in the header's order and spelling, each
+# `name:type` with the types of _TYPES (a bare name: a pointer passed as void*), the return type in front.
+# tests/test_call_names.py holds it to the header; SIGNATURES and PARAMS derive from it.
+_ABI = f"""
+i srfrd_layout_init(lay:lay kind:i n_items:i max_len:i d_item:i d_fake:i n_labels:i n_blocks:i n_heads:i)
+i srfrd_lds_bytes(lay:lay L:i fwd_bytes:pq bwd_bytes:pq)
+i srfrd_scratch_floats(lay:lay B:i L:i fwd_floats:pq bwd_floats:pq)
+i srfrd_bwd_grid(lay:lay B:i L:i)
+i srfrd_debug_shape(lay:lay L:i slot_floats:pq n_slots:pi)
+q srfrd_packed_floats(lay:lay)
+i srfrd_pack_weights(lay:lay dense packed state lr:d beta1:d beta2:d stream)
+i srfrd_encoder_fwd({_ENC_HEAD} loss_part scratch scratch_floats:q dbg dbg_seq:i stream)
+i srfrd_encoder_fwd_last(lay:lay item_table dense packed input_ids fake_ids B:i L:i hidden_last scratch scratch_floats:q stream)
+i srfrd_encoder_bwd({_ENC_HEAD} d_hidden d_pos d_neg fused_bce:i grad_table table_contrib grad_slabs scratch scratch_floats:q
+    dbg dbg_seq:i stream)
+q srfrd_sched_ints(B:i)
+i srfrd_seq_order(input_ids B:i L:i pair_stride:i sched stream)
+i srfrd_encoder_plan(lay:lay B:i L:i mode:i switches:i n_cu:i scratch_floats:q fwd_name bwd_name name_len:i grids)
+i srfrd_encoder_fwd_sched({_ENC_HEAD} loss_part scratch scratch_floats:q sched sched_mode:i stream)
+i srfrd_encoder_bwd_sched({_ENC_HEAD} d_hidden d_pos d_neg fused_bce:i grad_table table_contrib grad_slabs scratch
+    scratch_floats:q sched sched_mode:i stream)
+i srfrd_encoder_plan_train(lay:lay B:i L:i mode:i switches:i n_cu:i scratch_floats:q name name_len:i grid)
+q srfrd_train_scratch_floats(lay:lay B:i L:i)
+i srfrd_encoder_train_sched({_ENC_HEAD} loss_part d_hidden d_pos d_neg fused_bce:i grad_table table_contrib grad_slabs scratch
+    scratch_floats:q sched sched_mode:i stream)
+i srfrd_encoder_train_ranked({_ENC_HEAD} loss_part fused_bce:i grad_table table_contrib grad_slabs pair_stride:i stream)
+i srfrd_table_reduce(sorted_keys order table_contrib n:q d_item:i grad_table stream)
+q srfrd_aux_floats(lay:lay B:i L:i)
+i srfrd_reduce_dense(grad_slabs n_slabs:i n_dense:q grad_dense loss_part B:i stats loss_out stream)
+i srfrd_loss_stats(loss_part B:i stats loss_out stream)
+i srfrd_step_begin(state lr:d beta1:d beta2:d stream)
+i srfrd_adam_step(param grad m v n:q i0:q i1:q n_zero:q beta1:d beta2:d eps:d state stats table_bf16 n_table:q stream)
+i srfrd_adam_pack_step(lay:lay param grad m v n:q n_table_pad:q n_zero:q lr:d beta1:d beta2:d eps:d state stats packed
+    table_bf16 stream)
+i srfrd_step_begin_sched(state opts:opt stream)
+i srfrd_grad_norm(grad n:q stats max_norm:d partial out stream)
+i srfrd_adamw_step(param grad m v n:q i0:q i1:q n_zero:q beta1:d beta2:d eps:d state stats clip table_bf16 n_table:q stream)
+i srfrd_adamw_pack_step(lay:lay param grad m v n:q n_table_pad:q n_zero:q opts:opt eps:d state stats clip packed table_bf16
+    stream)
+i srfrd_table_to_bf16(src n:q out stream)
+i srfrd_loss_finalize(stats loss_out stream)
+i srfrd_skew_mask(out_dev stream)
+i srfrd_l2_norms(param seg_off seg_len n_seg:i n_table_pad:q l2_emb:d partial l2buf dense_scale stream)
+i srfrd_l2_apply(grad param i0:q i1:q n_table_pad:q l2buf dense_scale stats stream)
+i srfrd_user_labels(kind:i fake_ids B:i L:i labels stream)
+i srfrd_check_ids(item_a item_b item_c fake_a fake_b fake_c n:q n_items:q fake_hi:q err_word stream)
+i srfrd_predict_logits(lay:lay item_table dense hidden B:i L:i cand n_cand:i cand_stride:q user_label logits stream)
+q srfrd_topk_workspace_bytes(B:i k:i n_rows:q)
+i srfrd_logits_topk(lay:lay item_table dense hidden B:i L:i item_lo:q item_hi:q exclude_pad:i user_label k:i topk_idx topk_val
+    workspace stream)
+i srfrd_topk_merge(cand_idx cand_val B:i n_cand:i k:i topk_idx topk_val stream)
+q srfrd_excl_workspace_bytes(B:i max_row:i n_rows:q)
+i srfrd_logits_topk_excl(lay:lay item_table dense hidden B:i L:i item_lo:q item_hi:q exclude_pad:i user_label k:i excl_ptr
+    excl_items max_row:i topk_idx topk_val workspace excl_workspace stream)
+i srfrd_target_rank(lay:lay item_table dense hidden B:i L:i item_lo:q item_hi:q exclude_pad:i user_label targets excl_ptr
+    excl_items max_row:i cut_k:i rank metric_acc workspace stream)
+i srfrd_rank_plan(lay:lay op:i B:i k:i item_lo:q item_hi:q excl:i switches:i n_cu:i max_launches:i names name_len:i geom)
+i srfrd_eval_rank(logits B:i n_cand:i rank metric_acc stream)
+i srfrd_sample_batch(user_ptr items reviews usernum:i itemnum:i B:i L:i seed:u batch_index:u out_user out_packed stream)
+q srfrd_xent_workspace_floats(lay:lay B:i L:i)
+i srfrd_xent_fwd(lay:lay table hidden targets B:i L:i token_loss lse stats workspace ws_floats:q stream)
+i srfrd_xent_bwd(lay:lay table hidden targets lse d_token_loss B:i L:i d_hidden grad_table accumulate:i workspace ws_floats:q
+    stream)
+q srfrd_sxent_workspace_floats(lay:lay B:i L:i K:i)
+i srfrd_sxent_fwd(lay:lay table hidden targets negatives log_q K:i remove_hits:i B:i L:i token_loss lse stats workspace
+    ws_floats:q stream)
+i srfrd_sxent_bwd(lay:lay table hidden targets negatives log_q K:i remove_hits:i lse d_token_loss B:i L:i d_hidden table_contrib
+    contrib_keys workspace ws_floats:q stream)
+i srfrd_shared_negatives(state n_items:i K:i alias_prob alias_idx item_log_q out_ids out_log_q stream)
+i srfrd_token_negatives(user_ptr items usernum:i n_items:i max_hist:i users targets B:i L:i K:i seed:u batch_index:u state
+    alias_prob alias_idx item_log_q user_log_keep exclude_history:i out_ids out_log_q stream)
+q srfrd_tneg_workspace_floats(lay:lay B:i L:i K:i)
+i srfrd_tneg_fwd(lay:lay table hidden targets negatives log_q K:i objective:i beta:d remove_hits:i B:i L:i token_loss lse stats
+    workspace ws_floats:q stream)
+i srfrd_tneg_bwd(lay:lay table hidden targets negatives log_q K:i objective:i beta:d remove_hits:i lse d_token_loss B:i L:i
+    d_hidden contrib_coef contrib_keys workspace ws_floats:q stream)
+i srfrd_table_reduce_rank1(sorted_keys order contrib_coef hidden d_out:i rows_per_token:i n:q d_item:i grad_table workspace
+    ws_floats:q stream)
+q srfrd_table_reduce_mixed_workspace_floats(n:q d_item:i)
+i srfrd_table_reduce_mixed(sorted_keys order n:q rows n_rows:q contrib_coef hidden d_out:i rows_per_token:i d_item:i grad_table
+    workspace ws_floats:q stream)
+"""
+
+
+def _parse(params):
+    pairs = [(p + ":p").split(":")[:2] for p in params.split()]
+    return [_TYPES[t] for _, t in pairs], tuple(n for n, _ in pairs)
+
+
+_PARSED = {name: (_TYPES[res], *_parse(params)) for res, name, params in re.findall(r"(\w) (srfrd_\w+)\(([^)]*)\)", _ABI)}
+SIGNATURES = {name: (res, types) for name, (res, types, _) in _PARSED.items()}      # name -> (restype, argtypes)
+PARAMS = {name: names for name, (_, _, names) in _PARSED.items()}                   # name -> parameter names, in order
+ENCODER_HEAD = _parse(_ENC_HEAD)[1]
+# name -> (its names as a set, the fetch of a dict's values in parameter order, the positions that hold a pointer)
+_MARSHAL = {name: (frozenset(names), operator.itemgetter(*names) if len(names) > 1 else (lambda a, n=names[0]: (a[n],)),
+                   tuple(i for i, t in enumerate(types) if t not in (_i, _i64, _u32, _d)))
+            for name, (_, types, names) in _PARSED.items()}
 
 _lib = None
 
@@ -153,23 +188,67 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def stream():
+    """the current torch stream, as the launchers' `stream` argument"""
+    return torch.cuda.current_stream().cuda_stream
+
+
+def dense_ptr(flat, n_table_pad):
+    """address of the dense part of a flat [table | pad | dense] vector (parameters, gradient or moments)"""
+    return flat.data_ptr() + 4 * n_table_pad
+
+
+def query(name, /, **args):
+    """The C entry point ``name`` with its parameters BY NAME (PARAMS: the header's; all of them, except that ``stream`` defaults
+    to the current torch stream) -> its raw return value.  In a pointer's place a tensor passes its ``data_ptr()``, None is
+    NULL, a ctypes structure goes by reference, anything else (an address as an int, a ctypes buffer) as it is.  A missing or
+    unknown name raises TypeError before the library is touched; the function is looked up on the handle at every call."""
+    known, fetch, pointers = _MARSHAL[name]
+    if "stream" in known and "stream" not in args:
+        args["stream"] = stream()
+    if args.keys() != known:
+        raise TypeError(f"{name}: missing {sorted(known - args.keys())}, unknown {sorted(args.keys() - known)}")
+    argv = list(fetch(args))
+    for i in pointers:
+        v = argv[i]
+        if isinstance(v, torch.Tensor):
+            argv[i] = v.data_ptr()
+        elif isinstance(v, C.Structure):
+            argv[i] = C.byref(v)
+    return getattr(lib(), name)(*argv)
+
+
+def call(name, /, **args):
+    """``query`` for a launcher: a non-zero return raises (``check``)."""
+    check(query(name, **args), name)
+
+
+def encoder_head(table_args, flat, n_table_pad, packed, ids, B, L, dropout_p, seq0, out, seed=0, seed_dev=None):
+    """The named values every encoder entry point begins with (ENCODER_HEAD): a model's ``_table_args()`` pair, flat vector and
+    packed weights, the six id planes (None where absent; an absent target plane takes its logits with it), the dropout seed
+    (host value) or ``seed_dev`` (address of its device word), the first global sequence, ``out``: the forward's six outputs."""
+    out = (out[0], out[1] if ids[2] is not None else None, out[2] if ids[4] is not None else None, *out[3:])
+    return dict(zip(ENCODER_HEAD, (*table_args, dense_ptr(flat, n_table_pad), packed, *ids, B, L, float(dropout_p),
+                                   int(seed) & 0xFFFFFFFF, seed_dev, int(seq0), *out)))
+
+
 def make_layout(kind: str, n_items: int, max_len: int, d_item: int, d_fake: int = 0, n_labels: int = 0,
                 n_blocks: int = 2, n_heads: int = 1) -> Layout:
     lay = Layout()
-    check(lib().srfrd_layout_init(C.byref(lay), KINDS[kind], n_items, max_len, d_item, d_fake, n_labels, n_blocks,
-                                  n_heads), "srfrd_layout_init")
+    call("srfrd_layout_init", lay=lay, kind=KINDS[kind], n_items=n_items, max_len=max_len, d_item=d_item, d_fake=d_fake,
+         n_labels=n_labels, n_blocks=n_blocks, n_heads=n_heads)
     return lay
 
 
 def lds_bytes(lay: Layout, L: int):
     f, b = _i64(0), _i64(0)
-    check(lib().srfrd_lds_bytes(C.byref(lay), L, C.byref(f), C.byref(b)), "srfrd_lds_bytes")
+    call("srfrd_lds_bytes", lay=lay, L=L, fwd_bytes=C.byref(f), bwd_bytes=C.byref(b))
     return f.value, b.value
 
 
 def scratch_floats(lay: Layout, B: int, L: int):
     f, b = _i64(0), _i64(0)
-    check(lib().srfrd_scratch_floats(C.byref(lay), B, L, C.byref(f), C.byref(b)), "srfrd_scratch_floats")
+    call("srfrd_scratch_floats", lay=lay, B=B, L=L, fwd_floats=C.byref(f), bwd_floats=C.byref(b))
     return f.value, b.value
 
 
@@ -183,8 +262,8 @@ def encoder_plan(lay: Layout, B: int, L: int, mode: int, switches: int = 0, n_cu
     """srfrd_encoder_plan (no GPU needed) -> ((forward kernel, grid), (backward kernel, grid)); a direction the encoder
     refuses with SRFRD_E_UNSUPPORTED reads ("", -2)."""
     fwd, bwd, grids = C.create_string_buffer(128), C.create_string_buffer(128), (C.c_int32 * 2)()
-    check(lib().srfrd_encoder_plan(C.byref(lay), B, L, mode, switches, n_cu, scratch_floats, fwd, bwd, 128, grids),
-          "srfrd_encoder_plan")
+    call("srfrd_encoder_plan", lay=lay, B=B, L=L, mode=mode, switches=switches, n_cu=n_cu, scratch_floats=scratch_floats,
+         fwd_name=fwd, bwd_name=bwd, name_len=128, grids=grids)
     return (fwd.value.decode(), grids[0]), (bwd.value.decode(), grids[1])
 
 
@@ -192,8 +271,8 @@ def encoder_plan_train(lay: Layout, B: int, L: int, mode: int, switches: int = 0
     """srfrd_encoder_plan_train (no GPU needed) -> (train kernel, grid): what srfrd_encoder_train_sched launches, or ("", -2)
     where it refuses with SRFRD_E_UNSUPPORTED."""
     name, grid = C.create_string_buffer(128), C.c_int32(0)
-    check(lib().srfrd_encoder_plan_train(C.byref(lay), B, L, mode, switches, n_cu, scratch_floats, name, 128, C.byref(grid)),
-          "srfrd_encoder_plan_train")
+    call("srfrd_encoder_plan_train", lay=lay, B=B, L=L, mode=mode, switches=switches, n_cu=n_cu, scratch_floats=scratch_floats,
+         name=name, name_len=128, grid=C.byref(grid))
     return name.value.decode(), grid.value
 
 
@@ -220,7 +299,8 @@ def rank_plan(lay: Layout, op: int, B: int, k: int, item_lo: int, item_hi: int, 
     negative code the call refuses with (SRFRD_E_UNSUPPORTED, SRFRD_E_ARG)."""
     n, w = 8, 96
     names, geom = C.create_string_buffer(n * w), (C.c_int32 * (3 * n))()
-    rc = lib().srfrd_rank_plan(C.byref(lay), op, B, k, item_lo, item_hi, int(excl), switches, n_cu, n, names, w, geom)
+    rc = query("srfrd_rank_plan", lay=lay, op=op, B=B, k=k, item_lo=item_lo, item_hi=item_hi, excl=int(excl), switches=switches,
+               n_cu=n_cu, max_launches=n, names=names, name_len=w, geom=geom)
     if rc < 0:
         return rc
     return [(names.raw[i * w:(i + 1) * w].split(b"\0")[0].decode(), geom[3 * i], geom[3 * i + 1], geom[3 * i + 2])

@@ -8,14 +8,13 @@ so every consumer is a vectorised numpy / device operation instead of the refere
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, ptr
+from ._lib import call
 from .sampler import alias_table, history_log_keep, negative_q
 
 
@@ -248,10 +247,9 @@ class DeviceSampler:
             out = torch.empty(6, self.B, self.L, device=self.device, dtype=torch.int64)
         elif out.shape != (6, self.B, self.L) or out.dtype != torch.int64 or not out.is_contiguous() or out.device.type != "cuda":
             raise ValueError("out must be a contiguous int64 (6, B, L) tensor on the sampler's device")
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(_lib.lib().srfrd_sample_batch(ptr(self.ptr), ptr(self.items), ptr(self.reviews), self.data.usernum,
-                                            self.data.itemnum, self.B, self.L, self.seed & 0xFFFFFFFF,
-                                            self.index & 0xFFFFFFFF, ptr(user), ptr(out), st), "srfrd_sample_batch")
+        call("srfrd_sample_batch", user_ptr=self.ptr, items=self.items, reviews=self.reviews, usernum=self.data.usernum,
+             itemnum=self.data.itemnum, B=self.B, L=self.L, seed=self.seed & 0xFFFFFFFF, batch_index=self.index & 0xFFFFFFFF,
+             out_user=user, out_packed=out)
         if self.K > 0:
             self.negatives, self.log_q = self.token_negatives(user, out[2], index=self.index, out=neg_out, out_log_q=log_q_out)
         self.index += 1
@@ -285,12 +283,11 @@ class DeviceSampler:
             out = torch.empty(B, L, self.K, device=self.device, dtype=torch.int64)
         if out_log_q is None:
             out_log_q = torch.empty(B, L, self.K, device=self.device, dtype=torch.float32)
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(_lib.lib().srfrd_token_negatives(ptr(self.ptr), ptr(self.items), self.data.usernum, self.data.itemnum, self.max_hist,
-                                               ptr(user), ptr(pos), B, L, self.K, self.seed & 0xFFFFFFFF, int(index) & 0xFFFFFFFF,
-                                               ptr(state), ptr(self.alias_prob), ptr(self.alias_idx), ptr(self.item_log_q),
-                                               ptr(self.user_log_keep), int(self.exclude_history), ptr(out), ptr(out_log_q), st),
-              "srfrd_token_negatives")
+        call("srfrd_token_negatives", user_ptr=self.ptr, items=self.items, usernum=self.data.usernum, n_items=self.data.itemnum,
+             max_hist=self.max_hist, users=user, targets=pos, B=B, L=L, K=self.K, seed=self.seed & 0xFFFFFFFF,
+             batch_index=int(index) & 0xFFFFFFFF, state=state, alias_prob=self.alias_prob, alias_idx=self.alias_idx,
+             item_log_q=self.item_log_q, user_log_keep=self.user_log_keep, exclude_history=int(self.exclude_history), out_ids=out,
+             out_log_q=out_log_q)
         return out, out_log_q
 
     def close(self):

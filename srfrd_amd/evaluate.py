@@ -7,12 +7,10 @@ HR@10 += rank < 10, NDCG@10 += 1 / log2(rank + 2).
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _lib, ops  # noqa: F401  (ops: registers torch.ops.srfrd.*)
-from ._lib import check, ptr
+from . import ops  # noqa: F401  (registers torch.ops.srfrd.*)
+from ._lib import call
 
 
 def ranks_from_logits(logits: torch.Tensor, metric_acc: torch.Tensor | None = None) -> torch.Tensor:
@@ -24,8 +22,7 @@ def ranks_from_logits(logits: torch.Tensor, metric_acc: torch.Tensor | None = No
     logits = logits.contiguous()
     B, n = logits.shape
     rank = torch.empty(B, device=logits.device, dtype=torch.int32)
-    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    check(_lib.lib().srfrd_eval_rank(ptr(logits), B, n, ptr(rank), ptr(metric_acc), st), "srfrd_eval_rank")
+    call("srfrd_eval_rank", logits=logits, B=B, n_cand=n, rank=rank, metric_acc=metric_acc)
     return rank
 
 

@@ -18,17 +18,11 @@ allocate may be handed in instead (a persistent-buffer step allocates nothing); 
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Callable, NamedTuple, Optional
 
 import torch
 
-from . import _lib
-from ._lib import check, ptr
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._lib import call, query
 
 
 def table_dense(lay, hidden, K, rows, keys, ws, d_table):
@@ -47,23 +41,22 @@ def table_rows(lay, hidden, K, rows, keys, ws, d_table):
     """every item's contribution rows (its negative slots in slot order, then its target tokens in position order) summed in
     that fixed order"""
     skeys, order, d_table = _sorted_keys(lay, keys, d_table)
-    check(_lib.lib().srfrd_table_reduce(ptr(skeys), ptr(order), ptr(rows), skeys.numel(), lay.d_item, ptr(d_table), _stream()),
-          "srfrd_table_reduce")
+    call("srfrd_table_reduce", sorted_keys=skeys, order=order, table_contrib=rows, n=skeys.numel(), d_item=lay.d_item,
+         grad_table=d_table)
     return d_table
 
 
 def table_rank1(lay, hidden, K, rows, keys, ws, d_table):
     """every item's rank-1 rows coef * hidden[t] summed in list order (position-major, the target before its negatives)"""
     skeys, order, d_table = _sorted_keys(lay, keys, d_table)
-    check(_lib.lib().srfrd_table_reduce_rank1(ptr(skeys), ptr(order), ptr(rows), ptr(hidden), lay.d_out, 1 + K, skeys.numel(),
-                                              lay.d_item, ptr(d_table), ptr(ws), ws.numel(), _stream()),
-          "srfrd_table_reduce_rank1")
+    call("srfrd_table_reduce_rank1", sorted_keys=skeys, order=order, contrib_coef=rows, hidden=hidden, d_out=lay.d_out,
+         rows_per_token=1 + K, n=skeys.numel(), d_item=lay.d_item, grad_table=d_table, workspace=ws, ws_floats=ws.numel())
     return d_table
 
 
 def mixed_workspace(n, d_item):
     """floats of workspace srfrd_table_reduce_mixed needs for a list of n entries (0: it refuses them)"""
-    return int(_lib.lib().srfrd_table_reduce_mixed_workspace_floats(int(n), int(d_item)))
+    return int(query("srfrd_table_reduce_mixed_workspace_floats", n=int(n), d_item=int(d_item)))
 
 
 def table_mixed(lay, hidden, K, full_rows, coef, keys, ws, d_table, sorted_pair=None):
@@ -91,9 +84,9 @@ def table_mixed(lay, hidden, K, full_rows, coef, keys, ws, d_table, sorted_pair=
         skeys, order = sorted_pair
         if skeys.numel() != n or order.numel() != n or skeys.dtype != torch.int64 or order.dtype != torch.int64:
             raise ValueError(f"sorted_pair must be two int64 tensors of {n} elements")
-    check(_lib.lib().srfrd_table_reduce_mixed(ptr(skeys), ptr(order), n, ptr(full_rows), n_rows, ptr(coef),
-                                              ptr(hidden) if n_coef else None, lay.d_out, 1 + K, lay.d_item, ptr(d_table),
-                                              ptr(ws), ws.numel(), _stream()), "srfrd_table_reduce_mixed")
+    call("srfrd_table_reduce_mixed", sorted_keys=skeys, order=order, n=n, rows=full_rows, n_rows=n_rows, contrib_coef=coef,
+         hidden=hidden if n_coef else None, d_out=lay.d_out, rows_per_token=1 + K, d_item=lay.d_item, grad_table=d_table,
+         workspace=ws, ws_floats=ws.numel())
     return d_table
 
 
@@ -101,28 +94,38 @@ class Head(NamedTuple):
     fwd: str                        # the C entry points
     bwd: str
     n_neg: Optional[Callable]       # negatives tensor -> K (None: the head takes no arguments of its own)
-    workspace: Callable             # (lib, layout, B, L, K) -> workspace floats
+    scalars: tuple                  # the C names of the head's scalar arguments, in the order `args` gives them
+    workspace: Callable             # (layout, B, L, K) -> workspace floats
+    grad: tuple                     # the C names of the backward's two table-gradient arguments
     rows: Optional[Callable]        # (layout, T, K) -> shape of the backward's contribution list (None: dense table gradient)
     finish: Callable                # table_dense | table_rows | table_rank1
 
 
-XENT = Head("srfrd_xent_fwd", "srfrd_xent_bwd", None,
-            lambda L_, lay, B, L, K: L_.srfrd_xent_workspace_floats(C.byref(lay), B, L), None, table_dense)
-SXENT = Head("srfrd_sxent_fwd", "srfrd_sxent_bwd", lambda neg: neg.numel(),
-             lambda L_, lay, B, L, K: L_.srfrd_sxent_workspace_floats(C.byref(lay), B, L, K),
-             lambda lay, T, K: (K + T, lay.d_item), table_rows)
-TNEG = Head("srfrd_tneg_fwd", "srfrd_tneg_bwd", lambda neg: neg.shape[2],
-            lambda L_, lay, B, L, K: max(L_.srfrd_tneg_workspace_floats(C.byref(lay), B, L, K), 1),
-            lambda lay, T, K: (T * (1 + K),), table_rank1)
+XENT = Head("srfrd_xent_fwd", "srfrd_xent_bwd", None, (),
+            lambda lay, B, L, K: query("srfrd_xent_workspace_floats", lay=lay, B=B, L=L),
+            ("grad_table", "accumulate"), None, table_dense)
+SXENT = Head("srfrd_sxent_fwd", "srfrd_sxent_bwd", lambda neg: neg.numel(), ("remove_hits",),
+             lambda lay, B, L, K: query("srfrd_sxent_workspace_floats", lay=lay, B=B, L=L, K=K),
+             ("table_contrib", "contrib_keys"), lambda lay, T, K: (K + T, lay.d_item), table_rows)
+TNEG = Head("srfrd_tneg_fwd", "srfrd_tneg_bwd", lambda neg: neg.shape[2], ("objective", "beta", "remove_hits"),
+            lambda lay, B, L, K: max(query("srfrd_tneg_workspace_floats", lay=lay, B=B, L=L, K=K), 1),
+            ("contrib_coef", "contrib_keys"), lambda lay, T, K: (T * (1 + K),), table_rank1)
 
 
-def _head_args(head, args):
-    """(negatives, log_q, *scalars) -> (K, the C arguments between the targets and lse / B)"""
-    if head.n_neg is None:
-        return 0, ()
-    negatives, log_q, *scalars = args
-    K = head.n_neg(negatives)
-    return K, (ptr(negatives), ptr(log_q), K, *(int(s) if isinstance(s, bool) else s for s in scalars))
+def _head_args(head, lay, table_ptr, hidden, targets, args, ws):
+    """(negatives, log_q, *scalars) -> (K, the workspace, the named C arguments both directions of the head share)"""
+    B, L = targets.shape
+    named = dict(lay=lay, table=table_ptr, hidden=hidden, targets=targets, B=B, L=L)
+    K = 0
+    if head.n_neg is not None:
+        negatives, log_q, *scalars = args
+        K = head.n_neg(negatives)
+        named.update(negatives=negatives, log_q=log_q, K=K)
+        named.update(zip(head.scalars, (int(s) if isinstance(s, bool) else s for s in scalars)))
+    if ws is None:
+        ws = torch.empty(head.workspace(lay, B, L, K), device=hidden.device, dtype=torch.float32)
+    named.update(workspace=ws, ws_floats=ws.numel())
+    return K, ws, named
 
 
 def launch_fwd(head: Head, lay, table_ptr, hidden, targets, args=(), *, out=None, ws=None):
@@ -130,13 +133,9 @@ def launch_fwd(head: Head, lay, table_ptr, hidden, targets, args=(), *, out=None
     module docstring); ``out``: those three tensors, ``ws``: the workspace, where the caller keeps them"""
     B, L = targets.shape
     f32 = dict(device=hidden.device, dtype=torch.float32)
-    L_ = _lib.lib()
-    K, cargs = _head_args(head, args)
-    if ws is None:
-        ws = torch.empty(head.workspace(L_, lay, B, L, K), **f32)
+    _, _, named = _head_args(head, lay, table_ptr, hidden, targets, args, ws)
     tl, lse, stats = out if out is not None else (torch.empty(B, L, **f32), torch.empty(B, L, **f32), torch.empty(2, **f32))
-    check(getattr(L_, head.fwd)(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), *cargs, B, L, ptr(tl), ptr(lse), ptr(stats),
-                                ptr(ws), ws.numel(), _stream()), head.fwd)
+    call(head.fwd, **named, token_loss=tl, lse=lse, stats=stats)
     return tl, lse, stats
 
 
@@ -149,23 +148,19 @@ def launch_bwd(head: Head, lay, table_ptr, hidden, targets, args, lse, d_token_l
     rows of its own."""
     B, L = targets.shape
     f32 = dict(device=hidden.device, dtype=torch.float32)
-    L_ = _lib.lib()
-    K, cargs = _head_args(head, args)
-    if ws is None:
-        ws = torch.empty(head.workspace(L_, lay, B, L, K), **f32)
+    K, ws, named = _head_args(head, lay, table_ptr, hidden, targets, args, ws)
     if d_hidden is None:
         d_hidden = torch.empty(B, L, lay.d_out, **f32)
     if head.rows is None:
         if d_table is None:
             d_table = torch.empty(lay.n_items + 1, lay.d_item, **f32)
-        grad_args = (ptr(d_table), int(accumulate))
+        grad = (d_table, int(accumulate))
     else:
         shape = head.rows(lay, B * L, K)
         if rows is None:
             rows = torch.empty(shape, **f32)
         if keys is None:
             keys = torch.empty(shape[0], device=hidden.device, dtype=torch.int64)
-        grad_args = (ptr(rows), ptr(keys))
-    check(getattr(L_, head.bwd)(C.byref(lay), table_ptr, ptr(hidden), ptr(targets), *cargs, ptr(lse), ptr(d_token_loss), B, L,
-                                ptr(d_hidden), *grad_args, ptr(ws), ws.numel(), _stream()), head.bwd)
+        grad = (rows, keys)
+    call(head.bwd, **named, lse=lse, d_token_loss=d_token_loss, d_hidden=d_hidden, **dict(zip(head.grad, grad)))
     return d_hidden, (head.finish(lay, hidden, K, rows, keys, ws, d_table) if finish else None)

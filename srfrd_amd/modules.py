@@ -9,14 +9,13 @@ All arithmetic runs in ``libsrfrd_hip.so``; on a non-CUDA device or without the 
 """
 from __future__ import annotations
 
-import ctypes as C
 import weakref
 
 import torch
 import torch.nn as nn
 
 from . import _lib, loss_heads, ops
-from ._lib import check, ptr
+from ._lib import call, ptr
 
 
 FLAT_SLACK = 4096        # floats of zero padding kept behind a model's flat parameter vector
@@ -30,10 +29,6 @@ def flat_owner(storage_ptr: int):
     if m is None or m._flat is None or m._flat.untyped_storage().data_ptr() != storage_ptr:
         return None
     return m
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _ids(t, device, shape=None):
@@ -90,6 +85,9 @@ class SRFU_Embedding(nn.Module):
         return self.user_label_embed
 
 
+OUT_KEYS = ("hidden", "pos_logits", "neg_logits", "save_x", "save_h1", "save_aux")      # what _launch_fwd returns, in order
+
+
 class _EncoderFn(torch.autograd.Function):
     """forward() of the drop-in modules under autograd: the same two launches as the registered ``srfrd::encoder_fwd`` /
     ``srfrd::encoder_bwd`` custom ops (srfrd_amd/ops.py - dispatcher-visible, opcheck'ed, and what ``module.library_ops =
@@ -102,31 +100,20 @@ class _EncoderFn(torch.autograd.Function):
     def forward(ctx, model, p, seed, inp, fk, pos, pfk, neg, nfk, *params):
         out = model._launch_fwd(inp, fk, pos, pfk, neg, nfk, p, seed, True)
         ctx.model, ctx.meta = model, (p, seed)
-        ctx.id_present = tuple(t is not None for t in (inp, fk, pos, pfk, neg, nfk))
-        ctx.have = (pos is not None, neg is not None)
         ctx.set_materialize_grads(False)
         hidden = out["hidden"]
         pl = out["pos_logits"] if pos is not None else hidden.new_empty(0)
         nl = out["neg_logits"] if neg is not None else hidden.new_empty(0)
-        ctx.save_for_backward(hidden, pl, nl, out["save_x"], out["save_h1"], out["save_aux"],
-                              *[t for t in (inp, fk, pos, pfk, neg, nfk) if t is not None])
+        saved, ctx.id_present = ops.pack_saved((hidden, pl, nl, out["save_x"], out["save_h1"], out["save_aux"]),
+                                           (inp, fk, pos, pfk, neg, nfk))
+        ctx.save_for_backward(*saved)
         return hidden, pl, nl
 
     @staticmethod
     def backward(ctx, d_hidden, d_pl, d_nl):
-        m = ctx.model
-        p, seed = ctx.meta
-        saved = ctx.saved_tensors
-        hidden, pl, nl, sx, sh, sa = saved[:6]
-        rest = iter(saved[6:])
-        inp, fk, pos, pfk, neg, nfk = (next(rest) if present else None for present in ctx.id_present)
-        out = {"hidden": hidden, "pos_logits": pl if ctx.have[0] else None, "neg_logits": nl if ctx.have[1] else None,
-               "save_x": sx, "save_h1": sh, "save_aux": sa}
-        gflat = m._launch_bwd(inp, fk, pos, pfk, neg, nfk, p, seed, out,
-                              None if d_hidden is None else d_hidden.contiguous(),
-                              None if (d_pl is None or pos is None) else d_pl.contiguous(),
-                              None if (d_nl is None or neg is None) else d_nl.contiguous())
-        return (None,) * 9 + m._grad_views(gflat)
+        out, ids, upstream = ops.unpack_saved(ctx.saved_tensors, ctx.id_present, (d_hidden, d_pl, d_nl))
+        gflat = ctx.model._launch_bwd(*ids, *ctx.meta, dict(zip(OUT_KEYS, out)), *upstream)
+        return (None,) * 9 + ctx.model._grad_views(gflat)
 
 
 class _LossHeadFn(torch.autograd.Function):
@@ -323,8 +310,7 @@ class _SRFRDBase(nn.Module):
         if self._table16 is not None:
             if self._table16.device != self._flat.device:
                 self._table16 = torch.empty(self.layout.n_table, device=self._flat.device, dtype=torch.int16)
-            check(_lib.lib().srfrd_table_to_bf16(ptr(self._flat), self.layout.n_table, ptr(self._table16), _stream()),
-                  "srfrd_table_to_bf16")
+            call("srfrd_table_to_bf16", src=self._flat, n=self.layout.n_table, out=self._table16)
 
     # ---- key-padding mask (the original SASRec's; no reference counterpart: it passes none, SRFR_model.py:112)
     def use_key_padding_mask(self, on: bool = True):
@@ -358,9 +344,9 @@ class _SRFRDBase(nn.Module):
         if getattr(self, "_bf16_auto", True):
             self.refresh_bf16_table()
         if self._packed is None or self._packed.device != flat.device:
-            self._packed = torch.empty(_lib.lib().srfrd_packed_floats(C.byref(lay)), device=flat.device, dtype=torch.float32)
-        check(_lib.lib().srfrd_pack_weights(C.byref(lay), C.c_void_p(flat.data_ptr() + 4 * self.n_table_pad),
-                                            ptr(self._packed), None, 0.0, 0.0, 0.0, _stream()), "srfrd_pack_weights")
+            self._packed = torch.empty(_lib.query("srfrd_packed_floats", lay=lay), device=flat.device, dtype=torch.float32)
+        call("srfrd_pack_weights", lay=lay, dense=_lib.dense_ptr(flat, self.n_table_pad), packed=self._packed, state=None,
+             lr=0.0, beta1=0.0, beta2=0.0)
         return self._packed
 
     def _scratch_for(self, B, L, backward):
@@ -373,59 +359,53 @@ class _SRFRDBase(nn.Module):
         return self._scratch, need
 
     # ---- launches
-    def _launch_fwd(self, inp, fk, pos, pfk, neg, nfk, dropout_p, seed, save, seq0=0, dbg=None, dbg_seq=0):
-        lay, flat = self.layout, self._flat
+    def _enc_head(self, ids, dropout_p, seed, seq0, out):
+        """_lib.encoder_head of this model for the id planes ``ids`` and the forward's outputs ``out`` (a dict by OUT_KEYS)"""
+        B, L = ids[0].shape
+        return _lib.encoder_head(self._table_args(), self._flat, self.n_table_pad, self._packed, ids, B, L, dropout_p, seq0,
+                                 [out[k] for k in OUT_KEYS], seed=seed)
+
+    def _launch_fwd(self, inp, fk, pos, pfk, neg, nfk, dropout_p, seed, save, seq0=0, dbg=None, dbg_seq=0, out=None):
+        """``out``: the caller's output buffers by OUT_KEYS (None: allocated here, only those the call writes)"""
+        lay = self.layout
         B, L = inp.shape
-        dev = inp.device
-        hidden = torch.empty(B, L, lay.d_out, device=dev, dtype=torch.float32)
-        pl = torch.empty(B, L, device=dev, dtype=torch.float32) if pos is not None else None
-        nl = torch.empty(B, L, device=dev, dtype=torch.float32) if neg is not None else None
-        sx = torch.empty(B, lay.n_blocks + 1, L, lay.D, device=dev, dtype=torch.float32) if save else None
-        sh = torch.empty(B, lay.n_blocks, L, lay.D, device=dev, dtype=torch.float32) if save else None
-        sa = torch.empty(_lib.lib().srfrd_aux_floats(C.byref(lay), B, L), device=dev, dtype=torch.float32) if save else None
-        packed = self.pack_weights()          # parameters may have been stepped since the last call
+        if out is None:
+            f32 = dict(device=inp.device, dtype=torch.float32)
+            out = {"hidden": torch.empty(B, L, lay.d_out, **f32),
+                   "pos_logits": torch.empty(B, L, **f32) if pos is not None else None,
+                   "neg_logits": torch.empty(B, L, **f32) if neg is not None else None,
+                   "save_x": torch.empty(B, lay.n_blocks + 1, L, lay.D, **f32) if save else None,
+                   "save_h1": torch.empty(B, lay.n_blocks, L, lay.D, **f32) if save else None,
+                   "save_aux": torch.empty(_lib.query("srfrd_aux_floats", lay=lay, B=B, L=L), **f32) if save else None}
+        self.pack_weights()          # parameters may have been stepped since the last call
         scratch, n_scr = self._scratch_for(B, L, backward=False)
-        lay_t, tab = self._table_args()
-        check(_lib.lib().srfrd_encoder_fwd(
-            C.byref(lay_t), tab, C.c_void_p(flat.data_ptr() + 4 * self.n_table_pad), ptr(packed),
-            ptr(inp), ptr(fk), ptr(pos), ptr(pfk), ptr(neg), ptr(nfk), B, L, float(dropout_p), int(seed) & 0xFFFFFFFF,
-            None, int(seq0), ptr(hidden), ptr(pl), ptr(nl), ptr(sx), ptr(sh), ptr(sa), None, ptr(scratch), n_scr, ptr(dbg),
-            int(dbg_seq), _stream()), "srfrd_encoder_fwd")
-        return {"hidden": hidden, "pos_logits": pl, "neg_logits": nl, "save_x": sx, "save_h1": sh, "save_aux": sa}
+        call("srfrd_encoder_fwd", **self._enc_head((inp, fk, pos, pfk, neg, nfk), dropout_p, seed, seq0, out), loss_part=None,
+             scratch=scratch, scratch_floats=n_scr, dbg=dbg, dbg_seq=int(dbg_seq))
+        return out
 
     def _launch_fwd_last(self, inp, fk):
         """Eval-mode encoder state of the last position only, (B, 1, d_out): what predict() / topk() rank with."""
-        lay, flat = self.layout, self._flat
         B, L = inp.shape
-        hidden = torch.empty(B, 1, lay.d_out, device=inp.device, dtype=torch.float32)
-        packed = self.pack_weights()
+        hidden = torch.empty(B, 1, self.layout.d_out, device=inp.device, dtype=torch.float32)
+        self.pack_weights()
         scratch, n_scr = self._scratch_for(B, L, backward=False)
-        lay_t, tab = self._table_args()
-        check(_lib.lib().srfrd_encoder_fwd_last(
-            C.byref(lay_t), tab, C.c_void_p(flat.data_ptr() + 4 * self.n_table_pad), ptr(packed), ptr(inp), ptr(fk), B, L,
-            ptr(hidden), ptr(scratch), n_scr, _stream()), "srfrd_encoder_fwd_last")
+        head = self._enc_head((inp, fk, None, None, None, None), 0.0, 0, 0, dict.fromkeys(OUT_KEYS))
+        call("srfrd_encoder_fwd_last", **{k: head[k] for k in _lib.ENCODER_HEAD[:6]}, B=B, L=L, hidden_last=hidden,
+             scratch=scratch, scratch_floats=n_scr)
         return hidden
 
-    def _launch_bwd(self, inp, fk, pos, pfk, neg, nfk, dropout_p, seed, out, d_hidden, d_pl, d_nl, seq0=0,
-                    dbg=None, dbg_seq=0):
-        lay, flat = self.layout, self._flat
+    def _launch_bwd(self, inp, fk, pos, pfk, neg, nfk, dropout_p, seed, out, d_hidden, d_pl, d_nl, seq0=0, dbg=None, dbg_seq=0):
+        lay = self.layout
         B, L = inp.shape
-        dev = inp.device
-        gflat = torch.zeros(self.n_flat, device=dev, dtype=torch.float32)
-        n_slabs = _lib.lib().srfrd_bwd_grid(C.byref(lay), B, L)
-        slabs = torch.empty(n_slabs, lay.n_dense, device=dev, dtype=torch.float32)
+        gflat = torch.zeros(self.n_flat, device=inp.device, dtype=torch.float32)
+        n_slabs = _lib.query("srfrd_bwd_grid", lay=lay, B=B, L=L)
+        slabs = torch.empty(n_slabs, lay.n_dense, device=inp.device, dtype=torch.float32)
         scratch, n_scr = self._scratch_for(B, L, backward=True)
-        lay_t, tab = self._table_args()
-        check(_lib.lib().srfrd_encoder_bwd(
-            C.byref(lay_t), tab, C.c_void_p(flat.data_ptr() + 4 * self.n_table_pad), ptr(self._packed),
-            ptr(inp), ptr(fk), ptr(pos), ptr(pfk), ptr(neg), ptr(nfk), B, L, float(dropout_p), int(seed) & 0xFFFFFFFF,
-            None, int(seq0), ptr(out["hidden"]), ptr(out["pos_logits"]), ptr(out["neg_logits"]), ptr(out["save_x"]),
-            ptr(out["save_h1"]), ptr(out["save_aux"]), ptr(d_hidden), ptr(d_pl), ptr(d_nl), 0, ptr(gflat), None, ptr(slabs), ptr(scratch), n_scr,
-            ptr(dbg), int(dbg_seq), _stream()), "srfrd_encoder_bwd")
-        check(_lib.lib().srfrd_reduce_dense(ptr(slabs), n_slabs, lay.n_dense,
-                                            C.c_void_p(gflat.data_ptr() + 4 * self.n_table_pad), None, B, None, None,
-                                            _stream()),
-              "srfrd_reduce_dense")
+        call("srfrd_encoder_bwd", **self._enc_head((inp, fk, pos, pfk, neg, nfk), dropout_p, seed, seq0, out),
+             d_hidden=d_hidden, d_pos=d_pl, d_neg=d_nl, fused_bce=0, grad_table=gflat, table_contrib=None, grad_slabs=slabs,
+             scratch=scratch, scratch_floats=n_scr, dbg=dbg, dbg_seq=int(dbg_seq))
+        call("srfrd_reduce_dense", grad_slabs=slabs, n_slabs=n_slabs, n_dense=lay.n_dense,
+             grad_dense=_lib.dense_ptr(gflat, self.n_table_pad), loss_part=None, B=B, stats=None, loss_out=None)
         return gflat
 
     def _validate(self, inp, fk, pos, pfk, neg, nfk):
@@ -433,9 +413,8 @@ class _SRFRDBase(nn.Module):
             return
         self._err_word(inp.device)
         embeds_fake = self._kind in ("SRFR", "SRFRN")      # SRFU_* only count ids 1 / 2; SASRec ignores them
-        check(_lib.lib().srfrd_check_ids(ptr(inp), ptr(pos), ptr(neg), ptr(fk) if embeds_fake else None,
-                                         ptr(pfk), ptr(nfk), inp.numel(), self.layout.n_items, 2, ptr(self._err),
-                                         _stream()), "srfrd_check_ids")
+        call("srfrd_check_ids", item_a=inp, item_b=pos, item_c=neg, fake_a=fk if embeds_fake else None, fake_b=pfk, fake_c=nfk,
+             n=inp.numel(), n_items=self.layout.n_items, fake_hi=2, err_word=self._err)
         if self.validate_ids == "eager":
             self.check_ids()
 
@@ -541,8 +520,8 @@ class _SRFRDBase(nn.Module):
         if not self.validate_ids:
             return
         for t in ids:
-            check(_lib.lib().srfrd_check_ids(ptr(t), None, None, None, None, None, t.numel(), self.layout.n_items, 2,
-                                             ptr(self._err_word(t.device)), _stream()), "srfrd_check_ids")
+            call("srfrd_check_ids", item_a=t, item_b=None, item_c=None, fake_a=None, fake_b=None, fake_c=None, n=t.numel(),
+                 n_items=self.layout.n_items, fake_hi=2, err_word=self._err_word(t.device))
         if self.validate_ids == "eager":
             self.check_ids()
 
@@ -643,26 +622,29 @@ class _SRFRDBase(nn.Module):
         kind = _lib.KINDS[self._kind] if self._kind != "SRFR" else _lib.KINDS["SRFRN"]
         return torch.ops.srfrd.user_labels(fk, kind)
 
+    def _rank_inputs(self, input_ids, fake_ids, exclude=None):
+        """what every ranking call starts from -> (last-position hidden state (B, 1, d_out), the user labels (SRFRN; else None),
+        the exclusion triple of ops.excl_csr)"""
+        with torch.no_grad():
+            ids = self._prep(input_ids, fake_ids, None, None, None, None)
+            hidden = self._launch_fwd_last(ids[0], ids[1])
+        ulab = self.user_labels(ids[1]) if self._kind == "SRFRN" else None
+        return hidden, ulab, ops.excl_csr(exclude, ids[0], hidden.shape[0], hidden.device)
+
     def predict(self, user_ids, input_ids, fake_ids, label):
         """reference predict(): logits of the candidate items ``label`` against the last position's state.
         ``label`` is (I_c,) shared by the batch (reference utils.py:589) or (B, I_c) per user (batched eval);
         returns (I_c,) for a single sequence, else (B, I_c) - the reference's ``.squeeze()`` behaviour."""
-        with torch.no_grad():
-            ids = self._prep(input_ids, fake_ids, None, None, None, None)
-            hidden = self._launch_fwd_last(ids[0], ids[1])
-        logits = self.candidate_logits(hidden, ids[1], label)
-        return logits.squeeze()
+        hidden, ulab, _ = self._rank_inputs(input_ids, fake_ids)
+        return self.candidate_logits(hidden, None, label, ulab).squeeze()
 
-    def candidate_logits(self, hidden, fake_ids, cand):
-        lay = self.layout
-        dev = hidden.device
-        B, L = hidden.shape[0], hidden.shape[1]
-        cand = _ids(cand, dev)
-        stride = 0 if cand.dim() == 1 else cand.shape[1]
-        n_cand = cand.shape[-1]
-        if cand.dim() == 2 and cand.shape[0] != B:
+    def candidate_logits(self, hidden, fake_ids, cand, ulab=None):
+        """``ulab``: SRFRN's user labels where the caller has them already (else derived from ``fake_ids``)"""
+        cand = _ids(cand, hidden.device)
+        if cand.dim() == 2 and cand.shape[0] != hidden.shape[0]:
             raise ValueError("per-user candidates must be (B, I_c)")
-        ulab = self.user_labels(fake_ids) if self._kind == "SRFRN" else None
+        if ulab is None and self._kind == "SRFRN":
+            ulab = self.user_labels(fake_ids)
         self._check_item_ids(cand)
         return torch.ops.srfrd.predict_logits(hidden.contiguous(), cand.contiguous(), ulab, ops.register_model(self))
 
@@ -670,36 +652,23 @@ class _SRFRDBase(nn.Module):
         """Full-catalog ranking: (indices int64 (B,k), scores (B,k)); the (B, I) logits never reach HBM.
         ``exclude``: items never to return, per user - None, "input" (the ids of the user's input window), a (ptr, items)
         CSR tuple over the batch, or a list of B 1-D tensors.  Fewer than k rankable items leave trailing -1 / -inf slots."""
-        with torch.no_grad():
-            ids = self._prep(input_ids, fake_ids, None, None, None, None)
-            hidden = self._launch_fwd_last(ids[0], ids[1])
-        lay = self.layout
-        lo, hi = item_range if item_range is not None else (0, lay.n_items + 1)
-        ulab = self.user_labels(ids[1]) if self._kind == "SRFRN" else None
+        hidden, ulab, excl = self._rank_inputs(input_ids, fake_ids, exclude)
+        lo, hi = item_range if item_range is not None else (0, self.layout.n_items + 1)
         if exclude is None:
-            idx, val = torch.ops.srfrd.logits_topk(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad))
-        else:
-            xp, xi, mr = ops.excl_csr(exclude, ids[0], hidden.shape[0], hidden.device)
-            idx, val = torch.ops.srfrd.logits_topk_excl(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad),
-                                                        xp, xi, mr)
-        return idx, val
+            return tuple(torch.ops.srfrd.logits_topk(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad)))
+        return tuple(torch.ops.srfrd.logits_topk_excl(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad), *excl))
 
     def target_rank(self, user_ids, input_ids, fake_ids, targets, exclude=None, item_range=None, exclude_pad=True):
         """Full-catalog rank of ``targets`` (B,): int32 (B,) counts of the items in ``item_range`` (default: the whole
         catalog) that score strictly higher than the user's target, skipping the ``exclude`` set (as in ``topk``) and,
         with ``exclude_pad``, item 0.  The target itself is ranked even when it is excluded; ranks over disjoint item
         ranges add up.  ``rank < K`` is a hit at K; NDCG@K = 1 / log2(rank + 2)."""
-        with torch.no_grad():
-            ids = self._prep(input_ids, fake_ids, None, None, None, None)
-            hidden = self._launch_fwd_last(ids[0], ids[1])
-        lay = self.layout
-        lo, hi = item_range if item_range is not None else (0, lay.n_items + 1)
-        ulab = self.user_labels(ids[1]) if self._kind == "SRFRN" else None
+        hidden, ulab, excl = self._rank_inputs(input_ids, fake_ids, exclude)
+        lo, hi = item_range if item_range is not None else (0, self.layout.n_items + 1)
         tg = _ids(targets, hidden.device).reshape(-1)
         if tg.numel() != hidden.shape[0]:
             raise ValueError("targets must hold one item id per user")
-        xp, xi, mr = ops.excl_csr(exclude, ids[0], hidden.shape[0], hidden.device)
-        return torch.ops.srfrd.target_rank(hidden, ulab, tg, ops.register_model(self), lo, hi, bool(exclude_pad), xp, xi, mr)
+        return torch.ops.srfrd.target_rank(hidden, ulab, tg, ops.register_model(self), lo, hi, bool(exclude_pad), *excl)
 
 
 class SRFR(_SRFRDBase):

@@ -31,14 +31,13 @@ registered for device type "cuda" only and raise elsewhere.
 """
 from __future__ import annotations
 
-import ctypes as C
 import weakref
 from typing import List, Optional
 
 import torch
 
 from . import _lib, loss_heads
-from ._lib import check, ptr
+from ._lib import call, ptr, query
 
 _MODELS: "weakref.WeakValueDictionary[int, torch.nn.Module]" = weakref.WeakValueDictionary()
 
@@ -54,10 +53,6 @@ def _model(key: int):
     if m is None:
         raise RuntimeError("srfrd op called with the key of a model that no longer exists")
     return m
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 # ------------------------------------------------------------------------------------------------ encoder forward
@@ -84,7 +79,7 @@ def _(params, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, model_k
             torch.empty(B, L, **f) if neg_ids is not None else torch.empty(0, **f),
             torch.empty(B, lay.n_blocks + 1, L, lay.D, **f) if save else torch.empty(0, **f),
             torch.empty(B, lay.n_blocks, L, lay.D, **f) if save else torch.empty(0, **f),
-            torch.empty(_lib.lib().srfrd_aux_floats(C.byref(lay), B, L), **f) if save else torch.empty(0, **f)]
+            torch.empty(query("srfrd_aux_floats", lay=lay, B=B, L=L), **f) if save else torch.empty(0, **f)]
 
 
 # ------------------------------------------------------------------------------------------------ encoder backward
@@ -96,8 +91,7 @@ def encoder_bwd(input_ids: torch.Tensor, fake_ids: Optional[torch.Tensor], pos_i
                 d_hidden: Optional[torch.Tensor], d_pos: Optional[torch.Tensor], d_neg: Optional[torch.Tensor]) -> torch.Tensor:
     """-> the flat gradient vector [item table | pad | dense] of the model's flat parameter layout."""
     m = _model(model_key)
-    out = {"hidden": hidden, "pos_logits": pos_logits if pos_ids is not None else None,
-           "neg_logits": neg_logits if neg_ids is not None else None, "save_x": save_x, "save_h1": save_h1, "save_aux": save_aux}
+    out = dict(hidden=hidden, pos_logits=pos_logits, neg_logits=neg_logits, save_x=save_x, save_h1=save_h1, save_aux=save_aux)
     return m._launch_bwd(input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, dropout_p, seed, out, d_hidden, d_pos, d_neg,
                          seq0=seq0)
 
@@ -108,6 +102,18 @@ def _(input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, model_key, drop
     return torch.empty(_model(model_key).n_flat, device=hidden.device, dtype=torch.float32)
 
 
+def pack_saved(out, ids):
+    """the encoder autograd's saved tuple: the forward's six outputs, then the id planes that are present -> (it, which are)"""
+    return (*out, *[t for t in ids if t is not None]), tuple(t is not None for t in ids)
+
+
+def unpack_saved(saved, id_present, grads):
+    """-> (the six outputs, the six id planes with None where absent, the upstream gradients that count, contiguous)"""
+    rest = iter(saved[6:])
+    ids = tuple(next(rest) if present else None for present in id_present)
+    return saved[:6], ids, [None if g is None or t is None else g.contiguous() for g, t in zip(grads, (saved[0], ids[2], ids[4]))]
+
+
 def _fwd_setup(ctx, inputs, output):
     (params, input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake, model_key, dropout_p, seed, seq0, save) = inputs
     if not save:
@@ -115,24 +121,16 @@ def _fwd_setup(ctx, inputs, output):
     # outputs and id tensors through save_for_backward (no output -> grad_fn -> ctx -> output cycle: the checkpoints - B x
     # (n_blocks + 1) x L x D floats - are released by refcount after the backward, and torch's version counters guard them);
     # only ints / flags stay on ctx
-    ids = (input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake)
-    ctx.id_present = tuple(t is not None for t in ids)
+    saved, ctx.id_present = pack_saved(output, (input_ids, fake_ids, pos_ids, pos_fake, neg_ids, neg_fake))
     ctx.meta = (model_key, dropout_p, seed, seq0, len(params))
-    ctx.save_for_backward(*output, *[t for t in ids if t is not None])
+    ctx.save_for_backward(*saved)
 
 
 def _fwd_backward(ctx, grads):
     model_key, p, seed, seq0, n_params = ctx.meta
     m = _model(model_key)
-    saved = ctx.saved_tensors
-    hidden, pl, nl, sx, sh, sa = saved[:6]
-    rest = iter(saved[6:])
-    inp, fk, pos, pfk, neg, nfk = (next(rest) if present else None for present in ctx.id_present)
-    d_hidden, d_pl, d_nl = grads[0], grads[1], grads[2]
-    gflat = torch.ops.srfrd.encoder_bwd(inp, fk, pos, pfk, neg, nfk, model_key, p, seed, seq0, hidden, pl, nl, sx, sh, sa,
-                                        None if d_hidden is None else d_hidden.contiguous(),
-                                        None if (d_pl is None or pos is None) else d_pl.contiguous(),
-                                        None if (d_nl is None or neg is None) else d_nl.contiguous())
+    out, ids, upstream = unpack_saved(ctx.saved_tensors, ctx.id_present, grads)
+    gflat = torch.ops.srfrd.encoder_bwd(*ids, model_key, p, seed, seq0, *out, *upstream)
     per_param = list(m._grad_views(gflat))
     assert len(per_param) == n_params
     return (per_param,) + (None,) * 11
@@ -146,7 +144,7 @@ encoder_fwd.register_autograd(_fwd_backward, setup_context=_fwd_setup)
 def user_labels(fake_ids: torch.Tensor, kind: int) -> torch.Tensor:
     fk = fake_ids.contiguous()
     lab = torch.empty(fk.shape[0], device=fk.device, dtype=torch.int64)
-    check(_lib.lib().srfrd_user_labels(kind, ptr(fk), fk.shape[0], fk.shape[1], ptr(lab), _stream()), "srfrd_user_labels")
+    call("srfrd_user_labels", kind=kind, fake_ids=fk, B=fk.shape[0], L=fk.shape[1], labels=lab)
     return lab
 
 
@@ -155,17 +153,38 @@ def _(fake_ids, kind):
     return torch.empty(fake_ids.shape[0], device=fake_ids.device, dtype=torch.int64)
 
 
+def rank_head(m, hidden, user_label, item_range=None, exclude_pad=False, excl=None):
+    """The named values srfrd_predict_logits, srfrd_logits_topk(_excl) and srfrd_target_rank share, of a model ``m`` (its
+    ``_table_args()``, ``_flat``, ``n_table_pad``); ``item_range`` (lo, hi) and ``exclude_pad``: the three ranking calls';
+    ``excl``: the exclusion triple of ``excl_csr``."""
+    lay, tab = m._table_args()
+    head = dict(lay=lay, item_table=tab, dense=_lib.dense_ptr(m._flat, m.n_table_pad), hidden=hidden, B=hidden.shape[0],
+                L=hidden.shape[1], user_label=user_label)
+    if item_range is not None:
+        head.update(item_lo=item_range[0], item_hi=item_range[1], exclude_pad=1 if exclude_pad else 0)
+    if excl is not None:
+        head.update(excl_ptr=excl[0], excl_items=excl[1], max_row=excl[2])
+    return head
+
+
+def _rank_workspaces(hidden, k, n_rows, max_row):
+    """(top-k workspace, exclusion workspace) of a ranking call for ``hidden``'s batch over ``n_rows`` items; None for None"""
+    B = hidden.shape[0]
+    sizes = (None if k is None else query("srfrd_topk_workspace_bytes", B=B, k=k, n_rows=n_rows),
+             None if max_row is None else query("srfrd_excl_workspace_bytes", B=B, max_row=min(max_row, _lib.EXCL_CAP), n_rows=n_rows))
+    return [None if n is None else torch.empty(max(n, 8), device=hidden.device, dtype=torch.uint8) for n in sizes]
+
+
+def _topk_out(rows, k):
+    return [torch.empty(rows.shape[0], k, device=rows.device, dtype=dt) for dt in (torch.int64, torch.float32)]
+
+
 @torch.library.custom_op("srfrd::predict_logits", mutates_args=(), device_types="cuda")
 def predict_logits(hidden: torch.Tensor, cand: torch.Tensor, user_label: Optional[torch.Tensor], model_key: int) -> torch.Tensor:
-    m = _model(model_key)
-    lay, tab = m._table_args()
-    B, L = hidden.shape[0], hidden.shape[1]
-    stride = 0 if cand.dim() == 1 else cand.shape[1]
     n_cand = cand.shape[-1]
-    logits = torch.empty(B, n_cand, device=hidden.device, dtype=torch.float32)
-    check(_lib.lib().srfrd_predict_logits(C.byref(lay), tab, C.c_void_p(m._flat.data_ptr() + 4 * m.n_table_pad), ptr(hidden),
-                                          B, L, ptr(cand), n_cand, stride, ptr(user_label), ptr(logits), _stream()),
-          "srfrd_predict_logits")
+    logits = torch.empty(hidden.shape[0], n_cand, device=hidden.device, dtype=torch.float32)
+    call("srfrd_predict_logits", **rank_head(_model(model_key), hidden, user_label), cand=cand, n_cand=n_cand,
+         cand_stride=0 if cand.dim() == 1 else cand.shape[1], logits=logits)
     return logits
 
 
@@ -177,23 +196,11 @@ def _(hidden, cand, user_label, model_key):
 @torch.library.custom_op("srfrd::logits_topk", mutates_args=(), device_types="cuda")
 def logits_topk(hidden: torch.Tensor, user_label: Optional[torch.Tensor], model_key: int, item_lo: int, item_hi: int, k: int,
                 exclude_pad: bool) -> List[torch.Tensor]:
-    m = _model(model_key)
-    lay, tab = m._table_args()
-    B, L = hidden.shape[0], hidden.shape[1]
-    dev = hidden.device
-    ws = torch.empty(max(_lib.lib().srfrd_topk_workspace_bytes(B, k, item_hi - item_lo), 8), device=dev, dtype=torch.uint8)
-    idx = torch.empty(B, k, device=dev, dtype=torch.int64)
-    val = torch.empty(B, k, device=dev, dtype=torch.float32)
-    check(_lib.lib().srfrd_logits_topk(C.byref(lay), tab, C.c_void_p(m._flat.data_ptr() + 4 * m.n_table_pad), ptr(hidden), B, L,
-                                       item_lo, item_hi, 1 if exclude_pad else 0, ptr(user_label), k, ptr(idx), ptr(val), ptr(ws),
-                                       _stream()), "srfrd_logits_topk")
+    ws, _ = _rank_workspaces(hidden, k, item_hi - item_lo, None)
+    idx, val = _topk_out(hidden, k)
+    call("srfrd_logits_topk", **rank_head(_model(model_key), hidden, user_label, item_range=(item_lo, item_hi), exclude_pad=exclude_pad),
+         k=k, topk_idx=idx, topk_val=val, workspace=ws)
     return [idx, val]
-
-
-@logits_topk.register_fake
-def _(hidden, user_label, model_key, item_lo, item_hi, k, exclude_pad):
-    B = hidden.shape[0]
-    return [torch.empty(B, k, device=hidden.device, dtype=torch.int64), torch.empty(B, k, device=hidden.device, dtype=torch.float32)]
 
 
 def excl_csr(exclude, input_ids: Optional[torch.Tensor], B: int, device):
@@ -236,46 +243,28 @@ def excl_csr(exclude, input_ids: Optional[torch.Tensor], B: int, device):
 def logits_topk_excl(hidden: torch.Tensor, user_label: Optional[torch.Tensor], model_key: int, item_lo: int, item_hi: int, k: int,
                      exclude_pad: bool, excl_ptr: Optional[torch.Tensor], excl_items: Optional[torch.Tensor],
                      max_row: int) -> List[torch.Tensor]:
-    m = _model(model_key)
-    lay, tab = m._table_args()
-    B, L = hidden.shape[0], hidden.shape[1]
-    dev = hidden.device
-    L_ = _lib.lib()
-    ws = torch.empty(max(L_.srfrd_topk_workspace_bytes(B, k, item_hi - item_lo), 8), device=dev, dtype=torch.uint8)
-    xws = None
-    if excl_ptr is not None:
-        xws = torch.empty(max(L_.srfrd_excl_workspace_bytes(B, min(max_row, _lib.EXCL_CAP), item_hi - item_lo), 8), device=dev,
-                          dtype=torch.uint8)
-    idx = torch.empty(B, k, device=dev, dtype=torch.int64)
-    val = torch.empty(B, k, device=dev, dtype=torch.float32)
-    check(L_.srfrd_logits_topk_excl(C.byref(lay), tab, C.c_void_p(m._flat.data_ptr() + 4 * m.n_table_pad), ptr(hidden), B, L,
-                                    item_lo, item_hi, 1 if exclude_pad else 0, ptr(user_label), k, ptr(excl_ptr), ptr(excl_items),
-                                    max_row, ptr(idx), ptr(val), ptr(ws), ptr(xws), _stream()), "srfrd_logits_topk_excl")
+    ws, xws = _rank_workspaces(hidden, k, item_hi - item_lo, max_row if excl_ptr is not None else None)
+    idx, val = _topk_out(hidden, k)
+    call("srfrd_logits_topk_excl", **rank_head(_model(model_key), hidden, user_label, item_range=(item_lo, item_hi),
+                                                exclude_pad=exclude_pad, excl=(excl_ptr, excl_items, max_row)),
+         k=k, topk_idx=idx, topk_val=val, workspace=ws, excl_workspace=xws)
     return [idx, val]
 
 
-@logits_topk_excl.register_fake
-def _(hidden, user_label, model_key, item_lo, item_hi, k, exclude_pad, excl_ptr, excl_items, max_row):
-    B = hidden.shape[0]
-    return [torch.empty(B, k, device=hidden.device, dtype=torch.int64), torch.empty(B, k, device=hidden.device, dtype=torch.float32)]
+for _op in (logits_topk, logits_topk_excl):
+    _op.register_fake(lambda hidden, user_label, model_key, item_lo, item_hi, k, *rest: _topk_out(hidden, k))
 
 
 @torch.library.custom_op("srfrd::target_rank", mutates_args=(), device_types="cuda")
 def target_rank(hidden: torch.Tensor, user_label: Optional[torch.Tensor], targets: torch.Tensor, model_key: int, item_lo: int,
                 item_hi: int, exclude_pad: bool, excl_ptr: Optional[torch.Tensor], excl_items: Optional[torch.Tensor],
                 max_row: int) -> torch.Tensor:
-    m = _model(model_key)
-    lay, tab = m._table_args()
-    B, L = hidden.shape[0], hidden.shape[1]
-    dev = hidden.device
-    L_ = _lib.lib()
-    mr = min(max_row, _lib.EXCL_CAP) if excl_ptr is not None else 0
-    ws = torch.empty(max(L_.srfrd_excl_workspace_bytes(B, mr, item_hi - item_lo), 8), device=dev, dtype=torch.uint8)
-    rank = torch.empty(B, device=dev, dtype=torch.int32)
-    targets = targets.to(device=dev, dtype=torch.int64).contiguous()
-    check(L_.srfrd_target_rank(C.byref(lay), tab, C.c_void_p(m._flat.data_ptr() + 4 * m.n_table_pad), ptr(hidden), B, L,
-                               item_lo, item_hi, 1 if exclude_pad else 0, ptr(user_label), ptr(targets), ptr(excl_ptr),
-                               ptr(excl_items), max_row, 10, ptr(rank), None, ptr(ws), _stream()), "srfrd_target_rank")
+    _, ws = _rank_workspaces(hidden, None, item_hi - item_lo, max_row if excl_ptr is not None else 0)
+    rank = torch.empty(hidden.shape[0], device=hidden.device, dtype=torch.int32)
+    targets = targets.to(device=hidden.device, dtype=torch.int64).contiguous()
+    call("srfrd_target_rank", **rank_head(_model(model_key), hidden, user_label, item_range=(item_lo, item_hi),
+                                           exclude_pad=exclude_pad, excl=(excl_ptr, excl_items, max_row)),
+         targets=targets, cut_k=10, rank=rank, metric_acc=None, workspace=ws)
     return rank
 
 
@@ -288,16 +277,14 @@ def _(hidden, user_label, targets, model_key, item_lo, item_hi, exclude_pad, exc
 def topk_merge(cand_idx: torch.Tensor, cand_val: torch.Tensor, k: int) -> List[torch.Tensor]:
     cand_idx, cand_val = cand_idx.contiguous(), cand_val.contiguous()
     B, n = cand_idx.shape
-    idx = torch.empty(B, k, device=cand_idx.device, dtype=torch.int64)
-    val = torch.empty(B, k, device=cand_idx.device, dtype=torch.float32)
-    check(_lib.lib().srfrd_topk_merge(ptr(cand_idx), ptr(cand_val), B, n, k, ptr(idx), ptr(val), _stream()), "srfrd_topk_merge")
+    idx, val = _topk_out(cand_idx, k)
+    call("srfrd_topk_merge", cand_idx=cand_idx, cand_val=cand_val, B=B, n_cand=n, k=k, topk_idx=idx, topk_val=val)
     return [idx, val]
 
 
 @topk_merge.register_fake
 def _(cand_idx, cand_val, k):
-    B = cand_idx.shape[0]
-    return [torch.empty(B, k, device=cand_idx.device, dtype=torch.int64), torch.empty(B, k, device=cand_idx.device, dtype=torch.float32)]
+    return _topk_out(cand_idx, k)
 
 
 @torch.library.custom_op("srfrd::eval_rank", mutates_args=(), device_types="cuda")
@@ -305,7 +292,7 @@ def eval_rank(logits: torch.Tensor) -> torch.Tensor:
     logits = logits.contiguous()
     B, n = logits.shape
     rank = torch.empty(B, device=logits.device, dtype=torch.int32)
-    check(_lib.lib().srfrd_eval_rank(ptr(logits), B, n, ptr(rank), None, _stream()), "srfrd_eval_rank")
+    call("srfrd_eval_rank", logits=logits, B=B, n_cand=n, rank=rank, metric_acc=None)
     return rank
 
 

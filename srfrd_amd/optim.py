@@ -22,12 +22,10 @@ behind ``srfrd_step_begin_sched`` at the group's current ``lr`` (a constant sche
 rewrite ``lr`` between steps)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
-from ._lib import check, ptr
+from ._lib import call
 
 
 class Adam(torch.optim.Optimizer):
@@ -107,7 +105,7 @@ class Adam(torch.optim.Optimizer):
             # (one dtype / device test: tensors laid out at the parameters' own offsets of one buffer are views of one vector)
             st = last.untyped_storage()
             if st.data_ptr() <= base and base + 4 * self._flat.numel() <= st.data_ptr() + st.nbytes():
-                return C.c_void_p(base), last          # (keep a reference alive until the launch is enqueued)
+                return base, last          # (the vector's address; keep a reference alive until the launch is enqueued)
         if self._gbuf is None:
             self._gbuf = torch.zeros_like(self._flat)
         for p, off, n in self._spans:
@@ -115,7 +113,7 @@ class Adam(torch.optim.Optimizer):
                 self._gbuf[off:off + n].zero_()
             else:
                 self._gbuf[off:off + n].copy_(p.grad.reshape(-1))
-        return ptr(self._gbuf), self._gbuf
+        return self._gbuf, self._gbuf
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -138,8 +136,6 @@ class Adam(torch.optim.Optimizer):
                 groups.setdefault(self._counts[i], []).append((off, k))
         gptr, keep = self._flat_grad(self._full and len(groups) == 1 and sum(map(len, groups.values())) == len(ps))
         n = self._flat.numel()
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        L_ = _lib.lib()
         for count, spans in sorted(groups.items()):
             # Each launch steps all of [0, n).  Off the in-place path, what it must not step - parameters left out of the
             # list, listed ones without a gradient or of another step count - is saved here and put back after it: the
@@ -154,7 +150,7 @@ class Adam(torch.optim.Optimizer):
             if count != self._steps:
                 self._dev_state[0] = count
             # t += 1 and the bias corrections in double precision on the device, then the step over the whole vector
-            self._launch(L_, gptr, n, g, st)
+            self._launch(gptr, n, g)
             self._steps = count + 1
             for lo, hi, p, m, v in held:
                 self._flat[lo:hi].copy_(p); self._m[lo:hi].copy_(m); self._v[lo:hi].copy_(v)
@@ -164,11 +160,14 @@ class Adam(torch.optim.Optimizer):
         del keep
         return loss
 
-    def _launch(self, L_, gptr, n, g, st):
-        lr, (b1, b2), eps = g["lr"], g["betas"], g["eps"]
-        check(L_.srfrd_step_begin(ptr(self._dev_state), lr, b1, b2, st), "srfrd_step_begin")
-        check(L_.srfrd_adam_step(ptr(self._flat), gptr, ptr(self._m), ptr(self._v), n, 0, n, 0, b1, b2, eps,
-                                 ptr(self._dev_state), None, None, 0, st), "srfrd_adam_step")
+    def _vector(self, gptr, n, g):
+        """what both Adam entry points take of this optimizer: the whole flat vector, no loss statistics, no bf16 shadow"""
+        return dict(param=self._flat, grad=gptr, m=self._m, v=self._v, n=n, i0=0, i1=n, n_zero=0, beta1=g["betas"][0],
+                    beta2=g["betas"][1], eps=g["eps"], state=self._dev_state, stats=None, table_bf16=None, n_table=0)
+
+    def _launch(self, gptr, n, g):
+        call("srfrd_step_begin", state=self._dev_state, lr=g["lr"], beta1=g["betas"][0], beta2=g["betas"][1])
+        call("srfrd_adam_step", **self._vector(gptr, n, g))
 
     def _decay_of(self, g):
         """what state_dict()'s param group says about the decay"""
@@ -222,13 +221,12 @@ class AdamW(Adam):
         super().__init__(params, lr, betas, eps)
         self.param_groups[0]["weight_decay"] = float(weight_decay)
 
-    def _launch(self, L_, gptr, n, g, st):
+    def _launch(self, gptr, n, g):
         # a constant schedule at the group's CURRENT rate: state[4] = lr / bc1, state[7] = 1 - lr * weight_decay
         opts = _lib.OptimOpts(float(g["lr"]), g["betas"][0], g["betas"][1], float(g["weight_decay"]), 0.0, 0, 0,
                               _lib.SCHEDULES["constant"], 0)
-        check(L_.srfrd_step_begin_sched(ptr(self._dev_state), C.byref(opts), st), "srfrd_step_begin_sched")
-        check(L_.srfrd_adamw_step(ptr(self._flat), gptr, ptr(self._m), ptr(self._v), n, 0, n, 0, g["betas"][0], g["betas"][1],
-                                  g["eps"], ptr(self._dev_state), None, None, None, 0, st), "srfrd_adamw_step")
+        call("srfrd_step_begin_sched", state=self._dev_state, opts=opts)
+        call("srfrd_adamw_step", **self._vector(gptr, n, g), clip=None)
 
     def _decay_of(self, g):
         return {"weight_decay": g["weight_decay"], "decoupled_weight_decay": True}

@@ -19,13 +19,8 @@ ids agree wherever two scores differ by more than an fp32 rounding and the value
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.distributed as dist
-
-from . import _lib
-from ._lib import check, ptr
 
 
 def row_shards(n_rows: int, n_shards: int):
@@ -87,13 +82,8 @@ class ShardedRanker:
         return ptr_all, pad_all.reshape(-1).contiguous(), M
 
     def _users(self, input_ids, fake_ids, exclude):
-        from . import ops
-        m = self.model
-        ids = m._prep(input_ids, fake_ids, None, None, None, None)
-        h_last = m._launch_fwd_last(ids[0], ids[1])[:, 0, :]          # (B, d_out)
-        ulab = m.user_labels(ids[1]) if m._kind == "SRFRN" else None
-        excl = ops.excl_csr(exclude, ids[0], h_last.shape[0], h_last.device) if exclude is not None else None
-        return h_last, ulab, excl
+        hidden, ulab, excl = self.model._rank_inputs(input_ids, fake_ids, exclude)
+        return hidden[:, 0, :], ulab, (excl if exclude is not None else None)          # (B, d_out)
 
     @torch.no_grad()
     def topk(self, user_ids, input_ids, fake_ids, k: int = 10, exclude_pad: bool = True, check_batch: bool = True, exclude=None):

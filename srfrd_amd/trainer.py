@@ -21,7 +21,6 @@ mean-over-all-targets loss of trainer.py:36-38 (not an average of per-rank means
 from __future__ import annotations
 
 import contextlib
-import ctypes as C
 import math
 import os
 
@@ -31,7 +30,7 @@ import torch.distributed as dist
 import numpy as np
 
 from . import _lib, loss_heads
-from ._lib import check, ptr
+from ._lib import call, ptr, query
 from .exchange import GradExchange, exchange_active, shard_bounds  # noqa: F401  (shard_bounds re-exported)
 from .sampler import alias_table, negative_q
 
@@ -228,7 +227,7 @@ class FusedTrainer:
         # through the scratch: srfrd_train_scratch_floats)
         fused = _lib.PLAN_POS | _lib.PLAN_NEG | _lib.PLAN_CKPT | _lib.PLAN_LOSS | _lib.PLAN_FUSED_BCE
         has_train = bool(_lib.encoder_plan_train(self.lay, self.B, self.L, fused)[0])
-        n_t = int(_lib.lib().srfrd_train_scratch_floats(C.byref(self.lay), self.B, self.L)) if has_train else 0
+        n_t = int(query("srfrd_train_scratch_floats", lay=self.lay, B=self.B, L=self.L)) if has_train else 0
         self.n_scratch = max(n_f, n_b, n_t)
         self.scratch = torch.empty(self.n_scratch, device=dev, dtype=torch.float32) if self.n_scratch else None
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
@@ -290,7 +289,7 @@ class FusedTrainer:
         # (the sampled and the token-negatives steps keep the encoder's contribution rows in buffers of their own, below)
         self.contrib = torch.zeros(3, B, L, lay.d_item, **f32) if self.deterministic and not (self.sampled or self.token) else None
         self.keys = torch.zeros(3, B, L, device=dev, dtype=torch.int64) if self.deterministic else None
-        self.n_slabs = _lib.lib().srfrd_bwd_grid(C.byref(lay), B, L)
+        self.n_slabs = query("srfrd_bwd_grid", lay=lay, B=B, L=L)
         self.slabs = torch.empty(self.n_slabs, lay.n_dense, **f32)
         # Input ring: `slots` resident (6, B, L) id buffers.  A producer (DeviceSampler, a loader thread's H2D copy)
         # fills slot k + 1 while step k runs and calls step_slot(k + 1): no staging copy on the step's stream.  Slot 0
@@ -305,7 +304,7 @@ class FusedTrainer:
         # wrote must never hold a NaN pattern if a full-row kernel is switched in between two steps)
         self.save_x = torch.zeros(B, lay.n_blocks + 1, L, lay.D, **f32)
         self.save_h1 = torch.zeros(B, lay.n_blocks, L, lay.D, **f32)
-        self.save_aux = torch.zeros(_lib.lib().srfrd_aux_floats(C.byref(lay), B, L), **f32)
+        self.save_aux = torch.zeros(query("srfrd_aux_floats", lay=lay, B=B, L=L), **f32)
         self.loss_part = torch.empty(B, 3, **f32)
         self.loss = torch.zeros(1, **f32)
         # Sequence -> workgroup schedule of the seq_len-50 ragged kernels (include/srfrd_hip.h, srfrd_seq_order): one small
@@ -316,8 +315,8 @@ class FusedTrainer:
         plan_mode = fused if loss == "bce" else _lib.PLAN_CKPT
         ragged = _lib.encoder_plan(lay, B, L, plan_mode)[0][0].startswith("srfrd::encoder_fwd_ragged_kernel<")
         self.sched_mode = min(1, int(os.environ.get("SRFRD_SCHED", "1"))) if ragged else 0
-        self.sched = torch.zeros(int(_lib.lib().srfrd_sched_ints(B)), device=dev, dtype=torch.int32) if self.sched_mode else None
-        self.pair_stride = max(1, _lib.lib().srfrd_bwd_grid(C.byref(lay), 1 << 30, L) // 2)      # CUs: workgroups of the first round
+        self.sched = torch.zeros(int(query("srfrd_sched_ints", B=B)), device=dev, dtype=torch.int32) if self.sched_mode else None
+        self.pair_stride = max(1, query("srfrd_bwd_grid", lay=lay, B=1 << 30, L=L) // 2)      # CUs: workgroups of the first round
         # single rank: forward + backward as one launch where the plan has a train kernel (srfrd_encoder_train_ranked), asked
         # at every enqueue under the environment's switches then; False: always the two launches (A/B comparisons)
         self._train_mode = fused
@@ -402,7 +401,7 @@ class FusedTrainer:
             self.ce_contrib = self.contrib
             self.ce_keys, self.ce_rows = (self.keys_in, self.contrib[2]) if det else (None, None)
         self.ce_head = head
-        n_ws = head.workspace(_lib.lib(), lay, B, L, self.K if self.sampled or self.token else 0)
+        n_ws = head.workspace(lay, B, L, self.K if self.sampled or self.token else 0)
         if self.token:
             # the mixed reduction's list is T (2 + K) long: more than srfrd_tneg_workspace_floats covers
             n_mix = loss_heads.mixed_workspace(T * (2 + self.K), lay.d_item)
@@ -439,80 +438,72 @@ class FusedTrainer:
         return self.state[3:4].view(torch.float32)[0] if self.opts is not None else None
 
     # ---- pieces -------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def _step_begin(self):
         """state words of the step t = state[0] + 1: plain, or (an option set) under the schedule"""
         if self.opts is None:
-            check(_lib.lib().srfrd_step_begin(ptr(self.state), self.lr, self.betas[0], self.betas[1], self._stream()),
-                  "srfrd_step_begin")
+            call("srfrd_step_begin", state=self.state, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1])
         else:
-            check(_lib.lib().srfrd_step_begin_sched(ptr(self.state), C.byref(self.opts), self._stream()), "srfrd_step_begin_sched")
-
-    def _dense_ptr(self, base):
-        return C.c_void_p(base.data_ptr() + 4 * self.n_tab)
+            call("srfrd_step_begin_sched", state=self.state, opts=self.opts)
 
     def _enc_args(self, slot, targets: bool):
-        """the arguments every encoder entry point begins with: layout and tables, the slot's id planes (``targets``: the
-        positive / negative planes and their logits too; else NULL - checkpoints and hidden states only), shape, dropout
-        rate and seed word, this rank's first global sequence, then the forward's outputs and checkpoints"""
+        """the named arguments every encoder entry point begins with (_lib.encoder_head): layout and tables, the slot's id
+        planes (``targets``: the positive / negative planes and their logits too; else NULL - checkpoints and hidden states
+        only), shape, dropout rate and seed word, this rank's first global sequence, then the forward's outputs and checkpoints"""
         ids, kind = self.ids_ring[slot], self.lay.kind
         fk = ids[1] if kind != 0 else None
-        pos, neg, pl, nl = (ids[2], ids[4], self.pl, self.nl) if targets else (None, None, None, None)
+        pos, neg = (ids[2], ids[4]) if targets else (None, None)
         pfk, nfk = (ids[3], ids[5]) if targets and kind == 2 else (None, None)
         p = self.model.dropout_rate if self.model.training else 0.0
-        lay_t, tab = self.model._table_args()
-        return (C.byref(lay_t), tab, self._dense_ptr(self.flat), ptr(self.packed), ptr(ids[0]), ptr(fk), ptr(pos), ptr(pfk),
-                ptr(neg), ptr(nfk), self.B, self.L, p, 0, C.c_void_p(self.state.data_ptr() + 8), self.rank * self.B,
-                ptr(self.hidden), ptr(pl), ptr(nl), ptr(self.save_x), ptr(self.save_h1), ptr(self.save_aux))
+        return _lib.encoder_head(self.model._table_args(), self.flat, self.n_tab, self.packed, (ids[0], fk, pos, pfk, neg, nfk),
+                                 self.B, self.L, p, self.rank * self.B,
+                                 (self.hidden, self.pl, self.nl, self.save_x, self.save_h1, self.save_aux),
+                                 seed_dev=self.state.data_ptr() + 8)
 
     def _bwd_args(self, d_hidden, contrib):
         """what a backward adds to `_enc_args`: the hidden-state gradient it starts from (None: the BCE gradient of the
         target logits, fused), the gradient vector, the item-table contribution rows (None: float atomics into the gradient),
         the dense slabs and the scratch"""
-        return (ptr(d_hidden), None, None, int(d_hidden is None), ptr(self.grad), ptr(contrib), ptr(self.slabs),
-                ptr(self.scratch), self.n_scratch)
+        return dict(d_hidden=d_hidden, d_pos=None, d_neg=None, fused_bce=int(d_hidden is None), grad_table=self.grad,
+                    table_contrib=contrib, grad_slabs=self.slabs, scratch=self.scratch, scratch_floats=self.n_scratch)
 
     def _sched_args(self):
-        return ptr(self.sched), self.sched_mode, self._stream()
+        return dict(sched=self.sched, sched_mode=self.sched_mode)
 
     def _launch_fwd(self, slot, targets: bool):
-        check(_lib.lib().srfrd_encoder_fwd_sched(*self._enc_args(slot, targets), ptr(self.loss_part) if targets else None,
-                                                 ptr(self.scratch), self.n_scratch, *self._sched_args()), "srfrd_encoder_fwd_sched")
+        call("srfrd_encoder_fwd_sched", **self._enc_args(slot, targets), loss_part=self.loss_part if targets else None,
+             scratch=self.scratch, scratch_floats=self.n_scratch, **self._sched_args())
 
     def _launch_bwd(self, slot, d_hidden=None, contrib=None):
-        check(_lib.lib().srfrd_encoder_bwd_sched(*self._enc_args(slot, d_hidden is None), *self._bwd_args(d_hidden, contrib),
-                                                 *self._sched_args()), "srfrd_encoder_bwd_sched")
+        call("srfrd_encoder_bwd_sched", **self._enc_args(slot, d_hidden is None), **self._bwd_args(d_hidden, contrib),
+             **self._sched_args())
 
     def _launch_train(self, slot):
         """forward and BCE backward of every sequence as one launch; the kernel ranks the batch by length itself (no
         srfrd_seq_order in front, `sched` untouched): the two launches' sequence -> workgroup order, so their bits"""
-        check(_lib.lib().srfrd_encoder_train_ranked(*self._enc_args(slot, True), ptr(self.loss_part), 1, ptr(self.grad),
-                                                    ptr(self.contrib), ptr(self.slabs), self.pair_stride if self.sched_mode else 0,
-                                                    self._stream()), "srfrd_encoder_train_ranked")
+        call("srfrd_encoder_train_ranked", **self._enc_args(slot, True), loss_part=self.loss_part, fused_bce=1,
+             grad_table=self.grad, table_contrib=self.contrib, grad_slabs=self.slabs,
+             pair_stride=self.pair_stride if self.sched_mode else 0)
 
     def _enqueue_prologue(self, slot, schedule: bool = True):
         """ahead of the forward: the norms of the parameters it uses (l2_emb), the batch's sequence -> workgroup schedule
         (``schedule`` False: the launch that follows ranks the batch itself)"""
-        L_, st = _lib.lib(), self._stream()
         if self.l2 != 0.0:
-            check(L_.srfrd_l2_norms(ptr(self.flat), ptr(self.seg_off), ptr(self.seg_len), self.seg_off.numel(), self.n_tab,
-                                    self.l2, ptr(self.l2_partial), ptr(self.l2buf), ptr(self.l2_dense), st), "srfrd_l2_norms")
+            call("srfrd_l2_norms", param=self.flat, seg_off=self.seg_off, seg_len=self.seg_len, n_seg=self.seg_off.numel(),
+                 n_table_pad=self.n_tab, l2_emb=self.l2, partial=self.l2_partial, l2buf=self.l2buf, dense_scale=self.l2_dense)
         if self.sched_mode and schedule:
-            check(L_.srfrd_seq_order(ptr(self.ids_ring[slot][0]), self.B, self.L, self.pair_stride, ptr(self.sched), st),
-                  "srfrd_seq_order")
+            call("srfrd_seq_order", input_ids=self.ids_ring[slot][0], B=self.B, L=self.L, pair_stride=self.pair_stride,
+                 sched=self.sched)
 
-    def _enqueue_l2_apply(self, grad_ptr, param, i0, i1):
+    def _enqueue_l2_apply(self, grad, param, i0, i1):
         """grad[i0:i1] += count * l2_emb * p / ||p|| (the Adam step that follows divides by the count)"""
-        check(_lib.lib().srfrd_l2_apply(grad_ptr, ptr(param), i0, min(i1, self.n_flat), self.n_tab, ptr(self.l2buf),
-                                        ptr(self.l2_dense), ptr(self.stats), self._stream()), "srfrd_l2_apply")
+        call("srfrd_l2_apply", grad=grad, param=param, i0=i0, i1=min(i1, self.n_flat), n_table_pad=self.n_tab, l2buf=self.l2buf,
+             dense_scale=self.l2_dense, stats=self.stats)
 
     def _enqueue_fwd(self, slot: int = 0):
         self._enqueue_prologue(slot)
         self._launch_fwd(slot, True)
         if self.mode == "sharded":       # the statistics are forward outputs: reduce them now, exchange them under the backward
-            check(_lib.lib().srfrd_loss_stats(ptr(self.loss_part), self.B, ptr(self.stats), None, self._stream()), "srfrd_loss_stats")
+            call("srfrd_loss_stats", loss_part=self.loss_part, B=self.B, stats=self.stats, loss_out=None)
 
     def _enqueue_bwd(self, slot: int = 0):
         self._launch_bwd(slot, None, self.contrib)
@@ -520,21 +511,25 @@ class FusedTrainer:
 
     def _enqueue_grad_tail(self, slot: int = 0):
         """after the backward: the deterministic item-table reduction, then the dense-gradient slab reduction (+ loss)"""
-        L_, lay, st = _lib.lib(), self.lay, self._stream()
+        lay = self.lay
         ids = self.ids_ring[slot]
         if self.contrib is not None:
             # deterministic item-table scatter: stable sort of the 3 B L row keys (pos, neg, input ids - the row order of
             # `contrib`), then one wave per item adds its rows in that order
             torch.stack((ids[2], ids[4], ids[0]), out=self.keys)
             skeys, order = torch.sort(self.keys.view(-1), stable=True)
-            check(L_.srfrd_table_reduce(ptr(skeys), ptr(order), ptr(self.contrib), skeys.numel(), lay.d_item, ptr(self.grad), st),
-                  "srfrd_table_reduce")
+            call("srfrd_table_reduce", sorted_keys=skeys, order=order, table_contrib=self.contrib, n=skeys.numel(),
+                 d_item=lay.d_item, grad_table=self.grad)
         # single rank: the slab reduction also finalises the loss; all-reduce form: it leaves the local statistics behind the
         # gradient (one vector, one collective); sharded form: the statistics were reduced right after the forward
         fuse_stats = self.mode != "sharded"
-        check(L_.srfrd_reduce_dense(ptr(self.slabs), self.n_slabs, lay.n_dense, self._dense_ptr(self.grad),
-                                    ptr(self.loss_part) if fuse_stats else None, self.B, ptr(self.stats) if fuse_stats else None,
-                                    ptr(self.loss) if self.mode == "single" else None, st), "srfrd_reduce_dense")
+        self._enqueue_ce_dense(self.loss_part if fuse_stats else None, self.stats if fuse_stats else None,
+                               self.loss if self.mode == "single" else None)
+
+    def _enqueue_ce_dense(self, loss_part=None, stats=None, loss_out=None):
+        """the dense-gradient slab reduction (the cross-entropy step's: alone, its head has made the loss statistics)"""
+        call("srfrd_reduce_dense", grad_slabs=self.slabs, n_slabs=self.n_slabs, n_dense=self.lay.n_dense,
+             grad_dense=_lib.dense_ptr(self.grad, self.n_tab), loss_part=loss_part, B=self.B, stats=stats, loss_out=loss_out)
 
     def _sort_token_keys(self):
         """the token-negatives step's one stable key sort, into its persistent buffers; eager on the current stream, between the
@@ -548,11 +543,6 @@ class FusedTrainer:
         loss_heads.table_mixed(self.lay, self.hidden, self.K, self.contrib_tok[2].view(T, self.lay.d_item), self.coef_tok,
                                self.keys_tok, self.ce_ws, self.grad, sorted_pair=(self.skeys_tok, self.order_tok))
 
-    def _enqueue_ce_dense(self):
-        L_, lay = _lib.lib(), self.lay
-        check(L_.srfrd_reduce_dense(ptr(self.slabs), self.n_slabs, lay.n_dense, self._dense_ptr(self.grad), None, self.B, None, None,
-                                    self._stream()), "srfrd_reduce_dense")
-
     def _enqueue_ce_compute(self, slot: int = 0):
         """the cross-entropy step's compute (single rank): [shared negatives] -> encoder forward (checkpoints,
         hidden) -> loss head forward, {sum, count} into stats[1..2] -> loss head backward with d token loss = 1 -> encoder
@@ -562,9 +552,8 @@ class FusedTrainer:
         lay = self.lay
         self._enqueue_prologue(slot)
         if self.sampled:
-            check(_lib.lib().srfrd_shared_negatives(ptr(self.state), lay.n_items, self.K, ptr(self.alias_prob), ptr(self.alias_idx),
-                                                    ptr(self.item_log_q), ptr(self._negatives), ptr(self._log_q), self._stream()),
-                  "srfrd_shared_negatives")
+            call("srfrd_shared_negatives", state=self.state, n_items=lay.n_items, K=self.K, alias_prob=self.alias_prob,
+                 alias_idx=self.alias_idx, item_log_q=self.item_log_q, out_ids=self._negatives, out_log_q=self._log_q)
         self._launch_fwd(slot, False)
         # the loss head (loss_heads.py) on the step's own buffers; the fp32 item table is the flat vector's head
         if self.token:
@@ -594,8 +583,8 @@ class FusedTrainer:
         if rows is None:
             return
         skeys, order = torch.sort(keys, stable=True)
-        check(_lib.lib().srfrd_table_reduce(ptr(skeys), ptr(order), ptr(rows), skeys.numel(), lay.d_item, ptr(self.grad),
-                                            self._stream()), "srfrd_table_reduce")
+        call("srfrd_table_reduce", sorted_keys=skeys, order=order, table_contrib=rows, n=skeys.numel(), d_item=lay.d_item,
+             grad_table=self.grad)
 
     def _enqueue_compute(self, slot: int = 0):
         """forward and backward as their two launches (the data-parallel step, per-launch timing)"""
@@ -623,26 +612,22 @@ class FusedTrainer:
     def _enqueue_update(self):
         """single rank / all-reduce form: Adam over the whole flat vector + re-pack + optimizer-state advance, one launch
         (an optimizer option set: [the gradient norm, then] the AdamW form of that launch)"""
-        L_, st = _lib.lib(), self._stream()
         if self.l2 != 0.0:
-            self._enqueue_l2_apply(ptr(self.grad), self.flat, 0, self.n_flat)
+            self._enqueue_l2_apply(self.grad, self.flat, 0, self.n_flat)
+        vec = dict(lay=self.lay, param=self.flat, grad=self.grad, m=self.m, v=self.v, n=self.n_flat, n_table_pad=self.n_tab,
+                   n_zero=self.n_tab, eps=self.eps, state=self.state, stats=self.stats, packed=self.packed,
+                   table_bf16=self.model._table16)
         if self.opts is None:
-            check(L_.srfrd_adam_pack_step(C.byref(self.lay), ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v),
-                                          self.n_flat, self.n_tab, self.n_tab, self.lr, self.betas[0], self.betas[1], self.eps,
-                                          ptr(self.state), ptr(self.stats), ptr(self.packed), ptr(self.model._table16), st),
-                  "srfrd_adam_pack_step")
+            call("srfrd_adam_pack_step", **vec, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1])
         else:
             # the options (DESIGN section 19): the gradient's global norm and clip coefficient, measured behind the l2_emb term,
             # then Adam with the coefficient in its gradient scale, the decay factor of state[7], and the scheduled advance
             if self.max_norm is not None:
-                check(L_.srfrd_grad_norm(ptr(self.grad), self.n_flat, ptr(self.stats), self.max_norm, ptr(self.norm_partial),
-                                         ptr(self.clip), st), "srfrd_grad_norm")
-            check(L_.srfrd_adamw_pack_step(C.byref(self.lay), ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v),
-                                           self.n_flat, self.n_tab, self.n_tab, C.byref(self.opts), self.eps, ptr(self.state),
-                                           ptr(self.stats), ptr(self.clip) if self.max_norm is not None else None,
-                                           ptr(self.packed), ptr(self.model._table16), st), "srfrd_adamw_pack_step")
+                call("srfrd_grad_norm", grad=self.grad, n=self.n_flat, stats=self.stats, max_norm=self.max_norm,
+                     partial=self.norm_partial, out=self.clip)
+            call("srfrd_adamw_pack_step", **vec, opts=self.opts, clip=self.clip if self.max_norm is not None else None)
         if self.mode != "single" or self.loss_kind != "bce":      # (single-rank BCE: the slab reduction wrote the loss)
-            check(L_.srfrd_loss_finalize(ptr(self.stats), ptr(self.loss), st), "srfrd_loss_finalize")
+            call("srfrd_loss_finalize", stats=self.stats, loss_out=self.loss)
         if self.l2 != 0.0:
             self.loss.add_(self.l2buf[1:2])
 
@@ -650,16 +635,16 @@ class FusedTrainer:
         """sharded form, between the reduce-scatter and the all-gather: re-zero the local item-table gradient (the atomics
         of the next backward accumulate into it) and step this rank's slice; `recv`, `m`, `v` hold that slice only, so
         their pointers are biased by -i0 to be indexed with the global element index."""
-        L_, st, ex = _lib.lib(), self._stream(), self.ex
+        ex = self.ex
         self.grad[:self.n_tab].zero_()
         bias = 4 * ex.i0
         if self.l2 != 0.0:
-            self._enqueue_l2_apply(C.c_void_p(self.recv.data_ptr() - bias), self.flat_pad, ex.i0, ex.i1)
+            self._enqueue_l2_apply(self.recv.data_ptr() - bias, self.flat_pad, ex.i0, ex.i1)
         sg = self.shadow_gather      # (the owner writes the bf16 shadow of the table elements it steps)
-        check(L_.srfrd_adam_step(ptr(self.flat_pad), C.c_void_p(self.recv.data_ptr() - bias), C.c_void_p(self.m.data_ptr() - bias),
-                                 C.c_void_p(self.v.data_ptr() - bias), ex.n_pad, ex.i0, ex.i1, 0, self.betas[0], self.betas[1],
-                                 self.eps, ptr(self.state), ptr(self.stats), ptr(self.shadow_pad) if sg else None,
-                                 self.lay.n_table if sg else 0, st), "srfrd_adam_step")
+        call("srfrd_adam_step", param=self.flat_pad, grad=self.recv.data_ptr() - bias, m=self.m.data_ptr() - bias,
+             v=self.v.data_ptr() - bias, n=ex.n_pad, i0=ex.i0, i1=ex.i1, n_zero=0, beta1=self.betas[0], beta2=self.betas[1],
+             eps=self.eps, state=self.state, stats=self.stats, table_bf16=self.shadow_pad if sg else None,
+             n_table=self.lay.n_table if sg else 0)
         if sg:
             # this rank's part of the dense parameters into the exchange buffer (zeros elsewhere: the SUM all-reduce is a gather)
             self.dense_x.zero_()
@@ -685,12 +670,11 @@ class FusedTrainer:
 
     def _enqueue_shard_finish(self):
         """sharded form, after the all-gather: fragment-ordered copy of the stepped weights + optimizer-state advance + loss"""
-        L_, st = _lib.lib(), self._stream()
-        check(L_.srfrd_pack_weights(C.byref(self.lay), self._dense_ptr(self.flat), ptr(self.packed), ptr(self.state), self.lr,
-                                    self.betas[0], self.betas[1], st), "srfrd_pack_weights")
+        call("srfrd_pack_weights", lay=self.lay, dense=_lib.dense_ptr(self.flat, self.n_tab), packed=self.packed, state=self.state,
+             lr=self.lr, beta1=self.betas[0], beta2=self.betas[1])
         if self.model._table16 is not None and not self.shadow_gather:      # bf16 shadow of the all-gathered item table (every rank needs all rows)
-            check(L_.srfrd_table_to_bf16(ptr(self.flat), self.lay.n_table, ptr(self.model._table16), st), "srfrd_table_to_bf16")
-        check(L_.srfrd_loss_finalize(ptr(self.stats), ptr(self.loss), st), "srfrd_loss_finalize")
+            call("srfrd_table_to_bf16", src=self.flat, n=self.lay.n_table, out=self.model._table16)
+        call("srfrd_loss_finalize", stats=self.stats, loss_out=self.loss)
         if self.l2 != 0.0:
             self.loss.add_(self.l2buf[1:2])
 
@@ -948,9 +932,9 @@ class FusedTrainer:
         ids, kind = self.ids_ring[slot], self.lay.kind
         n = self.B * self.L
         embeds_fake = kind in (1, 2)
-        check(_lib.lib().srfrd_check_ids(ptr(ids[0]), ptr(ids[2]), ptr(ids[4]), ptr(ids[1]) if embeds_fake else None,
-                                         ptr(ids[3]) if kind == 2 else None, ptr(ids[5]) if kind == 2 else None,
-                                         n, self.lay.n_items, 2, ptr(self.err), self._stream()), "srfrd_check_ids")
+        call("srfrd_check_ids", item_a=ids[0], item_b=ids[2], item_c=ids[4], fake_a=ids[1] if embeds_fake else None,
+             fake_b=ids[3] if kind == 2 else None, fake_c=ids[5] if kind == 2 else None, n=n, n_items=self.lay.n_items, fake_hi=2,
+             err_word=self.err)
 
     def check(self):
         """Raise IndexError if a batch given to step() / step_packed() held an id outside the embedding tables (the

@@ -222,25 +222,15 @@ def _enc_forward(model, ids, p, seed, save):
     """modules._launch_fwd with ZEROED outputs: the ragged kernels write only the rows of a sequence's computed tiles, and what
     nobody wrote must not differ from run to run"""
     from srfrd_amd import _lib
-    from srfrd_amd._lib import check
-    inp, fk, pos, pfk, neg, nfk = ids
-    lay, flat = model.layout, model._flat
-    B, L = inp.shape
-    f32 = dict(device=inp.device, dtype=torch.float32)
-    out = {"hidden": torch.zeros(B, L, lay.d_out, **f32), "pos_logits": torch.zeros(B, L, **f32), "neg_logits": torch.zeros(B, L, **f32)}
-    if save:
-        out["save_x"] = torch.zeros(B, lay.n_blocks + 1, L, lay.D, **f32)
-        out["save_h1"] = torch.zeros(B, lay.n_blocks, L, lay.D, **f32)
-        out["save_aux"] = torch.zeros(_L().srfrd_aux_floats(C.byref(lay), B, L), **f32)
-    packed = model.pack_weights()
-    scratch, n_scr = model._scratch_for(B, L, backward=False)
-    lay_t, tab = model._table_args()
-    check(_L().srfrd_encoder_fwd(
-        C.byref(lay_t), tab, _p(flat, 4 * model.n_table_pad), _p(packed), _p(inp), _p(fk), _p(pos), _p(pfk), _p(neg), _p(nfk), B, L,
-        float(p), int(seed) & 0xFFFFFFFF, None, 0, _p(out["hidden"]), _p(out["pos_logits"]), _p(out["neg_logits"]),
-        _p(out.get("save_x")), _p(out.get("save_h1")), _p(out.get("save_aux")), None, _p(scratch), n_scr, None, 0, _st()),
-        "srfrd_encoder_fwd")
-    return out
+    lay = model.layout
+    B, L = ids[0].shape
+    f32 = dict(device=ids[0].device, dtype=torch.float32)
+    out = {"hidden": torch.zeros(B, L, lay.d_out, **f32), "pos_logits": torch.zeros(B, L, **f32), "neg_logits": torch.zeros(B, L, **f32),
+           "save_x": torch.zeros(B, lay.n_blocks + 1, L, lay.D, **f32) if save else None,
+           "save_h1": torch.zeros(B, lay.n_blocks, L, lay.D, **f32) if save else None,
+           "save_aux": torch.zeros(_lib.query("srfrd_aux_floats", lay=lay, B=B, L=L), **f32) if save else None}
+    model._launch_fwd(*ids, p, seed, save, out=out)
+    return {k: v for k, v in out.items() if v is not None}
 
 
 def _trainer_outputs(out, tag, losses, model, tr):
@@ -328,13 +318,12 @@ TRAIN_I, TRAIN_L, TRAIN_STEPS = 400, 50, 2
 def _launch_train_sched(tr):
     """the step's one launch through srfrd_seq_order + srfrd_encoder_train_sched (FusedTrainer itself takes
     srfrd_encoder_train_ranked, which ranks the batch inside the kernel)"""
-    from srfrd_amd._lib import check
+    from srfrd_amd._lib import call
 
     def launch(slot):
-        check(_L().srfrd_seq_order(_p(tr.ids_ring[slot][0]), tr.B, tr.L, tr.pair_stride, _p(tr.sched), tr._stream()), "srfrd_seq_order")
-        check(_L().srfrd_encoder_train_sched(*tr._enc_args(slot, True), _p(tr.loss_part), None, None, None, 1, _p(tr.grad),
-                                             _p(tr.contrib), _p(tr.slabs), _p(tr.scratch), tr.n_scratch, _p(tr.sched), tr.sched_mode,
-                                             tr._stream()), "srfrd_encoder_train_sched")
+        call("srfrd_seq_order", input_ids=tr.ids_ring[slot][0], B=tr.B, L=tr.L, pair_stride=tr.pair_stride, sched=tr.sched)
+        call("srfrd_encoder_train_sched", **tr._enc_args(slot, True), loss_part=tr.loss_part, **tr._bwd_args(None, tr.contrib),
+             **tr._sched_args())
     return launch
 
 

@@ -28,19 +28,17 @@ def t(fn, n=200):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n * 1000
 m.pack_weights()
-import ctypes as C
 from srfrd_amd import _lib
-from srfrd_amd._lib import ptr, check
 lay, flat = m.layout, m._flat
 B, L = 512, 50
 hidden = torch.empty(B, L, 50, device=dev); pl = torch.empty(B, L, device=dev); nl = torch.empty(B, L, device=dev)
 sx = torch.empty(3, B, L, 50, device=dev); sh = torch.empty(2, B, L, 50, device=dev)
-sa = torch.empty(_lib.lib().srfrd_aux_floats(C.byref(lay), B, L), device=dev); lp = torch.empty(B, 3, device=dev)
-st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+sa = torch.empty(_lib.query("srfrd_aux_floats", lay=lay, B=B, L=L), device=dev); lp = torch.empty(B, 3, device=dev)
 def launch(save, p):
-    check(_lib.lib().srfrd_encoder_fwd(C.byref(lay), ptr(flat), C.c_void_p(flat.data_ptr() + 4 * m.n_table_pad), ptr(m._packed),
-        ptr(ids[0]), None, ptr(ids[2]), None, ptr(ids[4]), None, B, L, p, 7, None, 0, ptr(hidden), ptr(pl), ptr(nl),
-        ptr(sx) if save else None, ptr(sh) if save else None, ptr(sa) if save else None, ptr(lp) if save else None, None, 0, None, 0, st), "fwd")
+    ckpt = (sx, sh, sa) if save else (None, None, None)
+    _lib.call("srfrd_encoder_fwd", **_lib.encoder_head((lay, flat), flat, m.n_table_pad, m._packed, (ids[0], None, ids[2], None, ids[4], None),
+                                                       B, L, p, 0, (hidden, pl, nl, *ckpt), seed=7),
+              loss_part=lp if save else None, scratch=None, scratch_floats=0, dbg=None, dbg_seq=0)
 for name, save, p in (("train (checkpoints, dropout 0.5)", True, 0.5), ("checkpoints, no dropout", True, 0.0), ("inference (no checkpoints)", False, 0.0)):
     print(f"{name:36s} {t(lambda: launch(save, p)):7.1f} us")
 for Bx in (64, 128, 256, 384, 512):

@@ -129,8 +129,7 @@ def run_c4(I=200_000, L=100, which="bwd_slots"):
     import torch
     os.environ["SRFRD_LIB_PATH"] = OUT
     import srfrd_amd
-    from srfrd_amd import _lib
-    from srfrd_amd._lib import check, ptr
+    from srfrd_amd._lib import call
     labels = json.load(open(OUT + ".labels.json"))
     B, D = 512, 50
     torch.manual_seed(0)
@@ -145,8 +144,7 @@ def run_c4(I=200_000, L=100, which="bwd_slots"):
     tr._enqueue_fwd()
 
     def bwd(dbg):      # the trainer's own backward arguments, the stamp buffer in the schedule's place
-        check(_lib.lib().srfrd_encoder_bwd(*tr._enc_args(0, True), *tr._bwd_args(None, None), ptr(dbg.view(torch.float32)), 0,
-                                           tr._stream()), "srfrd_encoder_bwd")
+        call("srfrd_encoder_bwd", **tr._enc_args(0, True), **tr._bwd_args(None, None), dbg=dbg.view(torch.float32), dbg_seq=0)
     dbg = torch.zeros(1024, 128, device="cuda", dtype=torch.int64)
     dbg2 = torch.zeros(1024, 128, device="cuda", dtype=torch.int64)
     bwd(dbg)
