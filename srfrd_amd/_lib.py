@@ -1,4 +1,5 @@
-"""ctypes binding of libsrfrd_hip.so (the C ABI declared in include/srfrd_hip.h).
+"""ctypes binding of libsrfrd_hip.so (the C ABI declared in include/srfrd_hip.h and, the lazy-Adam entry point,
+include/srfrd_hip_lazy.h).
 
 There is no CPU fallback: if the library is missing this module raises, and every op above it fails loudly.
 """
@@ -139,6 +140,12 @@ q srfrd_table_reduce_mixed_workspace_floats(n:q d_item:i)
 i srfrd_table_reduce_mixed(sorted_keys order n:q rows n_rows:q contrib_coef hidden d_out:i rows_per_token:i d_item:i grad_table
     workspace ws_floats:q stream)
 """
+# The second table: what include/srfrd_hip_lazy.h declares, in the same notation (tests/test_lazy_adam_abi.py holds it to that
+# header; LAZY_SIGNATURES and LAZY_PARAMS derive from it).  `query` / `call` consult it after the main one.
+_LAZY_ABI = """
+i srfrd_table_reduce_adam(sorted_keys order table_contrib n:q d_item:i n_rows:q table m v beta1:d beta2:d eps:d state stats
+    table_bf16 stream)
+"""
 
 
 def _parse(params):
@@ -146,14 +153,21 @@ def _parse(params):
     return [_TYPES[t] for _, t in pairs], tuple(n for n, _ in pairs)
 
 
-_PARSED = {name: (_TYPES[res], *_parse(params)) for res, name, params in re.findall(r"(\w) (srfrd_\w+)\(([^)]*)\)", _ABI)}
+def _parse_abi(text):
+    return {name: (_TYPES[res], *_parse(params)) for res, name, params in re.findall(r"(\w) (srfrd_\w+)\(([^)]*)\)", text)}
+
+
+_PARSED = _parse_abi(_ABI)
 SIGNATURES = {name: (res, types) for name, (res, types, _) in _PARSED.items()}      # name -> (restype, argtypes)
 PARAMS = {name: names for name, (_, _, names) in _PARSED.items()}                   # name -> parameter names, in order
+_LAZY_PARSED = _parse_abi(_LAZY_ABI)
+LAZY_SIGNATURES = {name: (res, types) for name, (res, types, _) in _LAZY_PARSED.items()}
+LAZY_PARAMS = {name: names for name, (_, _, names) in _LAZY_PARSED.items()}
 ENCODER_HEAD = _parse(_ENC_HEAD)[1]
 # name -> (its names as a set, the fetch of a dict's values in parameter order, the positions that hold a pointer)
 _MARSHAL = {name: (frozenset(names), operator.itemgetter(*names) if len(names) > 1 else (lambda a, n=names[0]: (a[n],)),
                    tuple(i for i, t in enumerate(types) if t not in (_i, _i64, _u32, _d)))
-            for name, (_, types, names) in _PARSED.items()}
+            for name, (_, types, names) in {**_PARSED, **_LAZY_PARSED}.items()}
 
 _lib = None
 
@@ -168,11 +182,20 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **LAZY_SIGNATURES}.items():
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
         _lib = handle
     return _lib
+
+
+def _lazy_entry(handle, name):
+    """entry point ``name`` of the second table on ``handle``.  A handle that was bound from SIGNATURES alone (another build of
+    the library, loaded beside the product's) gets the types here: an unbound ctypes function would take an address as a C int"""
+    fn = getattr(handle, name)
+    if getattr(fn, "argtypes", ()) is None:          # (a ctypes function nobody has typed yet)
+        fn.restype, fn.argtypes = LAZY_SIGNATURES[name]
+    return fn
 
 
 def check(rc: int, what: str):
@@ -199,7 +222,7 @@ def dense_ptr(flat, n_table_pad):
 
 
 def query(name, /, **args):
-    """The C entry point ``name`` with its parameters BY NAME (PARAMS: the header's; all of them, except that ``stream`` defaults
+    """The C entry point ``name`` with its parameters BY NAME (PARAMS, then LAZY_PARAMS: the headers'; all of them, except that ``stream`` defaults
     to the current torch stream) -> its raw return value.  In a pointer's place a tensor passes its ``data_ptr()``, None is
     NULL, a ctypes structure goes by reference, anything else (an address as an int, a ctypes buffer) as it is.  A missing or
     unknown name raises TypeError before the library is touched; the function is looked up on the handle at every call."""
@@ -215,7 +238,7 @@ def query(name, /, **args):
             argv[i] = v.data_ptr()
         elif isinstance(v, C.Structure):
             argv[i] = C.byref(v)
-    return getattr(lib(), name)(*argv)
+    return (getattr(lib(), name) if name in SIGNATURES else _lazy_entry(lib(), name))(*argv)
 
 
 def call(name, /, **args):

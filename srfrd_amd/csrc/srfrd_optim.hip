@@ -1,6 +1,7 @@
 // Gradient reduction, loss finalisation and the dense Adam step (torch.optim.Adam semantics,
 // reference trainer.py:36-41, :390).  All streaming, HBM-bound, float4-wide.
 #include "srfrd_dev.h"
+#include "../../include/srfrd_hip_lazy.h"
 
 namespace srfrd {
 
@@ -141,6 +142,76 @@ __device__ __forceinline__ void shadow_store4(uint16_t* __restrict__ shadow, int
     if (i + 1 < n_shadow) shadow[i + 1] = h1;
     if (i + 2 < n_shadow) shadow[i + 2] = h2;
   }
+}
+
+// Lazy Adam of the item table (srfrd_hip_lazy.h): table_reduce_kernel's wave per sorted position, but the head of a run steps
+// its row right away - its gradient never exists in memory, and a row nobody named is neither read nor written.  No LDS, no
+// barrier: the four waves of a workgroup share nothing.
+// A run of one hot item is thousands of rows long and keys[j] -> order[j] -> row is a chain of dependent loads, so the run is
+// walked 64 positions at a time: lane l reads keys[j0 + l] and order[j0 + l] (one coalesced load each), a ballot gives the
+// length of the run inside the chunk, and the rows are fetched kLazyDepth at a time - their addresses come out of the lanes'
+// registers, all loads are issued before the first addition - and added in ascending sorted position: the fp32 chain from
+// 0.f of table_reduce_kernel, so its bits.
+constexpr int kLazyDepth = 8;
+
+// adam_one<false> with its contractions spelled out.  The source of adam_one leaves the choice of which product of
+// `m * b1 + (1 - b1) * g` joins the addition in an fma to the compiler, and the choice follows the surroundings: the dense
+// kernels' loops hoist 1 - b1 and 1 - b2 and get fma(1 - b1, g, m b1), fma((1 - b2) g, g, v b2), fma(-step_size, m / denom, p);
+// the row kernel has no loop around its one update and got fma(m, b1, (1 - b1) g) from the same line - other bits.  A touched
+// row must get the dense kernels' bits (tests/test_gpu_lazy_adam.py holds the two together), so their forms are written
+// out here and nothing else may fuse.
+__device__ __forceinline__ void adam_one_dense_bits(float& p, float g, float& m, float& v, float b1, float b2, float eps,
+                                                    float step_size, float bc2s) {
+#pragma clang fp contract(off)
+  m = __builtin_fmaf(1.0f - b1, g, m * b1);
+  v = __builtin_fmaf((1.0f - b2) * g, g, v * b2);
+  const float denom = sqrtf(v) / bc2s + eps;
+  p = __builtin_fmaf(-step_size, m / denom, p);
+}
+
+__global__ void __launch_bounds__(256) table_reduce_adam_kernel(const int64_t* __restrict__ keys, const int64_t* __restrict__ order,
+                                                               const float* __restrict__ contrib, int64_t n, int di, int64_t n_rows,
+                                                               float* __restrict__ table, float* __restrict__ m,
+                                                               float* __restrict__ v, float b1, float b2, float eps,
+                                                               const uint32_t* __restrict__ state, const float* __restrict__ stats,
+                                                               uint16_t* __restrict__ shadow) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const int64_t key = keys[i];
+  // padding_idx row, a key outside the table (never dereferenced), or not the head of its run: all wave-uniform
+  if (key <= 0 || key >= n_rows || (i > 0 && keys[i - 1] == key)) return;
+  const bool col = lane < di;
+  const int64_t e = key * di + lane;
+  float p = 0.f, mm = 0.f, vv = 0.f;
+  if (col) { p = table[e]; mm = m[e]; vv = v[e]; }               // in flight under the whole reduction
+  float acc = 0.f;
+  for (int64_t j0 = i; j0 < n; j0 += 64) {
+    const int64_t j = j0 + lane;
+    const bool in = j < n && keys[j] == key;
+    const int64_t o = in ? order[j] : 0;
+    const uint64_t mask = __ballot(in);                           // sorted keys: the lanes of the run are a prefix
+    const int cnt = ~mask == 0 ? 64 : __builtin_ctzll(~mask);
+    for (int r = 0; r < cnt; r += kLazyDepth) {                   // (r + u <= 63: r is a multiple of kLazyDepth below 64)
+      float a[kLazyDepth];
+#pragma unroll
+      for (int u = 0; u < kLazyDepth; ++u) {
+        const int64_t row = __shfl(o, r + u, 64);
+        a[u] = (r + u < cnt && col) ? contrib[row * di + lane] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < kLazyDepth; ++u)
+        if (r + u < cnt) acc += a[u];
+    }
+    if (cnt < 64) break;
+  }
+  if (!col) return;
+  const float step_size = ((const float*)state)[4];
+  const float bc2s = ((const float*)state)[5];
+  const float gscale = stats ? 1.0f / stats[2] : 1.0f;
+  adam_one_dense_bits(p, acc * gscale, mm, vv, b1, b2, eps, step_size, bc2s);
+  table[e] = p; m[e] = mm; v[e] = vv;
+  if (shadow != nullptr) shadow[e] = f32_to_bf16(p);
 }
 
 __global__ void __launch_bounds__(256) table_to_bf16_kernel(const float* __restrict__ src, int64_t n, uint16_t* __restrict__ out) {
@@ -482,6 +553,17 @@ extern "C" int srfrd_table_reduce(const int64_t* sorted_keys, const int64_t* ord
   if (!sorted_keys || !order || !table_contrib || !grad_table || n <= 0 || d_item <= 0 || d_item > 64) return SRFRD_E_ARG;
   hipLaunchKernelGGL(table_reduce_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sorted_keys, order,
                      table_contrib, n, d_item, grad_table);
+  return (int)hipGetLastError();
+}
+
+extern "C" int srfrd_table_reduce_adam(const int64_t* sorted_keys, const int64_t* order, const float* table_contrib, int64_t n,
+                                       int d_item, int64_t n_rows, float* table, float* m, float* v, double beta1, double beta2,
+                                       double eps, const uint32_t* state, const float* stats, uint16_t* table_bf16, void* stream) {
+  if (!sorted_keys || !order || !table_contrib || !table || !m || !v || !state || n < 0 || d_item < 1 || d_item > 64 || n_rows < 1)
+    return SRFRD_E_ARG;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(table_reduce_adam_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sorted_keys, order,
+                     table_contrib, n, d_item, n_rows, table, m, v, (float)beta1, (float)beta2, (float)eps, state, stats, table_bf16);
   return (int)hipGetLastError();
 }
 

@@ -9,6 +9,10 @@ loop, all behaviour-preserving: the loss is never synchronised to the host (``lo
 ``l2_emb * ||p||`` terms (trainer.py:39: one Frobenius norm per parameter tensor) cost two small launches and one pass over
 the gradient when l2_emb != 0 and nothing at the reference's 0.0, and dropout masks come from the coordinate hash of csrc/srfrd_rng.h instead of torch's Bernoulli stream.
 
+``lazy_table=True`` (no reference counterpart) swaps the optimizer of the item table for lazy Adam: only the
+rows a batch names are stepped (srfrd_table_reduce_adam, from the sorted row keys), the dense Adam tail covers the dense
+parameters alone.
+
 Data parallel (no reference counterpart): one process per GPU, the global batch split by sequence,
 parameters replicated, dropout masks keyed by the GLOBAL sequence index.  srfrd_amd/exchange.py holds the two forms of
 the per-step exchange; both divide by the GLOBAL count of non-pad targets, so N ranks reproduce the single-process
@@ -38,13 +42,18 @@ LOSSES = ("bce", "sampled_softmax", "softmax", "token_softmax", "gbce")
 TOKEN_LOSSES = {"token_softmax": "softmax", "gbce": "gbce"}      # -> the objective of srfrd_tneg_fwd / _bwd
 
 
-def step_program(mode: str, token: bool = False):
+def step_program(mode: str, token: bool = False, lazy: bool = False):
     """THE order of a train step under exchange ``mode`` ("single" | "allreduce" | "sharded"; ``token``: a loss with K negatives
-    per position): FusedTrainer's eager step, graph capture, replay and spin_up all walk this list of stages (kind, per_slot,
+    per position; ``lazy``: ``lazy_table``, single rank and BCE only): FusedTrainer's eager step, graph capture, replay and
+    spin_up all walk this list of stages (kind, per_slot,
     calls) - FusedTrainer methods called in order, with the input slot where per_slot.  "graph": they only enqueue stream work,
     so the stage is captured (per slot where per_slot: the kernels' id pointers are baked in).  "eager" / "collective": a host
     action between two graphs - the token step's key sort, which is never captured / the exchange."""
     G, E, X = "graph", "eager", "collective"
+    if lazy:
+        if mode != "single" or token:
+            raise ValueError("lazy_table steps on a single rank under loss='bce'")
+        return [(G, True, ("_enqueue_lazy_step",))]
     if mode == "single" and token:
         return [(G, True, ("_enqueue_ce_compute",)), (E, False, ("_sort_token_keys",)),
                 (G, False, ("_enqueue_token_table", "_enqueue_ce_dense", "_enqueue_update"))]
@@ -171,6 +180,30 @@ def _optim_config(lr, betas, weight_decay=0.0, max_grad_norm=None, lr_schedule="
     return opts, max_norm
 
 
+def _lazy_config(lazy_table, loss="bce", process_group=None, shadow_gather=False, l2_emb=0.0, weight_decay=0.0,
+                 max_grad_norm=None) -> bool:
+    """The refusals of FusedTrainer's ``lazy_table`` option, made on the host before anything is allocated; -> the option as a
+    bool.  Lazy Adam steps the item rows a batch names and nothing else of the table: whatever needs the
+    whole table's gradient, or another rank's, is refused."""
+    if not lazy_table:
+        return False
+    if loss != "bce":
+        raise ValueError(f"lazy_table=True trains loss='bce' only (got loss={loss!r}): the catalog losses' table gradients "
+                         "reach rows the batch does not name")
+    if exchange_active(process_group):
+        raise ValueError("lazy_table=True trains on a single rank: the data-parallel step exchanges a dense table gradient")
+    if shadow_gather:
+        raise ValueError("lazy_table=True and shadow_gather exclude each other: shadow_gather belongs to the sharded exchange")
+    if float(l2_emb) != 0.0:
+        raise ValueError(f"lazy_table=True needs l2_emb == 0 (got {l2_emb}): the norm term's gradient touches every row")
+    if float(weight_decay) != 0.0:
+        raise ValueError(f"lazy_table=True needs weight_decay == 0 (got {weight_decay}): the decay multiplies every row")
+    if max_grad_norm is not None:
+        raise ValueError(f"lazy_table=True needs max_grad_norm=None (got {max_grad_norm}): the table gradient is never "
+                         "materialised, so there is nothing to take a norm of")
+    return True
+
+
 class FusedTrainer:
     """Owns optimizer state and step buffers for one model on one GPU (one rank of a DP job)."""
 
@@ -180,7 +213,8 @@ class FusedTrainer:
                  loss: str = "bce", num_negatives: int = 1024, neg_counts=None, neg_alpha: float = 1.0,
                  logq_correction: bool = True, remove_accidental_hits: bool = True, gbce_beta: float = 1.0,
                  weight_decay: float = 0.0, max_grad_norm: float | None = None, lr_schedule: str = "constant",
-                 warmup_steps: int = 0, total_steps: int | None = None, final_lr_ratio: float = 0.0):
+                 warmup_steps: int = 0, total_steps: int | None = None, final_lr_ratio: float = 0.0,
+                 lazy_table: bool = False):
         """``shadow_gather`` (sharded exchange over a bf16 item-table shadow, ``model.use_bf16_table()``; SURVEY 8e's alternative
         for BASELINE configs[4]): the fp32 master of an item row and its Adam moments live on the OWNER rank only; after the
         sharded Adam step the all-gather carries the bf16 SHADOW of the table (2 bytes per element: 90 MB instead of 180 MB at
@@ -210,7 +244,15 @@ class FusedTrainer:
         ``lr_schedule`` ("constant" | "linear" | "cosine") with ``warmup_steps``, ``total_steps`` and ``final_lr_ratio``
         (``srfrd_amd.lr_at`` is the formula): all three live on the device, inside the captured step -
         ``grad_norm`` and ``next_lr`` show them.  Single rank.  With every one at its default the step issues exactly the
-        launches of plain Adam."""
+        launches of plain Adam.
+        ``lazy_table``: lazy Adam for the item table - a row's value and moments are stepped only on the
+        steps whose batch names it (as an input, positive or negative id), with the global step's bias correction; every
+        other row keeps its bits, and the dense parameters step as always.  A different optimizer, not a faster dense one:
+        after the first step the parameters differ from the dense trainer's.  The table's share of the step then costs in
+        proportion to the batch, not the catalog.  Implies ``deterministic``; single rank, ``loss="bce"``, no ``l2_emb`` /
+        ``weight_decay`` / ``max_grad_norm`` / ``shadow_gather`` (``lr_schedule`` / ``warmup_steps`` are fine).  The state
+        format is the dense trainer's: checkpoints move between the two."""
+        self.lazy_table = _lazy_config(lazy_table, loss, process_group, shadow_gather, l2_emb, weight_decay, max_grad_norm)
         self.opts, self.max_norm = _optim_config(lr, betas, weight_decay, max_grad_norm, lr_schedule, warmup_steps, total_steps,
                                                  final_lr_ratio, process_group)
         q = _loss_config(model, loss, num_negatives, neg_counts, neg_alpha, process_group, gbce_beta,
@@ -282,7 +324,9 @@ class FusedTrainer:
         if self.max_norm is not None:        # srfrd_grad_norm's workspace and its {norm, coefficient}
             self.norm_partial = torch.zeros(_lib.GRAD_NORM_PARTIALS, device=dev, dtype=torch.float64)
             self.clip = torch.zeros(2, **f32)
-        self.deterministic = bool(deterministic)
+        self.deterministic = bool(deterministic) or self.lazy_table      # (lazy Adam starts from the sorted row keys)
+        if self.lazy_table and (self.n_tab & 3 or self.flat.data_ptr() & 15):
+            raise RuntimeError("lazy_table: the dense parameters do not start on a float4 boundary of the flat vector")
         self.loss_kind = loss
         self.sampled = loss == "sampled_softmax"
         self.token = loss in TOKEN_LOSSES
@@ -326,7 +370,7 @@ class FusedTrainer:
         self.packed = model.pack_weights()
         self._step_begin()
         self.use_graph = bool(use_graph)
-        self._program = step_program(self.mode, self.token)
+        self._program = step_program(self.mode, self.token, self.lazy_table)
         self._graphs = None              # (stages, their graphs) once captured: `captured`
         self._stats_handle = None        # sharded form: the statistics all-reduce in flight between two eager stages
         self.graph_form = None           # "one" | "split" once captured (data parallel: one graph with the collectives inside, or graphs around them)
@@ -518,13 +562,21 @@ class FusedTrainer:
             # `contrib`), then one wave per item adds its rows in that order
             torch.stack((ids[2], ids[4], ids[0]), out=self.keys)
             skeys, order = torch.sort(self.keys.view(-1), stable=True)
-            call("srfrd_table_reduce", sorted_keys=skeys, order=order, table_contrib=self.contrib, n=skeys.numel(),
-                 d_item=lay.d_item, grad_table=self.grad)
+            if not self.lazy_table:
+                call("srfrd_table_reduce", sorted_keys=skeys, order=order, table_contrib=self.contrib, n=skeys.numel(),
+                     d_item=lay.d_item, grad_table=self.grad)
         # single rank: the slab reduction also finalises the loss; all-reduce form: it leaves the local statistics behind the
         # gradient (one vector, one collective); sharded form: the statistics were reduced right after the forward
         fuse_stats = self.mode != "sharded"
         self._enqueue_ce_dense(self.loss_part if fuse_stats else None, self.stats if fuse_stats else None,
                                self.loss if self.mode == "single" else None)
+        if self.lazy_table:
+            # lazy Adam: from the sorted keys straight to the stepped rows - behind the slab reduction,
+            # which finalised the count in `stats`, and ahead of the dense update, which advances `state`.  No table gradient:
+            # its slice of `grad` is never written and stays zero.
+            call("srfrd_table_reduce_adam", sorted_keys=skeys, order=order, table_contrib=self.contrib, n=skeys.numel(),
+                 d_item=lay.d_item, n_rows=lay.n_items + 1, table=self.flat, m=self.m, v=self.v, beta1=self.betas[0],
+                 beta2=self.betas[1], eps=self.eps, state=self.state, stats=self.stats, table_bf16=self.model._table16)
 
     def _enqueue_ce_dense(self, loss_part=None, stats=None, loss_out=None):
         """the dense-gradient slab reduction (the cross-entropy step's: alone, its head has made the loss statistics)"""
@@ -608,6 +660,25 @@ class FusedTrainer:
         """the single-rank step, whole: one graph per slot"""
         self._enqueue_step_compute(slot)
         self._enqueue_update()
+
+    def _enqueue_lazy_step(self, slot: int = 0):
+        """the ``lazy_table`` step, whole: one graph per slot.  The compute of the single-rank step with the sorted scatter;
+        `_enqueue_grad_tail` ends in srfrd_table_reduce_adam in place of srfrd_table_reduce; then the dense parameters"""
+        self._enqueue_step_compute(slot)
+        self._enqueue_lazy_update()
+
+    def _enqueue_lazy_update(self):
+        """``lazy_table``: the fused Adam tail over the dense parameters alone - every vector biased by the padded table, so
+        the launch sees a flat vector without a table (n_table_pad 0: its pack indices are the dense ones).  It re-packs the
+        stepped weights and advances `state`, as always; the bf16 shadow belongs to the row kernel."""
+        nt = self.n_tab
+        vec = dict(lay=self.lay, param=_lib.dense_ptr(self.flat, nt), grad=_lib.dense_ptr(self.grad, nt),
+                   m=_lib.dense_ptr(self.m, nt), v=_lib.dense_ptr(self.v, nt), n=self.n_flat - nt, n_table_pad=0, n_zero=0,
+                   eps=self.eps, state=self.state, stats=self.stats, packed=self.packed, table_bf16=None)
+        if self.opts is None:
+            call("srfrd_adam_pack_step", **vec, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1])
+        else:       # (a schedule: the W form at decay 1 runs the plain form's arithmetic - srfrd_optim.hip, mul_rounded)
+            call("srfrd_adamw_pack_step", **vec, opts=self.opts, clip=None)
 
     def _enqueue_update(self):
         """single rank / all-reduce form: Adam over the whole flat vector + re-pack + optimizer-state advance, one launch
@@ -899,6 +970,8 @@ class FusedTrainer:
         max_norm = extra["max_grad_norm"] if "schedule" in extra or "max_grad_norm" in extra else self.max_norm
         opts, max_norm = _optim_config(lr, betas, float(group.get("weight_decay") or 0.0), max_norm, sch["kind"],
                                        sch.get("warmup_steps", 0), sch.get("total_steps"), sch.get("final_lr_ratio", 0.0), self.group)
+        # (a lazy trainer takes a dense trainer's checkpoint and the other way round - unless it carries an option lazy Adam refuses)
+        _lazy_config(self.lazy_table, self.loss_kind, self.group, False, self.l2, float(group.get("weight_decay") or 0.0), max_norm)
         dev = self.flat.device
         if max_norm is not None and self.max_norm is None:
             self.norm_partial = torch.zeros(_lib.GRAD_NORM_PARTIALS, device=dev, dtype=torch.float64)
