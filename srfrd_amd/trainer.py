@@ -42,21 +42,59 @@ LOSSES = ("bce", "sampled_softmax", "softmax", "token_softmax", "gbce")
 TOKEN_LOSSES = {"token_softmax": "softmax", "gbce": "gbce"}      # -> the objective of srfrd_tneg_fwd / _bwd
 
 
-def step_program(mode: str, token: bool = False, lazy: bool = False):
+# The longest key list whose stable sort a graph may hold.  Above rocprim's merge_sort_limit (MergeSortLimit = 1024 * 1024 in
+# rocprim/device/device_radix_sort_config.hpp; `size <= limit` takes the merge sort) the radix sort clears its histogram and
+# look-back states with hipMemsetAsync, a replayed memset node does not reliably zero its buffer on this runtime, and a captured
+# sort of 1 689 600 keys faulted the GPU on replay.  A longer list is sorted eagerly, between two graphs.
+SORT_CAPTURE_LIMIT = 1 << 20
+
+
+def sort_key_count(loss: str, deterministic: bool, lazy: bool, B: int, L: int, K: int = 0) -> int:
+    """the length of the key list a train step sorts (0: it sorts nothing - the float-atomic scatter)"""
+    T = int(B) * int(L)
+    if loss in TOKEN_LOSSES:
+        return T * (2 + int(K))              # the input ids, then the head's (1 + K) rank-1 rows per position
+    if loss == "sampled_softmax":
+        return 2 * T + int(K)                # the input ids, then the head's negatives and targets
+    if loss == "softmax":
+        return T if deterministic else 0     # the input ids
+    return 3 * T if deterministic or lazy else 0      # BCE: the positive, negative and input ids
+
+
+def sort_plan(mode: str, n_keys: int, use_graph: bool = True):
+    """THE decision where a step's key sort runs, from the length of its list: -> (eager_sort, use_graph, reason).  Up to
+    SORT_CAPTURE_LIMIT keys the sort is captured with the step.  A longer list on a single rank: ``eager_sort``, step_program's
+    two graphs around the sort.  The exchange programs have no such form: there the step runs without graphs, and ``reason``
+    (FusedTrainer.graph_capture_error) says so."""
+    if n_keys <= SORT_CAPTURE_LIMIT or mode == "single":
+        return n_keys > SORT_CAPTURE_LIMIT, use_graph, None
+    reason = (f"a sort of {n_keys} keys (more than {SORT_CAPTURE_LIMIT}) is not captured, and the {mode!r} exchange program has no "
+              "form with an eager sort: the step runs without graphs")
+    return False, False, reason if use_graph else None
+
+
+def step_program(mode: str, token: bool = False, lazy: bool = False, eager_sort: bool = False):
     """THE order of a train step under exchange ``mode`` ("single" | "allreduce" | "sharded"; ``token``: a loss with K negatives
-    per position; ``lazy``: ``lazy_table``, single rank and BCE only): FusedTrainer's eager step, graph capture, replay and
+    per position; ``lazy``: ``lazy_table``, single rank and BCE only; ``eager_sort``: single rank, a key list too long to sort
+    inside a graph - sort_plan): FusedTrainer's eager step, graph capture, replay and
     spin_up all walk this list of stages (kind, per_slot,
     calls) - FusedTrainer methods called in order, with the input slot where per_slot.  "graph": they only enqueue stream work,
     so the stage is captured (per slot where per_slot: the kernels' id pointers are baked in).  "eager" / "collective": a host
-    action between two graphs - the token step's key sort, which is never captured / the exchange."""
+    action between two graphs - the key sort of a token step (at every size) or of a long list / the
+    exchange."""
     G, E, X = "graph", "eager", "collective"
-    if lazy:
-        if mode != "single" or token:
-            raise ValueError("lazy_table steps on a single rank under loss='bce'")
-        return [(G, True, ("_enqueue_lazy_step",))]
+    if lazy and (mode != "single" or token):
+        raise ValueError("lazy_table steps on a single rank under loss='bce'")
     if mode == "single" and token:
-        return [(G, True, ("_enqueue_ce_compute",)), (E, False, ("_sort_token_keys",)),
-                (G, False, ("_enqueue_token_table", "_enqueue_ce_dense", "_enqueue_update"))]
+        return [(G, True, ("_enqueue_ce_compute",)), (E, False, ("_sort_keys",)),
+                (G, False, ("_enqueue_table_reduce", "_enqueue_ce_dense", "_enqueue_update"))]
+    if eager_sort:       # the pieces of `_enqueue_step_compute`, cut at the sort; then the update
+        if mode != "single":
+            raise ValueError("the exchange programs have no form with an eager sort")
+        return [(G, True, ("_enqueue_to_keys",)), (E, False, ("_sort_keys",)),
+                (G, False, ("_enqueue_reduce", "_enqueue_lazy_update" if lazy else "_enqueue_update"))]
+    if lazy:
+        return [(G, True, ("_enqueue_lazy_step",))]
     if mode == "single":
         return [(G, True, ("_enqueue_compute_update",))]
     if mode == "allreduce":
@@ -332,7 +370,14 @@ class FusedTrainer:
         self.token = loss in TOKEN_LOSSES
         # (the sampled and the token-negatives steps keep the encoder's contribution rows in buffers of their own, below)
         self.contrib = torch.zeros(3, B, L, lay.d_item, **f32) if self.deterministic and not (self.sampled or self.token) else None
-        self.keys = torch.zeros(3, B, L, device=dev, dtype=torch.int64) if self.deterministic else None
+        # A sorted step's key list (a row of the table per entry), where its stable sort lands, and the contribution rows the
+        # list keys, in list order (BCE: the pos, neg and input planes of `contrib`; the other losses: _init_ce).  An unsorted
+        # trainer has none of this.
+        self.n_keys = sort_key_count(loss, self.deterministic, self.lazy_table, B, L,
+                                     num_negatives if self.sampled or self.token else 0)
+        self.keys = torch.zeros(self.n_keys, device=dev, dtype=torch.int64) if self.n_keys else None
+        self.skeys, self.order = (torch.zeros_like(self.keys), torch.zeros_like(self.keys)) if self.n_keys else (None, None)
+        self.key_rows = self.contrib
         self.n_slabs = query("srfrd_bwd_grid", lay=lay, B=B, L=L)
         self.slabs = torch.empty(self.n_slabs, lay.n_dense, **f32)
         # Input ring: `slots` resident (6, B, L) id buffers.  A producer (DeviceSampler, a loader thread's H2D copy)
@@ -369,12 +414,12 @@ class FusedTrainer:
             self._init_ce(q, num_negatives, logq_correction, remove_accidental_hits, gbce_beta)
         self.packed = model.pack_weights()
         self._step_begin()
-        self.use_graph = bool(use_graph)
-        self._program = step_program(self.mode, self.token, self.lazy_table)
+        # (a key list too long to sort inside a graph: two graphs around the sort; data parallel: no graphs, and why)
+        eager_sort, self.use_graph, self.graph_capture_error = sort_plan(self.mode, self.n_keys, bool(use_graph))
+        self._program = step_program(self.mode, self.token, self.lazy_table, eager_sort)
         self._graphs = None              # (stages, their graphs) once captured: `captured`
         self._stats_handle = None        # sharded form: the statistics all-reduce in flight between two eager stages
-        self.graph_form = None           # "one" | "split" once captured (data parallel: one graph with the collectives inside, or graphs around them)
-        self.graph_capture_error = None
+        self.graph_form = None           # "one" | "split" once captured (one graph per step, or graphs around the eager stages)
         self.steps_done = 0
         self.err = torch.zeros(1, device=dev, dtype=torch.int32)   # srfrd_check_ids word of step() / step_packed() inputs
         self._fresh = False      # packed weights known to match the parameters (see refresh())
@@ -406,7 +451,6 @@ class FusedTrainer:
             # one contribution buffer for the whole table gradient: rows [0, 3T) the encoder's (pos, neg, input planes; only
             # the input plane carries anything here), rows [3T, 3T + K + T) the loss head's; keys of rows [2T, 4T + K)
             self.contrib_ce = torch.zeros(4 * T + K, lay.d_item, **f32)
-            self.keys_ce = torch.zeros(2 * T + K, device=dev, dtype=torch.int64)
         elif self.token:
             K = self.K = int(num_negatives)
             self.objective = _lib.TNEG_OBJECTIVES[TOKEN_LOSSES[self.loss_kind]]
@@ -417,33 +461,25 @@ class FusedTrainer:
             self.log_q_ring = torch.zeros(self.slots, B, L, K, **f32)
             self._last_slot = 0
             # the encoder's contribution planes (pos, neg, input; only the input plane carries anything here), the head's
-            # rank-1 coefficients, and ONE key list: [clamped input ids (T) | the head's keys (T (1 + K))]
+            # rank-1 coefficients; the step's ONE key list is [clamped input ids (T) | the head's keys (T (1 + K))]
             self.contrib_tok = torch.zeros(3, B, L, lay.d_item, **f32)
             self.coef_tok = torch.zeros(T * (1 + K), **f32)
-            self.keys_tok = torch.zeros(T + T * (1 + K), device=dev, dtype=torch.int64)
-            # ... and where its stable sort lands.  The sort is never captured ("The sort stays outside
-            # the graph"): above 2^20 keys rocprim's radix sort zeroes its state with memset nodes, section 14's graph pitfall
-            self.skeys_tok = torch.zeros_like(self.keys_tok)
-            self.order_tok = torch.zeros_like(self.keys_tok)
         elif self.deterministic:
-            self.keys_in = torch.zeros(T, device=dev, dtype=torch.int64)
             self.de_ce = torch.zeros(lay.n_items + 1, lay.d_item, **f32)
         # What the step's compute asks of the loss: its head, where the head's backward leaves the table gradient, the encoder
-        # backward's contribution buffer, the key list whose first T entries are the clamped input ids and the rows it keys
-        # (ce_rows None: the token step's program sorts and reduces its list; ce_keys None: nothing to reduce)
+        # backward's contribution buffer, and the full rows that `keys` - its first T entries the clamped input ids - keys
         if self.token:       #  T (1 + K) coefficients and, behind the T input keys, their keys, unreduced
-            head, self.ce_grad_to = loss_heads.TNEG, dict(rows=self.coef_tok, keys=self.keys_tok[T:], finish=False)
-            self.ce_contrib, self.ce_keys, self.ce_rows = self.contrib_tok, self.keys_tok, None
+            head, self.ce_grad_to = loss_heads.TNEG, dict(rows=self.coef_tok, keys=self.keys[T:], finish=False)
+            self.ce_contrib, self.key_rows = self.contrib_tok, self.contrib_tok[2].view(T, lay.d_item)
         elif self.sampled:   # its rows and keys land behind the encoder's in the merged buffers, unreduced: one sort for both
-            head, self.ce_grad_to = loss_heads.SXENT, dict(rows=self.contrib_ce[3 * T:], keys=self.keys_ce[T:], finish=False)
-            self.ce_contrib, self.ce_keys, self.ce_rows = self.contrib_ce, self.keys_ce, self.contrib_ce[2 * T:]
+            head, self.ce_grad_to = loss_heads.SXENT, dict(rows=self.contrib_ce[3 * T:], keys=self.keys[T:], finish=False)
+            self.ce_contrib, self.key_rows = self.contrib_ce, self.contrib_ce[2 * T:]
         else:
             # xent_bwd writes a dense table gradient; the deterministic encoder table reduction STORES its rows (the input
             # plane of `contrib`), so there the head's part waits in de_ce and is added afterwards
             det = self.contrib is not None
             head, self.ce_grad_to = loss_heads.XENT, dict(d_table=self.de_ce if det else self.grad, accumulate=not det)
-            self.ce_contrib = self.contrib
-            self.ce_keys, self.ce_rows = (self.keys_in, self.contrib[2]) if det else (None, None)
+            self.ce_contrib, self.key_rows = self.contrib, self.contrib[2] if det else None
         self.ce_head = head
         n_ws = head.workspace(lay, B, L, self.K if self.sampled or self.token else 0)
         if self.token:
@@ -553,18 +589,51 @@ class FusedTrainer:
         self._launch_bwd(slot, None, self.contrib)
         self._enqueue_grad_tail(slot)
 
-    def _enqueue_grad_tail(self, slot: int = 0):
-        """after the backward: the deterministic item-table reduction, then the dense-gradient slab reduction (+ loss)"""
-        lay = self.lay
+    # A step with a key list is cut at the same place into three pieces: up to the key list (the compute, then `_write_keys`),
+    # the sort (`_sort_keys`), and what follows it (`_enqueue_reduce`, then the update).  Where the sort is captured they run
+    # back to back (`_enqueue_grad_tail`, `_enqueue_step_compute`); step_program(eager_sort=True) makes them three stages.
+    def _write_keys(self, slot: int = 0):
+        """the slot's ids into the key list: BCE, the pos, neg and input planes (the row order of `contrib`); a cross-entropy
+        loss, the clamped input ids into the list's head (the head's backward wrote the rest)"""
+        if self.keys is None:        # (the float-atomic scatter)
+            return
         ids = self.ids_ring[slot]
-        if self.contrib is not None:
-            # deterministic item-table scatter: stable sort of the 3 B L row keys (pos, neg, input ids - the row order of
-            # `contrib`), then one wave per item adds its rows in that order
-            torch.stack((ids[2], ids[4], ids[0]), out=self.keys)
-            skeys, order = torch.sort(self.keys.view(-1), stable=True)
-            if not self.lazy_table:
-                call("srfrd_table_reduce", sorted_keys=skeys, order=order, table_contrib=self.contrib, n=skeys.numel(),
-                     d_item=lay.d_item, grad_table=self.grad)
+        if self.loss_kind == "bce":
+            torch.stack((ids[2], ids[4], ids[0]), out=self.keys.view(3, self.B, self.L))
+        else:
+            torch.clamp(ids[0].reshape(-1), 0, self.lay.n_items, out=self.keys[:self.B * self.L])
+
+    def _sort_keys(self):
+        """THE stable sort of the step's key list, into its persistent buffers.  Captured with the step up to
+        SORT_CAPTURE_LIMIT keys; a longer list (and the token step's, always) is sorted eagerly, between the step's two graphs -
+        checked here on the host, ahead of the sort: a mistake in a program costs an error, not a machine"""
+        if self.keys.numel() > SORT_CAPTURE_LIMIT and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"a sort of {self.keys.numel()} keys (more than {SORT_CAPTURE_LIMIT}) must not be captured: "
+                               "its memset nodes do not replay reliably (DESIGN section 18)")
+        torch.sort(self.keys, stable=True, out=(self.skeys, self.order))
+
+    def _enqueue_table_reduce(self):
+        """the table gradient from the sorted key list, one ordered sum per item: of the full rows the list keys; the token
+        step's, per item its input positions' full rows, then its rank-1 rows coef * hidden[t] (the backward read `hidden`, it
+        did not write it).  Lazy Adam makes no table gradient: `_enqueue_reduce` steps the rows instead."""
+        lay = self.lay
+        if self.token:
+            loss_heads.table_mixed(lay, self.hidden, self.K, self.key_rows, self.coef_tok, self.keys, self.ce_ws, self.grad,
+                                   sorted_pair=(self.skeys, self.order))
+        elif not self.lazy_table:
+            call("srfrd_table_reduce", sorted_keys=self.skeys, order=self.order, table_contrib=self.key_rows, n=self.n_keys,
+                 d_item=lay.d_item, grad_table=self.grad)
+            if self.loss_kind == "softmax":      # (the reduction stored the rows: the head's dense part waited in de_ce)
+                self.grad[:lay.n_table].add_(self.de_ce.view(-1))
+
+    def _enqueue_reduce(self):
+        """after the sort (an unsorted step: after the backward): the table gradient from the sorted keys, the dense-gradient
+        slab reduction (+ loss), lazy Adam's rows"""
+        if self.keys is not None:
+            self._enqueue_table_reduce()
+        if self.loss_kind != "bce":
+            self._enqueue_ce_dense()
+            return
         # single rank: the slab reduction also finalises the loss; all-reduce form: it leaves the local statistics behind the
         # gradient (one vector, one collective); sharded form: the statistics were reduced right after the forward
         fuse_stats = self.mode != "sharded"
@@ -574,33 +643,27 @@ class FusedTrainer:
             # lazy Adam: from the sorted keys straight to the stepped rows - behind the slab reduction,
             # which finalised the count in `stats`, and ahead of the dense update, which advances `state`.  No table gradient:
             # its slice of `grad` is never written and stays zero.
-            call("srfrd_table_reduce_adam", sorted_keys=skeys, order=order, table_contrib=self.contrib, n=skeys.numel(),
-                 d_item=lay.d_item, n_rows=lay.n_items + 1, table=self.flat, m=self.m, v=self.v, beta1=self.betas[0],
+            call("srfrd_table_reduce_adam", sorted_keys=self.skeys, order=self.order, table_contrib=self.key_rows, n=self.n_keys,
+                 d_item=self.lay.d_item, n_rows=self.lay.n_items + 1, table=self.flat, m=self.m, v=self.v, beta1=self.betas[0],
                  beta2=self.betas[1], eps=self.eps, state=self.state, stats=self.stats, table_bf16=self.model._table16)
+
+    def _enqueue_grad_tail(self, slot: int = 0):
+        """after the BCE backward: the key list, its sort and what follows it (an unsorted step: the slab reduction alone)"""
+        self._write_keys(slot)
+        if self.keys is not None:
+            self._sort_keys()
+        self._enqueue_reduce()
 
     def _enqueue_ce_dense(self, loss_part=None, stats=None, loss_out=None):
         """the dense-gradient slab reduction (the cross-entropy step's: alone, its head has made the loss statistics)"""
         call("srfrd_reduce_dense", grad_slabs=self.slabs, n_slabs=self.n_slabs, n_dense=self.lay.n_dense,
              grad_dense=_lib.dense_ptr(self.grad, self.n_tab), loss_part=loss_part, B=self.B, stats=stats, loss_out=loss_out)
 
-    def _sort_token_keys(self):
-        """the token-negatives step's one stable key sort, into its persistent buffers; eager on the current stream, between the
-        step's two graphs"""
-        torch.sort(self.keys_tok, stable=True, out=(self.skeys_tok, self.order_tok))
-
-    def _enqueue_token_table(self):
-        """the token-negatives step's table gradient from the sorted key list: per item its input positions' full rows
-        (contrib_tok's input plane), then its rank-1 rows coef * hidden[t] (the backward read `hidden`, it did not write it)"""
-        T = self.B * self.L
-        loss_heads.table_mixed(self.lay, self.hidden, self.K, self.contrib_tok[2].view(T, self.lay.d_item), self.coef_tok,
-                               self.keys_tok, self.ce_ws, self.grad, sorted_pair=(self.skeys_tok, self.order_tok))
-
-    def _enqueue_ce_compute(self, slot: int = 0):
-        """the cross-entropy step's compute (single rank): [shared negatives] -> encoder forward (checkpoints,
+    def _launch_ce(self, slot: int = 0):
+        """the cross-entropy step's launches (single rank): [shared negatives] -> encoder forward (checkpoints,
         hidden) -> loss head forward, {sum, count} into stats[1..2] -> loss head backward with d token loss = 1 -> encoder
-        backward from d_hidden -> table gradient -> dense slab reduction.  stats[0] stays 0, so the Adam tail's 1 / stats[2]
-        and srfrd_loss_finalize give the gradient of the mean and the mean.  The token-negatives step's ends with its key list:
-        the sort, the table gradient and the slab reduction are the step program's next stages."""
+        backward from d_hidden.  stats[0] stays 0, so the Adam tail's 1 / stats[2] and srfrd_loss_finalize give the gradient of
+        the mean and the mean."""
         lay = self.lay
         self._enqueue_prologue(slot)
         if self.sampled:
@@ -619,42 +682,41 @@ class FusedTrainer:
         loss_heads.launch_bwd(self.ce_head, lay, table, self.hidden, tgt, args, self.lse, self.d_token, ws=self.ce_ws,
                               d_hidden=self.d_hidden, **self.ce_grad_to)
         self._launch_bwd(slot, self.d_hidden, self.ce_contrib)
-        if self.ce_keys is not None:
-            self._enqueue_table_tail(slot, self.ce_keys, self.ce_rows)
-        if self.token:
-            return
-        if self.ce_rows is not None and not self.sampled:
-            self.grad[:lay.n_table].add_(self.de_ce.view(-1))
-        self._enqueue_ce_dense()
 
-    def _enqueue_table_tail(self, slot, keys, rows):
-        """the clamped input ids into the head of the key list ``keys``; then (``rows`` given: the contribution rows the list
-        keys, in list order) one stable sort and one ordered sum per item into the table gradient"""
-        lay = self.lay
-        torch.clamp(self.ids_ring[slot][0].reshape(-1), 0, lay.n_items, out=keys[:self.B * self.L])
-        if rows is None:
-            return
-        skeys, order = torch.sort(keys, stable=True)
-        call("srfrd_table_reduce", sorted_keys=skeys, order=order, table_contrib=rows, n=skeys.numel(), d_item=lay.d_item,
-             grad_table=self.grad)
+    def _enqueue_ce_compute(self, slot: int = 0):
+        """the cross-entropy step's compute, through the table gradient and the dense slab reduction.  The token-negatives
+        step's ends with its key list: the sort, the table gradient and the slab reduction are the step program's next stages."""
+        if self.token:
+            self._enqueue_to_keys(slot)
+        else:
+            self._enqueue_step_compute(slot)
 
     def _enqueue_compute(self, slot: int = 0):
         """forward and backward as their two launches (the data-parallel step, per-launch timing)"""
         self._enqueue_fwd(slot)
         self._enqueue_bwd(slot)
 
-    def _enqueue_step_compute(self, slot: int = 0):
-        """the single-rank step's compute: forward and backward as ONE launch where the kernel plan offers a train kernel (each
-        workgroup runs its sequence's backward right after its forward; the same bits as the two launches), else the two"""
+    def _enqueue_to_keys(self, slot: int = 0):
+        """the single-rank step up to its key list: the loss's launches - BCE: forward and backward as ONE launch where the
+        kernel plan offers a train kernel (each workgroup runs its sequence's backward right after its forward; the same bits as
+        the two launches), else the two - then the slot's ids into the list"""
         if self.loss_kind != "bce":
-            self._enqueue_ce_compute(slot)
+            self._launch_ce(slot)
         elif self.mode == "single" and self.train_launch and _lib.encoder_plan_train(
                 self.lay, self.B, self.L, self._train_mode, _lib.env_switches())[0]:
             self._enqueue_prologue(slot, schedule=False)
             self._launch_train(slot)
-            self._enqueue_grad_tail(slot)
         else:
-            self._enqueue_compute(slot)
+            self._enqueue_fwd(slot)
+            self._launch_bwd(slot, None, self.contrib)
+        self._write_keys(slot)
+
+    def _enqueue_step_compute(self, slot: int = 0):
+        """the single-rank step's compute: its three pieces back to back"""
+        self._enqueue_to_keys(slot)
+        if self.keys is not None:
+            self._sort_keys()
+        self._enqueue_reduce()
 
     def _enqueue_compute_update(self, slot: int = 0):
         """the single-rank step, whole: one graph per slot"""
@@ -663,7 +725,7 @@ class FusedTrainer:
 
     def _enqueue_lazy_step(self, slot: int = 0):
         """the ``lazy_table`` step, whole: one graph per slot.  The compute of the single-rank step with the sorted scatter;
-        `_enqueue_grad_tail` ends in srfrd_table_reduce_adam in place of srfrd_table_reduce; then the dense parameters"""
+        `_enqueue_reduce` ends in srfrd_table_reduce_adam in place of srfrd_table_reduce; then the dense parameters"""
         self._enqueue_step_compute(slot)
         self._enqueue_lazy_update()
 

@@ -4,7 +4,10 @@ An ordered recorder stands in ``_lib._lib`` (the seam tests/skew_cases.use swaps
 the handle, size and plan queries included, while a path runs once at the smallest shapes: SRFRN 45 + 5 over 300 items, B = 4,
 L = 20 (its fake planes exercise pos_fake / neg_fake), and SASRec 50, B = 8, L = 50 (the one-launch train kernel exists only at
 that length).  The expected lists below were recorded on the commit before the Python layer went over to calls by parameter
-name (``_lib.call``); the test uses nothing but that seam, so it holds for both sides of that change and for every later one."""
+name (``_lib.call``); the test uses nothing but that seam, so it holds for both sides of that change and for every later one.
+Four lists came later, with the trainer's one key sort: ``lazy_table`` and ``softmax`` with ``deterministic``, read off the
+launches of the commit before it, and the step cut into three stages at an eager sort (``deterministic``,
+``sampled_softmax``), which must ask for exactly what the one-stage step asks for."""
 import contextlib
 
 import pytest
@@ -62,13 +65,19 @@ def _autograd(library_ops):
     return run
 
 
-def _step(shape, **options):
+def _step(shape, sort_limit=None, **options):
+    """``sort_limit``: srfrd_amd.trainer.SORT_CAPTURE_LIMIT while the trainer is built (0: the program with the eager key sort)"""
     def run():
         import srfrd_amd
+        from srfrd_amd import trainer
         m, batch = _model(shape)
         m.train()
         _, _, L, B = SHAPES[shape]
-        tr = srfrd_amd.FusedTrainer(m, B, L, use_graph=False, **options)
+        with pytest.MonkeyPatch.context() as mp:
+            if sort_limit is not None:
+                mp.setattr(trainer, "SORT_CAPTURE_LIMIT", sort_limit)
+            tr = srfrd_amd.FusedTrainer(m, B, L, use_graph=False, **options)
+        assert len(tr._program) == (3 if sort_limit == 0 else 1)
         tr.step(None, *batch)
     return run
 
@@ -102,6 +111,10 @@ PATHS = {
     "step-l2-emb": _step("srfrn20", l2_emb=1e-3),
     "step-sampled-softmax": _step("sasrec50", loss="sampled_softmax", num_negatives=16),
     "step-max-grad-norm": _step("srfrn20", max_grad_norm=1.0),
+    "step-lazy-table": _step("sasrec50", lazy_table=True),
+    "step-softmax-deterministic": _step("sasrec50", loss="softmax", deterministic=True),
+    "step-deterministic-eager-sort": _step("sasrec50", sort_limit=0, deterministic=True),
+    "step-sampled-softmax-eager-sort": _step("sasrec50", sort_limit=0, loss="sampled_softmax", num_negatives=16),
     "predict": _rank("predict"),
     "topk-exclude-input": _rank("topk"),
     "target-rank": _rank("target_rank"),
@@ -141,6 +154,14 @@ EXPECTED = {
     "step-max-grad-norm": ("layout_init scratch_floats encoder_plan_train bwd_grid aux_floats encoder_plan bwd_grid packed_floats "
                            "pack_weights step_begin_sched check_ids pack_weights encoder_plan_train encoder_fwd_sched encoder_bwd_sched "
                            "reduce_dense grad_norm adamw_pack_step"),
+    # (lazy Adam's row kernel sits behind the slab reduction, ahead of the dense update)
+    "step-lazy-table": ("layout_init scratch_floats encoder_plan_train train_scratch_floats bwd_grid aux_floats encoder_plan "
+                        "sched_ints bwd_grid packed_floats pack_weights step_begin check_ids pack_weights encoder_plan_train "
+                        "encoder_train_ranked reduce_dense table_reduce_adam adam_pack_step"),
+    "step-softmax-deterministic": ("layout_init scratch_floats encoder_plan_train train_scratch_floats bwd_grid aux_floats encoder_plan "
+                                   "sched_ints bwd_grid xent_workspace_floats packed_floats pack_weights step_begin check_ids "
+                                   "pack_weights seq_order encoder_fwd_sched xent_fwd xent_bwd encoder_bwd_sched table_reduce "
+                                   "reduce_dense adam_pack_step loss_finalize"),
     "predict": ("layout_init check_ids packed_floats pack_weights scratch_floats encoder_fwd_last user_labels check_ids "
                 "predict_logits"),
     "topk-exclude-input": ("layout_init check_ids packed_floats pack_weights scratch_floats encoder_fwd_last user_labels "
@@ -152,6 +173,11 @@ EXPECTED = {
     "sharded-target-rank": ("layout_init check_ids packed_floats pack_weights scratch_floats encoder_fwd_last user_labels "
                             "excl_workspace_bytes target_rank excl_workspace_bytes target_rank"),
 }
+
+
+# a step cut at its key sort into three stages asks for what the one-stage step asks for
+EXPECTED["step-deterministic-eager-sort"] = EXPECTED["step-deterministic"]
+EXPECTED["step-sampled-softmax-eager-sort"] = EXPECTED["step-sampled-softmax"]
 
 
 def test_every_path_is_listed():

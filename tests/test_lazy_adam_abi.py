@@ -240,8 +240,8 @@ def test_step_program_keeps_its_results_and_adds_the_lazy_form():
     G, E, X = "graph", "eager", "collective"
     assert step_program("single") == step_program("single", False) == step_program("single", False, False) == \
         [(G, True, ("_enqueue_compute_update",))]
-    assert step_program("single", True) == [(G, True, ("_enqueue_ce_compute",)), (E, False, ("_sort_token_keys",)),
-                                            (G, False, ("_enqueue_token_table", "_enqueue_ce_dense", "_enqueue_update"))]
+    assert step_program("single", True) == [(G, True, ("_enqueue_ce_compute",)), (E, False, ("_sort_keys",)),
+                                            (G, False, ("_enqueue_table_reduce", "_enqueue_ce_dense", "_enqueue_update"))]
     assert step_program("allreduce") == [(G, True, ("_enqueue_compute",)), (X, False, ("_all_reduce_grad",)),
                                          (G, False, ("_enqueue_update",))]
     assert step_program("sharded") == [(G, True, ("_enqueue_fwd",)), (X, False, ("_start_stats_reduce",)), (G, True, ("_enqueue_bwd",)),

@@ -19,8 +19,8 @@ SHAPES = {
 # what one eager step on slot 1 calls, in order; per stage
 EAGER = {
     "single": [[("_enqueue_step_compute", 1), ("_enqueue_update",)]],
-    "token": [[("_enqueue_ce_compute", 1)], [("_sort_token_keys",)],
-              [("_enqueue_token_table",), ("_enqueue_ce_dense",), ("_enqueue_update",)]],
+    "token": [[("_enqueue_ce_compute", 1)], [("_sort_keys",)],
+              [("_enqueue_table_reduce",), ("_enqueue_ce_dense",), ("_enqueue_update",)]],
     "allreduce": [[("_enqueue_compute", 1)], [("ex.all_reduce", "grad")], [("_enqueue_update",)]],
     "sharded": [[("_enqueue_fwd", 1)], [("ex.all_reduce_stats", "stats")], [("_enqueue_bwd", 1)],
                 [("ex.reduce_scatter", "grad", "recv"), ("handle.wait",)], [("_enqueue_shard_update",)],
@@ -71,7 +71,7 @@ class _Trainer:
         self._program = step_program(*FORMS[form])
 
     def __getattr__(self, name):
-        if not (name.startswith("_enqueue_") or name == "_sort_token_keys"):
+        if not (name.startswith("_enqueue_") or name == "_sort_keys"):
             raise AttributeError(name)
         return lambda *args: self.log.append((name,) + args)
 
@@ -113,7 +113,7 @@ def test_local_walk_drops_the_collectives_and_keeps_the_sort(form):
     want = _flat(calls for calls, (kind, _) in zip(EAGER[form], SHAPES[form]) if kind != X)
     assert tr.log == want
     assert not any(c[0].startswith(("ex.", "handle.")) for c in tr.log)
-    assert (("_sort_token_keys",) in tr.log) == (form == "token")
+    assert (("_sort_keys",) in tr.log) == (form == "token")
 
 
 @pytest.mark.parametrize("form", FORMS)
