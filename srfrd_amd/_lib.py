@@ -1,5 +1,5 @@
 """ctypes binding of libsrfrd_hip.so (the C ABI declared in include/srfrd_hip.h and, the lazy-Adam entry point,
-include/srfrd_hip_lazy.h).
+include/srfrd_hip_lazy.h; the device key sort, include/srfrd_hip_sort.h).
 
 There is no CPU fallback: if the library is missing this module raises, and every op above it fails loudly.
 """
@@ -146,6 +146,12 @@ _LAZY_ABI = """
 i srfrd_table_reduce_adam(sorted_keys order table_contrib n:q d_item:i n_rows:q table m v beta1:d beta2:d eps:d state stats
     table_bf16 stream)
 """
+# The third table: what include/srfrd_hip_sort.h declares (tests/test_key_sort_abi.py holds it to that header; SORT_SIGNATURES and
+# SORT_PARAMS derive from it).  `query` / `call` consult it after the other two.
+_SORT_ABI = """
+q srfrd_sort_keys_workspace_bytes(n:q key_max:q)
+i srfrd_sort_keys(keys n:q key_max:q sorted_keys order workspace ws_bytes:q stream)
+"""
 
 
 def _parse(params):
@@ -163,11 +169,14 @@ PARAMS = {name: names for name, (_, _, names) in _PARSED.items()}               
 _LAZY_PARSED = _parse_abi(_LAZY_ABI)
 LAZY_SIGNATURES = {name: (res, types) for name, (res, types, _) in _LAZY_PARSED.items()}
 LAZY_PARAMS = {name: names for name, (_, _, names) in _LAZY_PARSED.items()}
+_SORT_PARSED = _parse_abi(_SORT_ABI)
+SORT_SIGNATURES = {name: (res, types) for name, (res, types, _) in _SORT_PARSED.items()}
+SORT_PARAMS = {name: names for name, (_, _, names) in _SORT_PARSED.items()}
 ENCODER_HEAD = _parse(_ENC_HEAD)[1]
 # name -> (its names as a set, the fetch of a dict's values in parameter order, the positions that hold a pointer)
 _MARSHAL = {name: (frozenset(names), operator.itemgetter(*names) if len(names) > 1 else (lambda a, n=names[0]: (a[n],)),
                    tuple(i for i, t in enumerate(types) if t not in (_i, _i64, _u32, _d)))
-            for name, (_, types, names) in {**_PARSED, **_LAZY_PARSED}.items()}
+            for name, (_, types, names) in {**_PARSED, **_LAZY_PARSED, **_SORT_PARSED}.items()}
 
 _lib = None
 
@@ -182,20 +191,29 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **LAZY_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **LAZY_SIGNATURES, **SORT_SIGNATURES}.items():
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
         _lib = handle
     return _lib
 
 
-def _lazy_entry(handle, name):
-    """entry point ``name`` of the second table on ``handle``.  A handle that was bound from SIGNATURES alone (another build of
-    the library, loaded beside the product's) gets the types here: an unbound ctypes function would take an address as a C int"""
+def _late_entry(handle, name, table):
+    """entry point ``name`` of ``table`` (the second or the third) on ``handle``.  A handle that was bound from SIGNATURES alone
+    (another build of the library, loaded beside the product's) gets the types here: an unbound ctypes function would take an
+    address as a C int"""
     fn = getattr(handle, name)
     if getattr(fn, "argtypes", ()) is None:          # (a ctypes function nobody has typed yet)
-        fn.restype, fn.argtypes = LAZY_SIGNATURES[name]
+        fn.restype, fn.argtypes = table[name]
     return fn
+
+
+def _lazy_entry(handle, name):
+    return _late_entry(handle, name, LAZY_SIGNATURES)
+
+
+def _sort_entry(handle, name):
+    return _late_entry(handle, name, SORT_SIGNATURES)
 
 
 def check(rc: int, what: str):
@@ -222,7 +240,7 @@ def dense_ptr(flat, n_table_pad):
 
 
 def query(name, /, **args):
-    """The C entry point ``name`` with its parameters BY NAME (PARAMS, then LAZY_PARAMS: the headers'; all of them, except that ``stream`` defaults
+    """The C entry point ``name`` with its parameters BY NAME (PARAMS, then LAZY_PARAMS, then SORT_PARAMS: the headers'; all of them, except that ``stream`` defaults
     to the current torch stream) -> its raw return value.  In a pointer's place a tensor passes its ``data_ptr()``, None is
     NULL, a ctypes structure goes by reference, anything else (an address as an int, a ctypes buffer) as it is.  A missing or
     unknown name raises TypeError before the library is touched; the function is looked up on the handle at every call."""
@@ -238,7 +256,9 @@ def query(name, /, **args):
             argv[i] = v.data_ptr()
         elif isinstance(v, C.Structure):
             argv[i] = C.byref(v)
-    return (getattr(lib(), name) if name in SIGNATURES else _lazy_entry(lib(), name))(*argv)
+    if name in SIGNATURES:
+        return getattr(lib(), name)(*argv)
+    return _late_entry(lib(), name, LAZY_SIGNATURES if name in LAZY_SIGNATURES else SORT_SIGNATURES)(*argv)
 
 
 def call(name, /, **args):

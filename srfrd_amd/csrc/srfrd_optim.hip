@@ -2,6 +2,8 @@
 // reference trainer.py:36-41, :390).  All streaming, HBM-bound, float4-wide.
 #include "srfrd_dev.h"
 #include "../../include/srfrd_hip_lazy.h"
+#include "../../include/srfrd_hip_sort.h"
+#include "srfrd_keysort.h"
 
 namespace srfrd {
 
@@ -565,6 +567,52 @@ extern "C" int srfrd_table_reduce_adam(const int64_t* sorted_keys, const int64_t
   hipLaunchKernelGGL(table_reduce_adam_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, sorted_keys, order,
                      table_contrib, n, d_item, n_rows, table, m, v, (float)beta1, (float)beta2, (float)eps, state, stats, table_bf16);
   return (int)hipGetLastError();
+}
+
+extern "C" int64_t srfrd_sort_keys_workspace_bytes(int64_t n, int64_t key_max) {
+  KeySortPlan p;
+  return keysort_plan(n, key_max, &p) ? p.bytes : 0;
+}
+
+extern "C" int srfrd_sort_keys(const int64_t* keys, int64_t n, int64_t key_max, int64_t* sorted_keys, int64_t* order,
+                               void* workspace, int64_t ws_bytes, void* stream) {
+  KeySortPlan p;
+  if (!keys || !sorted_keys || !order || !workspace || !keysort_plan(n, key_max, &p) || ws_bytes < p.bytes) return SRFRD_E_ARG;
+  if (((uintptr_t)workspace & 15) != 0 || sorted_keys == keys || order == keys || sorted_keys == order) return SRFRD_E_ARG;
+  if (n == 0) return 0;
+  char* ws = (char*)workspace;
+  uint32_t* dtot = (uint32_t*)ws;
+  uint32_t* hist = (uint32_t*)(ws + p.off_hist);
+  uint32_t* pair[2][2];
+  for (int b = 0; b < 2; ++b)
+    for (int a = 0; a < 2; ++a) pair[b][a] = (uint32_t*)(ws + p.off_pair[b][a]);
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 tiles(p.n_tiles), wg(256);
+  const uint32_t n32 = (uint32_t)n;
+  for (int pass = 0; pass < p.passes; ++pass) {
+    const bool first = pass == 0, last = pass == p.passes - 1;
+    const int shift = pass * p.digit_bits, bits = p.digit_bits;
+    uint32_t* const* in = pair[(pass + 1) & 1];          // pass 0 reads the keys; pass 1 reads pair 0, pass 2 pair 1, pass 3 pair 0
+    uint32_t* const* out = pair[pass & 1];
+    if (first)
+      hipLaunchKernelGGL(keysort_count_kernel<true>, tiles, wg, 0, st, keys, key_max, (const uint32_t*)nullptr, n32, shift, bits,
+                         hist, p.n_tiles);
+    else
+      hipLaunchKernelGGL(keysort_count_kernel<false>, tiles, wg, 0, st, keys, key_max, (const uint32_t*)in[0], n32, shift, bits,
+                         hist, p.n_tiles);
+    hipLaunchKernelGGL(keysort_rows_kernel, dim3(kSortRadix), wg, 0, st, hist, p.n_tiles, dtot);
+    with_flag(first, [&](auto f) {
+      return with_flag(last, [&](auto l) {
+        hipLaunchKernelGGL((keysort_scatter_kernel<decltype(f)::value, decltype(l)::value>), tiles, wg, 0, st, keys, key_max,
+                           (const uint32_t*)in[0], (const uint32_t*)in[1], n32, shift, bits, (const uint32_t*)hist,
+                           (const uint32_t*)dtot, p.n_tiles, out[0], out[1], sorted_keys, order);
+        return 0;
+      });
+    });
+    const int rc = (int)hipGetLastError();
+    if (rc != 0) return rc;
+  }
+  return 0;
 }
 
 extern "C" int srfrd_loss_stats(const float* loss_part, int B, float* stats, float* loss_out, void* stream) {

@@ -61,11 +61,17 @@ def sort_key_count(loss: str, deterministic: bool, lazy: bool, B: int, L: int, K
     return 3 * T if deterministic or lazy else 0      # BCE: the positive, negative and input ids
 
 
-def sort_plan(mode: str, n_keys: int, use_graph: bool = True):
+KEY_SORTS = ("torch", "device")
+
+
+def sort_plan(mode: str, n_keys: int, use_graph: bool = True, device_sort: bool = False):
     """THE decision where a step's key sort runs, from the length of its list: -> (eager_sort, use_graph, reason).  Up to
     SORT_CAPTURE_LIMIT keys the sort is captured with the step.  A longer list on a single rank: ``eager_sort``, step_program's
     two graphs around the sort.  The exchange programs have no such form: there the step runs without graphs, and ``reason``
-    (FusedTrainer.graph_capture_error) says so."""
+    (FusedTrainer.graph_capture_error) says so.  ``device_sort`` (``key_sort="device"``: srfrd_sort_keys, kernel launches and
+    nothing else - DESIGN section 24): captured at every length, in every mode."""
+    if device_sort:
+        return False, use_graph, None
     if n_keys <= SORT_CAPTURE_LIMIT or mode == "single":
         return n_keys > SORT_CAPTURE_LIMIT, use_graph, None
     reason = (f"a sort of {n_keys} keys (more than {SORT_CAPTURE_LIMIT}) is not captured, and the {mode!r} exchange program has no "
@@ -73,18 +79,24 @@ def sort_plan(mode: str, n_keys: int, use_graph: bool = True):
     return False, False, reason if use_graph else None
 
 
-def step_program(mode: str, token: bool = False, lazy: bool = False, eager_sort: bool = False):
+def step_program(mode: str, token: bool = False, lazy: bool = False, eager_sort: bool = False, device_sort: bool = False):
     """THE order of a train step under exchange ``mode`` ("single" | "allreduce" | "sharded"; ``token``: a loss with K negatives
     per position; ``lazy``: ``lazy_table``, single rank and BCE only; ``eager_sort``: single rank, a key list too long to sort
-    inside a graph - sort_plan): FusedTrainer's eager step, graph capture, replay and
+    inside a graph - sort_plan; ``device_sort``: the key sort is srfrd_sort_keys, captured wherever it stands - the token step
+    is then ONE stage, every other program its form without an eager sort): FusedTrainer's eager step, graph capture, replay and
     spin_up all walk this list of stages (kind, per_slot,
-    calls) - FusedTrainer methods called in order, with the input slot where per_slot.  "graph": they only enqueue stream work,
+    calls) - FusedTrainer methods called in order, with the input slot where per_slot (the pieces of SLOT_FREE, which read no
+    input slot: without it).  "graph": they only enqueue stream work,
     so the stage is captured (per slot where per_slot: the kernels' id pointers are baked in).  "eager" / "collective": a host
     action between two graphs - the key sort of a token step (at every size) or of a long list / the
     exchange."""
     G, E, X = "graph", "eager", "collective"
     if lazy and (mode != "single" or token):
         raise ValueError("lazy_table steps on a single rank under loss='bce'")
+    if device_sort and eager_sort:
+        raise ValueError("eager_sort and device_sort exclude each other: the device sort is captured at every length")
+    if mode == "single" and token and device_sort:
+        return [(G, True, ("_enqueue_ce_compute", "_sort_keys", "_enqueue_table_reduce", "_enqueue_ce_dense", "_enqueue_update"))]
     if mode == "single" and token:
         return [(G, True, ("_enqueue_ce_compute",)), (E, False, ("_sort_keys",)),
                 (G, False, ("_enqueue_table_reduce", "_enqueue_ce_dense", "_enqueue_update"))]
@@ -104,6 +116,9 @@ def step_program(mode: str, token: bool = False, lazy: bool = False, eager_sort:
             (X, False, ("_scatter_grad",)), (G, False, ("_enqueue_shard_update",)), (X, False, ("_gather_params",)),
             (G, False, ("_enqueue_shard_finish",))]
 
+
+# the pieces that read no input slot: a per-slot stage calls them without one (the token step's one stage under the device sort)
+SLOT_FREE = frozenset(("_sort_keys", "_enqueue_table_reduce", "_enqueue_ce_dense", "_enqueue_update"))
 
 # RCCL collectives are stream work: the whole data-parallel step, collectives included, as one graph per slot
 ONE_GRAPH = [("graph", True, ("_enqueue_step",))]
@@ -252,7 +267,7 @@ class FusedTrainer:
                  logq_correction: bool = True, remove_accidental_hits: bool = True, gbce_beta: float = 1.0,
                  weight_decay: float = 0.0, max_grad_norm: float | None = None, lr_schedule: str = "constant",
                  warmup_steps: int = 0, total_steps: int | None = None, final_lr_ratio: float = 0.0,
-                 lazy_table: bool = False):
+                 lazy_table: bool = False, key_sort: str = "torch"):
         """``shadow_gather`` (sharded exchange over a bf16 item-table shadow, ``model.use_bf16_table()``; SURVEY 8e's alternative
         for BASELINE configs[4]): the fp32 master of an item row and its Adam moments live on the OWNER rank only; after the
         sharded Adam step the all-gather carries the bf16 SHADOW of the table (2 bytes per element: 90 MB instead of 180 MB at
@@ -289,7 +304,14 @@ class FusedTrainer:
         after the first step the parameters differ from the dense trainer's.  The table's share of the step then costs in
         proportion to the batch, not the catalog.  Implies ``deterministic``; single rank, ``loss="bce"``, no ``l2_emb`` /
         ``weight_decay`` / ``max_grad_norm`` / ``shadow_gather`` (``lr_schedule`` / ``warmup_steps`` are fine).  The state
-        format is the dense trainer's: checkpoints move between the two."""
+        format is the dense trainer's: checkpoints move between the two.
+        ``key_sort``: who sorts a sorted step's key list - "torch" (rocprim through torch: a list over 2^20
+        keys is sorted eagerly between two graphs, and the token step's always) or "device" (``srfrd_sort_keys``: 2 or 3 radix
+        passes over the bits an item id has, kernel launches only, so the whole step - the token step too - is one graph at
+        every length).  A stable sort has one correct output: parameters, moments and loss are the same bits under both, and
+        the option is no part of ``state_dict()``.  A trainer that sorts nothing ignores it."""
+        if key_sort not in KEY_SORTS:
+            raise ValueError(f"key_sort must be one of {KEY_SORTS} (got {key_sort!r})")
         self.lazy_table = _lazy_config(lazy_table, loss, process_group, shadow_gather, l2_emb, weight_decay, max_grad_norm)
         self.opts, self.max_norm = _optim_config(lr, betas, weight_decay, max_grad_norm, lr_schedule, warmup_steps, total_steps,
                                                  final_lr_ratio, process_group)
@@ -378,6 +400,14 @@ class FusedTrainer:
         self.keys = torch.zeros(self.n_keys, device=dev, dtype=torch.int64) if self.n_keys else None
         self.skeys, self.order = (torch.zeros_like(self.keys), torch.zeros_like(self.keys)) if self.n_keys else (None, None)
         self.key_rows = self.contrib
+        # key_sort="device": the workspace of srfrd_sort_keys for this list and this table (None: torch sorts, or nothing is sorted)
+        self.key_sort = key_sort
+        self.sort_ws = None
+        if key_sort == "device" and self.n_keys:
+            n_ws = int(query("srfrd_sort_keys_workspace_bytes", n=self.n_keys, key_max=lay.n_items))
+            if n_ws <= 0:
+                raise ValueError(f"key_sort='device': srfrd_sort_keys refuses {self.n_keys} keys of a table of {lay.n_items} items")
+            self.sort_ws = torch.empty(n_ws, device=dev, dtype=torch.uint8)
         self.n_slabs = query("srfrd_bwd_grid", lay=lay, B=B, L=L)
         self.slabs = torch.empty(self.n_slabs, lay.n_dense, **f32)
         # Input ring: `slots` resident (6, B, L) id buffers.  A producer (DeviceSampler, a loader thread's H2D copy)
@@ -415,8 +445,9 @@ class FusedTrainer:
         self.packed = model.pack_weights()
         self._step_begin()
         # (a key list too long to sort inside a graph: two graphs around the sort; data parallel: no graphs, and why)
-        eager_sort, self.use_graph, self.graph_capture_error = sort_plan(self.mode, self.n_keys, bool(use_graph))
-        self._program = step_program(self.mode, self.token, self.lazy_table, eager_sort)
+        device_sort = self.sort_ws is not None
+        eager_sort, self.use_graph, self.graph_capture_error = sort_plan(self.mode, self.n_keys, bool(use_graph), device_sort)
+        self._program = step_program(self.mode, self.token, self.lazy_table, eager_sort, device_sort)
         self._graphs = None              # (stages, their graphs) once captured: `captured`
         self._stats_handle = None        # sharded form: the statistics all-reduce in flight between two eager stages
         self.graph_form = None           # "one" | "split" once captured (one graph per step, or graphs around the eager stages)
@@ -606,7 +637,14 @@ class FusedTrainer:
     def _sort_keys(self):
         """THE stable sort of the step's key list, into its persistent buffers.  Captured with the step up to
         SORT_CAPTURE_LIMIT keys; a longer list (and the token step's, always) is sorted eagerly, between the step's two graphs -
-        checked here on the host, ahead of the sort: a mistake in a program costs an error, not a machine"""
+        checked here on the host, ahead of the sort: a mistake in a program costs an error, not a machine.
+        ``key_sort="device"`` (a trainer with `sort_ws`): srfrd_sort_keys instead - the same bits from kernel launches alone,
+        captured wherever the program puts it"""
+        sort_ws = getattr(self, "sort_ws", None)
+        if sort_ws is not None:
+            call("srfrd_sort_keys", keys=self.keys, n=self.keys.numel(), key_max=self.lay.n_items, sorted_keys=self.skeys,
+                 order=self.order, workspace=sort_ws, ws_bytes=sort_ws.numel())
+            return
         if self.keys.numel() > SORT_CAPTURE_LIMIT and torch.cuda.is_current_stream_capturing():
             raise RuntimeError(f"a sort of {self.keys.numel()} keys (more than {SORT_CAPTURE_LIMIT}) must not be captured: "
                                "its memset nodes do not replay reliably (DESIGN section 18)")
@@ -833,7 +871,7 @@ class FusedTrainer:
                 gs[slot if per_slot else 0].replay()
             elif not (local and kind == "collective"):
                 for name in calls:
-                    getattr(self, name)(*((slot,) if per_slot else ()))
+                    getattr(self, name)(*((slot,) if per_slot and name not in SLOT_FREE else ()))
 
     def _enqueue_step(self, slot: int = 0, local: bool = False):
         """the whole step on the current stream: the eager step, and (data parallel over RCCL, whose collectives are stream
