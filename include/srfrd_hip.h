@@ -563,7 +563,11 @@ int srfrd_rank_plan(const srfrd_layout* lay, int op, int B, int k, int64_t item_
                     int n_cu, int max_launches, char* names, int name_len, int32_t* geom);
 
 /* HR@10 / NDCG@10 inputs (reference utils.py:589-597): rank[b] = #{i >= 1 : logits[b][i] > logits[b][0]};
- * metric_acc[0] += [rank<10] / log2(rank+2), metric_acc[1] += [rank<10], metric_acc[2] += 1 (double[3]). */
+ * metric_acc[0] += [rank<10] / log2(rank+2), metric_acc[1] += [rank<10], metric_acc[2] += 1 (double[3]).
+ * The compare is IEEE on the float32 values (a denormal is greater than 0; +0 and -0 tie).  NaN: a NaN target
+ * (logits[b][0]) counts every other candidate, rank n_cand - 1, which is where the reference's argsort puts it - a model
+ * that has diverged to NaN scores reads as a miss, not as rank 0; a NaN competitor of a finite target is not counted.
+ * rank and metric_acc may each be NULL. */
 int srfrd_eval_rank(const float* logits, int B, int n_cand, int32_t* rank, double* metric_acc, void* stream);
 
 /*
@@ -762,6 +766,9 @@ int srfrd_token_negatives(const int64_t* user_ptr, const int32_t* items, int use
  * user_ptr int64 (usernum + 2), items / reviews int32.  out_packed int64 (6, B, L) = [seq, rsq, pos, prs, neg, nrs].
  * Randomness: counter hash of (seed, batch_index, row, position, try) - reproducible, unlike the reference's
  * unseeded worker processes (utils.py:79).
+ * A row draws at most 4096 users: when none of them has more than one interaction the row comes out all-pad (0 in all six
+ * planes) and out_user names the last user drawn.  A negative draws at most 256 candidates: when every one is among the
+ * user's items (a user who holds the whole catalog) the negative is the last candidate, a history item.
  */
 int srfrd_sample_batch(const int64_t* user_ptr, const int32_t* items, const int32_t* reviews, int usernum, int itemnum,
                        int B, int L, uint32_t seed, uint32_t batch_index, int64_t* out_user, int64_t* out_packed,

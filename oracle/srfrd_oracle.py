@@ -373,8 +373,10 @@ def train_step(cfg: Cfg, sd, opt: Adam, batch, train=True, seed=0, b0=0, l2_emb=
 # ----------------------------------------------------------------------------------------------
 def rank_of_first(logits: torch.Tensor) -> torch.Tensor:
     """rank of candidate 0 among (U, C) logits: number of candidates scoring strictly higher
-    (== ``(-logits).argsort().argsort()[0]`` when there are no exact ties)."""
-    return (logits[:, 1:] > logits[:, :1]).sum(dim=1)
+    (== ``(-logits).argsort().argsort()[0]`` when there are no exact ties).  A NaN target counts every other candidate
+    (rank C - 1: the reference's argsort puts NaN last); a NaN competitor of a finite target is not counted."""
+    x0 = logits[:, :1]
+    return ((logits[:, 1:] > x0) | (x0 != x0)).sum(dim=1)
 
 
 def hr_ndcg_at_10(ranks: torch.Tensor):

@@ -1213,7 +1213,8 @@ __global__ void __launch_bounds__(256) topk_merge_kernel(const int64_t* __restri
 }
 
 // ---------------------------------------------------------------------------------------------
-// rank of candidate 0 (strictly-greater count) + HR@10 / NDCG@10 accumulation (fp64, as the host loop does)
+// rank of candidate 0 (strictly-greater count; a NaN target counts every other candidate) + HR@10 / NDCG@10 accumulation
+// (fp64, as the host loop does)
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) eval_rank_kernel(const float* __restrict__ logits, int B, int n_cand,
                                                        int32_t* __restrict__ rank, double* __restrict__ metric_acc) {
@@ -1223,7 +1224,7 @@ __global__ void __launch_bounds__(256) eval_rank_kernel(const float* __restrict_
   const float* row = logits + (int64_t)b * n_cand;
   const float x0 = row[0];
   int cnt = 0;
-  for (int j = 1 + lane; j < n_cand; j += 64) cnt += row[j] > x0;
+  for (int j = 1 + lane; j < n_cand; j += 64) cnt += (row[j] > x0) || (x0 != x0);      // (a NaN target ranks last)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
   if (lane == 0) {

@@ -4,6 +4,9 @@ whole batch of users per launch instead of one user (and one host sync) at a tim
 For each user: candidates = [held-out next item] + 100 sampled negatives, scores = predict(...), rank = position of
 the held-out item = number of candidates scoring strictly higher (``argsort().argsort()[0]`` in the reference),
 HR@10 += rank < 10, NDCG@10 += 1 / log2(rank + 2).
+
+NaN: a held-out item whose score is NaN ranks last (rank = n_cand - 1, where the reference's argsort puts it), so a model
+that has diverged to NaN weights reports misses, not HR@10 = NDCG@10 = 1; a NaN score of another candidate is not counted.
 """
 from __future__ import annotations
 
@@ -14,7 +17,8 @@ from ._lib import call
 
 
 def ranks_from_logits(logits: torch.Tensor, metric_acc: torch.Tensor | None = None) -> torch.Tensor:
-    """rank of candidate 0 per row of (B, n_cand) logits; optionally accumulates [ndcg_sum, hit_sum, users] (fp64)."""
+    """rank of candidate 0 per row of (B, n_cand) logits; optionally accumulates [ndcg_sum, hit_sum, users] (fp64).
+    A NaN logit of candidate 0 gives rank n_cand - 1."""
     if logits.device.type != "cuda":
         raise RuntimeError("ranks_from_logits runs on the ROCm GPU only")
     if metric_acc is None:

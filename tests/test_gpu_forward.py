@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import srfrd_oracle as O
+from tests.data_path_refs import _decile_rows
 from tests.helpers import GOLDEN, KINDS, golden_cfg, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -115,17 +116,6 @@ def test_eval_rank_and_metric():
     ndcg, hr = O.hr_ndcg_at_10(ro)
     a = acc.cpu()
     assert abs(float(a[0] / a[2]) - ndcg) < 1e-12 and abs(float(a[1] / a[2]) - hr) < 1e-12
-
-
-def _decile_rows(L):
-    """fake/real windows whose fake ratio sits exactly on a decile boundary (n1 / tot = k / 10), plus their neighbours:
-    the cases where a division lowered to x * rcp(y) lands one ulp under the integer and the floor drops by one."""
-    rows = []
-    for tot in range(1, L + 1):
-        for n1 in range(0, tot + 1):
-            if (10 * n1) % tot == 0 or (10 * n1 + 10) % tot == 0:
-                rows.append([0] * (L - tot) + [1] * n1 + [2] * (tot - n1))
-    return torch.tensor(rows, dtype=torch.int64)
 
 
 def test_user_labels_inside_the_encoder_match_get_labels():
