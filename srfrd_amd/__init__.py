@@ -3,6 +3,7 @@
 Drop-in module classes (same constructors / forward / predict / state_dict as the reference's SRFR_model.py), a fused
 train step, batched evaluation and a synthetic sampler, all on top of the C ABI in include/srfrd_hip.h.
 """
+from ._lib import TOPK_WIDE_MAX  # noqa: F401
 from .modules import SASRec, SRFR, SRFRN, SRFU, SRFU_B, SRFU_F, SRFU_R  # noqa: F401
 from .trainer import FusedTrainer, flat_allreduce, shard_bounds, lr_at  # noqa: F401
 from .evaluate import evaluate_batches, ranks_from_logits  # noqa: F401
@@ -19,4 +20,4 @@ __all__ = ["SASRec", "SRFR", "SRFRN", "SRFU", "SRFU_B", "SRFU_F", "SRFU_R", "Fus
            "shard_bounds", "evaluate_batches", "ranks_from_logits", "synthetic_batch", "eval_candidates", "InteractionData",
            "partition", "load_csv", "eval_inputs", "evaluation", "DeviceSampler", "load_reference_checkpoint", "ShardedRanker",
            "row_shards", "topk_merge", "GradExchange", "Adam", "AdamW", "lr_at", "sample_negatives", "sample_token_negatives", "gbce_beta",
-           "history_log_keep", "sort_keys"]
+           "history_log_keep", "sort_keys", "TOPK_WIDE_MAX"]

@@ -1,5 +1,5 @@
 """ctypes binding of libsrfrd_hip.so (the C ABI declared in include/srfrd_hip.h and, the lazy-Adam entry point,
-include/srfrd_hip_lazy.h; the device key sort, include/srfrd_hip_sort.h).
+include/srfrd_hip_lazy.h; the device key sort, include/srfrd_hip_sort.h; the wide top-k, include/srfrd_hip_topk_wide.h).
 
 There is no CPU fallback: if the library is missing this module raises, and every op above it fails loudly.
 """
@@ -19,6 +19,7 @@ MAX_BLOCKS = 8
 MAX_D = 64
 LAYOUT_MASK_PAD_KEYS = 1        # SRFRD_LAYOUT_MASK_PAD_KEYS: srfrd_layout.flags, the leading pads leave the attention keys
 EXCL_CAP = 4096                 # SRFRD_EXCL_CAP: most ids one row of an exclusion set may hold
+TOPK_WIDE_MAX = 1024            # SRFRD_TOPK_WIDE_MAX: largest k of srfrd_logits_topk_wide (include/srfrd_hip_topk_wide.h)
 KINDS = {"SASRec": 0, "SRFR": 1, "SRFRN": 2, "SRFU_B": 3, "SRFU_F": 4, "SRFU_R": 5}
 _ERR = {-1: "SRFRD_E_ARG (bad argument)", -2: "SRFRD_E_UNSUPPORTED (configuration outside the fused kernels: "
         "hidden width > 64, hidden width not divisible by num_heads, a debug tap of a kernel without taps, or a caller-provided "
@@ -152,6 +153,14 @@ _SORT_ABI = """
 q srfrd_sort_keys_workspace_bytes(n:q key_max:q)
 i srfrd_sort_keys(keys n:q key_max:q sorted_keys order workspace ws_bytes:q stream)
 """
+# The fourth table: what include/srfrd_hip_topk_wide.h declares (tests/test_topk_wide_abi.py holds it to that header;
+# WIDE_SIGNATURES and WIDE_PARAMS derive from it).  `query` / `call` consult it after the other three.
+_WIDE_ABI = """
+i srfrd_topk_wide_plan(lay:lay B:i k:i item_lo:q item_hi:q excl:i switches:i n_cu:i max_launches:i names name_len:i geom sizes)
+q srfrd_topk_wide_workspace_bytes(B:i k:i n_rows:q)
+i srfrd_logits_topk_wide(lay:lay item_table dense hidden B:i L:i item_lo:q item_hi:q exclude_pad:i user_label k:i excl_ptr
+    excl_items max_row:i topk_idx topk_val workspace ws_bytes:q excl_workspace stream)
+"""
 
 
 def _parse(params):
@@ -172,11 +181,14 @@ LAZY_PARAMS = {name: names for name, (_, _, names) in _LAZY_PARSED.items()}
 _SORT_PARSED = _parse_abi(_SORT_ABI)
 SORT_SIGNATURES = {name: (res, types) for name, (res, types, _) in _SORT_PARSED.items()}
 SORT_PARAMS = {name: names for name, (_, _, names) in _SORT_PARSED.items()}
+_WIDE_PARSED = _parse_abi(_WIDE_ABI)
+WIDE_SIGNATURES = {name: (res, types) for name, (res, types, _) in _WIDE_PARSED.items()}
+WIDE_PARAMS = {name: names for name, (_, _, names) in _WIDE_PARSED.items()}
 ENCODER_HEAD = _parse(_ENC_HEAD)[1]
 # name -> (its names as a set, the fetch of a dict's values in parameter order, the positions that hold a pointer)
 _MARSHAL = {name: (frozenset(names), operator.itemgetter(*names) if len(names) > 1 else (lambda a, n=names[0]: (a[n],)),
                    tuple(i for i, t in enumerate(types) if t not in (_i, _i64, _u32, _d)))
-            for name, (_, types, names) in {**_PARSED, **_LAZY_PARSED, **_SORT_PARSED}.items()}
+            for name, (_, types, names) in {**_PARSED, **_LAZY_PARSED, **_SORT_PARSED, **_WIDE_PARSED}.items()}
 
 _lib = None
 
@@ -191,7 +203,7 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **LAZY_SIGNATURES, **SORT_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **LAZY_SIGNATURES, **SORT_SIGNATURES, **WIDE_SIGNATURES}.items():
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
         _lib = handle
@@ -199,7 +211,7 @@ def lib():
 
 
 def _late_entry(handle, name, table):
-    """entry point ``name`` of ``table`` (the second or the third) on ``handle``.  A handle that was bound from SIGNATURES alone
+    """entry point ``name`` of ``table`` (the second, third or fourth) on ``handle``.  A handle that was bound from SIGNATURES alone
     (another build of the library, loaded beside the product's) gets the types here: an unbound ctypes function would take an
     address as a C int"""
     fn = getattr(handle, name)
@@ -214,6 +226,10 @@ def _lazy_entry(handle, name):
 
 def _sort_entry(handle, name):
     return _late_entry(handle, name, SORT_SIGNATURES)
+
+
+def _wide_entry(handle, name):
+    return _late_entry(handle, name, WIDE_SIGNATURES)
 
 
 def check(rc: int, what: str):
@@ -240,7 +256,7 @@ def dense_ptr(flat, n_table_pad):
 
 
 def query(name, /, **args):
-    """The C entry point ``name`` with its parameters BY NAME (PARAMS, then LAZY_PARAMS, then SORT_PARAMS: the headers'; all of them, except that ``stream`` defaults
+    """The C entry point ``name`` with its parameters BY NAME (PARAMS, then LAZY_PARAMS, SORT_PARAMS and WIDE_PARAMS: the headers'; all of them, except that ``stream`` defaults
     to the current torch stream) -> its raw return value.  In a pointer's place a tensor passes its ``data_ptr()``, None is
     NULL, a ctypes structure goes by reference, anything else (an address as an int, a ctypes buffer) as it is.  A missing or
     unknown name raises TypeError before the library is touched; the function is looked up on the handle at every call."""
@@ -258,7 +274,8 @@ def query(name, /, **args):
             argv[i] = C.byref(v)
     if name in SIGNATURES:
         return getattr(lib(), name)(*argv)
-    return _late_entry(lib(), name, LAZY_SIGNATURES if name in LAZY_SIGNATURES else SORT_SIGNATURES)(*argv)
+    table = LAZY_SIGNATURES if name in LAZY_SIGNATURES else SORT_SIGNATURES if name in SORT_SIGNATURES else WIDE_SIGNATURES
+    return _late_entry(lib(), name, table)(*argv)
 
 
 def call(name, /, **args):
@@ -348,3 +365,21 @@ def rank_plan(lay: Layout, op: int, B: int, k: int, item_lo: int, item_hi: int, 
         return rc
     return [(names.raw[i * w:(i + 1) * w].split(b"\0")[0].decode(), geom[3 * i], geom[3 * i + 1], geom[3 * i + 2])
             for i in range(rc)]
+
+
+# paths of a wide top-k plan (SRFRD_WIDE_*)
+WIDE_FINE, WIDE_CHUNK, WIDE_ALL = 0, 1, 2
+
+
+def topk_wide_plan(lay: Layout, B: int, k: int, item_lo: int, item_hi: int, excl: bool = False, switches: int = 0,
+                   n_cu: int = 256):
+    """srfrd_topk_wide_plan (no GPU needed) -> ([(kernel, workgroups, threads, dynamic LDS bytes)] in launch order,
+    (path, candidate capacity per user, group maxima per user)), or the negative code the call refuses with."""
+    n, w = 8, 96
+    names, geom, sizes = C.create_string_buffer(n * w), (C.c_int32 * (3 * n))(), (C.c_int32 * 3)()
+    rc = query("srfrd_topk_wide_plan", lay=lay, B=B, k=k, item_lo=item_lo, item_hi=item_hi, excl=int(excl), switches=switches,
+               n_cu=n_cu, max_launches=n, names=names, name_len=w, geom=geom, sizes=sizes)
+    if rc < 0:
+        return rc
+    return ([(names.raw[i * w:(i + 1) * w].split(b"\0")[0].decode(), geom[3 * i], geom[3 * i + 1], geom[3 * i + 2])
+             for i in range(rc)], tuple(sizes))

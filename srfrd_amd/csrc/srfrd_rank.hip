@@ -1588,6 +1588,9 @@ extern "C" int srfrd_target_rank(const srfrd_layout* lay, const void* item_table
   return run_plan(p, a, io, (hipStream_t)stream);
 }
 
+// k up to SRFRD_TOPK_WIDE_MAX: new kernels over the stream templates above, their plan and srfrd_logits_topk_wide
+#include "srfrd_rank_wide.h"
+
 extern "C" int srfrd_topk_merge(const int64_t* cand_idx, const float* cand_val, int B, int n_cand, int k, int64_t* topk_idx,
                                 float* topk_val, void* stream) {
   if (!cand_idx || !cand_val || !topk_idx || !topk_val || B <= 0 || n_cand <= 0 || k <= 0 || n_cand > 4096) return SRFRD_E_ARG;

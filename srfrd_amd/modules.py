@@ -651,9 +651,15 @@ class _SRFRDBase(nn.Module):
     def topk(self, user_ids, input_ids, fake_ids, k=10, exclude_pad=True, item_range=None, exclude=None):
         """Full-catalog ranking: (indices int64 (B,k), scores (B,k)); the (B, I) logits never reach HBM.
         ``exclude``: items never to return, per user - None, "input" (the ids of the user's input window), a (ptr, items)
-        CSR tuple over the batch, or a list of B 1-D tensors.  Fewer than k rankable items leave trailing -1 / -inf slots."""
+        CSR tuple over the batch, or a list of B 1-D tensors.  Fewer than k rankable items leave trailing -1 / -inf slots.
+        k <= 64 takes the threshold ranking built for evaluation; 64 < k <= srfrd_amd.TOPK_WIDE_MAX the wide one (the same
+        scores and order law)."""
+        if not 1 <= k <= _lib.TOPK_WIDE_MAX:
+            raise ValueError(f"topk: k = {k} is outside 1..srfrd_amd.TOPK_WIDE_MAX ({_lib.TOPK_WIDE_MAX})")
         hidden, ulab, excl = self._rank_inputs(input_ids, fake_ids, exclude)
         lo, hi = item_range if item_range is not None else (0, self.layout.n_items + 1)
+        if k > 64:
+            return tuple(torch.ops.srfrd.logits_topk_wide(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad), *excl))
         if exclude is None:
             return tuple(torch.ops.srfrd.logits_topk(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad)))
         return tuple(torch.ops.srfrd.logits_topk_excl(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad), *excl))

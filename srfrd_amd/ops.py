@@ -12,6 +12,7 @@ autograd function and FusedTrainer), and their fakes and autograd are registered
     srfrd::predict_logits  candidate logits of predict() (SRFR_model.py:144-152 and twins)
     srfrd::logits_topk     full-catalog top-k over an item range, logits never in HBM
     srfrd::logits_topk_excl  the same with a per-user exclusion set (CSR over the batch) masked inside the ranking passes
+    srfrd::logits_topk_wide  exact top-k for k up to 1024 (TOPK_WIDE_MAX), exclusion set optional
     srfrd::target_rank     full-catalog rank of a target item per user (strictly-greater count), exclusion set optional
     srfrd::topk_merge      merge of per-shard top-k lists
     srfrd::user_labels     get_Labels (SRFR_model.py:546-570)
@@ -251,7 +252,23 @@ def logits_topk_excl(hidden: torch.Tensor, user_label: Optional[torch.Tensor], m
     return [idx, val]
 
 
-for _op in (logits_topk, logits_topk_excl):
+@torch.library.custom_op("srfrd::logits_topk_wide", mutates_args=(), device_types="cuda")
+def logits_topk_wide(hidden: torch.Tensor, user_label: Optional[torch.Tensor], model_key: int, item_lo: int, item_hi: int, k: int,
+                     exclude_pad: bool, excl_ptr: Optional[torch.Tensor], excl_items: Optional[torch.Tensor],
+                     max_row: int) -> List[torch.Tensor]:
+    """srfrd_logits_topk_wide: 1 <= k <= _lib.TOPK_WIDE_MAX; ``excl_ptr`` None: no exclusion sets"""
+    n_rows = item_hi - item_lo
+    _, xws = _rank_workspaces(hidden, None, n_rows, max_row if excl_ptr is not None else None)
+    n = query("srfrd_topk_wide_workspace_bytes", B=hidden.shape[0], k=k, n_rows=n_rows)
+    ws = torch.empty(max(n, 8), device=hidden.device, dtype=torch.uint8)
+    idx, val = _topk_out(hidden, k)
+    call("srfrd_logits_topk_wide", **rank_head(_model(model_key), hidden, user_label, item_range=(item_lo, item_hi),
+                                                exclude_pad=exclude_pad, excl=(excl_ptr, excl_items, max_row)),
+         k=k, topk_idx=idx, topk_val=val, workspace=ws, ws_bytes=n, excl_workspace=xws)
+    return [idx, val]
+
+
+for _op in (logits_topk, logits_topk_excl, logits_topk_wide):
     _op.register_fake(lambda hidden, user_label, model_key, item_lo, item_hi, k, *rest: _topk_out(hidden, k))
 
 
@@ -400,5 +417,5 @@ _register_head(sxent_fwd, sxent_bwd, 4)
 _register_head(tneg_fwd, tneg_bwd, 4)
 
 
-OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "target_rank", "topk_merge",
+OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "logits_topk_wide", "target_rank", "topk_merge",
        "eval_rank", "xent_fwd", "xent_bwd", "sxent_fwd", "sxent_bwd", "tneg_fwd", "tneg_bwd")
