@@ -13,6 +13,7 @@ from .ranker import ShardedRanker, row_shards, topk_merge  # noqa: F401
 from .exchange import GradExchange  # noqa: F401
 from .optim import Adam, AdamW  # noqa: F401
 from .keysort import sort_keys  # noqa: F401
+from .filters import ItemFilter  # noqa: F401
 from .dataset import (InteractionData, partition, load_csv, eval_inputs, evaluation, DeviceSampler,  # noqa: F401
                       load_reference_checkpoint)
 
@@ -20,4 +21,4 @@ __all__ = ["SASRec", "SRFR", "SRFRN", "SRFU", "SRFU_B", "SRFU_F", "SRFU_R", "Fus
            "shard_bounds", "evaluate_batches", "ranks_from_logits", "synthetic_batch", "eval_candidates", "InteractionData",
            "partition", "load_csv", "eval_inputs", "evaluation", "DeviceSampler", "load_reference_checkpoint", "ShardedRanker",
            "row_shards", "topk_merge", "GradExchange", "Adam", "AdamW", "lr_at", "sample_negatives", "sample_token_negatives", "gbce_beta",
-           "history_log_keep", "sort_keys", "TOPK_WIDE_MAX"]
+           "history_log_keep", "sort_keys", "TOPK_WIDE_MAX", "ItemFilter"]

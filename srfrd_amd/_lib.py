@@ -1,5 +1,6 @@
 """ctypes binding of libsrfrd_hip.so (the C ABI declared in include/srfrd_hip.h and, the lazy-Adam entry point,
-include/srfrd_hip_lazy.h; the device key sort, include/srfrd_hip_sort.h; the wide top-k, include/srfrd_hip_topk_wide.h).
+include/srfrd_hip_lazy.h; the device key sort, include/srfrd_hip_sort.h; the wide top-k, include/srfrd_hip_topk_wide.h; the
+item filters, include/srfrd_hip_filter.h).
 
 There is no CPU fallback: if the library is missing this module raises, and every op above it fails loudly.
 """
@@ -161,6 +162,19 @@ q srfrd_topk_wide_workspace_bytes(B:i k:i n_rows:q)
 i srfrd_logits_topk_wide(lay:lay item_table dense hidden B:i L:i item_lo:q item_hi:q exclude_pad:i user_label k:i excl_ptr
     excl_items max_row:i topk_idx topk_val workspace ws_bytes:q excl_workspace stream)
 """
+# The fifth table: what include/srfrd_hip_filter.h declares (tests/test_topk_allow_abi.py holds it to that header;
+# FILTER_SIGNATURES and FILTER_PARAMS derive from it).  `query` / `call` consult it after the other four.
+_FILTER_ABI = """
+q srfrd_item_mask_words(n_rows:q)
+i srfrd_item_mask_pack(mask n_groups:i n_rows:q words stream)
+i srfrd_topk_allow_plan(lay:lay B:i k:i item_lo:q item_hi:q excl:i switches:i n_cu:i max_launches:i names name_len:i geom sizes)
+q srfrd_topk_allow_workspace_bytes(B:i k:i n_rows:q)
+i srfrd_logits_topk_allow(lay:lay item_table dense hidden B:i L:i item_lo:q item_hi:q exclude_pad:i user_label k:i excl_ptr
+    excl_items max_row:i topk_idx topk_val workspace ws_bytes:q excl_workspace allow_words n_groups:i words_per_group:q allow_group
+    stream)
+i srfrd_target_rank_allow(lay:lay item_table dense hidden B:i L:i item_lo:q item_hi:q exclude_pad:i user_label targets excl_ptr
+    excl_items max_row:i cut_k:i rank metric_acc workspace allow_words n_groups:i words_per_group:q allow_group stream)
+"""
 
 
 def _parse(params):
@@ -184,11 +198,15 @@ SORT_PARAMS = {name: names for name, (_, _, names) in _SORT_PARSED.items()}
 _WIDE_PARSED = _parse_abi(_WIDE_ABI)
 WIDE_SIGNATURES = {name: (res, types) for name, (res, types, _) in _WIDE_PARSED.items()}
 WIDE_PARAMS = {name: names for name, (_, _, names) in _WIDE_PARSED.items()}
+_FILTER_PARSED = _parse_abi(_FILTER_ABI)
+FILTER_SIGNATURES = {name: (res, types) for name, (res, types, _) in _FILTER_PARSED.items()}
+FILTER_PARAMS = {name: names for name, (_, _, names) in _FILTER_PARSED.items()}
 ENCODER_HEAD = _parse(_ENC_HEAD)[1]
 # name -> (its names as a set, the fetch of a dict's values in parameter order, the positions that hold a pointer)
 _MARSHAL = {name: (frozenset(names), operator.itemgetter(*names) if len(names) > 1 else (lambda a, n=names[0]: (a[n],)),
                    tuple(i for i, t in enumerate(types) if t not in (_i, _i64, _u32, _d)))
-            for name, (_, types, names) in {**_PARSED, **_LAZY_PARSED, **_SORT_PARSED, **_WIDE_PARSED}.items()}
+            for name, (_, types, names) in {**_PARSED, **_LAZY_PARSED, **_SORT_PARSED, **_WIDE_PARSED,
+                                               **_FILTER_PARSED}.items()}
 
 _lib = None
 
@@ -203,7 +221,8 @@ def lib():
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**SIGNATURES, **LAZY_SIGNATURES, **SORT_SIGNATURES, **WIDE_SIGNATURES}.items():
+        for name, (res, args) in {**SIGNATURES, **LAZY_SIGNATURES, **SORT_SIGNATURES, **WIDE_SIGNATURES,
+                                  **FILTER_SIGNATURES}.items():
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
         _lib = handle
@@ -211,7 +230,7 @@ def lib():
 
 
 def _late_entry(handle, name, table):
-    """entry point ``name`` of ``table`` (the second, third or fourth) on ``handle``.  A handle that was bound from SIGNATURES alone
+    """entry point ``name`` of ``table`` (the second to the fifth) on ``handle``.  A handle that was bound from SIGNATURES alone
     (another build of the library, loaded beside the product's) gets the types here: an unbound ctypes function would take an
     address as a C int"""
     fn = getattr(handle, name)
@@ -230,6 +249,10 @@ def _sort_entry(handle, name):
 
 def _wide_entry(handle, name):
     return _late_entry(handle, name, WIDE_SIGNATURES)
+
+
+def _filter_entry(handle, name):
+    return _late_entry(handle, name, FILTER_SIGNATURES)
 
 
 def check(rc: int, what: str):
@@ -256,7 +279,7 @@ def dense_ptr(flat, n_table_pad):
 
 
 def query(name, /, **args):
-    """The C entry point ``name`` with its parameters BY NAME (PARAMS, then LAZY_PARAMS, SORT_PARAMS and WIDE_PARAMS: the headers'; all of them, except that ``stream`` defaults
+    """The C entry point ``name`` with its parameters BY NAME (PARAMS, then LAZY_PARAMS, SORT_PARAMS, WIDE_PARAMS and FILTER_PARAMS: the headers'; all of them, except that ``stream`` defaults
     to the current torch stream) -> its raw return value.  In a pointer's place a tensor passes its ``data_ptr()``, None is
     NULL, a ctypes structure goes by reference, anything else (an address as an int, a ctypes buffer) as it is.  A missing or
     unknown name raises TypeError before the library is touched; the function is looked up on the handle at every call."""
@@ -274,7 +297,7 @@ def query(name, /, **args):
             argv[i] = C.byref(v)
     if name in SIGNATURES:
         return getattr(lib(), name)(*argv)
-    table = LAZY_SIGNATURES if name in LAZY_SIGNATURES else SORT_SIGNATURES if name in SORT_SIGNATURES else WIDE_SIGNATURES
+    table = next(t for t in (LAZY_SIGNATURES, SORT_SIGNATURES, WIDE_SIGNATURES, FILTER_SIGNATURES) if name in t)
     return _late_entry(lib(), name, table)(*argv)
 
 
@@ -378,6 +401,21 @@ def topk_wide_plan(lay: Layout, B: int, k: int, item_lo: int, item_hi: int, excl
     n, w = 8, 96
     names, geom, sizes = C.create_string_buffer(n * w), (C.c_int32 * (3 * n))(), (C.c_int32 * 3)()
     rc = query("srfrd_topk_wide_plan", lay=lay, B=B, k=k, item_lo=item_lo, item_hi=item_hi, excl=int(excl), switches=switches,
+               n_cu=n_cu, max_launches=n, names=names, name_len=w, geom=geom, sizes=sizes)
+    if rc < 0:
+        return rc
+    return ([(names.raw[i * w:(i + 1) * w].split(b"\0")[0].decode(), geom[3 * i], geom[3 * i + 1], geom[3 * i + 2])
+             for i in range(rc)], tuple(sizes))
+
+
+def topk_allow_plan(lay: Layout, B: int, k: int, item_lo: int, item_hi: int, excl: bool = False, switches: int = 0,
+                    n_cu: int = 256):
+    """srfrd_topk_allow_plan (no GPU needed), in the form of ``topk_wide_plan``: ([(kernel, workgroups, threads, dynamic LDS
+    bytes)] in launch order, (path, candidate capacity per user, group maxima per user)), or the negative code the call
+    refuses with."""
+    n, w = 8, 96
+    names, geom, sizes = C.create_string_buffer(n * w), (C.c_int32 * (3 * n))(), (C.c_int32 * 3)()
+    rc = query("srfrd_topk_allow_plan", lay=lay, B=B, k=k, item_lo=item_lo, item_hi=item_hi, excl=int(excl), switches=switches,
                n_cu=n_cu, max_launches=n, names=names, name_len=w, geom=geom, sizes=sizes)
     if rc < 0:
         return rc

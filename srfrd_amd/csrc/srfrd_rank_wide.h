@@ -239,10 +239,11 @@ __global__ void __launch_bounds__(kWideBlock) wide_select_kernel(const TopkArgs 
 // fp64 chain in channel order, rounded once: a row's value does not depend on where it sits, so bit-identical rows tie
 // exactly - and keeps the best 1024 keys sorted in LDS.  Keys that beat the current k-th are appended behind them; when the
 // next block's would not fit, the 2048 keys are sorted again.
-__global__ void __launch_bounds__(kWideBlock) wide_fallback_kernel(const TopkArgs a, const WideArgs w, int64_t* __restrict__ topk_idx,
-                                                                   float* __restrict__ topk_val) {
+// (the body, shared with the filtered form of srfrd_rank_filter.h: allowed(item) is one more test beside excl_has)
+template <class ALLOWED>
+__device__ __forceinline__ void wide_fallback_user(const TopkArgs& a, const WideArgs& w, int64_t* __restrict__ topk_idx,
+                                                   float* __restrict__ topk_val, ALLOWED&& allowed) {
   const int b = blockIdx.x, tid = threadIdx.x;
-  if (a.ccnt[b] <= w.cap) return;
   __shared__ unsigned long long sk[2 * kWideBlock];
   __shared__ float sh[SRFRD_MAX_D];
   __shared__ double s_side;
@@ -279,6 +280,7 @@ __global__ void __launch_bounds__(kWideBlock) wide_fallback_kernel(const TopkArg
     const int64_t item = r0 + tid;
     bool ok = item < a.item_hi && !(a.exclude_pad && item == 0);
     if (ok && w.excl) ok = !excl_has(a, b, item);
+    if (ok) ok = allowed(item);
     unsigned long long key = kWideEmpty;
     if (ok) {
       double s = 0.0;
@@ -295,6 +297,12 @@ __global__ void __launch_bounds__(kWideBlock) wide_fallback_kernel(const TopkArg
   }
   merge();
   wide_write(sk, kWideBlock, b, a.k, topk_idx, topk_val);
+}
+
+__global__ void __launch_bounds__(kWideBlock) wide_fallback_kernel(const TopkArgs a, const WideArgs w, int64_t* __restrict__ topk_idx,
+                                                                   float* __restrict__ topk_val) {
+  if (a.ccnt[blockIdx.x] <= w.cap) return;
+  wide_fallback_user(a, w, topk_idx, topk_val, [](int64_t) { return true; });
 }
 
 // ---- the plan ----------------------------------------------------------------------------------------------------------------

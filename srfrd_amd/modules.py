@@ -648,32 +648,64 @@ class _SRFRDBase(nn.Module):
         self._check_item_ids(cand)
         return torch.ops.srfrd.predict_logits(hidden.contiguous(), cand.contiguous(), ulab, ops.register_model(self))
 
-    def topk(self, user_ids, input_ids, fake_ids, k=10, exclude_pad=True, item_range=None, exclude=None):
+    def item_filter(self, mask):
+        """``srfrd_amd.ItemFilter`` of ``mask`` ((n_items + 1,) or (G, n_items + 1)) for this model's catalog, on its device"""
+        from .filters import ItemFilter
+        return ItemFilter(mask, self.layout.n_items, self._item_param().device)
+
+    def _allow_args(self, allow, allow_group, B, device, what):
+        """the (words, group) pair of a filtered ranking call"""
+        from .filters import ItemFilter
+        if not isinstance(allow, ItemFilter):
+            raise ValueError(f"{what}: allow must be an srfrd_amd.ItemFilter (got {type(allow).__name__})")
+        if allow.n_items != self.layout.n_items:
+            raise ValueError(f"{what}: the filter was built for n_items = {allow.n_items}, the model has {self.layout.n_items}")
+        return allow.words, allow.group_arg(allow_group, B, device)
+
+    def topk(self, user_ids, input_ids, fake_ids, k=10, exclude_pad=True, item_range=None, exclude=None, *, allow=None,
+             allow_group=None):
         """Full-catalog ranking: (indices int64 (B,k), scores (B,k)); the (B, I) logits never reach HBM.
         ``exclude``: items never to return, per user - None, "input" (the ids of the user's input window), a (ptr, items)
         CSR tuple over the batch, or a list of B 1-D tensors.  Fewer than k rankable items leave trailing -1 / -inf slots.
         k <= 64 takes the threshold ranking built for evaluation; 64 < k <= srfrd_amd.TOPK_WIDE_MAX the wide one (the same
-        scores and order law)."""
+        scores and order law).
+        ``allow``: an ``srfrd_amd.ItemFilter`` (``model.item_filter(mask)``) - only the items it allows are ranked, beside
+        ``item_range``, ``exclude`` and ``exclude_pad``; ``allow_group`` int64 (B,): the filter row of each user (required when
+        the filter has more than one group).  Any k in 1..TOPK_WIDE_MAX then takes the filtered ranking."""
         if not 1 <= k <= _lib.TOPK_WIDE_MAX:
             raise ValueError(f"topk: k = {k} is outside 1..srfrd_amd.TOPK_WIDE_MAX ({_lib.TOPK_WIDE_MAX})")
+        if allow is None and allow_group is not None:
+            raise ValueError("topk: allow_group needs allow")
         hidden, ulab, excl = self._rank_inputs(input_ids, fake_ids, exclude)
         lo, hi = item_range if item_range is not None else (0, self.layout.n_items + 1)
+        if allow is not None:
+            words, group = self._allow_args(allow, allow_group, hidden.shape[0], hidden.device, "topk")
+            return tuple(torch.ops.srfrd.logits_topk_allow(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad), *excl,
+                                                           words, group))
         if k > 64:
             return tuple(torch.ops.srfrd.logits_topk_wide(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad), *excl))
         if exclude is None:
             return tuple(torch.ops.srfrd.logits_topk(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad)))
         return tuple(torch.ops.srfrd.logits_topk_excl(hidden, ulab, ops.register_model(self), lo, hi, k, bool(exclude_pad), *excl))
 
-    def target_rank(self, user_ids, input_ids, fake_ids, targets, exclude=None, item_range=None, exclude_pad=True):
+    def target_rank(self, user_ids, input_ids, fake_ids, targets, exclude=None, item_range=None, exclude_pad=True, *, allow=None,
+                    allow_group=None):
         """Full-catalog rank of ``targets`` (B,): int32 (B,) counts of the items in ``item_range`` (default: the whole
         catalog) that score strictly higher than the user's target, skipping the ``exclude`` set (as in ``topk``) and,
         with ``exclude_pad``, item 0.  The target itself is ranked even when it is excluded; ranks over disjoint item
-        ranges add up.  ``rank < K`` is a hit at K; NDCG@K = 1 / log2(rank + 2)."""
+        ranges add up.  ``rank < K`` is a hit at K; NDCG@K = 1 / log2(rank + 2).
+        ``allow`` / ``allow_group``: as in ``topk`` - only allowed items are counted; a disallowed target is still ranked."""
+        if allow is None and allow_group is not None:
+            raise ValueError("target_rank: allow_group needs allow")
         hidden, ulab, excl = self._rank_inputs(input_ids, fake_ids, exclude)
         lo, hi = item_range if item_range is not None else (0, self.layout.n_items + 1)
         tg = _ids(targets, hidden.device).reshape(-1)
         if tg.numel() != hidden.shape[0]:
             raise ValueError("targets must hold one item id per user")
+        if allow is not None:
+            words, group = self._allow_args(allow, allow_group, hidden.shape[0], hidden.device, "target_rank")
+            return torch.ops.srfrd.target_rank_allow(hidden, ulab, tg, ops.register_model(self), lo, hi, bool(exclude_pad), *excl,
+                                                     words, group)
         return torch.ops.srfrd.target_rank(hidden, ulab, tg, ops.register_model(self), lo, hi, bool(exclude_pad), *excl)
 
 

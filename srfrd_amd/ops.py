@@ -13,6 +13,7 @@ autograd function and FusedTrainer), and their fakes and autograd are registered
     srfrd::logits_topk     full-catalog top-k over an item range, logits never in HBM
     srfrd::logits_topk_excl  the same with a per-user exclusion set (CSR over the batch) masked inside the ranking passes
     srfrd::logits_topk_wide  exact top-k for k up to 1024 (TOPK_WIDE_MAX), exclusion set optional
+    srfrd::logits_topk_allow the same over the items an ItemFilter allows (srfrd::target_rank_allow: the target rank)
     srfrd::target_rank     full-catalog rank of a target item per user (strictly-greater count), exclusion set optional
     srfrd::topk_merge      merge of per-shard top-k lists
     srfrd::user_labels     get_Labels (SRFR_model.py:546-570)
@@ -268,7 +269,29 @@ def logits_topk_wide(hidden: torch.Tensor, user_label: Optional[torch.Tensor], m
     return [idx, val]
 
 
-for _op in (logits_topk, logits_topk_excl, logits_topk_wide):
+def _allow_args(allow_words, allow_group):
+    """the four filter arguments of srfrd_logits_topk_allow / srfrd_target_rank_allow from an ItemFilter's words (G, W) int32"""
+    return dict(allow_words=allow_words, n_groups=allow_words.shape[0], words_per_group=allow_words.shape[1], allow_group=allow_group)
+
+
+@torch.library.custom_op("srfrd::logits_topk_allow", mutates_args=(), device_types="cuda")
+def logits_topk_allow(hidden: torch.Tensor, user_label: Optional[torch.Tensor], model_key: int, item_lo: int, item_hi: int, k: int,
+                      exclude_pad: bool, excl_ptr: Optional[torch.Tensor], excl_items: Optional[torch.Tensor], max_row: int,
+                      allow_words: torch.Tensor, allow_group: Optional[torch.Tensor]) -> List[torch.Tensor]:
+    """srfrd_logits_topk_allow: 1 <= k <= _lib.TOPK_WIDE_MAX over the items ``allow_words`` (an ItemFilter's packed rows) allows;
+    ``allow_group`` int64 (B,) or None (row 0); ``excl_ptr`` None: no exclusion sets"""
+    n_rows = item_hi - item_lo
+    _, xws = _rank_workspaces(hidden, None, n_rows, max_row if excl_ptr is not None else None)
+    n = query("srfrd_topk_allow_workspace_bytes", B=hidden.shape[0], k=k, n_rows=n_rows)
+    ws = torch.empty(max(n, 8), device=hidden.device, dtype=torch.uint8)
+    idx, val = _topk_out(hidden, k)
+    call("srfrd_logits_topk_allow", **rank_head(_model(model_key), hidden, user_label, item_range=(item_lo, item_hi),
+                                                 exclude_pad=exclude_pad, excl=(excl_ptr, excl_items, max_row)),
+         k=k, topk_idx=idx, topk_val=val, workspace=ws, ws_bytes=n, excl_workspace=xws, **_allow_args(allow_words, allow_group))
+    return [idx, val]
+
+
+for _op in (logits_topk, logits_topk_excl, logits_topk_wide, logits_topk_allow):
     _op.register_fake(lambda hidden, user_label, model_key, item_lo, item_hi, k, *rest: _topk_out(hidden, k))
 
 
@@ -287,6 +310,25 @@ def target_rank(hidden: torch.Tensor, user_label: Optional[torch.Tensor], target
 
 @target_rank.register_fake
 def _(hidden, user_label, targets, model_key, item_lo, item_hi, exclude_pad, excl_ptr, excl_items, max_row):
+    return torch.empty(hidden.shape[0], device=hidden.device, dtype=torch.int32)
+
+
+@torch.library.custom_op("srfrd::target_rank_allow", mutates_args=(), device_types="cuda")
+def target_rank_allow(hidden: torch.Tensor, user_label: Optional[torch.Tensor], targets: torch.Tensor, model_key: int, item_lo: int,
+                      item_hi: int, exclude_pad: bool, excl_ptr: Optional[torch.Tensor], excl_items: Optional[torch.Tensor],
+                      max_row: int, allow_words: torch.Tensor, allow_group: Optional[torch.Tensor]) -> torch.Tensor:
+    """srfrd_target_rank_allow: ``target_rank`` over the items ``allow_words`` allows"""
+    _, ws = _rank_workspaces(hidden, None, item_hi - item_lo, max_row if excl_ptr is not None else 0)
+    rank = torch.empty(hidden.shape[0], device=hidden.device, dtype=torch.int32)
+    targets = targets.to(device=hidden.device, dtype=torch.int64).contiguous()
+    call("srfrd_target_rank_allow", **rank_head(_model(model_key), hidden, user_label, item_range=(item_lo, item_hi),
+                                                 exclude_pad=exclude_pad, excl=(excl_ptr, excl_items, max_row)),
+         targets=targets, cut_k=10, rank=rank, metric_acc=None, workspace=ws, **_allow_args(allow_words, allow_group))
+    return rank
+
+
+@target_rank_allow.register_fake
+def _(hidden, user_label, targets, model_key, item_lo, item_hi, exclude_pad, excl_ptr, excl_items, max_row, allow_words, allow_group):
     return torch.empty(hidden.shape[0], device=hidden.device, dtype=torch.int32)
 
 
@@ -417,5 +459,6 @@ _register_head(sxent_fwd, sxent_bwd, 4)
 _register_head(tneg_fwd, tneg_bwd, 4)
 
 
-OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "logits_topk_wide", "target_rank", "topk_merge",
+OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "logits_topk_wide", "logits_topk_allow", "target_rank",
+       "target_rank_allow", "topk_merge",
        "eval_rank", "xent_fwd", "xent_bwd", "sxent_fwd", "sxent_bwd", "tneg_fwd", "tneg_bwd")
