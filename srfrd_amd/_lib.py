@@ -1,6 +1,6 @@
 """ctypes binding of libsrfrd_hip.so (the C ABI declared in include/srfrd_hip.h and, the lazy-Adam entry point,
 include/srfrd_hip_lazy.h; the device key sort, include/srfrd_hip_sort.h; the wide top-k, include/srfrd_hip_topk_wide.h; the
-item filters, include/srfrd_hip_filter.h).
+item filters, include/srfrd_hip_filter.h; the merge of sorted lists, include/srfrd_hip_merge.h).
 
 There is no CPU fallback: if the library is missing this module raises, and every op above it fails loudly.
 """
@@ -175,6 +175,12 @@ i srfrd_logits_topk_allow(lay:lay item_table dense hidden B:i L:i item_lo:q item
 i srfrd_target_rank_allow(lay:lay item_table dense hidden B:i L:i item_lo:q item_hi:q exclude_pad:i user_label targets excl_ptr
     excl_items max_row:i cut_k:i rank metric_acc workspace allow_words n_groups:i words_per_group:q allow_group stream)
 """
+# The sixth table: what include/srfrd_hip_merge.h declares (tests/test_topk_merge_abi.py holds it to that header; MERGE_SIGNATURES
+# and MERGE_PARAMS derive from it).  `query` / `call` consult it after the other five.
+_MERGE_ABI = """
+q srfrd_topk_merge_runs_lds_bytes(n_lists:i list_len:i)
+i srfrd_topk_merge_runs(cand_idx cand_val B:i n_lists:i list_len:i user_stride:q list_stride:q k:i topk_idx topk_val path stream)
+"""
 
 
 def _parse(params):
@@ -201,12 +207,15 @@ WIDE_PARAMS = {name: names for name, (_, _, names) in _WIDE_PARSED.items()}
 _FILTER_PARSED = _parse_abi(_FILTER_ABI)
 FILTER_SIGNATURES = {name: (res, types) for name, (res, types, _) in _FILTER_PARSED.items()}
 FILTER_PARAMS = {name: names for name, (_, _, names) in _FILTER_PARSED.items()}
+_MERGE_PARSED = _parse_abi(_MERGE_ABI)
+MERGE_SIGNATURES = {name: (res, types) for name, (res, types, _) in _MERGE_PARSED.items()}
+MERGE_PARAMS = {name: names for name, (_, _, names) in _MERGE_PARSED.items()}
 ENCODER_HEAD = _parse(_ENC_HEAD)[1]
 # name -> (its names as a set, the fetch of a dict's values in parameter order, the positions that hold a pointer)
 _MARSHAL = {name: (frozenset(names), operator.itemgetter(*names) if len(names) > 1 else (lambda a, n=names[0]: (a[n],)),
                    tuple(i for i, t in enumerate(types) if t not in (_i, _i64, _u32, _d)))
             for name, (_, types, names) in {**_PARSED, **_LAZY_PARSED, **_SORT_PARSED, **_WIDE_PARSED,
-                                               **_FILTER_PARSED}.items()}
+                                               **_FILTER_PARSED, **_MERGE_PARSED}.items()}
 
 _lib = None
 
@@ -222,7 +231,7 @@ def lib():
                 "There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **LAZY_SIGNATURES, **SORT_SIGNATURES, **WIDE_SIGNATURES,
-                                  **FILTER_SIGNATURES}.items():
+                                  **FILTER_SIGNATURES, **MERGE_SIGNATURES}.items():
             fn = getattr(handle, name)
             fn.restype, fn.argtypes = res, args
         _lib = handle
@@ -230,7 +239,7 @@ def lib():
 
 
 def _late_entry(handle, name, table):
-    """entry point ``name`` of ``table`` (the second to the fifth) on ``handle``.  A handle that was bound from SIGNATURES alone
+    """entry point ``name`` of ``table`` (the second to the sixth) on ``handle``.  A handle that was bound from SIGNATURES alone
     (another build of the library, loaded beside the product's) gets the types here: an unbound ctypes function would take an
     address as a C int"""
     fn = getattr(handle, name)
@@ -253,6 +262,10 @@ def _wide_entry(handle, name):
 
 def _filter_entry(handle, name):
     return _late_entry(handle, name, FILTER_SIGNATURES)
+
+
+def _merge_entry(handle, name):
+    return _late_entry(handle, name, MERGE_SIGNATURES)
 
 
 def check(rc: int, what: str):
@@ -279,7 +292,7 @@ def dense_ptr(flat, n_table_pad):
 
 
 def query(name, /, **args):
-    """The C entry point ``name`` with its parameters BY NAME (PARAMS, then LAZY_PARAMS, SORT_PARAMS, WIDE_PARAMS and FILTER_PARAMS: the headers'; all of them, except that ``stream`` defaults
+    """The C entry point ``name`` with its parameters BY NAME (PARAMS, then LAZY_PARAMS, SORT_PARAMS, WIDE_PARAMS, FILTER_PARAMS and MERGE_PARAMS: the headers'; all of them, except that ``stream`` defaults
     to the current torch stream) -> its raw return value.  In a pointer's place a tensor passes its ``data_ptr()``, None is
     NULL, a ctypes structure goes by reference, anything else (an address as an int, a ctypes buffer) as it is.  A missing or
     unknown name raises TypeError before the library is touched; the function is looked up on the handle at every call."""
@@ -297,7 +310,7 @@ def query(name, /, **args):
             argv[i] = C.byref(v)
     if name in SIGNATURES:
         return getattr(lib(), name)(*argv)
-    table = next(t for t in (LAZY_SIGNATURES, SORT_SIGNATURES, WIDE_SIGNATURES, FILTER_SIGNATURES) if name in t)
+    table = next(t for t in (LAZY_SIGNATURES, SORT_SIGNATURES, WIDE_SIGNATURES, FILTER_SIGNATURES, MERGE_SIGNATURES) if name in t)
     return _late_entry(lib(), name, table)(*argv)
 
 

@@ -1592,6 +1592,8 @@ extern "C" int srfrd_target_rank(const srfrd_layout* lay, const void* item_table
 #include "srfrd_rank_wide.h"
 // item filters: masked forms of the wide scheme's stream passes, their plan, srfrd_logits_topk_allow and srfrd_target_rank_allow
 #include "srfrd_rank_filter.h"
+// merge of sorted lists of up to SRFRD_TOPK_WIDE_MAX entries: the tail of the wide sort's network, and srfrd_topk_merge_runs
+#include "srfrd_rank_merge.h"
 
 extern "C" int srfrd_topk_merge(const int64_t* cand_idx, const float* cand_val, int B, int n_cand, int k, int64_t* topk_idx,
                                 float* topk_val, void* stream) {

@@ -16,6 +16,7 @@ autograd function and FusedTrainer), and their fakes and autograd are registered
     srfrd::logits_topk_allow the same over the items an ItemFilter allows (srfrd::target_rank_allow: the target rank)
     srfrd::target_rank     full-catalog rank of a target item per user (strictly-greater count), exclusion set optional
     srfrd::topk_merge      merge of per-shard top-k lists
+    srfrd::topk_merge_runs merge of per-shard lists of up to 1024 entries as sorted runs, read where they lie (strides)
     srfrd::user_labels     get_Labels (SRFR_model.py:546-570)
     srfrd::eval_rank       rank of candidate 0 (utils.py:589-597)
     srfrd::xent_fwd        full-catalog softmax cross-entropy per token (logits never in HBM); backward = srfrd::xent_bwd
@@ -346,6 +347,32 @@ def _(cand_idx, cand_val, k):
     return _topk_out(cand_idx, k)
 
 
+@torch.library.custom_op("srfrd::topk_merge_runs", mutates_args=(), device_types="cuda")
+def topk_merge_runs(cand_idx: torch.Tensor, cand_val: torch.Tensor, k: int) -> List[torch.Tensor]:
+    """srfrd_topk_merge_runs: ``cand_idx`` int64 / ``cand_val`` fp32 (n_lists, B, list_len), each list sorted by the order law
+    (an unsorted one is sorted, ``path`` says so) -> [idx (B, k), val (B, k), path int32 (B,)].  The strides are read, so a view
+    with innermost stride 1 (a ``permute`` of a (B, n_lists, list_len) tensor, a slice) merges where it lies."""
+    if cand_idx.dim() != 3 or cand_idx.shape != cand_val.shape:
+        raise ValueError("topk_merge_runs: cand_idx and cand_val must be (n_lists, B, list_len) tensors of one shape")
+    if cand_idx.dtype != torch.int64 or cand_val.dtype != torch.float32:
+        raise ValueError("topk_merge_runs: cand_idx must be int64 and cand_val float32")
+    if cand_idx.stride(2) != 1 or cand_idx.stride() != cand_val.stride():
+        cand_idx, cand_val = cand_idx.contiguous(), cand_val.contiguous()
+    S, B, n = cand_idx.shape
+    idx, val = _topk_out(cand_idx[0], k)
+    path = torch.empty(B, device=cand_idx.device, dtype=torch.int32)
+    # (a dimension of size 1 may carry any stride: give it the one a contiguous tensor would have)
+    call("srfrd_topk_merge_runs", cand_idx=cand_idx, cand_val=cand_val, B=B, n_lists=S, list_len=n,
+         user_stride=cand_idx.stride(1) if B > 1 else n, list_stride=cand_idx.stride(0) if S > 1 else n, k=k,
+         topk_idx=idx, topk_val=val, path=path)
+    return [idx, val, path]
+
+
+@topk_merge_runs.register_fake
+def _(cand_idx, cand_val, k):
+    return _topk_out(cand_idx[0], k) + [torch.empty(cand_idx.shape[1], device=cand_idx.device, dtype=torch.int32)]
+
+
 @torch.library.custom_op("srfrd::eval_rank", mutates_args=(), device_types="cuda")
 def eval_rank(logits: torch.Tensor) -> torch.Tensor:
     logits = logits.contiguous()
@@ -460,5 +487,5 @@ _register_head(tneg_fwd, tneg_bwd, 4)
 
 
 OPS = ("encoder_fwd", "encoder_bwd", "user_labels", "predict_logits", "logits_topk", "logits_topk_excl", "logits_topk_wide", "logits_topk_allow", "target_rank",
-       "target_rank_allow", "topk_merge",
+       "target_rank_allow", "topk_merge", "topk_merge_runs",
        "eval_rank", "xent_fwd", "xent_bwd", "sxent_fwd", "sxent_bwd", "tneg_fwd", "tneg_bwd")

@@ -2,11 +2,16 @@
 """One-shard-per-rank full-catalog ranking == unsharded ranking (srfrd_amd/ranker.py), N ranks.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 \\
-        tools/sharded_rank_parity.py [--backend nccl|gloo] [--kind SASRec|SRFRN]
+        tools/sharded_rank_parity.py [--backend nccl|gloo] [--kind SASRec|SRFRN] [--k K] [--allow]
 
 Every rank holds different users; ShardedRanker all-gathers their last hidden states, ranks all users against the rank's
 own rows, all-gathers the (users, k) lists and merges.  Each rank compares its result with model.topk() over the whole
 catalog (bit-equal indices and values).  One JSON line on rank 0; exit code 0 = parity.
+
+--k K (default 10): k > 64 takes the wide route - per-shard srfrd_logits_topk_wide, the lists exchanged by all-to-all (a rank
+receives its own users' lists only) and merged as sorted runs.  --allow: a two-group random item filter, the same on every rank,
+with each user's group drawn by a rank-dependent seed (the filtered route at any k).  With either option the ranks also compare
+ShardedRanker.target_rank with model.target_rank (equal counts); without options the run is what it always was.
 """
 import argparse
 import json
@@ -21,6 +26,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--backend", default=None)
     ap.add_argument("--kind", default="SRFRN", choices=["SASRec", "SRFRN"])
+    ap.add_argument("--k", type=int, default=None)
+    ap.add_argument("--allow", action="store_true")
     args = ap.parse_args()
     world, rank, local = int(os.environ["WORLD_SIZE"]), int(os.environ["RANK"]), int(os.environ.get("LOCAL_RANK", "0"))
     import torch
@@ -34,7 +41,8 @@ def main():
     else:
         dist.init_process_group(backend)
     import srfrd_amd
-    I, L, B, k = 20011, 30, 19, 10
+    I, L, B, k = 20011, 30, 19, args.k or 10
+    extended = args.k is not None or args.allow
     torch.manual_seed(0)
     m = srfrd_amd.SASRec(I, L, 50, 0.0, 2, 1, dev) if args.kind == "SASRec" else srfrd_amd.SRFRN(I, L, 45, 5, 0.0, 2, 1, dev)
     for _, p in m.named_parameters():
@@ -47,9 +55,19 @@ def main():
     _, seq, rsq, *_ = srfrd_amd.synthetic_batch(I, L, B, seed=3, rank=rank, device=dev)
     r = srfrd_amd.ShardedRanker(m)
     assert r.world == world and r.n_shards == world
-    idx, val = r.topk(None, seq, rsq, k=k)
-    wi, wv = m.topk(None, seq, rsq, k=k)
+    filt = {}
+    if args.allow:
+        g = torch.Generator().manual_seed(17)                        # the same bitmap on every rank
+        mask = torch.rand(2, I + 1, generator=g) < torch.tensor([[0.5], [0.1]])
+        groups = torch.randint(0, 2, (B,), generator=torch.Generator().manual_seed(100 + rank))
+        filt = dict(allow=m.item_filter(mask), allow_group=groups.to(dev))
+    idx, val = r.topk(None, seq, rsq, k=k, **filt)
+    wi, wv = m.topk(None, seq, rsq, k=k, **filt)
     ok = bool(torch.equal(idx, wi) and torch.equal(val, wv))
+    if extended:
+        targets = torch.randint(1, I + 1, (B,), generator=torch.Generator().manual_seed(200 + rank)).to(dev)
+        sharded = r.target_rank(None, seq, rsq, targets, **filt)      # (collectives: every rank calls it, whatever `ok` says)
+        ok = bool(torch.equal(sharded, m.target_rank(None, seq, rsq, targets, **filt))) and ok
     flag = torch.tensor([1 if ok else 0], dtype=torch.int32)
     dist.all_reduce(flag, op=dist.ReduceOp.MIN) if backend != "nccl" else None
     if backend == "nccl":
@@ -58,6 +76,7 @@ def main():
         flag = f.cpu()
     if rank == 0:
         print(json.dumps({"backend": backend, "world": world, "kind": args.kind, "items": I, "users_per_rank": B, "k": k,
+                          "allow": bool(args.allow), "target_rank": extended,
                           "shards": r.shards, "ok": bool(int(flag.item()) == 1)}), flush=True)
     dist.barrier()
     dist.destroy_process_group()
