@@ -99,6 +99,13 @@ def _twin(cid, n, **names):
 DEPTH = [_twin(cid, n) for n in (1, 3) for cid in _TWINS_1_3] + [_twin(cid, 8, **names) for cid, names in _DEPTH8.items()]
 ALL_CASES = DEPTH2_CASES + DEPTH
 BY_ID = {c.id: c for c in ALL_CASES}
+OTHER = {}                # id -> Case held by another module outside ALL_CASES (tests/dp_refs.py registers its own here)
+
+
+def case_of(cid):
+    return BY_ID[cid] if cid in BY_ID else OTHER[cid]
+
+
 TRAIN_KERNEL_IDS = ("t0", "t1", "t2", "t3", "t0.1", "t0.3", "t0.8")          # run with train_launch on and off
 L2_ID = "t0"                                         # the one fused case that also runs with l2_emb = L2_EMB
 # leading pad counts of the tile-boundary batch: the boundaries tests/fuzz_ragged.py names, with both neighbours
@@ -335,8 +342,25 @@ def dup_batch(seed, B=12, L=50):
     return _reviews(g, seq, pos, neg)
 
 
+# leading pad counts of the skewed batches (tests/dp_refs.py: split over 2 or 3 ranks, a rank's share of the targets is a tenth
+# of another's, or nothing): v0 ends in single-item sequences and one all-pad sequence, v1 in four all-pad sequences
+SKEW_PADS = {"v0": (0, 1, 2, 3, 30, 37, 44, 48, 49, 49, 49, 50), "v1": (0, 1, 2, 3, 0, 17, 40, 47, 50, 50, 50, 50)}
+
+
+def skew_batch(seed, pads, L=50):
+    """sequence i with pads[i] leading pads, inputs and both targets zero there"""
+    g = torch.Generator().manual_seed(seed)
+    seq, pos, neg = (torch.randint(1, I + 1, (len(pads), L), generator=g) for _ in range(3))
+    for b, t0 in enumerate(pads):
+        for x in (seq, pos, neg):
+            x[b, :t0] = 0
+    return _reviews(g, seq, pos, neg)
+
+
 def batch_of(c, seed):
     import srfrd_amd
+    if c.id in SKEW_PADS:
+        return skew_batch(seed, SKEW_PADS[c.id])
     if c.id.startswith("t"):
         return tile_batch(seed)
     if c.id.startswith("u"):
@@ -363,7 +387,7 @@ def cfg_of(c, mode):
 @functools.lru_cache(maxsize=None)
 def weights(cid, sd_seed=None):
     from tests.gpu_util import random_sd
-    return random_sd(cfg_of(BY_ID[cid], "autograd"), sd_seed or SD_SEEDS.get(cid, SD_SEED))
+    return random_sd(cfg_of(case_of(cid), "autograd"), sd_seed or SD_SEEDS.get(cid, SD_SEED))
 
 
 def build_ref(c, mode, seed, l2=0.0):
@@ -400,7 +424,7 @@ def reference(cid, mode, l2=0.0):
 def scan_seeds(job):
     """(case id, mode, count) -> [[seed, worst e32, relu margin], ...] from first_seed on, on THIS machine's CPU"""
     cid, mode, count = job
-    c = BY_ID[cid]
+    c = case_of(cid)
     out = []
     for seed in range(first_seed(c, mode), first_seed(c, mode) + count):
         ref = build_head_ref(head_job(cid, mode[5:]), seed).ref if mode.startswith("head/") else build_ref(c, mode, seed)
