@@ -68,6 +68,8 @@ FWD_SEEDS.update({("g.1", "eval"): 10, ("i.1", "eval"): 10, ("t0.3", "eval"): 12
 # the condition without the headroom, the others over it.
 FWD_OVER_CAP = frozenset((c.id, "train") for c in G.DEPTH if c.blocks == 8)
 MAX_OVER_CAP = len(ALL_CASES) * len(MODES) // 10
+# the same two tables for the cases of grad_refs.OTHER that run through `reference` (tests/geom_refs.py registers its own)
+OTHER_FWD_SEEDS, OTHER_FWD_OVER_CAP = {}, set()
 
 
 def plan_bits(mode):
@@ -85,7 +87,8 @@ def plan_name(c, mode):
 
 
 def seed_of(cid, mode):
-    return FWD_SEEDS.get((cid, mode), G.SEEDS[cid, "fused" if mode == "train" else "autograd"])
+    own = FWD_SEEDS if cid in G.BY_ID else OTHER_FWD_SEEDS
+    return own[cid, mode] if (cid, mode) in own else G.seed_of(cid, "fused" if mode == "train" else "autograd")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -188,7 +191,8 @@ def _outputs(cfg, sd, batch, mode, train, seed, cands):
 
 
 def build_ref(c, mode, seed):
-    return _build(cfg_of(c, mode), G.weights(c.id), G.batch_of(c, seed), mode, seed, (c.id, mode) in FWD_OVER_CAP)
+    clamp = (c.id, mode) in FWD_OVER_CAP or (c.id, mode) in OTHER_FWD_OVER_CAP
+    return _build(cfg_of(c, mode), G.weights(c.id), G.batch_of(c, seed), mode, seed, clamp)
 
 
 def _build(cfg, sd, batch, mode, seed, clamp):
@@ -205,7 +209,7 @@ def _build(cfg, sd, batch, mode, seed, clamp):
 
 @functools.lru_cache(maxsize=None)
 def reference_at(cid, mode, seed):
-    return build_ref(G.BY_ID[cid], mode, seed)
+    return build_ref(G.case_of(cid), mode, seed)
 
 
 def reference(cid, mode):
@@ -249,7 +253,7 @@ def loss_reference(ref, l2=0.0):
 def fused_step_reference(cid):
     """the train-mode FwdRef on the batch of the GRADIENT suite's fused step (grad_refs.SEEDS[cid, "fused"], whatever
     FWD_SEEDS says): its fp64 loss is the loss of grad_refs.reference(cid, "fused")"""
-    return reference_at(cid, "train", G.SEEDS[cid, "fused"])
+    return reference_at(cid, "train", G.seed_of(cid, "fused"))
 
 
 def worst_e32(ref):
@@ -268,8 +272,8 @@ def scan_seeds(job):
     """(case id, mode, count) -> [[seed, worst e32, 1.0], ...] from the gradient suite's seed on, on THIS machine's CPU (the
     rows grad_refs.pick_seed reads; the forward has no ReLU-margin condition, so the third column always passes)"""
     cid, mode, count = job
-    first = G.SEEDS[cid, "fused" if mode == "train" else "autograd"]
-    return [[seed, worst_e32(build_ref(G.BY_ID[cid], mode, seed)), 1.0] for seed in range(first, first + count)]
+    first = G.seed_of(cid, "fused" if mode == "train" else "autograd")
+    return [[seed, worst_e32(build_ref(G.case_of(cid), mode, seed)), 1.0] for seed in range(first, first + count)]
 
 
 def pick_seed(scans):

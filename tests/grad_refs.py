@@ -100,10 +100,18 @@ DEPTH = [_twin(cid, n) for n in (1, 3) for cid in _TWINS_1_3] + [_twin(cid, 8, *
 ALL_CASES = DEPTH2_CASES + DEPTH
 BY_ID = {c.id: c for c in ALL_CASES}
 OTHER = {}                # id -> Case held by another module outside ALL_CASES (tests/dp_refs.py registers its own here)
+# What `reference`, `weights` and fwd_refs' lookups read for an OTHER case that runs through them (tests/geom_refs.py registers
+# its own here; the tables below - SEEDS, SD_SEEDS, OVER_CAP - stay the 61 cases'): (id, mode) -> batch seed, id -> weight seed,
+# the (id, mode) jobs whose bound is clamped at CAP.
+OTHER_SEEDS, OTHER_SD_SEEDS, OTHER_OVER_CAP = {}, {}, set()
 
 
 def case_of(cid):
     return BY_ID[cid] if cid in BY_ID else OTHER[cid]
+
+
+def seed_of(cid, mode):
+    return SEEDS[cid, mode] if cid in BY_ID else OTHER_SEEDS[cid, mode]
 
 
 TRAIN_KERNEL_IDS = ("t0", "t1", "t2", "t3", "t0.1", "t0.3", "t0.8")          # run with train_launch on and off
@@ -387,7 +395,7 @@ def cfg_of(c, mode):
 @functools.lru_cache(maxsize=None)
 def weights(cid, sd_seed=None):
     from tests.gpu_util import random_sd
-    return random_sd(cfg_of(case_of(cid), "autograd"), sd_seed or SD_SEEDS.get(cid, SD_SEED))
+    return random_sd(cfg_of(case_of(cid), "autograd"), sd_seed or SD_SEEDS.get(cid) or OTHER_SD_SEEDS.get(cid, SD_SEED))
 
 
 def build_ref(c, mode, seed, l2=0.0):
@@ -399,7 +407,7 @@ def build_ref(c, mode, seed, l2=0.0):
     g32 = fp32_grads(cfg, sd, batch, train=train, seed=dseed, l2_emb=l2)
     e32 = {k: tensor_figures(k, g32[k], g64[k], g32[k], cfg.D, kbias=l2 == 0.0)["e32"] for k in g64}
     margin = relu_margin(cfg, {k: v.double() for k, v in sd.items()}, batch, train=train, seed=dseed)
-    return Ref(cfg, sd, batch, train, dseed, l2, g64, g32, e32, margin, (c.id, mode) in OVER_CAP)
+    return Ref(cfg, sd, batch, train, dseed, l2, g64, g32, e32, margin, (c.id, mode) in OVER_CAP or (c.id, mode) in OTHER_OVER_CAP)
 
 
 def under_cap(ref):
@@ -418,7 +426,7 @@ def assert_admissible(ref, what):
 @functools.lru_cache(maxsize=None)
 def reference(cid, mode, l2=0.0):
     """the Ref of one case and mode at its SEEDS entry, shared by every test of the process; treat as read-only"""
-    return build_ref(BY_ID[cid], mode, SEEDS[cid, mode], l2)
+    return build_ref(case_of(cid), mode, seed_of(cid, mode), l2)
 
 
 def scan_seeds(job):

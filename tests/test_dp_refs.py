@@ -22,7 +22,9 @@ worlds = pytest.mark.parametrize("world", D.WORLDS, ids=[f"w{w}" for w in D.WORL
 def test_all_cases_is_the_list_it_was():
     """the new cases live in dp_refs; the suites that parametrize over grad_refs.ALL_CASES do not grow"""
     assert len(G.ALL_CASES) == 61 and not {c.id for c in D.NEW} & set(G.BY_ID)
-    assert set(G.OTHER) == {"v0", "v1", "g6", "j6", "e38"} and all(G.case_of(c.id) is c for c in D.CASES)
+    from tests import geom_refs                  # (the other module that registers cases there: sixteen of its own)
+    assert set(G.OTHER) == {"v0", "v1", "g6", "j6", "e38"} | set(geom_refs.BY_ID) and len(G.OTHER) == 5 + 16
+    assert all(G.case_of(c.id) is c for c in D.CASES)
     assert [c.id for c in D.CASES] == list(D.REUSED) + ["v0", "v1", "g6", "j6", "e38"]
     for cid, twin in (("g6", "g"), ("j6", "j"), ("e38", "e")):
         assert D.BY_ID[cid]._replace(id=twin, B=G.BY_ID[twin].B, L=G.BY_ID[twin].L, fused_seed=G.BY_ID[twin].fused_seed) == G.BY_ID[twin]
